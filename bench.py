@@ -11,8 +11,15 @@ MSE, one block-Gibbs draw, fused MMD fwd+bwd, Adam; the GRBM quasi-NLL branch (s
 sufficient statistics, Adam) runs at its natural duty of every 10th step.  Prints ONE JSON line.
 
 Workload: BASELINE.json's metric names no configuration, so the N=1 line is the LARGEST single-GPU configuration,
-c3 (configs[2]: B=4096, 512-spin Zephyr GRBM, 200-sweep PCD); c2 and c1 are timed by child runs and reported under
-`extra`.  At N>1 every rank runs the c3 workload (= configs[3] at N=8), weak scaling.
+c3 (configs[2]: B=4096, 512-spin Zephyr GRBM, 200-sweep PCD).  At N>1 every rank runs the c3 workload (= configs[3] at
+N=8), weak scaling.
+
+A plain run sets up, warms up, times the K steps and prints the line (images/s, ms_per_step, the last timed step's
+losses).  `--full` adds everything else the line can carry: the per-kernel roofline (eager passes of the same steps after
+the timed region), the CPU oracle baseline, the 12-step loss parity against the committed fixture, and child runs of the
+other operand modes (f32x3, bf16 inputs), of c2 and c1 (under `extra`) and of the layer-by-layer decoder head.
+`--dump-outputs DIR` writes what the last timed step computed (losses, the updated parameters and BatchNorm statistics)
+as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared array by array.
 """
 import argparse
 import json
@@ -48,6 +55,7 @@ PEAK_F32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, den
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: bf16 MFMA, dense (the spin-path MMD gradient GEMM runs there)
 PEAK_HBM_GBS = 8000.0
 N_CUS, CLOCK_GHZ = 256, 2.4  # MI355X_MICROARCH.md chip-level parameters
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all
 
 
 def baseline_metric():
@@ -65,6 +73,34 @@ def write_yaml(cfg, path, precision="f32"):
                 GIBBS_PERSISTENT=cfg["persistent"], CONV_PRECISION=precision)
     with open(path, "w") as f:
         yaml.safe_dump(base, f)
+
+
+def dump_outputs(model, directory):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array -- its losses (`nll` only
+    when that step trained the GRBM) and every floating-point tensor of the two state_dicts it updated (parameters and
+    BatchNorm running statistics: what ``ModelWrapper.save`` would write), float32 (float64 where the tensor is).  Above
+    DUMP_BUDGET_BYTES in all, every array is cut to the same fixed, seeded sample of its entries in every run."""
+    import numpy as np
+
+    from image_generation_amd.model_wrapper import train_grbm
+
+    tensors = {"mse": model.last["mse"], "mmd": model.last["mmd"]}
+    if train_grbm(model._tpar["opt_step"] - 1, 0):  # (bench steps run in epoch 0)
+        tensors["nll"] = model.last["nll"]
+    for prefix, net in (("dvae", model._dvae), ("grbm", model._grbm)):
+        for k, v in net.state_dict().items():
+            if v.is_floating_point():
+                tensors[f"{prefix}.{k}"] = v
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+              for k, v in tensors.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        for k, a in arrays.items():
+            m = max(1, int(a.size * DUMP_BUDGET_BYTES / total))
+            arrays[k] = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, m, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, f"{k}.npy"), a)
 
 
 def net_flops_per_image(n, R):
@@ -264,7 +300,7 @@ def bf16_inputs_run(args):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", str(args.steps), "--warmup",
-           str(args.warmup), "--precision", "bf16", "--no-cpu-baseline", "--child"] + (["--eager"] if args.eager else [])
+           str(args.warmup), "--precision", "bf16", "--no-cpu-baseline", "--child", "--full"] + (["--eager"] if args.eager else [])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -285,7 +321,7 @@ def split3_run(args):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", str(args.steps), "--warmup",
-           str(args.warmup), "--precision", "f32x3", "--no-cpu-baseline", "--child", "--parity"] + (["--eager"] if args.eager else [])
+           str(args.warmup), "--precision", "f32x3", "--no-cpu-baseline", "--child", "--parity", "--full"] + (["--eager"] if args.eager else [])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -304,7 +340,7 @@ def extra_config_run(args, config):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--config", config, "--steps", "30", "--warmup", "5", "--child",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
 
     def child(extra):
         r = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=600)
@@ -343,7 +379,7 @@ def layerwise_run(args):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", str(args.steps), "--warmup",
-           str(args.warmup), "--no-cpu-baseline", "--child"]
+           str(args.warmup), "--no-cpu-baseline", "--child", "--full"]
     try:
         r = subprocess.run(cmd + ["--option", "dec_lc0=0", "--option", "dec_d22=0"], capture_output=True, text=True, timeout=900)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -411,6 +447,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel roofline, the CPU baseline, the loss parity and the child runs of the other "
+                         "precisions and configurations (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's losses and the parameters it produced to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--child", action="store_true", help="(internal) a child run of another configuration: no extras")
     ap.add_argument("--parity", action="store_true", help="(internal) run the 12-step loss-parity check in this arithmetic mode")
@@ -434,6 +475,10 @@ def main():
     if args.cpu_leg:
         _cpu_leg(args.cpu_leg, args.threads, args.leg_warm, args.leg_steps, args.leg_seconds, args.leg_natural)
         return
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    # per-kernel HIP-event timing: the roofline of --full, or the breakdown file asked for
+    profile = args.full or bool(args.breakdown)
     cfg = CONFIGS[args.config]
     if args.batch > 0:  # size studies only (tools/): the reported line is always the named configuration
         if not args.child:
@@ -502,7 +547,7 @@ def main():
     run(args.warmup)
     torch.cuda.synchronize()
     L.dvg_prof_reset()
-    if not model.use_graph:
+    if profile and not model.use_graph:
         L.dvg_prof_enable(mask)  # eager: per-kernel HIP events over the timed region itself
     dp.barrier()
     torch.cuda.synchronize()
@@ -523,6 +568,8 @@ def main():
                        "note": "losses of the LAST timed step and finiteness of every parameter after the timed region"}
     if not (params_finite and all(v == v and abs(v) != float("inf") for v in (last_mse, last_mmd))):
         raise SystemExit(f"bench: rank {dp.rank}: the timed steps produced non-finite numbers: {workload_losses}")
+    if args.dump_outputs and dp.rank == 0:  # (before the eager passes of --full below, which step the model further)
+        dump_outputs(model, args.dump_outputs)
     per_rank = dp.gather_objects({"rank": dp.rank, "dist": dp.describe(), "mse": last_mse, "mmd": last_mmd})
     prof_steps = args.steps
     import ctypes
@@ -541,7 +588,7 @@ def main():
         return res
 
     passes = []
-    if model.use_graph:
+    if profile and model.use_graph:
         # hipGraph replays cannot carry per-kernel event records, so the per-kernel HIP-event timing behind
         # `roofline` comes from eager passes of the SAME steps right after the timed region (same kernels, same
         # shapes, same streams).  THREE passes, the per-kernel MEDIAN is reported and the spread of the headline
@@ -557,13 +604,14 @@ def main():
             L.dvg_prof_enable(0)
             passes.append(query_kernels())
         model.use_graph = True
-    else:
+    elif profile:
         passes.append(query_kernels())
     per_kernel = {}
-    for nm in passes[0]:
+    for nm in (passes[0] if passes else ()):
         rows = sorted((p_[nm] for p_ in passes if nm in p_), key=lambda r_: r_["total_ms"])
         per_kernel[nm] = dict(rows[len(rows) // 2], total_ms_passes=[r_["total_ms"] for r_ in rows])
-    if dp.rank == 0:
+    roofline = None
+    if dp.rank == 0 and profile:
         # dominant kernel = the GEMM kernel (one template instantiation = one rocprof kernel name) with the
         # largest total time; achieved = its executed FLOPs (2*rows*Cin*Cout*taps per launch -- the folded-upsample
         # layers are credited their 4 or 16 folded taps, not the 9 they replace -- summed by the library over the
@@ -652,6 +700,7 @@ def main():
         roofline["all_gemm_kernels"] = {k: {"tflops": v["work"] / (v["total_ms"] * 1e-3) / 1e12,
                                             "ms_per_step": v["total_ms"] / prof_steps,
                                             "avg_launch_us": v["total_ms"] * 1e3 / v["launches"]} for k, v in cands.items()}
+    if dp.rank == 0:
         ips = args.gpus * cfg["B"] * args.steps / elapsed
         out = {
             "metric": baseline_metric(), "metric_id": "dvae_grbm_train_step_images_per_s", "value": ips,
@@ -680,9 +729,10 @@ def main():
                                                 "device_name": r["dist"].get("device_name"),
                                                 "world_size_seen": r["dist"].get("world_size_seen"),
                                                 "mse": r["mse"], "mmd": r["mmd"]} for r in per_rank]),
-            "roofline": roofline,
         }
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if roofline is not None:
+            out["roofline"] = roofline
+        if args.gpus == 1 and args.full and not args.no_cpu_baseline:
             try:  # (a failed or timed-out child must not cost the line its GPU measurement)
                 out["cpu_baseline"] = cpu_baseline(args.config)
             except Exception as exc:
@@ -691,7 +741,7 @@ def main():
         if args.parity and args.gpus == 1:
             out["loss_parity"] = dict(loss_parity(args.precision if args.precision != "f32" else None),
                                       note="12 fixture steps in this arithmetic mode (every forward / data-gradient launch)")
-        if args.gpus == 1 and not args.child and not args.no_cpu_baseline and args.precision == "f32":
+        if args.gpus == 1 and args.full and not args.child and not args.no_cpu_baseline and args.precision == "f32":
             out["f32x3"] = split3_run(args)
             out["bf16_inputs"] = bf16_inputs_run(args)
             if args.config == "c3":

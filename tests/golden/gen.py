@@ -98,3 +98,54 @@ def figure_image(fig):
 
     raw = base64.b64decode(get("source").split(",", 1)[1])
     return np.asarray(Image.open(io.BytesIO(raw)).convert("RGB"), dtype=np.uint8)
+
+
+# A committed fixture file stays below 1 MiB: larger fixtures are written as several .npz files (``stem.npz``,
+# ``stem.1.npz``, ...), with any array above PART_BYTES split along its first axis into pieces ``name@000``, ``name@001``...
+PART_BYTES = 900_000
+
+
+def save_npz_parts(path, arrays):
+    """np.savez_compressed of ``arrays`` into ``path`` and as many ``path[:-4].K.npz`` as keep each below PART_BYTES."""
+    import os
+
+    pieces = []
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.nbytes <= PART_BYTES:
+            pieces.append((name, a))
+            continue
+        rows = max(1, PART_BYTES // max(1, a.nbytes // a.shape[0]))
+        for i, r0 in enumerate(range(0, a.shape[0], rows)):
+            pieces.append((f"{name}@{i:03d}", a[r0:r0 + rows]))
+    files, size = [{}], 0
+    for name, a in pieces:
+        if files[-1] and size + a.nbytes > PART_BYTES:
+            files.append({})
+            size = 0
+        files[-1][name] = a
+        size += a.nbytes
+    stem = path[:-len(".npz")]
+    for k, f in enumerate(files):
+        np.savez_compressed(path if k == 0 else f"{stem}.{k}.npz", **f)
+    k = len(files)
+    while os.path.exists(f"{stem}.{k}.npz"):  # (parts left over from a larger earlier fixture)
+        os.remove(f"{stem}.{k}.npz")
+        k += 1
+
+
+def load_npz_parts(path):
+    """The arrays :func:`save_npz_parts` wrote to ``path``, split arrays joined again."""
+    import os
+
+    out, stem, k = {}, path[:-len(".npz")], 0
+    while os.path.exists(path if k == 0 else f"{stem}.{k}.npz"):
+        with np.load(path if k == 0 else f"{stem}.{k}.npz") as z:
+            out.update({n: z[n] for n in z.files})
+        k += 1
+    if not out:
+        raise FileNotFoundError(path)
+    split = sorted(n for n in out if "@" in n)
+    for name in sorted({n.split("@")[0] for n in split}):
+        out[name] = np.concatenate([out.pop(n) for n in split if n.split("@")[0] == name])
+    return out

@@ -14,6 +14,8 @@ Fixtures:
                        ModelWrapper on the CPU oracle: losses, progress calls, side files, figure contents.
   ckpt_adv2_40.npz     a shipped checkpoint (models/Advantage2_system1_40_epochs/dvae.pth) as float32 arrays plus the
                        reference modules' eval-mode outputs on fixed inputs (``checkpoint`` target).
+  ref_checkpoints.npz  all six shipped checkpoints as key lists, shapes, GRBM states and small DVAE tensors
+                       (``ref_checkpoints`` target).
   grbm_ckpt.npz        the GRBM half of two shipped checkpoints (Zephyr + Pegasus real-QPU sub-graphs, trained h / J in the
                        checkpoint's own edge order) as data, oracle draws / energies on them, and the reference's verbatim
                        ModelWrapper.load + generate_output on the Zephyr one (``grbm_checkpoint`` target).
@@ -496,8 +498,28 @@ def checkpoint_fixture(model="Advantage2_system1_40_epochs", B=32, R=2):
     for k, v in sd.items():
         out[f"sd/{k}"] = v.numpy()
     path = os.path.join(OUT, "ckpt_adv2_40.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes; n =", n)
+    gen.save_npz_parts(path, out)  # (4.3 MB: several files of less than 1 MiB, gen.load_npz_parts reads them)
+    print("wrote", path, "and its parts; n =", n)
+
+
+def ref_checkpoints_fixture(small=4096):
+    """The six checkpoints shipped with the reference (``models/*/{dvae,grbm}.pth``, 25 MB) as what
+    tests/test_checkpoints.py needs of them: every ``state_dict`` key in order with its shape; the GRBM state and every
+    DVAE tensor of at most ``small`` entries (biases, BatchNorm weights and running statistics, the small layers) as
+    data.  The large DVAE weights of one checkpoint are in ckpt_adv2_40.npz already."""
+    out = {}
+    for folder in sorted(os.listdir(os.path.join(REF, "models"))):
+        for net in ("dvae", "grbm"):
+            sd = torch.load(os.path.join(REF, "models", folder, f"{net}.pth"), weights_only=True)
+            out[f"{folder}/{net}_keys"] = np.array(list(sd))
+            for k, v in sd.items():
+                if net == "grbm" or v.numel() <= small:
+                    out[f"{folder}/{net}/{k}"] = v.numpy()
+                else:
+                    out[f"{folder}/{net}_shape/{k}"] = np.array(v.shape, dtype=np.int64)
+    path = os.path.join(OUT, "ref_checkpoints.npz")
+    gen.save_npz_parts(path, out)
+    print("wrote", path, "and its parts")
 
 
 def grbm_checkpoint_fixture(reads=32, sweeps=20):
@@ -637,5 +659,7 @@ if __name__ == "__main__":
         resize_fixture()
     if "checkpoint" in which:
         checkpoint_fixture()
+    if "ref_checkpoints" in which:
+        ref_checkpoints_fixture()
     if "grbm_checkpoint" in which:
         grbm_checkpoint_fixture()

@@ -17,7 +17,7 @@ from image_generation_amd.plugin import DiscreteVariationalAutoencoder
 
 @pytest.fixture(scope="module")
 def fx(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "ckpt_adv2_40.npz")))
+    return gen.load_npz_parts(os.path.join(golden_dir, "ckpt_adv2_40.npz"))
 
 
 def _state_dict(fx):

@@ -90,7 +90,7 @@ def test_load_then_generate_output_matches_the_reference_on_a_shipped_checkpoint
     pytest.importorskip("plotly")
     from image_generation_amd.model_wrapper import ModelWrapper
 
-    ck = dict(np.load(os.path.join(golden_dir, "ckpt_adv2_40.npz")))
+    ck = gen.load_npz_parts(os.path.join(golden_dir, "ckpt_adv2_40.npz"))
     folder = tmp_path / "Advantage2_system1_40_epochs"
     folder.mkdir()
     torch.save({k[3:]: torch.from_numpy(np.array(v)) for k, v in ck.items() if k.startswith("sd/")}, folder / "dvae.pth")

@@ -149,13 +149,13 @@ def test_chunked_mmd_of_the_full_size_checker_equals_the_plain_estimator():
 @pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference tree exists in the build container only")
 def test_every_fixture_regenerates_identically_in_one_process(golden_dir, tmp_path):
     """`make_golden.py epoch` used to reproduce only in a process of its own (the `step` target
-    left its capturing noise hook installed and `epoch` wrapped it).  All seven targets, ONE invocation, into a scratch
+    left its capturing noise hook installed and `epoch` wrapped it).  All eight targets, ONE invocation, into a scratch
     directory: every array / JSON value equals the committed fixture."""
     import subprocess
     import sys
 
     env = dict(os.environ, DVG_GOLDEN_OUT=str(tmp_path))
-    targets = ["enc_dec", "common", "step", "epoch", "resize", "checkpoint", "grbm_checkpoint"]
+    targets = ["enc_dec", "common", "step", "epoch", "resize", "checkpoint", "ref_checkpoints", "grbm_checkpoint"]
     subprocess.run([sys.executable, os.path.join(golden_dir, "make_golden.py")] + targets, check=True, env=env,
                    stdout=subprocess.DEVNULL, timeout=900)
     made = sorted(os.listdir(tmp_path))
@@ -168,4 +168,4 @@ def test_every_fixture_regenerates_identically_in_one_process(golden_dir, tmp_pa
         want, got = np.load(os.path.join(golden_dir, name)), np.load(tmp_path / name)
         assert sorted(want.files) == sorted(got.files), name
         for k in want.files:
-            assert want[k].dtype == got[k].dtype and np.array_equal(want[k], got[k], equal_nan=True), (name, k)
+            assert want[k].dtype == got[k].dtype and np.array_equal(want[k], got[k], equal_nan=want[k].dtype.kind in "fc"), (name, k)

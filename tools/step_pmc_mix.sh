@@ -5,7 +5,7 @@ set -u
 C=${1:-c3}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/step_mix; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d $OUT/a -- python3 $ROOT/bench.py --config $C --eager --no-cpu-baseline --child --steps 3 --warmup 2 > $OUT/a.log 2>&1
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d $OUT/a -- python3 $ROOT/bench.py --full --config $C --eager --no-cpu-baseline --child --steps 3 --warmup 2 > $OUT/a.log 2>&1
 cd $ROOT
 python3 - <<'PY'
 import csv, glob, collections
