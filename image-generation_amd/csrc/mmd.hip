@@ -1575,15 +1575,27 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
     //        lookups of chunk t+1          its Gram tile (registers) -> the next weights
     //        Gram of chunk t+2             int8 rows of chunk t+2          from stage (k + 2) % 3
     //        LDS-DMA: int8 rows of chunk t+4 -> stage (k+1) % 3,  transposed copy of chunk t+2 -> stage (k+2) % 3
-    // with ONE workgroup barrier, at the TOP of the iteration and in front of the DMA issue: the stages the DMA
-    // overwrites were last read in iteration k-1 (every wave is past it), and what it fetches is first read in
-    // iteration k+2, behind the next barrier, in front of which each wave has waited for its own pieces (a whole
-    // iteration after issuing them: that wait does not stall).  With two stages (round 3) the barrier had to sit
-    // BETWEEN an iteration's last reads and the next one's first, i.e. every chunk ended in
-    // `wait - barrier - first operand reads - wait`, a serial stretch with the matrix pipe empty; here the operand reads
-    // of the next chunk's first tile go out beside the last tile's MFMAs and the tile pipeline never drains.  The
-    // block-uniform bookkeeping of the NEXT iteration (chunk meta, DMA offsets, stage addresses: ~60 scalar and a dozen
-    // vector instructions) is computed in the middle of the current one, between MFMAs, for the same reason.
+    //        (last tile) first-tile operands of iteration k+1: transposed copy of chunk t+1 from stage (k+1) % 3 and
+    //        int8 rows of chunk t+3 from stage k % 3 -- both filled by iteration k-1's DMA
+    // with ONE workgroup barrier per iteration.  The invariant, for every wave: each ds_read of a stage comes after a
+    // vmcnt wait that covers this wave's DMA pieces into it, followed by a barrier (so every wave's pieces have landed);
+    // each DMA into a stage comes after a barrier in front of which every wave has received all its reads of the
+    // chunk the stage held before.  Where the barrier sits:
+    //   GPT = 1 (d <= 512): at the TOP of the iteration, behind vmcnt(0).  That covers iteration k-1's pieces, the
+    //     newest anything in iteration k reads (the last-tile prefetch included); the stages iteration k's DMA
+    //     overwrites were last read in iteration k-1, whose reads every wave has received before its last tile.
+    //   GPT > 1 (d = 1024): in the LAST tile, in front of the prefetch, behind vmcnt(NZ8 + NZT): only iteration k's own
+    //     pieces stay in flight, iteration k-1's -- what the prefetch and all of iteration k+1 read -- have landed.  An
+    //     iteration there is shorter than the LDS-DMA round trip under load, so the wait sits exactly where the first
+    //     reader needs it (at least 1.25 iterations after the pieces went out), not a whole iteration earlier.  The stages
+    //     iteration k+1's DMA overwrites (int8 (k+2) % 3, transposed k % 3) were last read in tiles whose operands every
+    //     wave has received at the top of the last tile, in front of that barrier.
+    // With two stages (round 3) the barrier had to sit BETWEEN an iteration's last reads and the next one's first, i.e.
+    // every chunk ended in `wait - barrier - first operand reads - wait`, a serial stretch with the matrix pipe empty;
+    // here the operand reads of the next chunk's first tile go out beside the last tile's MFMAs and the tile pipeline
+    // never drains.  The block-uniform bookkeeping of the NEXT iteration (chunk meta, DMA offsets, stage addresses: ~60
+    // scalar and a dozen vector instructions) is computed in the middle of the current one, between MFMAs, for the
+    // same reason.
     issue_z8((int)t0, 0);
     issue_z8((int)t0 + 1, 1);
     issue_z8((int)t0 + 2, 2);
@@ -1601,10 +1613,14 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
       flush_lsum(m.cols_x);
     }
     i32x16 Sa = gram(1), Sb = {0};  // Sa: Gram tile of chunk t0+1 (a repeat of chunk t0's rows if T == 1: masked by its fixup)
+    // (both Gram tiles live in vector registers from here on: see the tile loop.  GPT > 1 pins them in front of the barrier:
+    // no barrier follows before iteration 0's DMA overwrites stage 1 with chunk t0+4, so every wave must have received its
+    // reads of that stage here.  GPT = 1 has the top barrier of iteration 0 for that.)
+    if constexpr (NST / NFT > 1) asm volatile("" : "+v"(Sa), "+v"(Sb));
     __builtin_amdgcn_s_barrier();   // every wave is done with stage 0 of the int8 ring: chunk t0+3 may land there
     issue_z8((int)t0 + 3, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("" : "+v"(Sa), "+v"(Sb));  // both Gram tiles live in vector registers from here on (see the tile loop)
+    if constexpr (NST / NFT == 1) asm volatile("" : "+v"(Sa), "+v"(Sb));
 
     // pair-rows [rb(ft), rb(ft+1)) are requested beside feature tile ft < NFT - 1 and consumed beside tile ft + 1
     auto rb = [](int ft) { return ft >= NFT - 1 ? 16 : (16 * ft + NFT - 2) / (NFT - 1); };
@@ -1660,13 +1676,12 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
 
     auto iteration = [&](int k, auto parity, i32x16& Scur, i32x16& Snext) {
       (void)parity;  // (the two instantiations differ in which accumulator set is current: Scur / Snext)
-      // ---- top: the one barrier (behind the wait for this wave's pieces of the previous iteration), the rare fixup
-      // (sliced form, d = 1024: an iteration is 48 MFMAs, 0.6 us -- less than the LDS-DMA round trip under 256 blocks' load,
-      // and the wait was the chunk's time, 3.5 us.  What iteration k fetches is first read in iteration k + 2: the wait
-      // leaves the newest iteration's pieces in flight; the barrier then still publishes everything iteration k + 1 reads.)
-      if constexpr (GPT > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NZ8 + NZT) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
+      // ---- top: GPT = 1, the one barrier behind the wait for all of this wave's pieces (those of iteration k-1 are the
+      // newest this iteration reads); GPT > 1 has it in the last tile instead (see the ring above).  Then the rare fixup.
+      if constexpr (GPT == 1) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+      }
       asm volatile("" : "+v"(Scur));
       if (cy.fix) {
         asm volatile("" ::: "memory");
@@ -1716,8 +1731,16 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
 #pragma unroll
           for (int u = 0; u < GPT; ++u) zn[u] = zread(ad, (ft + 1) * GPT + u);
         } else {
-          // the NEXT iteration's first tile (its stages were published by this iteration's barrier or earlier): every read
-          // of this iteration's stages has been issued, so the addresses move on in place (stage + 1, or back by two)
+          // the NEXT iteration's first tile, filled by iteration k-1's DMA.  GPT > 1: wait for this wave's pieces of it
+          // (only this iteration's NZ8 + NZT newer ones may stay in flight) and publish everyone's with the barrier -- the
+          // operands of this tile, the last reads of this iteration's stages, have arrived (above) in every wave.  (GPT
+          // = 1: published by this iteration's top barrier.)  Every read of this iteration's stages has been issued, so
+          // the addresses move on in place (stage + 1, or back by two).
+          if constexpr (GPT > 1) {
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NZ8 + NZT) : "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+          }
           const int dzt = stg == 2 ? -2 * L::ZT_BYTES : L::ZT_BYTES;  // transposed copy: stage k % 3 -> (k + 1) % 3
           const int dz8 = stg == 0 ? -2 * L::Z8_BYTES : L::Z8_BYTES;  // int8 rows: stage (k + 2) % 3 -> k % 3
           ad.a0 += dzt; ad.a1 += dzt;
