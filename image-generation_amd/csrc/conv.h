@@ -228,10 +228,6 @@ struct ConvArgs {
 // by side on half the chip each -- (128, 128) 8.41 ms, (144, 112) 8.65, (112, 144) 8.64, (160, 96) 8.7-8.8, (96, 160)
 // 8.86 (round 5) -- the decoder's launches at the whole chip (its weight gradient at 128 / 192: 8.49 / 8.46 against 8.41).
 constexpr int WINO_CUS_ENC_DGRAD = 128, WINO_CUS_ENC_WGRAD = 128, WINO_CUS_DEC = 256;
-// encoder Winograd launches of a training call: from this many workgroups' worth of tile blocks up (measured, n = 512
-// model: 1024 / 512 / 256 -> B = 512: 2.16 / 2.13 / 2.06 ms, B = 1024: 3.03 / 2.82 / 2.82, B = 2048: 4.67 / 4.60 / 4.53;
-// c2: 0.920 / 0.924 / 0.953 -- 512 is the lowest value that costs c2 nothing)
-constexpr int WINO_MIN_BLOCKS = 512;
 // process-wide precision of the forward / data-gradient GEMMs (set through the ABI only: dvg_set_conv_precision; the library reads no environment variable)
 bool conv_precision_bf16();
 int conv_precision_mode();  // 0 f32, 1 bf16 inputs, 2 f32 as three bf16 pieces
@@ -245,30 +241,28 @@ bool conv_precision_matches_forward(const void* ws);   // backward calls: same m
 int launch_conv_igemm(const ConvArgs& a, hipStream_t s);
 // Winograd F(2x2,3x3) form of a stride-1 3x3 layer (conv_wino.hip): same ConvArgs, `wp` = the transformed pack of
 // launch_wino_weight_pack ([Cin][Cout][16] floats), stats rows = conv_wino_stats_blocks
-bool conv_wino_shape(int64_t M, int Cin, int Cout, int L);  // shape only
-bool conv_wino_ok(int64_t M, int Cin, int Cout, int L, int kind = 0);  // kind: 0 training forward, 1 data gradient, 2 evaluation forward
+// (these files say which SHAPES a form can run and how it is launched; which launches take it is conv_plan.cpp's)
+bool conv_wino_shape(int64_t M, int Cin, int Cout, int L);
+int64_t conv_wino_blocks(int64_t M, int Cout);  // workgroups' worth of tile blocks of a launch (what the planner's size rule counts)
 int conv_wino_stats_blocks(int64_t M, int Cout);
 int launch_conv_wino(const ConvArgs& a, hipStream_t s);
 int launch_wino_weight_pack(const float* w, const WeightMap& map, float* u, hipStream_t s);
 // Winograd F(4x4,3x3) form of the same layers (conv_wino4.hip): `wp` = the pack of a PackJob with wino = 2 (36 Cin Cout
 // floats: wino4_pack_entry), stats rows = conv_wino4_stats_blocks (tile blocks of 1024 pixels)
-bool conv_wino4_shape(int64_t M, int Cin, int Cout, int L);  // shape only
-bool conv_wino4_ok(int64_t M, int Cin, int Cout, int L);     // policy (option enc_wino4) + shape: asked for launches conv_wino_ok accepted
+bool conv_wino4_shape(int64_t M, int Cin, int Cout, int L);
 int conv_wino4_stats_blocks(int64_t M);
 int launch_conv_wino4(const ConvArgs& a, hipStream_t s);
 int launch_wino4_weight_pack(const float* w, const WeightMap& map, float* u, hipStream_t s, int ups = 0);  // ups: the 25-position pack
 // ... and of their weight gradients (conv_wino4_wgrad.hip): slabs [nsplit][36][Cin][Cout] (at most
 // conv_wino4_wgrad_slab_floats), summed and transformed back (G^T dU G) into the checkpoint layout `map` by the same call;
 // cus = CUs the launch is sized for (0: WINO_CUS_ENC_WGRAD)
-bool conv_wino4_wgrad_ok(int64_t M, int Cin, int Cout, int L);      // policy (option enc_wino4) + shape
-bool conv_wino4_wgrad_shape(int64_t M, int Cin, int Cout, int L);   // shape only
+bool conv_wino4_wgrad_shape(int64_t M, int Cin, int Cout, int L);
 size_t conv_wino4_wgrad_slab_floats(int64_t M, int Cin, int Cout);
 int launch_conv_wino4_wgrad(const float* in, const float* dy, int64_t M, int Cin, int Cout, int L, float* slabs,
                             const WeightMap& map, float* grad_w, hipStream_t s, int cus = 0);
 // Winograd form of a stride-1 3x3 layer's WEIGHT gradient (conv_wino_wgrad.hip): slabs [nslabs][16][Cin][Cout] (at most
 // conv_wino_wgrad_slab_floats), reduced and transformed back (G^T dU G) into the checkpoint layout `map` by the same call
-bool conv_wino_wgrad_ok(int64_t M, int Cin, int Cout, int L);      // policy (options) + shape
-bool conv_wino_wgrad_shape(int64_t M, int Cin, int Cout, int L);   // shape only
+bool conv_wino_wgrad_shape(int64_t M, int Cin, int Cout, int L);
 size_t conv_wino_wgrad_slab_floats(int64_t M, int Cin, int Cout, int L);
 // ups = 1: the decoder's Upsample(x2) + 3x3 layers (`in` = the source map, M / L of the output grid: 9 of the 16 position
 // GEMMs remain); cus = CUs the launch is sized for (0: WINO_CUS_ENC_WGRAD)

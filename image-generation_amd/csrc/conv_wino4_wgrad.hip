@@ -378,13 +378,6 @@ int launch_wino4_wgrad_cfg(const Wino4WgradArgs& a, double flops, dim3 grid, hip
 
 bool conv_wino4_wgrad_shape(int64_t M, int Cin, int Cout, int L) { return wino4_wgrad_shape_ok(M, Cin, Cout, L); }
 
-// option enc_wino4: 1 (default) the weight gradients of the layers on 4x4 images (alone on 128 CUs at c3 0.76 of the F(2x2)
-// kernel's time; on 8x8 and 16x16 images the two forms are level), 2 every layer the shape allows, 0 never
-bool conv_wino4_wgrad_ok(int64_t M, int Cin, int Cout, int L) {
-  const int64_t o = opt(OPT_ENC_WINO4);
-  return o != 0 && wino4_wgrad_shape_ok(M, Cin, Cout, L);  // (which layers: option enc_wino4_mask, encoder.cpp)
-}
-
 size_t conv_wino4_wgrad_slab_floats(int64_t M, int Cin, int Cout) {
   const Wino4WgradGeom g = wino4_wgrad_geom(M, Cin, Cout, 256);  // (the largest split any CU budget gives)
   return (size_t)g.nsplit * 36 * Cin * Cout;

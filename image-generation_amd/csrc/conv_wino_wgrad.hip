@@ -420,16 +420,6 @@ static WinoWgradGeom wino_wgrad_geom(int64_t M, int Cin, int Cout, int L, int cu
   return g;
 }
 
-// the weight gradient of a training call takes the Winograd form with the layer's other training launches (option enc_wino:
-// -1 from WINO_MIN_BLOCKS workgroups' worth of tile blocks up -- in every operand mode: weight gradients are float32 in
-// all of them; 0 never; 1 whenever the shape allows)
-bool conv_wino_wgrad_ok(int64_t M, int Cin, int Cout, int L) {
-  const int64_t o = opt(OPT_ENC_WINO);
-  if (o == 0 || !wino_wgrad_shape_ok(M, Cin, Cout, L)) return false;
-  if (o >= 1) return true;
-  return conv_wino_ok(M, Cin, Cout, L, 3);
-}
-
 size_t conv_wino_wgrad_slab_floats(int64_t M, int Cin, int Cout, int L) {
   const WinoWgradGeom g = wino_wgrad_geom(M, Cin, Cout, L, 256);  // (the largest split any CU budget gives)
   return (size_t)g.nslabs * 16 * Cin * Cout;

@@ -1,5 +1,5 @@
 // Development hooks (include/dvg_dev.h): direct launches of the MFMA GEMM kernels for unit tests / micro-benchmarks.
-#include "conv.h"
+#include "conv_plan.h"
 #include "../../include/dvg_dev.h"
 using namespace dvg;
 
@@ -43,7 +43,24 @@ extern "C" int dvg_dev_conv_wino4(const float* in, const float* w, int mode, flo
   return launch_conv_wino4(a, s);
 }
 extern "C" int dvg_dev_conv_wino4_shape(int64_t M, int Cin, int Cout, int L) { return conv_wino4_shape(M, Cin, Cout, L) ? 1 : 0; }
-extern "C" int dvg_dev_conv_wino_ok(int64_t M, int Cin, int Cout, int L) { return conv_wino_ok(M, Cin, Cout, L) ? 1 : 0; }
+extern "C" int dvg_dev_conv_wino_ok(int64_t M, int Cin, int Cout, int L) { return plan_enc_wino_fwd(M, Cin, Cout, L, true, plan_options()) ? 1 : 0; }
+
+// The plan of a network call under the current options and operand mode (conv_plan.h); needs no device.
+extern "C" int dvg_dev_plan_forms(int network, int64_t rows, int n_latents, int training, int out[15]) {
+  DVG_REQUIRE(out && (network == 0 || network == 1) && rows >= 1 && n_latents >= 32 && n_latents % 32 == 0, "dev_plan_forms: bad argument");
+  const PlanOptions o = plan_options();
+  ConvLayer y[4];
+  if (network == 0) plan_encoder_layers(rows, n_latents, training != 0, o, y);
+  else plan_decoder_layers(rows, n_latents, o, y);
+  for (int l = 0; l < 4; ++l)
+    for (int pass = 0; pass < 3; ++pass)
+      out[3 * l + pass] = (network == 0 ? l == 0 : l == 3) ? -1 : (int)y[l].form[pass];
+  const ConvForm f0 = y[0].form[PASS_FWD];
+  out[12] = network == 1 && (f0 == CF_D22 || f0 == CF_LC0);
+  out[13] = network == 1 && f0 == CF_LC0;
+  out[14] = network == 1 && o.v[OPT_DEC_TAIL_FUSED] != 0;
+  return DVG_OK;
+}
 extern "C" int dvg_dev_conv_wino_stats_blocks(int64_t M, int Cout) { return conv_wino_stats_blocks(M, Cout); }
 
 extern "C" size_t dvg_dev_conv_splitk_floats(int64_t M, int Cin, int Cout, int ntaps, int poolsum) {

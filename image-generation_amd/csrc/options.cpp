@@ -2,9 +2,9 @@
 // Rounds 1-2 selected kernel forms through ~26 environment variables read at scattered getenv() sites, some once per
 // process, some per call; the boundary, not the environment, selects them now.  Every option has a default that is the
 // product's path; the others exist for A/B measurements and for the tests that compare two forms of the same function.
-// Values are read per call (relaxed atomics): an option may be flipped between calls, and the forward / backward pair of
-// a network call records the plan-shaping ones in its workspace (decoder.cpp) so that a flip in between is an error,
-// not silent garbage.
+// Values are relaxed atomics: an option may be flipped between calls.  A network call reads the ones that shape its plan
+// once, into a snapshot (conv_plan.h: plan_options), and its forward / backward pair records that plan's signature in the
+// workspace so that a flip in between is an error, not silent garbage.
 #include <atomic>
 #include <cstring>
 #include <mutex>
@@ -32,7 +32,7 @@ const OptDef kDefs[OPT_COUNT] = {
     {"enc_l0_fused", 1, "encoder layer 0: 1 = its output is recomputed by every pass that needs it (BatchNorm statistics, BN/pool/LeakyReLU, the backward sums, the weight gradient) and never stored (default), 0 = stored and re-read (rounds 1-2)", true},
     {"dec_tail_fused", 1, "decoder: 1 = the 8x8x32 stage's BatchNorm / Dropout / LeakyReLU (forward and backward) run inside the 32 -> 1 layer's kernels, its activated map and that map's gradient are never stored (default), 0 = separate passes (rounds 1-2)", true},
     {"wino_dynamic", 1, "Winograd forward / data-gradient launches deal their tile blocks dynamically (an atomic counter per grid row) instead of round-robin: a workgroup that gets its CU late takes fewer blocks (1 default, 0 = the static deal of rounds 3-4)", true},
-    {"enc_wino4", 1, "encoder 3x3 layers that run in the Winograd domain: 1 (default) forward and data gradient in the F(4x4,3x3) form wherever the shape qualifies (36 position GEMMs per 4x4 output tile: 2.25 multiplies per output instead of 4.0), 0 the F(2x2,3x3) form everywhere"},
+    {"enc_wino4", 1, "every launch of the Winograd F(4x4,3x3) form -- forward, data gradient and weight gradient, encoder and decoder: 1 (default) the launches that run in the Winograd domain take it where the shape qualifies and their bit of the dev options enc_wino4_mask / dec_wino4_mask is set (36 position GEMMs per 4x4 output tile: 2.25 multiplies per output instead of 4.0; behind the decoder's upsample 25 of the 36), 0 none: the F(2x2,3x3) form everywhere"},
     {"enc_wino4_mask", 0x13c, "which encoder launches option enc_wino4 covers: bit l-1 the forward of layer l (1..3), bit 2+l its data gradient, bit 5+l its weight gradient (default 0x13c: layer 3's forward, every data gradient, layer 3's weight gradient -- the forwards of layers 1-2 gain nothing inside the step and their 7x float32 noise in front of two more max-pool stages moved the B = 1024 full-size gradient test from 4.6e-3 to 5.4e-3 of its 5e-3 bar; the weight gradients of layers 1-2 are level with the F(2x2,3x3) kernel)", true},
     {"enc_dgrad_cus", 0, "CUs the encoder's Winograd data-gradient launches are sized for (0: the measured constant of conv.h)", true},
     {"enc_wgrad_cus", 0, "CUs the encoder's Winograd weight-gradient launches are sized for (0: the measured constant of conv.h)", true},

@@ -21,6 +21,7 @@ _SIGS = {
     "dvg_dev_conv_wino4_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 4 +
                                  [ctypes.c_void_p]),
     "dvg_dev_conv_wino_ok": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dvg_dev_plan_forms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "dvg_dev_conv_wino_stats_blocks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int]),
     "dvg_dev_wgrad_slab_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_conv_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 +
@@ -87,6 +88,21 @@ def conv_igemm(x_m, w, mode, M, Cin, Cout, L, ntaps=9, ups=0, poolsum=0, bias=No
 
 def conv_wino_ok(M, Cin, Cout, L):
     return bool(lib().dvg_dev_conv_wino_ok(M, Cin, Cout, L))
+
+
+FORMS = ("direct", "fold", "d22", "lc0", "wino2", "wino4")  # csrc/conv_plan.h: ConvForm
+
+
+def plan_forms(network, rows, n_latents, training=True):
+    """The kernel forms a network call would take under the current options and operand mode (no device needed):
+    ``(layers, flags)`` with ``layers[l] = (forward, data gradient, weight gradient)`` as names of ``FORMS`` (``None`` for
+    the VALU layers) and ``flags = dict(d22, lc0, tail)``.  ``network``: ``"encoder"`` (rows = batch) or ``"decoder"``
+    (rows = batch x replicas)."""
+    out = (ctypes.c_int * 15)()
+    _lib.check(lib().dvg_dev_plan_forms({"encoder": 0, "decoder": 1}[network], rows, n_latents, int(training), out),
+               "dvg_dev_plan_forms")
+    layers = [tuple(FORMS[out[3 * l + k]] for k in range(3)) if out[3 * l] >= 0 else None for l in range(4)]
+    return layers, dict(d22=bool(out[12]), lc0=bool(out[13]), tail=bool(out[14]))
 
 
 def conv_wino(x_m, w, mode, M, Cin, Cout, L, bias=None, stats=False):

@@ -20,7 +20,15 @@ size_t dvg_dev_conv_splitk_floats(int64_t M, int Cin, int Cout, int ntaps, int p
  * Replaces (with the implicit GEMM above) /root/reference/src/encoder.py:28-36's nn.Conv2d calls. */
 int dvg_dev_conv_wino(const float *in, const float *w, int mode, float *u, const float *bias, float *out, float *stats,
                       int64_t M, int Cin, int Cout, int L, dvg_stream_t stream);
+/* ... whether a training call's forward launch of this shape takes that form under the current options and operand mode */
 int dvg_dev_conv_wino_ok(int64_t M, int Cin, int Cout, int L);
+/* The kernel form every MFMA convolution layer of a network call takes under the current options and operand mode
+ * (csrc/conv_plan.h; needs no device).  network: 0 encoder (rows = batch), 1 decoder (rows = batch x replicas).
+ * out[3 l + pass], l = 0..3, pass 0 forward / 1 data gradient / 2 weight gradient: 0 direct implicit GEMM, 1 folded
+ * upsample, 2 dense 2x2 map, 3 Linear composed with that map, 4 Winograd F(2x2,3x3), 5 Winograd F(4x4,3x3); -1 for the
+ * VALU layers (encoder layer 0, decoder layer 3).  out[12..14] = the decoder's d22 / lc0 / tail flags (encoder: 0).
+ * The decoder's plan does not depend on `training`; an evaluation-mode encoder plan reads 0 for its gradients. */
+int dvg_dev_plan_forms(int network, int64_t rows, int n_latents, int training, int out[15]);
 /* The same layer in the Winograd F(4x4,3x3) form (csrc/conv_wino4.hip: 36 position GEMMs per 4x4 output tile, 2.25 multiplies
  * per output where F(2x2,3x3) issues 4.0): `u` = scratch of 36*Cin*Cout floats, `stats` rows = M / 1024 (tile blocks of 64
  * tiles), cus = CUs the persistent grid is sized for (0 = 256).  Shapes: whole 1024-pixel blocks of 4x4 / 8x8 / 16x16 images. */

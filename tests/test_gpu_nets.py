@@ -833,6 +833,35 @@ def test_operand_mode_must_not_change_between_forward_and_backward():
         assert L.dvg_set_conv_precision(0) == 0
 
 
+def test_plan_shaping_option_must_not_change_between_forward_and_backward():
+    """A backward call plans again, from the options as they are then: one that changes the forward or data-gradient form
+    of a layer (so what the forward left in the workspace is not what the backward would read) is an error that names the
+    option; one that only chooses among weight-gradient kernels is not."""
+    n, B, R = 64, 2, 4
+    spins = torch.from_numpy(gen.make_spins(B, R, n, 11)).cuda()
+    dec = _load(Decoder(n), gen.make_params(n, "decoder", 5)).train()
+    # A: the decoder's first layer, dense 2x2 map -> 9-tap form
+    y = dec(spins.clone().requires_grad_(True))
+    with _lib.option_scope(dec_d22=0):
+        with pytest.raises(_lib.DvgError, match="dec_d22"):
+            y.sum().backward()
+    # B: the encoder's 3x3 layers, Winograd -> direct (B = 64: every layer's shape qualifies under enc_wino = 1)
+    enc = _load(Encoder(n), gen.make_params(n, "encoder", 5)).train()
+    x = (torch.rand(64, 1, 32, 32, generator=torch.Generator().manual_seed(3)) < 0.2).float().cuda()
+    with _lib.option_scope(enc_wino=1):
+        z = enc(x)
+        with _lib.option_scope(enc_wino=0):
+            with pytest.raises(_lib.DvgError, match="enc_wino"):
+                z.sum().backward()
+    # C: the staging of the weight-gradient GEMMs shapes nothing the forward wrote
+    sg = spins.clone().requires_grad_(True)
+    y = dec(sg)
+    with _lib.option_scope(wgrad_dma=0):
+        y.sum().backward()
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(sg.grad).all())
+
+
 def test_wide_tile_configuration_in_a_child_process():
     """The 128x128 convolution tile serves launches of >= 512 such blocks (c3-scale batches); option igemm_thr128 = 1 sends
     every 128-multiple layer of the small fixtures through it.  The whole selection of tests re-runs under it in a child."""

@@ -125,3 +125,47 @@ def test_schedule_decisions_of_the_wrapper_need_no_gpu():
     assert m._defer_undecided() is True                       # (a shape still being measured is not captured into a graph)
     assert m._defer_mmd_join(torch.empty(16, 32), torch.empty(4, 32)) is True and rec["lags"] == [0.004, 0.9]
     assert m._defer_undecided() is False and m.__dict__["_defer_by_rows"][16] is rec
+
+
+# Which kernel form every MFMA convolution layer takes (forward, data gradient, weight gradient) at the benchmark
+# configurations under the default options.  Transcribed from the arrays the planners carried BEFORE the forms became one
+# enum per pass (fold / wino / wino4 flags, resolved by the priority of the launch code: F(4x4) over F(2x2) over composed /
+# dense / folded over direct), not from the code under test: a threshold edit that moves a configuration to another
+# form has to change this table knowingly.
+_D, _F, _W2, _W4 = "direct", "fold", "wino2", "wino4"
+_DIRECT3, _FOLD3 = (_D, _D, _D), (_F, _F, _F)
+_ENC_ALL_DIRECT = [None, _DIRECT3, _DIRECT3, _DIRECT3]
+_DEC_SMALL = [("d22",) * 3, _FOLD3, _FOLD3, None]
+_DEC_SMALL_LC0 = [("lc0",) * 3, _FOLD3, _FOLD3, None]
+_PLANS = {  # (config, bf16-input mode): encoder in training mode, encoder in evaluation mode, decoder, the decoder's lc0
+    ("c1", 0): (_ENC_ALL_DIRECT, _ENC_ALL_DIRECT, _DEC_SMALL, False),
+    ("c1", 1): (_ENC_ALL_DIRECT, _ENC_ALL_DIRECT, _DEC_SMALL, False),
+    ("c2", 0): (_ENC_ALL_DIRECT, [None, (_W2, _D, _D), _DIRECT3, _DIRECT3], _DEC_SMALL, False),
+    ("c2", 1): (_ENC_ALL_DIRECT, _ENC_ALL_DIRECT, _DEC_SMALL, False),
+    ("c3", 0): ([None, (_W2, _W4, _W2), (_W2, _W4, _W2), (_W4, _W4, _W4)],
+                [None, (_W2, _D, _D), (_W2, _D, _D), (_W4, _D, _D)],
+                [("lc0",) * 3, (_W2, _W2, _W2), (_W4, _W2, _W2), None], True),
+    ("c3", 1): ([None, (_D, _D, _W2), (_D, _D, _W2), (_D, _D, _W4)], _ENC_ALL_DIRECT,
+                [("lc0",) * 3, (_F, _F, _W2), (_F, _F, _W2), None], True),
+    ("c5", 0): (_ENC_ALL_DIRECT, [None, (_W2, _D, _D), _DIRECT3, (_W2, _D, _D)], _DEC_SMALL_LC0, True),
+    ("c5", 1): (_ENC_ALL_DIRECT, _ENC_ALL_DIRECT, _DEC_SMALL_LC0, True),
+}
+_SHAPES = {"c1": (64, 8, 64), "c2": (256, 8, 128), "c3": (4096, 8, 512), "c5": (256, 8, 1024)}  # batch, replicas, n_latents
+
+
+@pytest.mark.parametrize("config,bf16", sorted(_PLANS))
+def test_benchmark_configurations_take_the_pinned_kernel_forms(config, bf16):
+    from image_generation_amd import _lib, dev
+    L = _lib.lib()
+    B, R, n = _SHAPES[config]
+    enc_train, enc_eval, dec, lc0 = _PLANS[(config, bf16)]
+    _lib.check(L.dvg_reset_options(), "dvg_reset_options")
+    before = L.dvg_get_conv_precision()
+    assert L.dvg_set_conv_precision(bf16) == 0
+    try:
+        assert dev.plan_forms("encoder", B, n, training=True) == (enc_train, dict(d22=False, lc0=False, tail=False))
+        assert dev.plan_forms("encoder", B, n, training=False) == (enc_eval, dict(d22=False, lc0=False, tail=False))
+        for training in (True, False):  # (the decoder's plan does not depend on the mode)
+            assert dev.plan_forms("decoder", B * R, n, training=training) == (dec, dict(d22=True, lc0=lc0, tail=True))
+    finally:
+        assert L.dvg_set_conv_precision(before) == 0
