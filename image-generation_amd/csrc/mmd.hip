@@ -43,6 +43,8 @@ struct MmdArgs {
   const uint16_t* zt;   // bf16 transposed copy [32-row block][d][32] of (x ; y), each padded to whole 128-row tiles
   int64_t ztb_y;        // first 32-row block of y inside zt
   const uint4* tab;     // [2][d + 1] pair table for +-1 rows (see mmd_table_kernel)
+  const uint8_t* zi4 = nullptr;  // [nx + ny][d / 2] FP4 (e2m1) copy of (x ; y), feature 2 i in the low nibble of byte i, +1 = 0x2, -1 = 0xA;
+                                 // null unless the plan runs a Gram on the FP4 matrix pipe (MmdPlan::fp4), valid when *not_pm1 == 0
 };
 
 constexpr int MMD_BI = 32;    // rows (i) per block
@@ -402,13 +404,27 @@ __device__ __forceinline__ void mmd_distsum_generic(const MmdArgs& a, unsigned c
 // on the source address, rows past the end read zeros and are masked), one barrier per chunk.  A pair's distance is
 // symmetric and zero on the diagonal: chunks inside the row block's own range count once (the square holds both
 // orders), chunks to its right twice.
-template <int NST>
+// FP4 (d = 256, 512; option mmd_gram_fp4): the same kernel on the packed FP4 copy of the rows (MmdArgs::zi4) and the scaled
+// FP4 MFMA, 32x32x64 in the cycles of the int8 32x32x32: +-1 and +-2 are e2m1 values, the E8M0 scale 127 is 1.0 and the
+// float32 accumulator holds the integer sums exactly, so the Gram is the same integers at half the row pitch (the L2 -> LDS
+// bytes the kernel is bound by), half the k-steps and half the resident registers.  Lane (c, hh) takes the 16 bytes
+// [row c][32 s + 16 hh] of k-step s on both sides.
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ f32x16 mfma_fp4(const i32x4& za, const i32x4& zb, const f32x16& c) {
+  const i32x8 a8 = {za[0], za[1], za[2], za[3], 0, 0, 0, 0}, b8 = {zb[0], zb[1], zb[2], zb[3], 0, 0, 0, 0};  // (FP4: the low four registers are read)
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 127, 0, 127);
+}
+
+template <int NST, bool FP4 = false>
 __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned char* dsm) {
-  constexpr int D = 32 * NST, CH = 32 * D, NPW = NST / 4;  // chunk bytes; 1 KiB DMA pieces per wave and chunk
+  static_assert(!FP4 || NST % 8 == 0, "FP4 rows: a wave's DMA piece is 1 KiB of a [32][d / 2] chunk");
+  // D features; P bytes per row, NK k-steps per Gram tile; chunk bytes; 1 KiB DMA pieces per wave and chunk
+  constexpr int D = 32 * NST, P = FP4 ? D / 2 : D, NK = FP4 ? NST / 2 : NST, CH = 32 * P, NPW = CH / 4096;
+  using acc_t = std::conditional_t<FP4, f32x16, i32x16>;
   typedef __attribute__((address_space(3))) void lds_void;
   double* red = reinterpret_cast<double*>(dsm);                  // [256]
   float* Dtab = reinterpret_cast<float*>(dsm + 2048);            // [D + 1]
-  unsigned char* zbuf = dsm + 2048 + ((D + 1) * 4 + 1023) / 1024 * 1024;  // [2][32][D]
+  unsigned char* zbuf = dsm + 2048 + ((D + 1) * 4 + 1023) / 1024 * 1024;  // [2][32][P]
   for (int h = threadIdx.x; h <= D; h += 256) {
     const float d2 = (float)(4 * h);  // |a|^2 + |b|^2 - 2ab with |.|^2 = d: exact
     Dtab[h] = a.squared ? d2 : sqrtf(d2);
@@ -430,16 +446,17 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
   }
   const int lane = threadIdx.x & 63, hh = lane >> 5, c = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t*>(a.zi8), 0, N * D, 0x00020000);
+  const unsigned char* zrows = FP4 ? reinterpret_cast<const unsigned char*>(a.zi4) : reinterpret_cast<const unsigned char*>(a.zi8);
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(zrows), 0, N * P, 0x00020000);
   // DMA pieces: piece q of this wave covers bytes 1024 (NPW wave + q) + 16 lane of the chunk image: row r, physical slot
   // sl; it fetches logical slot sl ^ f(r)  (a pre-swizzled copy that makes the pieces contiguous measured no faster)
   int poff[NPW];
 #pragma unroll
   for (int q = 0; q < NPW; ++q) {
     const int byte = (wave * NPW + q) * 1024 + lane * 16;
-    const int r = byte / D, sl = (byte % D) >> 4;
-    const int f = (D % 256 == 0) ? (r & 15) : ((r >> 1) & 7);
-    poff[q] = r * D + ((sl ^ f) << 4);
+    const int r = byte / P, sl = (byte % P) >> 4;
+    const int f = (P % 256 == 0) ? (r & 15) : ((r >> 1) & 7);
+    poff[q] = r * P + ((sl ^ f) << 4);
   }
   auto issue = [&](int t, int buf) {
     unsigned char* dst = zbuf + buf * CH + wave * NPW * 1024;
@@ -447,7 +464,7 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
     for (int q = 0; q < NPW; ++q)  // (rows past N: offset past num_records: zeros)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(dst + q * 1024), 16, poff[q], t * CH, 0, 0);
   };
-  const int fc = (D % 256 == 0) ? (c & 15) : ((c >> 1) & 7);
+  const int fc = (P % 256 == 0) ? (c & 15) : ((c >> 1) & 7);
   // LDS byte address of Dtab[h] for Gram value S: tb2 - 2 S  (h = (D - S) / 2).  The lookups address LDS absolutely
   // (accumulator value + immediate offset, no VALU in between): the kernel's dynamic LDS block must start at address 0.
   constexpr int tb2 = 2048 + 2 * D;
@@ -458,7 +475,7 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
   uint32_t zaddr[8];  // absolute LDS addresses of this lane's operand slots in stage 0 (see zread below)
 #pragma unroll
   for (int j = 0; j < 8; ++j)
-    zaddr[j] = (uint32_t)(2048 + ((D + 1) * 4 + 1023) / 1024 * 1024) + (uint32_t)(c * D + ((((hh ^ fc) ^ (2 * j)) & 15) << 4));
+    zaddr[j] = (uint32_t)(2048 + ((D + 1) * 4 + 1023) / 1024 * 1024) + (uint32_t)(c * P + ((((hh ^ fc) ^ (2 * j)) & 15) << 4));
   double total = 0.0;
   __syncthreads();
   // The walk of stream `by`: row blocks in the order 0, T-1, 1, T-2, ... (long and short alternate), row block g holding
@@ -479,32 +496,34 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
     const int k0 = lo > base ? lo - base : 0, k1 = hi - base < len ? hi - base : len;
     base += len;
     if (k1 <= k0) continue;  // (block-uniform)
-    i32x4 xb[2][NST];
+    i32x4 xb[2][NK];
     bool vi[2];
 #pragma unroll
     for (int rs = 0; rs < 2; ++rs) {
       const int gi = g * 256 + wave * 64 + rs * 32 + c;
       vi[rs] = gi < N;
-      const int8_t* xrow = a.zi8 + (int64_t)(vi[rs] ? gi : N - 1) * D + hh * 16;
+      const unsigned char* xrow = zrows + (int64_t)(vi[rs] ? gi : N - 1) * P + hh * 16;
 #pragma unroll
-      for (int s = 0; s < NST; ++s) {
-        // B operand = -2 x (bytes +1 / -1 -> 0xFE / 0x02): the Gram accumulator then holds -2 S, which IS the byte offset
-        // of the pair's distance in the table (tb2 - 2 S) -- no address arithmetic between the MFMA and the lookup
+      for (int s = 0; s < NK; ++s) {
+        // B operand = -2 x (bytes +1 / -1 -> 0xFE / 0x02; FP4 nibbles 0x2 / 0xA -> 0xC / 0x4): the Gram accumulator then
+        // holds -2 S, which IS the byte offset of the pair's distance in the table (tb2 - 2 S) -- no address arithmetic
+        // between the MFMA and the lookup (FP4: one float -> int conversion, the value is an exact integer)
         const i32x4 w = *reinterpret_cast<const i32x4*>(xrow + s * 32);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) xb[rs][s][u] = (int)((((uint32_t)w[u] << 1) & 0xFEFEFEFEu) ^ 0xFCFCFCFCu);
+        for (int u = 0; u < 4; ++u)
+          xb[rs][s][u] = FP4 ? (int)((uint32_t)w[u] ^ 0xEEEEEEEEu) : (int)((((uint32_t)w[u] << 1) & 0xFEFEFEFEu) ^ 0xFCFCFCFCu);
       }
     }
     const int t0 = g * 8 + by + S * k0, t_end = g * 8 + by + S * k1, t_own_end = g * 8 + 8;
     float part[2] = {0.f, 0.f};  // this segment's sums of the two row sets, flushed to double below
     double segsum[2] = {0.0, 0.0};
     // distances of one chunk's two Gram tiles (`masked`: the last chunk of the array may hold rows past the end)
-    auto lookups = [&](const i32x16& g0, const i32x16& g1, int t, bool masked) {
+    auto lookups = [&](const acc_t& g0, const acc_t& g1, int t, bool masked) {
       float p0 = 0.f, p1 = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float d0 = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)(g0[r] + tb2));
-        const float d1 = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)(g1[r] + tb2));
+        const float d0 = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)((int)g0[r] + tb2));
+        const float d1 = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)((int)g1[r] + tb2));
         const bool vj = !masked || t * 32 + crow(r, hh) < N;
         p0 += vj ? d0 : 0.f;
         p1 += vj ? d1 : 0.f;
@@ -522,8 +541,10 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
     // returns in order: they have landed once this step's operand has).  A chunk that is looked up here is never the
     // array's last one (that one ends its row block's run of chunks), so there are no masks; the first chunk of a run
     // looks up a zero tile with weight 0.  The two tile pairs swap roles from chunk to chunk (no register copies).
+    // (FP4: a step is the same two 32-cycle MFMAs, so the lead in steps stays that of the int8 form of the same d)
     constexpr int PF = NST >= 16 ? 4 : (NST >= 8 ? 2 : 1);
-    auto chunk = [&](int t, auto bufc, const i32x16 (&prev)[2], i32x16 (&cur)[2]) {
+    static_assert(PF < NK, "operand prefetch distance");
+    auto chunk = [&](int t, auto bufc, const acc_t (&prev)[2], acc_t (&cur)[2]) {
       constexpr int buf = decltype(bufc)::value;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -533,23 +554,28 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
       auto zread = [&](int st) -> i32x4 {
         return *reinterpret_cast<lds_ci32x4*>((uintptr_t)(zaddr[st & 7] + (uint32_t)(buf * CH + (st >> 3) * 256)));
       };
-      auto rb = [](int st) { return (16 * st) / NST; };
-      i32x4 zr[NST];
+      auto rb = [](int st) { return (16 * st) / NK; };
+      i32x4 zr[NK];
       float lk0[16], lk1[16], p0 = 0.f, p1 = 0.f;
 #pragma unroll
       for (int s = 0; s < PF; ++s) zr[s] = zread(s);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int s = 0; s < NST; ++s) {
+      for (int s = 0; s < NK; ++s) {
 #pragma unroll
         for (int r = rb(s); r < rb(s + 1); ++r) {
-          lk0[r] = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)(prev[0][r] + tb2));
-          lk1[r] = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)(prev[1][r] + tb2));
+          lk0[r] = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)((int)prev[0][r] + tb2));
+          lk1[r] = *reinterpret_cast<lds_cfloat*>((uintptr_t)(uint32_t)((int)prev[1][r] + tb2));
         }
-        if (s + PF < NST) zr[s + PF] = zread(s + PF);
+        if (s + PF < NK) zr[s + PF] = zread(s + PF);
         __builtin_amdgcn_sched_barrier(0);
-        cur[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(zr[s], xb[0][s], s == 0 ? (i32x16){0} : cur[0], 0, 0, 0);
-        cur[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(zr[s], xb[1][s], s == 0 ? (i32x16){0} : cur[1], 0, 0, 0);
+        if constexpr (FP4) {
+          cur[0] = mfma_fp4(zr[s], xb[0][s], s == 0 ? (f32x16){0} : cur[0]);
+          cur[1] = mfma_fp4(zr[s], xb[1][s], s == 0 ? (f32x16){0} : cur[1]);
+        } else {
+          cur[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(zr[s], xb[0][s], s == 0 ? (i32x16){0} : cur[0], 0, 0, 0);
+          cur[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(zr[s], xb[1][s], s == 0 ? (i32x16){0} : cur[1], 0, 0, 0);
+        }
         if (s >= PF) {
 #pragma unroll
           for (int r = rb(s - PF); r < rb(s - PF + 1); ++r) { p0 += lk0[r]; p1 += lk1[r]; }
@@ -557,7 +583,7 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
-      for (int r = rb(NST - PF); r < 16; ++r) { p0 += lk0[r]; p1 += lk1[r]; }
+      for (int r = rb(NK - PF); r < 16; ++r) { p0 += lk0[r]; p1 += lk1[r]; }
       const float wgt = tp < 0 ? 0.0f : (tp < t_own_end ? 1.0f : 2.0f);
       part[0] = fmaf(p0, wgt, part[0]);
       part[1] = fmaf(p1, wgt, part[1]);
@@ -568,8 +594,8 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
         since_flush = 0;
       }
     };
-    i32x16 accp[2], accq[2];  // Gram tiles of the previous / the current chunk: their lookups run under the next MFMAs
-    accp[0] = (i32x16){0}; accp[1] = (i32x16){0};
+    acc_t accp[2], accq[2];  // Gram tiles of the previous / the current chunk: their lookups run under the next MFMAs
+    accp[0] = (acc_t){0}; accp[1] = (acc_t){0};
     bool last_in_q = false;
     for (int t = t0; t < t_end; t += 2 * S) {
       chunk(t, std::integral_constant<int, 0>{}, accp, accq);
@@ -588,10 +614,10 @@ __device__ __forceinline__ void mmd_distsum_spin256(const MmdArgs& a, unsigned c
   if (threadIdx.x == 0) a.dist_part[(size_t)by * gridDim.x + bx] = sum;
 }
 
-template <int NST>
+template <int NST, bool FP4 = false>
 __global__ __launch_bounds__(256, 2) void mmd_distsum_spin256_kernel(MmdArgs a) {
   extern __shared__ __align__(16) unsigned char dsm[];
-  if (*a.not_pm1 == 0) mmd_distsum_spin256<NST>(a, dsm);
+  if (*a.not_pm1 == 0) mmd_distsum_spin256<NST, FP4>(a, dsm);
   else mmd_distsum_generic(a, dsm, false);
 }
 
@@ -831,7 +857,7 @@ __global__ __launch_bounds__(256) void mmd_bandwidth_table_kernel(MmdArgs a, con
 // flag says +-1.)
 __global__ __launch_bounds__(256) void mmd_prep_fused_kernel(MmdArgs a, float* __restrict__ sq, int8_t* __restrict__ zi8,
                                                              int* __restrict__ not_pm1, uint16_t* __restrict__ zt,
-                                                             int zero_loss_parts) {
+                                                             int zero_loss_parts, uint8_t* __restrict__ zi4) {
   extern __shared__ __align__(16) unsigned char prep_smem[];  // int8 signs [32][d + 16]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, d = a.d, pitch = d + 16;
   for (int64_t e = (int64_t)blockIdx.x * 256 + tid; e < 3 * (int64_t)zero_loss_parts; e += (int64_t)gridDim.x * 256)
@@ -861,6 +887,9 @@ __global__ __launch_bounds__(256) void mmd_prep_fused_kernel(MmdArgs a, float* _
                          (w.w > 0.f ? 0x01000000u : 0xff000000u);
       *reinterpret_cast<uint32_t*>(prep_smem + (wave + 4 * u) * pitch + 4 * k) = z;
       if (row < cnt) reinterpret_cast<uint32_t*>(zi8 + (goff + row) * d)[k] = z;
+      if (zi4 && row < cnt)  // the int8 sign bits 7, 15, 23, 31 -> bit 3 of nibbles 0 .. 3 over the magnitude pattern of 1.0
+        reinterpret_cast<uint16_t*>(zi4 + (goff + row) * (d >> 1))[k] =
+            (uint16_t)(0x2222u | ((z >> 4) & 0x8u) | ((z >> 8) & 0x80u) | ((z >> 12) & 0x800u) | ((z >> 16) & 0x8000u));
     }
   }
   if (__any(bad) && lane == 0) atomicOr(not_pm1, 1);
@@ -1294,15 +1323,20 @@ __device__ __forceinline__ void mmd_pm1_fq_body(const MmdArgs& a, unsigned char*
 // independent work while the lookups' LDS latencies elapse.
 // ONE: only the pair table of the block's own column kind is resident (x columns or y columns: the plan guarantees that no
 // block's chunk range spans both) -- the 8 KB that lets d = 1024 run with 256-feature slices of G^T (NFT = 8)
-template <int NST, int NFT, bool ONE = false>  // d = 32 NST features; a block accumulates 32 NFT of them (grid z covers the rest)
+// FP4 (NST == NFT, d = 256 / 512; option mmd_gram_fp4): the Gram on the scaled FP4 MFMA (32x32x64 in the cycles of the int8
+// 32x32x32) from the packed e2m1 copy of the rows -- the same integers from half the k-steps (one Gram instruction on every
+// second feature tile), half the ring bytes and DMA pieces and half the resident-row registers.  The resident rows are held
+// as -2x (nibble ^ 0xE), both E8M0 scales are 127 (1.0): the float32 accumulator is -2 S, half the table's byte offset.
+template <int NST, int NFT, bool ONE = false, bool FP4 = false>  // d = 32 NST features; a block accumulates 32 NFT of them (grid z covers the rest)
 struct W128 {
   static constexpr int D = 32 * NST;
+  static constexpr int P = FP4 ? D / 2 : D;      // bytes per row of the Gram operand copy
   static constexpr int TABN = D + 3;  // entries per table: h = 0 .. D, the all-zero entry D+1, the diagonal entry D+2
   // 8-byte entries {kernel sum (f32), weight as two bf16 terms hi | lo}: one ds_read_b64 per pair (round 3: 16 bytes with
   // the float32 weight beside its two terms; the row sums now add the two terms themselves, which is also what G^T holds)
   static constexpr int TAB_BYTES = ((ONE ? 1 : 2) * TABN * 8 + 1023) / 1024 * 1024;
   static constexpr int RED_BYTES = 2048;
-  static constexpr int Z8_BYTES = 32 * D;        // one chunk of int8 rows [32][D]
+  static constexpr int Z8_BYTES = 32 * P;        // one chunk of int8 (FP4) rows [32][P]
   static constexpr int ZT_BYTES = 64 * 32 * NFT; // one chunk of this block's slice of the transposed bf16 copy [32 NFT][32]
   static constexpr int NSTG = 3;                 // ring depth of both images (see the loop)
   static constexpr int OFF_RED = TAB_BYTES, OFF_Z8 = OFF_RED + RED_BYTES, OFF_ZT = OFF_Z8 + NSTG * Z8_BYTES;
@@ -1315,10 +1349,11 @@ __device__ __forceinline__ void dma16(const void* gsrc, unsigned char* lds_wave_
                                    (void __attribute__((address_space(3)))*)lds_wave_base, 16, 0, 0);
 }
 
-template <int NST, int NFT, bool ONE = false>
+template <int NST, int NFT, bool ONE = false, bool FP4 = false>
 __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned char* smem) {
-  using L = W128<NST, NFT, ONE>;
-  constexpr int D = L::D;
+  using L = W128<NST, NFT, ONE, FP4>;
+  static_assert(!FP4 || (NST == NFT && NST % 8 == 0), "FP4 Gram: one k-step per two feature tiles, 1 KiB DMA pieces");
+  constexpr int D = L::D, P = L::P, NK = FP4 ? NST / 2 : NST;  // row pitch and k-steps of the Gram operands
   typedef __attribute__((address_space(3))) void lds_void;
   typedef __attribute__((address_space(3))) unsigned char lds_byte;
   typedef int i32x2 __attribute__((ext_vector_type(2)));
@@ -1393,12 +1428,19 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
     const uint32_t lo = rn_bf16(w - __uint_as_float(hi));
     reinterpret_cast<uint2*>(smem)[e] = make_uint2(v.x, hi | (lo >> 16));
   }
-  i32x4 xb[NST];
+  const unsigned char* zrows = FP4 ? reinterpret_cast<const unsigned char*>(a.zi4) : reinterpret_cast<const unsigned char*>(a.zi8);
+  i32x4 xb[NK];
   {
-    const int8_t* xrow = a.zi8 + (goff_i + (vi ? gi : cnt_i - 1)) * D + hh * 16;
+    const unsigned char* xrow = zrows + (goff_i + (vi ? gi : cnt_i - 1)) * P + hh * 16;
 #pragma unroll
-    for (int s = 0; s < NST; ++s) xb[s] = *reinterpret_cast<const i32x4*>(xrow + s * 32);
+    for (int s = 0; s < NK; ++s) {
+      xb[s] = *reinterpret_cast<const i32x4*>(xrow + s * 32);
+      if constexpr (FP4) xb[s] ^= (i32x4){(int)0xEEEEEEEE, (int)0xEEEEEEEE, (int)0xEEEEEEEE, (int)0xEEEEEEEE};  // -2x
+    }
   }
+  // E8M0 scales of the FP4 Gram (1.0 on both sides), written once here: the inline-asm MFMAs of the tile loop read them
+  int sc_a = 127, sc_b = 127;
+  asm volatile("" : "+v"(sc_a), "+v"(sc_b));
 
   // ---- LDS-DMA of one chunk's images.  Destination = wave-uniform base + 16 lane (1 KiB per instruction); the source
   // address carries the swizzle: 16-byte slot `sl` of row `r` is stored at slot sl ^ f(r).
@@ -1410,20 +1452,20 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
   // its 64-bit per-lane pointer, its row clamp and the readfirstlane of its destination).  Rows past the end of x read
   // the first rows of y, rows past the end of y are out of the buffer's range and arrive as zeros: either way those
   // pairs are masked in the lookups.
-  constexpr int NZ8 = NST / 4, NZT = NFT / 2;
+  constexpr int NZ8 = L::Z8_BYTES / 4096, NZT = NFT / 2;
   int z8off[NZ8], ztoff0;  // (transposed copy: piece q of a wave = piece 0 + q KiB, the swizzle class does not change)
 #pragma unroll
   for (int q = 0; q < NZ8; ++q) {
-    const int byte = (wave * NZ8 + q) * 1024 + lane * 16;  // position in the [32][D] image
-    const int r = byte / D, sl = (byte % D) >> 4;
-    const int fz = (D % 256 == 0) ? (r & 15) : ((r >> 1) & 7);
-    z8off[q] = r * D + ((sl ^ fz) << 4);
+    const int byte = (wave * NZ8 + q) * 1024 + lane * 16;  // position in the [32][P] image
+    const int r = byte / P, sl = (byte % P) >> 4;
+    const int fz = (P % 256 == 0) ? (r & 15) : ((r >> 1) & 7);
+    z8off[q] = r * P + ((sl ^ fz) << 4);
   }
   {
     const int f = wave * NZT * 16 + (lane >> 2), sl = lane & 3;  // 1 KiB piece = 16 feature rows of 64 bytes
     ztoff0 = f * 64 + ((sl ^ ((f >> 2) & 3)) << 4);
   }
-  const __amdgpu_buffer_rsrc_t rsrc8 = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t*>(a.zi8), 0, (int)((a.nx + a.ny) * D), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc8 = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(zrows), 0, (int)((a.nx + a.ny) * P), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrct = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<uint16_t*>(a.zt), 0, (int)((a.ztb_y + (a.ny + 127) / 128 * 4) * (int64_t)D * 64), 0x00020000);
   const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(lds_byte*)smem);
@@ -1432,7 +1474,7 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
   auto z8_soff = [&](int t) -> int {
     t = t < tl_i ? t : tl_i;
     const bool cx = t < ncx_i;
-    return ((cx ? 0 : nx_i) + (cx ? t : t - ncx_i) * 32) * D;
+    return ((cx ? 0 : nx_i) + (cx ? t : t - ncx_i) * 32) * P;
   };
   auto zt_soff = [&](int t) -> int {
     t = t < tl_i ? t : tl_i;
@@ -1455,27 +1497,39 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
   };
 
   // per-lane LDS read offsets (constant over the kernel)
-  const int fz_c = (D % 256 == 0) ? (c & 15) : ((c >> 1) & 7);
+  const int fz_c = (P % 256 == 0) ? (c & 15) : ((c >> 1) & 7);
   const int sw_c = (c >> 2) & 3;
   const int aoff0 = c * 64 + ((hh ^ sw_c) << 4), aoff1 = c * 64 + (((2 + hh) ^ sw_c) << 4);
   // Byte offset of k-step s inside this lane's LDS row: ((2 s + hh) ^ fz_c) << 4.  The swizzle touches the low ZSW slots
   // only, so steps s and s + ZSW / 2 differ by a CONSTANT ZSW * 16 bytes: ZSW / 2 per-lane registers + immediates
   // instead of one register per k-step.
-  constexpr int ZSW = (D % 256 == 0) ? 16 : 8;
-  constexpr int NZB = ZSW / 2 < NST ? ZSW / 2 : NST;
+  constexpr int ZSW = (P % 256 == 0) ? 16 : 8;
+  constexpr int NZB = ZSW / 2 < NK ? ZSW / 2 : NK;
   int zlow[NZB];
 #pragma unroll
-  for (int m = 0; m < NZB; ++m) zlow[m] = c * D + (((2 * m + hh) ^ fz_c) << 4);
+  for (int m = 0; m < NZB; ++m) zlow[m] = c * P + (((2 * m + hh) ^ fz_c) << 4);
 
+  // The Gram tile is kept as 16 32-bit registers either way: the integer S (int8), or the bits of the float -2 S (FP4)
   auto gram = [&](int stg) -> i32x16 {
     const unsigned char* z = z8buf + stg * L::Z8_BYTES;
-    i32x16 acc = {0};
+    if constexpr (FP4) {
+      f32x16 acc = {0};
 #pragma unroll
-    for (int s = 0; s < NST; ++s) {
-      const i32x4 za = *reinterpret_cast<const i32x4*>(z + zlow[s % NZB] + (s / NZB) * (ZSW * 16));
-      acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(za, xb[s], acc, 0, 0, 0);
+      for (int s = 0; s < NK; ++s) {
+        const i32x4 za = *reinterpret_cast<const i32x4*>(z + zlow[s % NZB] + (s / NZB) * (ZSW * 16));
+        const i32x8 a8 = {za[0], za[1], za[2], za[3], 0, 0, 0, 0}, b8 = {xb[s][0], xb[s][1], xb[s][2], xb[s][3], 0, 0, 0, 0};
+        acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 4, 4, 0, 127, 0, 127);
+      }
+      return __builtin_bit_cast(i32x16, acc);
+    } else {
+      i32x16 acc = {0};
+#pragma unroll
+      for (int s = 0; s < NK; ++s) {
+        const i32x4 za = *reinterpret_cast<const i32x4*>(z + zlow[s % NZB] + (s / NZB) * (ZSW * 16));
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(za, xb[s], acc, 0, 0, 0);
+      }
+      return acc;
     }
-    return acc;
   };
 
   f32x16 G[NFT];
@@ -1514,9 +1568,9 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int jl = crow(r, hho);
-      int v = S[r];
-      v = jl == dloc ? -(D + 4) : v;
-      v = jl < m.nj ? v : -(D + 2);
+      int v = S[r];  // (FP4: the bits of -2 S)
+      v = jl == dloc ? (FP4 ? __float_as_int((float)(2 * (D + 4))) : -(D + 4)) : v;
+      v = jl < m.nj ? v : (FP4 ? __float_as_int((float)(2 * (D + 2))) : -(D + 2));
       S[r] = v;
     }
   };
@@ -1530,7 +1584,7 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
   uint32_t hm_prev = 0;
   constexpr int NTERM = 2;  // bf16 terms of a weight
   auto look_issue = [&](const i32x16& S, int r, const unsigned char* tb) -> i32x2 {
-    return *reinterpret_cast<const i32x2*>(tb + __mul24(S[r], -4));
+    return *reinterpret_cast<const i32x2*>(tb + (FP4 ? 2 * (int)__int_as_float(S[r]) : __mul24(S[r], -4)));
   };
   // (the empty asm statements pin each row's arithmetic to the tile it is written in: its results are only needed by the
   // NEXT iteration, and left alone the compiler sinks all of it into one VALU-only stretch during which the matrix pipe
@@ -1626,6 +1680,9 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
     auto rb = [](int ft) { return ft >= NFT - 1 ? 16 : (16 * ft + NFT - 2) / (NFT - 1); };
     constexpr int RMAX = (16 + NFT - 2) / (NFT - 1);
     constexpr int GPT = NST / NFT;  // Gram k-steps (MFMAs) beside each feature tile
+    // (FP4: a k-step covers two feature tiles' worth of features; the even tiles carry one, the odd tiles none)
+    auto gram_tile = [](int ft) { return !FP4 || (ft & 1) == 0; };
+    auto gram_step = [](int ft) { return FP4 ? ft / 2 : ft * GPT; };
     // what an iteration needs from the one before it (block-uniform unless said otherwise)
     struct Carry {
       int z8so, ztso;          // scalar source offsets of this iteration's DMA (int8 rows of chunk t+4, transposed copy of t+2)
@@ -1700,7 +1757,8 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
         // out (the compiler waits with lgkmcnt(0) at the first use; placed behind fresh requests that wait would sit
         // out their whole latency every tile).  The empty asm is that first use.
 #pragma unroll
-        for (int u = 0; u < GPT; ++u) asm volatile("" ::"v"(zc[u]));
+        for (int u = 0; u < GPT; ++u)
+          if (gram_tile(ft)) asm volatile("" ::"v"(zc[u]));
         asm volatile("" ::"v"(ac[0]), "v"(ac[1]));
         if (ft > 0) {
 #pragma unroll
@@ -1718,6 +1776,13 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
           if constexpr (GPT > 1) {
             if (ft == 0 && u == 0) Snext = (i32x16){0};
             Snext = __builtin_amdgcn_mfma_i32_32x32x32_i8(zc[u], xb[ft * GPT + u], Snext, 0, 0, 0);
+          } else if constexpr (FP4) {  // (one k-step of 64 features on every second tile)
+            if (ft == 0)
+              asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, 0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:4"
+                           : "=&v"(Snext) : "v"(zc[u]), "v"(xb[ft / 2]), "v"(sc_a), "v"(sc_b));
+            else if (gram_tile(ft))
+              asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 op_sel_hi:[0,0,0] cbsz:4 blgp:4"
+                           : "+v"(Snext) : "v"(zc[u]), "v"(xb[ft / 2]), "v"(sc_a), "v"(sc_b));
           } else
           if (ft == 0 && u == 0)
             asm volatile("v_mfma_i32_32x32x32_i8 %0, %1, %2, 0" : "=&v"(Snext) : "v"(zc[u]), "v"(xb[ft * GPT + u]));
@@ -1729,7 +1794,8 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
           an[0] = *reinterpret_cast<const i32x4*>(ad.a0 + (ft + 1) * 2048);
           an[1] = *reinterpret_cast<const i32x4*>(ad.a1 + (ft + 1) * 2048);
 #pragma unroll
-          for (int u = 0; u < GPT; ++u) zn[u] = zread(ad, (ft + 1) * GPT + u);
+          for (int u = 0; u < GPT; ++u)
+            if (gram_tile(ft + 1)) zn[u] = zread(ad, gram_step(ft + 1) + u);
         } else {
           // the NEXT iteration's first tile, filled by iteration k-1's DMA.  GPT > 1: wait for this wave's pieces of it
           // (only this iteration's NZ8 + NZT newer ones may stay in flight) and publish everyone's with the barrier -- the
@@ -1792,7 +1858,8 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
         for (int u = 0; u < RMAX; ++u) ent[u] = enew[u];
         ac[0] = an[0]; ac[1] = an[1];
 #pragma unroll
-        for (int u = 0; u < GPT; ++u) zc[u] = zn[u];
+        for (int u = 0; u < GPT; ++u)
+          if (gram_tile(ft + 1 < NFT ? ft + 1 : 0)) zc[u] = zn[u];
         // wanted order inside the tile: two of the next tile's reads and the DMA pieces, an MFMA, a read and a few vector
         // instructions of the lookups, an MFMA, ...
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
@@ -1878,11 +1945,11 @@ __device__ __forceinline__ void mmd_pm1_w128_body(const MmdArgs& a, unsigned cha
   }
 }
 
-template <int NST, int NFT, bool ONE = false>
+template <int NST, int NFT, bool ONE = false, bool FP4 = false>
 __global__ __launch_bounds__(256, 1) void mmd_pair_w128_kernel(MmdArgs a) {
   extern __shared__ __align__(16) unsigned char w128_smem[];
   if (*a.not_pm1 != 0) return;  // general rows: the f32 kernel launched behind this one serves them
-  mmd_pm1_w128_body<NST, NFT, ONE>(a, w128_smem);
+  mmd_pm1_w128_body<NST, NFT, ONE, FP4>(a, w128_smem);
 }
 
 template <int NFB>
@@ -1947,6 +2014,8 @@ __global__ __launch_bounds__(256) void mmd_final_kernel(const double* __restrict
 struct MmdPlan {
   int nfb, zslices, S, S1;
   bool d256;  // pass 1 by the 256-row-block spin kernel
+  bool fp4;   // that kernel and the 128-row-block pair kernel take their Gram on the FP4 matrix pipe, from the packed copy at off_zi4 (option mmd_gram_fp4)
+  size_t off_zi4;
   int64_t rbx, rby, GX1;
   size_t off_sq, off_coef, off_dist, off_loss, off_grad, off_flag, off_zi8, off_zt, off_tab, total;
   int pm1_ok;
@@ -2030,6 +2099,10 @@ static MmdPlan mmd_plan(int64_t nx, int64_t ny, int d) {
     const int64_t t256 = ceil_div(nx + ny, 256);
     p.d256 = p.pm1_ok && env != 0 && d % 128 == 0 && d <= 512 && (t256 >= 32 || env == 1) && (nx + ny) * (int64_t)d < 2147483647LL;
   }
+  // FP4 Gram: the packed row pitches with a 1 KiB DMA piece per wave (d / 2 = 128, 256 bytes).  The copy's place in the
+  // workspace depends on the shape alone: the option may be flipped between calls on one workspace.
+  const bool fp4_shape = p.pm1_ok && (d == 256 || d == 512);
+  p.fp4 = fp4_shape && (p.d256 || p.w128) && opt(OPT_MMD_GRAM_FP4) != 0;
   if (p.d256) {  // 256-row blocks
     p.GX1 = 64;  // 8 chunk streams (one per XCD) x 64 blocks of equal work: exactly two resident blocks per CU
     S1 = 8;
@@ -2066,6 +2139,7 @@ static MmdPlan mmd_plan(int64_t nx, int64_t ny, int d) {
   p.off_zi8 = o; o = align_up(o + (size_t)(nx + ny) * (size_t)d, 256);
   p.off_zt = o; o = align_up(o + (p.pm1_ok ? (size_t)(p.ztb_x + p.ztb_y) * (size_t)d * 32 * sizeof(uint16_t) : 0), 256);
   p.off_tab = o; o = align_up(o + (p.pm1_ok ? 2 * (size_t)(d + 1) * sizeof(uint4) : 0), 256);
+  p.off_zi4 = o; o = align_up(o + (fp4_shape ? (size_t)(nx + ny) * (size_t)(d / 2) : 0), 256);
   p.total = o;
   return p;
 }
@@ -2124,10 +2198,10 @@ static int launch_pair_fq(const MmdArgs& a, const MmdPlan& p, hipStream_t s) {
   return DVG_OK;
 }
 
-template <int NST, int NFT, bool ONE = false>
+template <int NST, int NFT, bool ONE = false, bool FP4 = false>
 static int launch_pair_w128(const MmdArgs& a, const MmdPlan& p, hipStream_t s) {
-  auto kern = mmd_pair_w128_kernel<NST, NFT, ONE>;
-  constexpr int lds = W128<NST, NFT, ONE>::LDS_BYTES;
+  auto kern = mmd_pair_w128_kernel<NST, NFT, ONE, FP4>;
+  constexpr int lds = W128<NST, NFT, ONE, FP4>::LDS_BYTES;
   if (lds > 64 * 1024)
     DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   DVG_LAUNCH_WORK(K_MMD_PM1, mmd_pm1_work(a, 2, NST / NFT), kern, dim3((unsigned)(p.rb128x + p.rb128y), (unsigned)p.S2, NST / NFT),
@@ -2206,6 +2280,7 @@ extern "C" int dvg_mmd_fwd_bwd(const float* x, int64_t nx, const float* y, int64
   a.zt = (const uint16_t*)(w + p.off_zt);
   a.ztb_y = p.ztb_x;
   a.tab = (const uint4*)(w + p.off_tab);
+  a.zi4 = p.fp4 ? (const uint8_t*)(w + p.off_zi4) : nullptr;
 
   // Two implementations of the pair kernels are enqueued back to back and gate themselves on a device flag the prep
   // kernel writes (are all entries exactly +-1?), so no host synchronisation is needed to choose between them.
@@ -2220,7 +2295,7 @@ extern "C" int dvg_mmd_fwd_bwd(const float* x, int64_t nx, const float* y, int64
   if (p.pm1_ok) {  // row norms, int8 copy, +-1 flag and the transposed bf16 copy in one pass over the rows
     DVG_LAUNCH(K_MMD_PREP, mmd_prep_fused_kernel, dim3((unsigned)(p.ztb_x + p.ztb_y)), dim3(256), (size_t)32 * (dim + 16), s, a,
                (float*)(w + p.off_sq), (int8_t*)(w + p.off_zi8), (int*)(w + p.off_flag), (uint16_t*)(w + p.off_zt),
-               p.w128 ? loss_parts : 0);
+               p.w128 ? loss_parts : 0, p.fp4 ? (uint8_t*)(w + p.off_zi4) : (uint8_t*)nullptr);
   } else {
     DVG_LAUNCH(K_MMD_PREP, mmd_prep_kernel, dim3((unsigned)ceil_div(nx + ny, 4)), dim3(256), 0, s, x, nx, y, ny, dim,
                (float*)(w + p.off_sq), (int8_t*)(w + p.off_zi8), (int*)(w + p.off_flag));
@@ -2247,7 +2322,8 @@ extern "C" int dvg_mmd_fwd_bwd(const float* x, int64_t nx, const float* y, int64
           DVG_LAUNCH(K_MMD_DISTSUM, kern, grid, dim3(256), lds_256, s, a);
           return DVG_OK;
         };
-        if (dim == 128) DVG_TRY(launch256(mmd_distsum_spin256_kernel<4>));
+        if (p.fp4) DVG_TRY(dim == 256 ? launch256(mmd_distsum_spin256_kernel<8, true>) : launch256(mmd_distsum_spin256_kernel<16, true>));
+        else if (dim == 128) DVG_TRY(launch256(mmd_distsum_spin256_kernel<4>));
         else if (dim == 256) DVG_TRY(launch256(mmd_distsum_spin256_kernel<8>));
         else if (dim == 384) DVG_TRY(launch256(mmd_distsum_spin256_kernel<12>));
         else DVG_TRY(launch256(mmd_distsum_spin256_kernel<16>));
@@ -2273,13 +2349,13 @@ extern "C" int dvg_mmd_fwd_bwd(const float* x, int64_t nx, const float* y, int64
     // once; it writes the same loss_part / grad_part slots when it does run).
     switch (dim / 128) {
       case 1: rc = launch_pair_w128<4, 4>(a, p, s); break;
-      case 2: rc = launch_pair_w128<8, 8>(a, p, s); break;
+      case 2: rc = p.fp4 ? launch_pair_w128<8, 8, false, true>(a, p, s) : launch_pair_w128<8, 8>(a, p, s); break;
       // One feature slice per block wherever the accumulators fit the 512-register file (d = 512: 256 of them hold G^T,
       // the compiler places the Gram tile and the operands in the other half without spills): the Gram and the lookups
       // are then computed once, 80 instead of 96 MFMAs per chunk: 2.70 -> 2.10 ms at c3 (the two-slice form is retired).
       case 3: rc = launch_pair_w128<12, 12>(a, p, s); break;
       case 8: rc = p.z128 == 4 ? launch_pair_w128<32, 8, true>(a, p, s) : launch_pair_w128<32, 4>(a, p, s); break;  // (four / eight feature slices: mmd_plan)
-      default: rc = launch_pair_w128<16, 16>(a, p, s); break;
+      default: rc = p.fp4 ? launch_pair_w128<16, 16, false, true>(a, p, s) : launch_pair_w128<16, 16>(a, p, s); break;
     }
     DVG_TRY(rc);
     MmdArgs g = a;

@@ -39,6 +39,7 @@ const OptDef kDefs[OPT_COUNT] = {
     {"dec_wino4_mask", 0x2, "which of the decoder's Winograd launches behind the upsample take the F(4x4,3x3) form with 25 of 36 positions (option enc_wino4 != 0): bit 0 / 1 the forward of the 128 -> 64 / 64 -> 32 layer (bit 0 off: with it the full-size decoder's reconstruction is 2.97e-6 from float64, the bar is 2e-6), bit 2 / 3 their data gradients", true},
     {"wgrad_reduce_tiled", 1, "weight-gradient slab sums of at most 8 slabs and at least 256 tiles by the tiled one-thread-per-element kernels (same bits; 0: the 8-lanes-per-element kernels everywhere)", true},
     {"enc_bn_reduce_pooled", 1, "encoder BatchNorm/pool backward: the (sum dz, sum dz zhat) pass reads the pooled activations the forward kept (2 floats per element) instead of the four pre-BatchNorm outputs of every window (5); 0: the window form", true},
+    {"mmd_gram_fp4", 1, "MMD: exact Gram of +-1 rows on the FP4 matrix pipe (scaled 32x32x64 MFMA on a packed e2m1 copy of the rows: the same integers at half the operand bytes and k-steps) in the 256-row distance-sum kernel and the 128-row-block pair kernel at d = 256, 512 (default); 0: the int8 form (A/B reference, same bits)", true},
 };
 std::atomic<int64_t> g_val[OPT_COUNT];
 std::once_flag g_once;
