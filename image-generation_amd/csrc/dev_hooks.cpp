@@ -1,5 +1,6 @@
 // Development hooks (include/dvg_dev.h): direct launches of the MFMA GEMM kernels for unit tests / micro-benchmarks.
 #include "conv_plan.h"
+#include "mmd_plan.h"
 #include "../../include/dvg_dev.h"
 using namespace dvg;
 
@@ -59,6 +60,17 @@ extern "C" int dvg_dev_plan_forms(int network, int64_t rows, int n_latents, int 
   out[12] = network == 1 && (f0 == CF_D22 || f0 == CF_LC0);
   out[13] = network == 1 && f0 == CF_LC0;
   out[14] = network == 1 && o.v[OPT_DEC_TAIL_FUSED] != 0;
+  return DVG_OK;
+}
+// The plan of an MMD call under the current options (mmd_plan.h); needs no device.
+extern "C" int dvg_dev_mmd_plan(int64_t nx, int64_t ny, int dim, int64_t out[24]) {
+  DVG_REQUIRE(out && nx >= 2 && ny >= 2 && dim >= 32 && dim % 32 == 0, "dev_mmd_plan: bad argument");
+  const MmdPlan p = mmd_plan(nx, ny, dim, mmd_options());
+  const int64_t v[24] = {p.pair, p.nfb, p.nfbw, p.nst, p.nft, p.one, p.dist, p.dist_ns, p.gram, p.splits, p.slices, p.gated_nfb,
+                         p.loss_parts, (int64_t)p.total, p.dist_splits, p.gram_passes, p.bf16_terms,
+                         p.pair_launch.grid[0], p.pair_launch.grid[1], p.pair_launch.grid[2], p.distsum.grid[0], p.distsum.grid[1],
+                         p.gated_nfb ? (int64_t)p.gated.grid[0] : 0, p.final_grad.grid[0]};
+  for (int i = 0; i < 24; ++i) out[i] = v[i];
   return DVG_OK;
 }
 extern "C" int dvg_dev_conv_wino_stats_blocks(int64_t M, int Cout) { return conv_wino_stats_blocks(M, Cout); }

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mmd_plan.h"
 
 namespace dvg {
 
@@ -44,12 +45,9 @@ struct MmdArgs {
   int64_t ztb_y;        // first 32-row block of y inside zt
   const uint4* tab;     // [2][d + 1] pair table for +-1 rows (see mmd_table_kernel)
   const uint8_t* zi4 = nullptr;  // [nx + ny][d / 2] FP4 (e2m1) copy of (x ; y), feature 2 i in the low nibble of byte i, +1 = 0x2, -1 = 0xA;
-                                 // null unless the plan runs a Gram on the FP4 matrix pipe (MmdPlan::fp4), valid when *not_pm1 == 0
+                                 // null unless the plan runs a Gram on the FP4 matrix pipe (MmdPlan::gram == MG_FP4), valid when *not_pm1 == 0
 };
 
-constexpr int MMD_BI = 32;    // rows (i) per block
-constexpr int MMD_BJ = 128;   // columns (j) per tile: 4 waves x 32
-constexpr int MMD_PITCH = 33;
 
 __device__ __forceinline__ int crow(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
@@ -108,8 +106,7 @@ __device__ __forceinline__ f32x16 gram_tile(const float* __restrict__ src_i, int
 
 // Exact Gram tile for +-1 inputs on the int8 MFMA (v_mfma_i32_32x32x32_i8: K = 32 per instruction, 32x the K-rate
 // of the f32 MFMA).  The A and B fragments are both "16 consecutive bytes of my row at the same k offset", so any
-// internal k ordering of the instruction cancels out of the dot product.  Whole 512-feature panels are staged at once.
-constexpr int MMD_I8_PANEL = 512;
+// internal k ordering of the instruction cancels out of the dot product.  Whole 512-feature panels (MMD_I8_PANEL) are staged at once.
 
 // Two-step staging of ROWS x (16 n16) bytes of int8 rows (n16 <= 32) so that a panel's global loads can be in flight
 // while the block computes: load() issues them all (8 threads cover one 128-byte row segment), store() writes LDS.
@@ -1312,10 +1309,11 @@ __device__ __forceinline__ void mmd_pm1_fq_body(const MmdArgs& a, unsigned char*
 // Against the 32-row forms above this reads every column row once per 128 (not 32) rows of x -- they were bound by
 // the L2 -> LDS traffic of their panels as much as by the matrix pipe -- keeps all of G^T (d x 32 per
 // wave = 16 d / 32 accumulator registers) in the wave that needs it, so there is no exchange of weight fragments and no
-// cross-wave reduction, and needs ONE workgroup barrier per chunk.  16 NFT accumulator registers hold G^T: d = 512 would
-// need all 256 AGPRs and leave none for the Gram tile (the compiler then shuffles hundreds of registers per chunk through
-// VGPRs and scratch), so d > 256 runs as two feature slices (grid z), each recomputing the Gram and the lookups: 128
-// instead of 112 MFMAs per chunk and slice pair, everything register-resident.  Both chunk images come in by LDS-DMA
+// cross-wave reduction, and needs ONE workgroup barrier per chunk.  16 NFT accumulator registers hold G^T: through d = 512
+// a block holds all of it (NFT = NST, one feature slice: at d = 512 the 256 accumulators fill half the 512-register file
+// and the compiler places the Gram tile and the operands in the other half without spills), so the Gram and the lookups
+// are computed once per pair; d = 1024 runs as four or eight feature slices (grid z), each recomputing them (mmd_plan.cpp).
+// Both chunk images come in by LDS-DMA
 // (global_load_lds_dwordx4: no staging registers, no ds_write pass), double buffered, issued a whole chunk ahead; the
 // bank-conflict-avoiding swizzles are applied to the per-lane SOURCE address (the DMA's LDS destination is
 // lane-linear).  The wave software-pipelines across chunks: the Gram of chunk t+1 is issued ahead of the gradient GEMM
@@ -2011,224 +2009,84 @@ __global__ __launch_bounds__(256) void mmd_final_kernel(const double* __restrict
   }
 }
 
-struct MmdPlan {
-  int nfb, zslices, S, S1;
-  bool d256;  // pass 1 by the 256-row-block spin kernel
-  bool fp4;   // that kernel and the 128-row-block pair kernel take their Gram on the FP4 matrix pipe, from the packed copy at off_zi4 (option mmd_gram_fp4)
-  size_t off_zi4;
-  int64_t rbx, rby, GX1;
-  size_t off_sq, off_coef, off_dist, off_loss, off_grad, off_flag, off_zi8, off_zt, off_tab, total;
-  int pm1_ok;
-  int64_t ztb_x, ztb_y;  // 32-row blocks of the transposed copy (whole 128-row tiles)
-  int w128, S2;          // 128-row-block pair kernel (large spin problems) and its column splits
-  int z128;              // ... its feature slices (grid z): 1; d = 1024: 4 (one resident table, W128<32, 8, true>) or 8 (W128<32, 4>)
-  int64_t rb128x, rb128y;
-};
-
-// option mmd_w128 = 1 / 0 forces the 128-row-block pair kernel on (wherever the shape allows it) / off: tests, A/B runs
-static int mmd_w128_env() {  // (read per call: the tests flip it inside one process)
-  const int64_t v = opt(OPT_MMD_W128);
-  return v < 0 ? -1 : (v ? 1 : 0);
+// ================================================================== host: the plan (mmd_plan.h) -> arguments and launches
+// (every pointer of the kernel argument from the plan's workspace layout)
+static MmdArgs mmd_args(const MmdPlan& p, const float* x, const float* y, const dvg_mmd_cfg_t* cfg, float* grad_x, char* w) {
+  MmdArgs a;
+  a.x = x; a.y = y; a.nx = p.nx; a.ny = p.ny; a.d = p.d;
+  a.sq = (float*)(w + p.off_sq);
+  a.coef = (float*)(w + p.off_coef);
+  a.n_kernels = cfg->n_kernels; a.squared = cfg->squared; a.reduce_mean = cfg->reduce_mean; a.biased = cfg->biased;
+  a.pow2 = cfg->factor == 2.0f;
+  a.loss_part = (double*)(w + p.off_loss);
+  a.grad_part = grad_x ? (p.splits > 1 ? (float*)(w + p.off_grad) : grad_x) : nullptr;
+  a.S = p.splits;
+  a.dist_part = (double*)(w + p.off_dist);
+  a.zi8 = (const int8_t*)(w + p.off_zi8);
+  a.not_pm1 = (const int*)(w + p.off_flag);
+  a.pm1_ok = p.spin;
+  a.gate_main = 0;
+  a.zt = (const uint16_t*)(w + p.off_zt);
+  a.ztb_y = p.ztb_x;
+  a.tab = (const uint4*)(w + p.off_tab);
+  a.zi4 = p.gram == MG_FP4 ? (const uint8_t*)(w + p.off_zi4) : nullptr;
+  return a;
 }
 
-// column splits of the pair kernel aim for this many blocks
-static int64_t mmd_target_blocks() { return 256; }
-// feature slices (grid z) of the 128-row-block pair kernel: NST / NFT of the instantiation dvg_mmd_fwd_bwd launches
-static int mmd_w128_slices(int d) { return d == 1024 ? 8 : 1; }
-
-static MmdPlan mmd_plan(int64_t nx, int64_t ny, int d) {
-  MmdPlan p;
-  const int fbt = d / 32;
-  p.nfb = fbt <= 2 ? 2 : (fbt <= 4 ? 4 : 8);  // 16 feature blocks (512 accumulator registers) would spill
-  p.zslices = (fbt + p.nfb - 1) / p.nfb;
-  p.rbx = ceil_div(nx, MMD_BI);
-  p.rby = ceil_div(ny, MMD_BI);
-  const int64_t tiles = ceil_div(nx, MMD_BJ) + ceil_div(ny, MMD_BJ);
-  // column splits: aim for mmd_target_blocks() blocks, never more splits than tiles
-  int64_t S = ceil_div(mmd_target_blocks(), p.rbx * p.zslices);
-  if (S > tiles) S = tiles;
-  if (S < 1) S = 1;
-  if (S > 16) S = 16;
-  p.S = (int)S;
-  p.pm1_ok = d <= 1024;  // LDS: table + resident X rows + one Z panel
-  // 128-row-block pair kernel: d = 128 .. 512 in steps of 128 (16 d / 32 accumulator registers per lane), and enough
-  // rows of x that 128-row blocks fill the chip with at most 4 column splits of >= 16 chunks each
-  // (d = 1024, round 6: the rows still fit the registers -- 128 of them hold a lane's 1024 int8 features -- and the LDS
-  // image fits with 128-feature slices of G^T, W128<32, 4>: eight feature slices per row block, each redoing the int8
-  // Gram (32 of its 48 MFMAs per chunk).  c5's per-GPU slice, 2048 + 2048 rows: 16 row blocks x 8 slices x 2 splits;
-  // the 32-row kernel it replaces there staged 192 KB through LDS per 32 x 128 pairs and held every CU's register file
-  // with one workgroup at 0.05 of the matrix peak.)
-  p.rb128x = ceil_div(nx, 128);
-  p.rb128y = ceil_div(ny, 128);
-  {
-    const int64_t chunks = ceil_div(nx, 32) + ceil_div(ny, 32);
-    const int env = mmd_w128_env();
-    auto splits_for = [&](int64_t z) {
-      int64_t S = ceil_div(mmd_target_blocks(), p.rb128x * z);
-      if (S > chunks / 16) S = chunks / 16;
-      if (S < 1) S = 1;
-      if (env == 1) { if (S > 16) S = 16; } else if (S > 4) S = 4;
-      return S;
-    };
-    // d = 1024: 256-feature slices (four of them: the int8 Gram redone 4 instead of 8 times, 48 instead of 40 KB staged for
-    // 64 instead of 48 MFMAs per chunk) need the LDS of one pair table: possible when no block's chunk range spans the x / y
-    // boundary, i.e. when the x chunks are a whole number of column splits (c5: 64 + 64 chunks in 4 splits of 32)
-    int64_t z128 = mmd_w128_slices(d);
-    if (d == 1024) {
-      const int64_t S4 = splits_for(4), per4 = ceil_div(chunks, S4);
-      if (ceil_div(nx, 32) % per4 == 0) z128 = 4;
-    }
-    p.z128 = (int)z128;
-    int64_t S2 = ceil_div(mmd_target_blocks(), p.rb128x * z128);
-    if (S2 > chunks / 16) S2 = chunks / 16;
-    if (S2 < 1) S2 = 1;
-    // (the 128-row-block kernel addresses both chunk images through 32-bit buffer offsets: the int8 rows and the bf16
-    // transposed copy, 2 (nx + ny) d bytes, must stay below 2^31 -- larger problems keep the 32-row kernels' 64-bit pointers)
-    const bool shape_ok = d % 128 == 0 && (d <= 512 || d == 1024) && (int64_t)(nx + ny) * (int64_t)d * 2 < 2147483647LL;
-    p.w128 = shape_ok && (env == 1 || (env != 0 && S2 <= 4 && p.rb128x * S2 * z128 >= 128));
-    if (env == 1 && shape_ok) { S2 = S2 > 16 ? 16 : S2; }
-    else if (S2 > 4) S2 = 4;
-    p.S2 = (int)S2;
-  }
-  // pass 1 (distance sum): spin-capable shapes launch the folded 128-row form, ceil(T/2) x S1 blocks of about
-  // (T+1)/S1 tiles each, two blocks per CU wanted; other shapes one block per 32-row block
-  int64_t S1;
-  {
-    const int64_t ov = opt(OPT_MMD_D256);  // 0: never, 1: whenever the shape allows (tests); read per call
-    const int env = ov < 0 ? -1 : (ov ? 1 : 0);
-    const int64_t t256 = ceil_div(nx + ny, 256);
-    p.d256 = p.pm1_ok && env != 0 && d % 128 == 0 && d <= 512 && (t256 >= 32 || env == 1) && (nx + ny) * (int64_t)d < 2147483647LL;
-  }
-  // FP4 Gram: the packed row pitches with a 1 KiB DMA piece per wave (d / 2 = 128, 256 bytes).  The copy's place in the
-  // workspace depends on the shape alone: the option may be flipped between calls on one workspace.
-  const bool fp4_shape = p.pm1_ok && (d == 256 || d == 512);
-  p.fp4 = fp4_shape && (p.d256 || p.w128) && opt(OPT_MMD_GRAM_FP4) != 0;
-  if (p.d256) {  // 256-row blocks
-    p.GX1 = 64;  // 8 chunk streams (one per XCD) x 64 blocks of equal work: exactly two resident blocks per CU
-    S1 = 8;
-  } else if (p.pm1_ok) {
-    p.GX1 = (tiles + 1) / 2;
-    S1 = ceil_div(512, p.GX1);
-    if (S1 > tiles + 1) S1 = tiles + 1;
-    if (S1 > 32) S1 = 32;
-  } else {
-    p.GX1 = p.rbx + p.rby;
-    S1 = ceil_div(1024, p.GX1);
-    if (S1 > tiles) S1 = tiles;
-    if (S1 > 16) S1 = 16;
-  }
-  if (S1 < 1) S1 = 1;
-  p.S1 = (int)S1;
-  size_t o = 0;
-  p.off_sq = o; o = align_up(o + sizeof(float) * (size_t)(nx + ny), 256);
-  p.off_coef = o; o = align_up(o + sizeof(float) * 16, 256);
-  p.off_dist = o; o = align_up(o + sizeof(double) * (size_t)(p.S1 * p.GX1), 256);
-  {
-    size_t nparts = (size_t)(p.S * (p.rbx + p.rby));
-    if (p.w128 && (size_t)(p.S2 * p.z128 * (p.rb128x + p.rb128y)) > nparts) nparts = (size_t)(p.S2 * p.z128 * (p.rb128x + p.rb128y));
-    if (p.w128 && (size_t)(p.S2 * (p.rbx + p.rby)) > nparts) nparts = (size_t)(p.S2 * (p.rbx + p.rby));
-    p.off_loss = o; o = align_up(o + sizeof(double) * 3 * nparts, 256);
-  }
-  {
-    const int smax = p.w128 && p.S2 > p.S ? p.S2 : p.S;
-    p.off_grad = o; o = align_up(o + (smax > 1 ? sizeof(float) * (size_t)smax * (size_t)nx * (size_t)d : 0), 256);
-  }
-  p.ztb_x = ceil_div(nx, MMD_BJ) * 4;
-  p.ztb_y = ceil_div(ny, MMD_BJ) * 4;
-  p.off_flag = o; o = align_up(o + sizeof(int), 256);
-  p.off_zi8 = o; o = align_up(o + (size_t)(nx + ny) * (size_t)d, 256);
-  p.off_zt = o; o = align_up(o + (p.pm1_ok ? (size_t)(p.ztb_x + p.ztb_y) * (size_t)d * 32 * sizeof(uint16_t) : 0), 256);
-  p.off_tab = o; o = align_up(o + (p.pm1_ok ? 2 * (size_t)(d + 1) * sizeof(uint4) : 0), 256);
-  p.off_zi4 = o; o = align_up(o + (fp4_shape ? (size_t)(nx + ny) * (size_t)(d / 2) : 0), 256);
-  p.total = o;
-  return p;
+// ---- one dispatcher per kernel family, in the order of the launches: the plan's integers -> the instantiation (null:
+// there is none) ----
+using MmdKernel = void (*)(MmdArgs);
+struct MmdKernelOf { int param; MmdKernel kern; };
+template <size_t N>
+static MmdKernel kernel_of(const MmdKernelOf (&table)[N], int param) {
+  for (const MmdKernelOf& k : table)
+    if (k.param == param) return k.kern;
+  return nullptr;
 }
-
-template <int NFB>
-static int launch_main(const MmdArgs& a, const MmdPlan& p, hipStream_t s) {
-  const size_t lds = sizeof(float) * (size_t)(MMD_BJ * MMD_PITCH + MMD_BI * MMD_PITCH + NFB * 32 * MMD_PITCH + 4 * 32 + 2) +
-                     sizeof(double) * 256;
-  auto kern = mmd_main_kernel<NFB>;  // d beyond the spin path's LDS budget: the f32 body alone
-  if (lds > 64 * 1024)
-    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const double N = (double)(a.nx + a.ny);
-  const double flops = 2.0 * N * N * a.d + 2.0 * (double)a.nx * N * a.d;  // Gram + gradient GEMM
-  if (a.gate_main) {
-    MmdArgs g = a;
-    g.vgx = (int)(p.rbx + p.rby); g.vgy = p.S; g.vgz = p.zslices;
-    const int64_t total = (int64_t)g.vgx * g.vgy * g.vgz;
-    DVG_LAUNCH_WORK(K_MMD_MAIN, flops, kern, dim3((unsigned)(total < 512 ? total : 512)), dim3(256), lds, s, g);
-    return DVG_OK;
-  }
-  DVG_LAUNCH_WORK(K_MMD_MAIN, flops, kern, dim3((unsigned)(p.rbx + p.rby), (unsigned)p.S, (unsigned)p.zslices), dim3(256), lds, s, a);
-  return DVG_OK;
+static MmdKernel mmd_distsum_kernel_of(const MmdPlan& p) {
+  static const MmdKernelOf spin256_fp4[] = {{8, mmd_distsum_spin256_kernel<8, true>}, {16, mmd_distsum_spin256_kernel<16, true>}};
+  static const MmdKernelOf spin256[] = {{4, mmd_distsum_spin256_kernel<4>}, {8, mmd_distsum_spin256_kernel<8>},
+                                        {12, mmd_distsum_spin256_kernel<12>}, {16, mmd_distsum_spin256_kernel<16>}};
+  static const MmdKernelOf spin[] = {{4, mmd_distsum_spin_kernel<4>}, {16, mmd_distsum_spin_kernel<16>}, {32, mmd_distsum_spin_kernel<32>}};
+  if (p.dist == MD_F32) return mmd_distsum_kernel;
+  if (p.dist == MD_SPIN) return kernel_of(spin, p.dist_ns);
+  return p.gram == MG_FP4 ? kernel_of(spin256_fp4, p.dist_ns) : kernel_of(spin256, p.dist_ns);
 }
-
-// Executed matrix work of a spin-path pair launch in bf16-MFMA-equivalent FLOPs (what bench.py prices against the
-// 2.5 PFLOP/s dense bf16 peak): the int8 Gram of every visited pair (x rows against all rows, y rows against y rows)
-// runs at twice the bf16 rate, hence the 0.5; the gradient GEMM runs `terms` bf16 products per pair and feature.
-// `gram_passes`: how often the x-row Gram is computed (the 128-row-block kernel recomputes it per feature slice).
-static void mmd_pm1_flops(int64_t nx_, int64_t ny_, int d_, bool grad, int terms, int gram_passes, double* i8, double* b16) {
-  const double nx = (double)nx_, ny = (double)ny_, d = (double)d_;
-  *i8 = 2.0 * (gram_passes * nx * (nx + ny) + ny * ny) * d;
-  *b16 = grad ? terms * 2.0 * nx * (nx + ny) * d : 0.0;
-}
-static double mmd_pm1_work(const MmdArgs& a, int terms, int gram_passes = 1) {
-  double i8, b16;
-  mmd_pm1_flops(a.nx, a.ny, a.d, a.grad_part != nullptr, terms, gram_passes, &i8, &b16);
-  return 0.5 * i8 + b16;
-}
-
-template <int NFBW>
-static int launch_pair_fq(const MmdArgs& a, const MmdPlan& p, hipStream_t s) {
-  constexpr int NFB = 4 * NFBW, NFBM = NFB > 8 ? 8 : NFB;
-  const int d = a.d, pw = d < MMD_I8_PANEL ? d : MMD_I8_PANEL;
-  const size_t zbytes = (size_t)MMD_BJ * (pw + 16), gbytes = sizeof(float) * NFB * 32 * MMD_PITCH;
-  const size_t zg = ((zbytes > gbytes ? zbytes : gbytes) + 15) / 16 * 16;
-  const size_t lds_s = 2 * (size_t)(d + 1) * sizeof(uint4) + sizeof(float) * 128 + sizeof(double) * 256 +
-                       (size_t)MMD_BI * (d + 16) + zg + sizeof(i32x4) * 24 * 64;
-  const size_t lds_m = sizeof(float) * (size_t)(MMD_BJ * MMD_PITCH + MMD_BI * MMD_PITCH + NFBM * 32 * MMD_PITCH + 4 * 32 + 2) +
-                       sizeof(double) * 256;
-  const size_t lds = lds_s > lds_m ? lds_s : lds_m;
-  auto kern = mmd_pair_fq_kernel<NFBW>;
-  if (lds > 64 * 1024)
-    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int zs = (d / 32 + NFBM - 1) / NFBM;  // slices the f32 body needs
-  DVG_LAUNCH_WORK(K_MMD_PM1, mmd_pm1_work(a, 3), kern, dim3((unsigned)(p.rbx + p.rby), (unsigned)p.S, (unsigned)zs), dim3(256), lds, s, a);
-  return DVG_OK;
-}
-
+// (the 128-row-block kernel's LDS image is a constant of the instantiation)
+struct W128Kernel { int nst, nft; bool one, fp4; MmdKernel kern; size_t lds; };
 template <int NST, int NFT, bool ONE = false, bool FP4 = false>
-static int launch_pair_w128(const MmdArgs& a, const MmdPlan& p, hipStream_t s) {
-  auto kern = mmd_pair_w128_kernel<NST, NFT, ONE, FP4>;
-  constexpr int lds = W128<NST, NFT, ONE, FP4>::LDS_BYTES;
-  if (lds > 64 * 1024)
-    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  DVG_LAUNCH_WORK(K_MMD_PM1, mmd_pm1_work(a, 2, NST / NFT), kern, dim3((unsigned)(p.rb128x + p.rb128y), (unsigned)p.S2, NST / NFT),
-                  dim3(256), (size_t)lds, s, a);
-  return DVG_OK;
+static W128Kernel w128_kernel() { return {NST, NFT, ONE, FP4, mmd_pair_w128_kernel<NST, NFT, ONE, FP4>, W128<NST, NFT, ONE, FP4>::LDS_BYTES}; }
+static MmdKernel mmd_pair_w128_kernel_of(const MmdPlan& p, size_t* lds) {
+  static const W128Kernel table[] = {w128_kernel<4, 4>(), w128_kernel<8, 8, false, true>(), w128_kernel<8, 8>(), w128_kernel<12, 12>(),
+                                     w128_kernel<32, 8, true>(), w128_kernel<32, 4>(),  // (d = 1024: four / eight feature slices)
+                                     w128_kernel<16, 16, false, true>(), w128_kernel<16, 16>()};
+  for (const W128Kernel& k : table)
+    if (k.nst == p.nst && k.nft == p.nft && k.one == p.one && k.fp4 == (p.gram == MG_FP4)) { *lds = k.lds; return k.kern; }
+  return nullptr;
+}
+static MmdKernel mmd_main_kernel_of(int nfb) {
+  static const MmdKernelOf table[] = {{2, mmd_main_kernel<2>}, {4, mmd_main_kernel<4>}, {8, mmd_main_kernel<8>}};
+  return kernel_of(table, nfb);
+}
+static MmdKernel mmd_pair_fq_kernel_of(int nfbw) {
+  static const MmdKernelOf table[] = {{1, mmd_pair_fq_kernel<1>}, {2, mmd_pair_fq_kernel<2>}, {3, mmd_pair_fq_kernel<3>}, {4, mmd_pair_fq_kernel<4>}};
+  return kernel_of(table, nfbw);
+}
+static MmdKernel mmd_pair_kernel_of(int nfb) {
+  static const MmdKernelOf table[] = {{8, mmd_pair_kernel<8>}, {4, mmd_pair_kernel<4>}, {2, mmd_pair_kernel<2>}, {1, mmd_pair_kernel<1>}};
+  return kernel_of(table, nfb);
 }
 
-template <int NFB>
-static int launch_pair(const MmdArgs& a, const MmdPlan& p, hipStream_t s) {
-  const int d = a.d, pw = d < MMD_I8_PANEL ? d : MMD_I8_PANEL;
-  const size_t zbytes = (size_t)MMD_BJ * (pw + 16), gbytes = sizeof(float) * NFB * 32 * MMD_PITCH;
-  const size_t lds_s = 2 * (size_t)(d + 1) * sizeof(uint4) + sizeof(float) * 128 + sizeof(double) * 256 +
-                       (size_t)MMD_BI * (d + 16) + (zbytes > gbytes ? zbytes : gbytes);
-  const size_t lds_m = sizeof(float) * (size_t)(MMD_BJ * MMD_PITCH + MMD_BI * MMD_PITCH + NFB * 32 * MMD_PITCH + 4 * 32 + 2) +
-                       sizeof(double) * 256;
-  const size_t lds = lds_s > lds_m ? lds_s : lds_m;
-  auto kern = mmd_pair_kernel<NFB>;
-  if (lds > 64 * 1024)
-    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int zs = d / (32 * NFB);
-  DVG_LAUNCH_WORK(K_MMD_PM1, mmd_pm1_work(a, 3), kern, dim3((unsigned)(p.rbx + p.rby), (unsigned)p.S, (unsigned)zs), dim3(256), lds, s, a);
+static int mmd_launch(KernelId id, double work, MmdKernel kern, const char* what, const MmdLaunch& l, hipStream_t s, const MmdArgs& a) {
+  DVG_REQUIRE(kern, "mmd: the plan names a %s the library does not instantiate", what);
+  if (l.lds > 64 * 1024)
+    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+  ProfScope ps(id, s, work);
+  hipLaunchKernelGGL(kern, dim3(l.grid[0], l.grid[1], l.grid[2]), dim3(256), l.lds, s, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error("launch of the mmd %s failed: %s", what, hipGetErrorString(e)); return DVG_E_HIP; }
   return DVG_OK;
 }
-
-// (the two-feature-slice form of the 128-row-block pair kernel at d > 256 -- the Gram and the lookups computed once per
-// slice -- was retired in round 3: the single-slice form replaced it at 2.70 -> 2.10 ms)
-static constexpr bool mmd_two_slices() { return false; }
 
 }  // namespace dvg
 
@@ -2236,19 +2094,15 @@ using namespace dvg;
 
 extern "C" int dvg_mmd_spin_flops(int64_t nx, int64_t ny, int dim, double* int8_flops, double* bf16_flops, int* bf16_terms) {
   DVG_REQUIRE(nx >= 2 && ny >= 2 && dim >= 32 && dim % 32 == 0 && int8_flops && bf16_flops && bf16_terms, "mmd_spin_flops: bad argument");
-  const MmdPlan p = mmd_plan(nx, ny, dim);
-  if (!p.pm1_ok) { *int8_flops = 0.0; *bf16_flops = 0.0; *bf16_terms = 0; return DVG_OK; }  // f32 kernels only
-  // the form dvg_mmd_fwd_bwd launches: ONE feature slice per block (the Gram and the lookups computed once) unless the
-  // two-slice form is asked for (mmd_two_slices(), d > 256 only)
-  const int passes = p.w128 ? p.z128 * ((dim > 256 && dim <= 512 && mmd_two_slices()) ? 2 : 1) : 1;
-  *bf16_terms = p.w128 ? 2 : 3;
-  mmd_pm1_flops(nx, ny, dim, true, *bf16_terms, passes, int8_flops, bf16_flops);
+  const MmdPlan p = mmd_plan(nx, ny, dim, mmd_options());
+  *int8_flops = 0.0; *bf16_flops = 0.0; *bf16_terms = p.bf16_terms;
+  if (p.spin) mmd_spin_flops(p, true, int8_flops, bf16_flops);  // (else: float32 kernels only)
   return DVG_OK;
 }
 
 extern "C" size_t dvg_mmd_workspace_bytes(int64_t nx, int64_t ny, int dim) {
   if (nx <= 0 || ny <= 0 || dim <= 0 || dim % 32) return 0;
-  return mmd_plan(nx, ny, dim).total;
+  return mmd_plan(nx, ny, dim, mmd_options()).total;
 }
 
 extern "C" int dvg_mmd_fwd_bwd(const float* x, int64_t nx, const float* y, int64_t ny, int dim,
@@ -2258,142 +2112,41 @@ extern "C" int dvg_mmd_fwd_bwd(const float* x, int64_t nx, const float* y, int64
   DVG_REQUIRE(nx >= 2 && ny >= 2, "mmd: need at least 2 rows in x and y (nx=%lld ny=%lld)", (long long)nx, (long long)ny);
   DVG_REQUIRE(dim >= 32 && dim % 32 == 0 && dim <= 16384, "mmd: dim=%d must be a multiple of 32", dim);
   DVG_REQUIRE(cfg->n_kernels >= 1 && cfg->n_kernels <= 8, "mmd: n_kernels=%d not in [1,8]", cfg->n_kernels);
-  const MmdPlan p = mmd_plan(nx, ny, dim);
+  const MmdPlan p = mmd_plan(nx, ny, dim, mmd_options());
   if (ws_bytes < p.total) { set_error("mmd: workspace %zu < %zu", ws_bytes, p.total); return DVG_E_WORKSPACE; }
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)ws;
-  MmdArgs a;
-  a.x = x; a.y = y; a.nx = nx; a.ny = ny; a.d = dim;
-  a.sq = (float*)(w + p.off_sq);
-  a.coef = (float*)(w + p.off_coef);
-  a.n_kernels = cfg->n_kernels; a.squared = cfg->squared; a.reduce_mean = cfg->reduce_mean; a.biased = cfg->biased;
-  a.pow2 = cfg->factor == 2.0f;
-  a.loss_part = (double*)(w + p.off_loss);
-  const int S_eff = p.w128 ? p.S2 : p.S;  // column splits of the pair kernel that will run for spin rows
-  a.grad_part = grad_x ? (S_eff > 1 ? (float*)(w + p.off_grad) : grad_x) : nullptr;
-  a.S = S_eff;
-  a.dist_part = (double*)(w + p.off_dist);
-  a.zi8 = (const int8_t*)(w + p.off_zi8);
-  a.not_pm1 = (const int*)(w + p.off_flag);
-  a.pm1_ok = p.pm1_ok;
-  a.gate_main = 0;
-  a.zt = (const uint16_t*)(w + p.off_zt);
-  a.ztb_y = p.ztb_x;
-  a.tab = (const uint4*)(w + p.off_tab);
-  a.zi4 = p.fp4 ? (const uint8_t*)(w + p.off_zi4) : nullptr;
+  const MmdArgs a = mmd_args(p, x, y, cfg, grad_x, w);
+  const bool gated = p.gated_nfb != 0;
 
-  // Two implementations of the pair kernels are enqueued back to back and gate themselves on a device flag the prep
-  // kernel writes (are all entries exactly +-1?), so no host synchronisation is needed to choose between them.
+  // The spin and the float32 implementations of the pair kernels gate themselves on a device flag the prep kernel
+  // writes (are all entries exactly +-1?), so no host synchronisation is needed to choose between them.
   DVG_CHECK_HIP(hipMemsetAsync(w + p.off_flag, 0, sizeof(int), s));
-  int loss_parts = (int)(p.S * (p.rbx + p.rby));
-  if (p.w128) {
-    // (the 128-row-block pair kernel and the float32 kernel behind it number their loss partials by their own grids and
-    // exactly one of them runs: the slots the other layout would have filled must read as zero in the final sum)
-    if ((int)(p.S2 * p.z128 * (p.rb128x + p.rb128y)) > loss_parts) loss_parts = (int)(p.S2 * p.z128 * (p.rb128x + p.rb128y));
-    if ((int)(p.S2 * (p.rbx + p.rby)) > loss_parts) loss_parts = (int)(p.S2 * (p.rbx + p.rby));
-  }
-  if (p.pm1_ok) {  // row norms, int8 copy, +-1 flag and the transposed bf16 copy in one pass over the rows
-    DVG_LAUNCH(K_MMD_PREP, mmd_prep_fused_kernel, dim3((unsigned)(p.ztb_x + p.ztb_y)), dim3(256), (size_t)32 * (dim + 16), s, a,
+  if (p.spin) {  // (zeroes the loss partials when two layouts share them: mmd_plan.cpp)
+    DVG_LAUNCH(K_MMD_PREP, mmd_prep_fused_kernel, dim3(p.prep.grid[0]), dim3(256), p.prep.lds, s, a,
                (float*)(w + p.off_sq), (int8_t*)(w + p.off_zi8), (int*)(w + p.off_flag), (uint16_t*)(w + p.off_zt),
-               p.w128 ? loss_parts : 0, p.fp4 ? (uint8_t*)(w + p.off_zi4) : (uint8_t*)nullptr);
+               gated ? p.loss_parts : 0, p.gram == MG_FP4 ? (uint8_t*)(w + p.off_zi4) : (uint8_t*)nullptr);
   } else {
-    DVG_LAUNCH(K_MMD_PREP, mmd_prep_kernel, dim3((unsigned)ceil_div(nx + ny, 4)), dim3(256), 0, s, x, nx, y, ny, dim,
+    DVG_LAUNCH(K_MMD_PREP, mmd_prep_kernel, dim3(p.prep.grid[0]), dim3(256), p.prep.lds, s, x, nx, y, ny, dim,
                (float*)(w + p.off_sq), (int8_t*)(w + p.off_zi8), (int*)(w + p.off_flag));
   }
-  int ndist = 0;
-  if (!(cfg->bandwidth > 0.f)) {
-    ndist = (int)(p.S1 * p.GX1);
-    const int pw = dim < MMD_I8_PANEL ? dim : MMD_I8_PANEL;
-    const size_t lds_f = 2048 + sizeof(float) * (MMD_BJ + MMD_BI) * MMD_PITCH;
-    const dim3 grid((unsigned)p.GX1, (unsigned)p.S1);
-    if (p.pm1_ok) {
-      const size_t lds_s = 2048 + ((size_t)(dim + 1) * 4 + 15) / 16 * 16 + (size_t)MMD_BJ * (pw + 16);
-      const size_t lds_d = lds_f > lds_s ? lds_f : lds_s;
-      auto launch = [&](auto kern) -> int {
-        if (lds_d > 64 * 1024)
-          DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d));
-        DVG_LAUNCH(K_MMD_DISTSUM, kern, grid, dim3(256), lds_d, s, a);
-        return DVG_OK;
-      };
-      if (p.d256) {
-        const size_t lds_2 = 2048 + ((size_t)(dim + 1) * 4 + 1023) / 1024 * 1024 + 2 * (size_t)32 * dim;
-        const size_t lds_256 = lds_f > lds_2 ? lds_f : lds_2;
-        auto launch256 = [&](auto kern) -> int {
-          DVG_LAUNCH(K_MMD_DISTSUM, kern, grid, dim3(256), lds_256, s, a);
-          return DVG_OK;
-        };
-        if (p.fp4) DVG_TRY(dim == 256 ? launch256(mmd_distsum_spin256_kernel<8, true>) : launch256(mmd_distsum_spin256_kernel<16, true>));
-        else if (dim == 128) DVG_TRY(launch256(mmd_distsum_spin256_kernel<4>));
-        else if (dim == 256) DVG_TRY(launch256(mmd_distsum_spin256_kernel<8>));
-        else if (dim == 384) DVG_TRY(launch256(mmd_distsum_spin256_kernel<12>));
-        else DVG_TRY(launch256(mmd_distsum_spin256_kernel<16>));
-      } else
-      if (dim <= 128) DVG_TRY(launch(mmd_distsum_spin_kernel<4>));
-      else if (dim <= 512) DVG_TRY(launch(mmd_distsum_spin_kernel<16>));
-      else DVG_TRY(launch(mmd_distsum_spin_kernel<32>));
-    } else {
-      const size_t lds_i = 2048 + (size_t)(MMD_BJ + MMD_BI) * (pw + 16);
-      const size_t lds_d = lds_f > lds_i ? lds_f : lds_i;
-      if (lds_d > 64 * 1024)
-        DVG_CHECK_HIP(hipFuncSetAttribute((const void*)mmd_distsum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d));
-      DVG_LAUNCH(K_MMD_DISTSUM, mmd_distsum_kernel, grid, dim3(256), lds_d, s, a);
-    }
-  }
-  DVG_LAUNCH(K_MMD_FINAL, mmd_bandwidth_table_kernel, dim3(1), dim3(256), 0, s, a, (const double*)(w + p.off_dist), ndist,
-             (double)(nx + ny), cfg->bandwidth, cfg->factor, (float*)(w + p.off_coef),
-             p.pm1_ok ? (uint4*)(w + p.off_tab) : (uint4*)nullptr);
-  int rc;
-  if (p.w128) {
-    // Large spin problems: 128-row blocks.  General (not +-1) rows cannot be known on the host without a sync, so the
-    // f32 kernel is launched behind it with the same split count and stands down on the device flag (its blocks exit at
-    // once; it writes the same loss_part / grad_part slots when it does run).
-    switch (dim / 128) {
-      case 1: rc = launch_pair_w128<4, 4>(a, p, s); break;
-      case 2: rc = p.fp4 ? launch_pair_w128<8, 8, false, true>(a, p, s) : launch_pair_w128<8, 8>(a, p, s); break;
-      // One feature slice per block wherever the accumulators fit the 512-register file (d = 512: 256 of them hold G^T,
-      // the compiler places the Gram tile and the operands in the other half without spills): the Gram and the lookups
-      // are then computed once, 80 instead of 96 MFMAs per chunk: 2.70 -> 2.10 ms at c3 (the two-slice form is retired).
-      case 3: rc = launch_pair_w128<12, 12>(a, p, s); break;
-      case 8: rc = p.z128 == 4 ? launch_pair_w128<32, 8, true>(a, p, s) : launch_pair_w128<32, 4>(a, p, s); break;  // (four / eight feature slices: mmd_plan)
-      default: rc = p.fp4 ? launch_pair_w128<16, 16, false, true>(a, p, s) : launch_pair_w128<16, 16>(a, p, s); break;
-    }
-    DVG_TRY(rc);
+  const bool measure = !(cfg->bandwidth > 0.f);  // no bandwidth given: from the mean distance
+  if (measure) DVG_TRY(mmd_launch(K_MMD_DISTSUM, 0.0, mmd_distsum_kernel_of(p), "distance-sum kernel", p.distsum, s, a));
+  DVG_LAUNCH(K_MMD_FINAL, mmd_bandwidth_table_kernel, dim3(1), dim3(256), 0, s, a, (const double*)(w + p.off_dist),
+             measure ? (int)(p.distsum.grid[0] * p.distsum.grid[1]) : 0, (double)(nx + ny), cfg->bandwidth, cfg->factor,
+             (float*)(w + p.off_coef), p.spin ? (uint4*)(w + p.off_tab) : (uint4*)nullptr);
+  MmdLaunch pl = p.pair_launch;
+  const MmdKernel pair = p.pair == MP_W128 ? mmd_pair_w128_kernel_of(p, &pl.lds) : p.pair == MP_FQ ? mmd_pair_fq_kernel_of(p.nfbw)
+                       : p.pair == MP_SLICED ? mmd_pair_kernel_of(p.nfb) : mmd_main_kernel_of(p.nfb);
+  if (p.spin) DVG_TRY(mmd_launch(K_MMD_PM1, mmd_spin_work(p, a.grad_part != nullptr), pair, "spin pair kernel", pl, s, a));
+  else DVG_TRY(mmd_launch(K_MMD_MAIN, mmd_f32_work(p), pair, "float32 pair kernel", pl, s, a));
+  if (gated) {  // the float32 kernel behind the 128-row-block kernel, for rows that are not +-1
     MmdArgs g = a;
     g.gate_main = 1;
-    MmdPlan pg = p;
-    pg.S = p.S2;
-    switch (p.nfb) {
-      case 2: rc = launch_main<2>(g, pg, s); break;
-      case 4: rc = launch_main<4>(g, pg, s); break;
-      default: rc = launch_main<8>(g, pg, s); break;
-    }
-  } else if (p.pm1_ok) {
-    // feature blocks per launch slice: the largest of 8/4/2/1 that divides d/32 (no feature guards in the spin body;
-    // 16 blocks = 256 accumulator registers makes the compiler shuffle accumulators through scratch)
-    const int fbt = dim / 32;
-    // d = 128, 256, 384, 512: feature-quarter form; other widths: the sliced form
-    if (dim % 128 == 0 && dim <= 512) {
-      switch (dim / 128) {
-        case 1: rc = launch_pair_fq<1>(a, p, s); break;
-        case 2: rc = launch_pair_fq<2>(a, p, s); break;
-        case 3: rc = launch_pair_fq<3>(a, p, s); break;
-        default: rc = launch_pair_fq<4>(a, p, s); break;
-      }
-    } else if (fbt % 8 == 0) rc = launch_pair<8>(a, p, s);
-    else if (fbt % 4 == 0) rc = launch_pair<4>(a, p, s);
-    else if (fbt % 2 == 0) rc = launch_pair<2>(a, p, s);
-    else rc = launch_pair<1>(a, p, s);
-  } else {
-    switch (p.nfb) {
-      case 2: rc = launch_main<2>(a, p, s); break;
-      case 4: rc = launch_main<4>(a, p, s); break;
-      default: rc = launch_main<8>(a, p, s); break;
-    }
+    g.vgx = p.gated.logical[0]; g.vgy = p.gated.logical[1]; g.vgz = p.gated.logical[2];
+    DVG_TRY(mmd_launch(K_MMD_MAIN, mmd_f32_work(p), mmd_main_kernel_of(p.gated_nfb), "gated float32 pair kernel", p.gated, s, g));
   }
-  DVG_TRY(rc);
-  const int64_t numel = nx * (int64_t)dim;
-  const unsigned fgrid = (grad_x && S_eff > 1) ? (unsigned)(ceil_div(numel, 256) > 2048 ? 2048 : ceil_div(numel, 256)) : 1u;
-  DVG_LAUNCH(K_MMD_FINAL, mmd_final_kernel, dim3(fgrid), dim3(256), 0, s, (const double*)(w + p.off_loss),
-             loss_parts, nx, ny, cfg->biased, loss_out, (const float*)(w + p.off_grad), S_eff, numel, grad_x);
+  DVG_LAUNCH(K_MMD_FINAL, mmd_final_kernel, dim3(grad_x ? p.final_grad.grid[0] : 1u), dim3(256), 0, s, (const double*)(w + p.off_loss),
+             p.loss_parts, nx, ny, cfg->biased, loss_out, (const float*)(w + p.off_grad), p.splits, nx * (int64_t)dim, grad_x);
   return DVG_OK;
 }

@@ -22,6 +22,7 @@ _SIGS = {
                                  [ctypes.c_void_p]),
     "dvg_dev_conv_wino_ok": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_plan_forms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "dvg_dev_mmd_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "dvg_dev_conv_wino_stats_blocks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int]),
     "dvg_dev_wgrad_slab_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_conv_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 +
@@ -103,6 +104,27 @@ def plan_forms(network, rows, n_latents, training=True):
                "dvg_dev_plan_forms")
     layers = [tuple(FORMS[out[3 * l + k]] for k in range(3)) if out[3 * l] >= 0 else None for l in range(4)]
     return layers, dict(d22=bool(out[12]), lc0=bool(out[13]), tail=bool(out[14]))
+
+
+MMD_PAIR_FORMS = ("f32", "sliced", "fq", "w128")  # csrc/mmd_plan.h: MmdPairForm
+MMD_DIST_FORMS = ("f32", "spin", "spin256")        # MmdDistForm
+MMD_GRAM_PIPES = ("int8", "fp4")                   # MmdGram
+
+
+def mmd_plan(nx, ny, d):
+    """The kernel forms ``F.mmd_loss_and_grad`` takes for x of (nx, d) and y of (ny, d) under the current options (no device
+    needed).  ``pair`` / ``pair_params``: the pair kernel and its template parameters; ``dist`` / ``dist_ns``: the
+    distance-sum kernel (launched when no bandwidth is given) and its parameter; ``gram``: the matrix pipe of the exact
+    spin Gram; ``gated_f32``: a float32 launch (``mmd_main_kernel<gated_nfb>``) follows the pair kernel."""
+    o = (ctypes.c_int64 * 24)()
+    _lib.check(lib().dvg_dev_mmd_plan(nx, ny, d, o), "dvg_dev_mmd_plan")
+    pair = MMD_PAIR_FORMS[o[0]]
+    params = {"f32": dict(NFB=o[1]), "sliced": dict(NFB=o[1]), "fq": dict(NFBW=o[2]),
+              "w128": dict(NST=o[3], NFT=o[4], ONE=bool(o[5]))}[pair]
+    return dict(pair=pair, pair_params=params, dist=MMD_DIST_FORMS[o[6]], dist_ns=o[7], gram=MMD_GRAM_PIPES[o[8]],
+                splits=o[9], slices=o[10], gated_f32=o[11] != 0, gated_nfb=o[11], loss_parts=o[12], workspace_bytes=o[13],
+                dist_splits=o[14], gram_passes=o[15], bf16_terms=o[16], pair_grid=(o[17], o[18], o[19]),
+                dist_grid=(o[20], o[21]), gated_grid=o[22], final_grid=o[23])
 
 
 def conv_wino(x_m, w, mode, M, Cin, Cout, L, bias=None, stats=False):

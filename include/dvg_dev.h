@@ -29,6 +29,18 @@ int dvg_dev_conv_wino_ok(int64_t M, int Cin, int Cout, int L);
  * VALU layers (encoder layer 0, decoder layer 3).  out[12..14] = the decoder's d22 / lc0 / tail flags (encoder: 0).
  * The decoder's plan does not depend on `training`; an evaluation-mode encoder plan reads 0 for its gradients. */
 int dvg_dev_plan_forms(int network, int64_t rows, int n_latents, int training, int out[15]);
+/* The kernel forms an MMD call (dvg_mmd_fwd_bwd) of this shape takes under the current options (csrc/mmd_plan.h; needs no
+ * device).  out[0] pair form: 0 float32 only (mmd_main_kernel<out[1]>), 1 sliced spin (mmd_pair_kernel<out[1]>), 2 feature-
+ * quarter (mmd_pair_fq_kernel<out[2]>), 3 128-row block (mmd_pair_w128_kernel<out[3], out[4], out[5], FP4>); out[1..5] =
+ * NFB, NFBW, NST, NFT, ONE (0 where the form has no such parameter).  out[6] distance-sum form: 0 float32
+ * (mmd_distsum_kernel), 1 mmd_distsum_spin_kernel<out[7]>, 2 mmd_distsum_spin256_kernel<out[7], FP4>.  out[8] matrix pipe of
+ * the exact spin Gram in the kernels that have the choice: 0 int8, 1 FP4.  out[9] column splits, out[10] feature slices
+ * (grid z) of the pair launch; out[11] NFB of the gated float32 launch behind the 128-row-block kernel (0: none);
+ * out[12] loss partials the final kernel sums; out[13] = dvg_mmd_workspace_bytes; out[14] column splits of the distance
+ * sum; out[15], out[16] Gram passes and bf16 terms as dvg_mmd_spin_flops prices them; out[17..19] grid of the pair
+ * launch, out[20..21] of the distance sum (when no bandwidth is given), out[22] of the gated launch, out[23] of the final
+ * kernel when a gradient is asked for. */
+int dvg_dev_mmd_plan(int64_t nx, int64_t ny, int dim, int64_t out[24]);
 /* The same layer in the Winograd F(4x4,3x3) form (csrc/conv_wino4.hip: 36 position GEMMs per 4x4 output tile, 2.25 multiplies
  * per output where F(2x2,3x3) issues 4.0): `u` = scratch of 36*Cin*Cout floats, `stats` rows = M / 1024 (tile blocks of 64
  * tiles), cus = CUs the persistent grid is sized for (0 = 256).  Shapes: whole 1024-pixel blocks of 4x4 / 8x8 / 16x16 images. */

@@ -54,9 +54,12 @@ def test_mmd_128_row_block_kernel_matches_oracle(monkeypatch, nx, ny, d, kw):
     want, gwant = _ref_mmd(x, y, **kw)
     w32, _ = _ref_mmd(x, y, dtype=torch.float32, **kw)
     out = {}
-    from image_generation_amd import _lib
+    from image_generation_amd import _lib, dev
     for flag in ("1", "0"):
         with _lib.option_scope(mmd_w128=int(flag), mmd_d256=int(flag)):  # (and the 256-row-block distance-sum kernel with it)
+            plan = dev.mmd_plan(nx, ny, d)  # the forced kernels are what runs (d = 1024 has no 256-row distance sum)
+            assert (plan["pair"] == "w128") == (flag == "1") and plan["gated_f32"] == (flag == "1")
+            assert (plan["dist"] == "spin256") == (flag == "1" and d <= 512)
             xg = x.cuda().requires_grad_(True)
             loss = F.mmd_loss(xg, y.cuda(), **kw)
             loss.backward()

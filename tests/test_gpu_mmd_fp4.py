@@ -10,7 +10,7 @@ import math
 import pytest
 import torch
 
-from image_generation_amd import _lib, functional as F
+from image_generation_amd import _lib, dev, functional as F
 
 gpu = pytest.mark.gpu
 
@@ -22,8 +22,8 @@ def _spins(g, rows, d, p):
     return ((torch.rand(rows, d, generator=g) < p).float() * 2 - 1).cuda()
 
 
-def _both(fn, force):
-    """fn() with the int8 Gram and with the FP4 Gram (force: the 128-row pair kernel and the 256-row distance-sum kernel
+def _both(fn, force, shape):
+    """fn() (an MMD call on `shape` = (nx, ny, d)) with the int8 Gram and with the FP4 Gram (force: the 128-row pair kernel and the 256-row distance-sum kernel
     whatever the size, as test_gpu_losses.py forces them on small shapes)."""
     out = {}
     for fp4 in (0, 1):
@@ -31,6 +31,7 @@ def _both(fn, force):
         if force:
             opts.update(mmd_w128=1, mmd_d256=1)
         with _lib.option_scope(**opts):
+            assert dev.mmd_plan(*shape)["gram"] == ("fp4" if fp4 else "int8")  # the pipe under test is the one that runs
             out[fp4] = fn()
         torch.cuda.synchronize()
     return out[0], out[1]
@@ -53,7 +54,7 @@ def test_c3_shape_with_duplicated_rows_is_bit_identical():
     x = _spins(g, nx, d, 0.4)
     x[40:44] = x[39]
     y = _spins(g, ny, d, 0.55)
-    a, b = _both(lambda: F.mmd_loss_and_grad(x, y), force=False)
+    a, b = _both(lambda: F.mmd_loss_and_grad(x, y), force=False, shape=(nx, ny, d))
     _assert_same(a, b, "c3")
     assert torch.isfinite(a[0]) and float(a[1].abs().max()) > 0
 
@@ -66,7 +67,7 @@ def test_ragged_shapes_are_bit_identical(nx, ny, d, kw):
     x = _spins(g, nx, d, 0.35)
     x[: nx // 4] = x[0]  # duplicated rows: Hamming distance 0 off the diagonal
     y = _spins(g, ny, d, 0.6)
-    a, b = _both(lambda: F.mmd_loss_and_grad(x, y, **kw), force=True)  # (bandwidth given: no distance-sum pass)
+    a, b = _both(lambda: F.mmd_loss_and_grad(x, y, **kw), force=True, shape=(nx, ny, d))  # (bandwidth given: no distance-sum pass)
     _assert_same(a, b, f"{(nx, ny, d)} {kw}")
     assert torch.isfinite(a[0]) and float(a[1].abs().max()) > 0
 
@@ -81,7 +82,7 @@ def test_loss_only_is_bit_identical(nx, ny, d):
         with torch.no_grad():
             return (F.mmd_loss(x, y),)
 
-    a, b = _both(run, force=True)
+    a, b = _both(run, force=True, shape=(nx, ny, d))
     _assert_same(a, b, f"loss only {(nx, ny, d)}")
 
 
@@ -92,7 +93,7 @@ def test_rows_that_are_not_spins_take_the_float_kernels(nx, ny, d):
     g = torch.Generator().manual_seed(7)
     x, y = _spins(g, nx, d, 0.4), _spins(g, ny, d, 0.5)
     x[3, 7] = 0.25
-    a, b = _both(lambda: F.mmd_loss_and_grad(x, y), force=True)
+    a, b = _both(lambda: F.mmd_loss_and_grad(x, y), force=True, shape=(nx, ny, d))
     _assert_same(a, b, "float rows")
     assert torch.isfinite(a[0])
 
@@ -182,8 +183,8 @@ def test_c3_shape_under_load_equals_the_idle_run():
     (32768, 256, 512, 1, 50903040),
 ])
 def test_flop_counts_keep_their_values_and_the_workspace_grows_by_the_fp4_copy(nx, ny, d, slices, ws_before):
-    """dvg_mmd_spin_flops prices the Gram as before whatever pipe runs it (bench.py and test_gpu_under_load.py derive the
-    kernel form from it); dvg_mmd_workspace_bytes grew by at most the packed copy (ws_before: the int8-only library)."""
+    """dvg_mmd_spin_flops prices the Gram as before whatever pipe runs it (bench.py derives the kernel
+    form from it); dvg_mmd_workspace_bytes grew by at most the packed copy (ws_before: the int8-only library)."""
     L = _lib.lib()
     for fp4 in (1, 0):
         with _lib.option_scope(mmd_gram_fp4=fp4):

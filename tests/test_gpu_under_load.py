@@ -7,7 +7,6 @@ is invisible on an idle device, where the DMA round trip is short; in the traini
 with the other stream (the MMD runs beside the decoder's backward) and with whatever else the machine runs.  The kernels
 are deterministic (no float atomics, fixed reduction orders), so any difference between runs is a fault, not noise.
 The idle run is held against float64 at the bars of the existing parity tests."""
-import ctypes
 import math
 
 import pytest
@@ -119,11 +118,9 @@ def _spins(g, rows, d, p):
 def _mmd_form(nx, ny, d):
     """(bf16 terms, int8 Gram passes) of the spin pair kernel dvg_mmd_fwd_bwd launches for this shape: 2 terms = the
     128-row-block kernel, whose passes are its feature slices (grid z)."""
-    i8, b16, terms = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
-    _lib.check(_lib.lib().dvg_mmd_spin_flops(nx, ny, d, ctypes.byref(i8), ctypes.byref(b16), ctypes.byref(terms)),
-               "dvg_mmd_spin_flops")
-    passes = (i8.value / (2.0 * d) - ny * ny) / (nx * (nx + ny))
-    return terms.value, int(round(passes))
+    plan = dev.mmd_plan(nx, ny, d)
+    assert (plan["pair"] == "w128") == (plan["bf16_terms"] == 2) and (plan["pair"] != "w128" or plan["gram_passes"] == plan["slices"])
+    return plan["bf16_terms"], plan["gram_passes"]
 
 
 @pytest.mark.parametrize("nx,ny,d,slices", [
@@ -135,7 +132,7 @@ def test_mmd_under_load_is_bit_identical_and_matches_float64(hog, nx, ny, d, sli
     """F.mmd_loss_and_grad (loss and gradient).  The d = 1024 forms run NST / NFT > 1 Gram k-steps per feature tile and
     pre-read the next chunk's first operands inside the current chunk -- the path whose ring wait must cover the DMA one
     chunk back; the d = 512 form (one Gram k-step per tile, vmcnt(0) at every chunk) is the control.  The form each shape
-    takes is asserted through the library's own plan (dvg_mmd_spin_flops)."""
+    takes is asserted through the library's own plan (dev.mmd_plan)."""
     assert _mmd_form(nx, ny, d) == (2, slices)
     g = torch.Generator().manual_seed(nx + d)
     x = _spins(g, nx, d, 0.4)

@@ -169,3 +169,61 @@ def test_benchmark_configurations_take_the_pinned_kernel_forms(config, bf16):
             assert dev.plan_forms("decoder", B * R, n, training=training) == (dec, dict(d22=True, lc0=lc0, tail=True))
     finally:
         assert L.dvg_set_conv_precision(before) == 0
+
+
+# Which kernels one MMD call launches at the benchmark configurations' shapes (x rows, y rows, latent width).  Transcribed
+# from the behaviour of the commit BEFORE the call got its plan (csrc/mmd_plan.h), not from the code under test: forms,
+# template arguments and grids (in workgroups) from that commit's kernel-trace rows (profiles/r08_mmd_trace_parent.txt),
+# workspace bytes and priced work from its dvg_mmd_workspace_bytes / dvg_mmd_spin_flops.  A threshold edit that moves a
+# configuration to another form has to change this table knowingly.
+_MMD_SHAPES = {"c1": (512, 256, 64), "c2": (2048, 256, 128), "c3": (32768, 256, 512), "c5": (2048, 2048, 1024)}
+_MMD_PLANS = {  # (config, options): pair kernel, its template arguments and grid; gated float32 launch (NFB, grid) or None;
+    # distance-sum kernel, its argument and grid; Gram pipe; final kernel's grid; workspace bytes; int8 FLOPs, bf16 FLOPs, terms
+    ("c1", ()): ("sliced", dict(NFB=2), (24, 6, 1), None, "spin", 4, (3, 7), "int8", 128,
+                 943616, 58720256.0, 150994944.0, 3),
+    ("c2", ()): ("fq", dict(NFBW=1), (72, 4, 1), None, "spin", 4, (9, 19), "int8", 1024,
+                 5101568, 1224736768.0, 3623878656.0, 3),
+    ("c3", ()): ("w128", dict(NST=16, NFT=16, ONE=False), (258, 1, 1), (8, 512), "spin256", 16, (64, 8), "fp4", 1,
+                 59357184, 1108168671232.0, 2216203124736.0, 2),
+    ("c5", ()): ("w128", dict(NST=32, NFT=8, ONE=True), (32, 4, 4), (8, 512), "spin", 32, (16, 32), "int8", 2048,
+                 46203648, 77309411328.0, 34359738368.0, 2),
+    ("c3", (("mmd_gram_fp4", 0),)): ("w128", dict(NST=16, NFT=16, ONE=False), (258, 1, 1), (8, 512), "spin256", 16, (64, 8), "int8", 1,
+                                     59357184, 1108168671232.0, 2216203124736.0, 2),
+    ("c2", (("mmd_w128", 1), ("mmd_d256", 1))): ("w128", dict(NST=4, NFT=4, ONE=False), (18, 4, 1), (4, 288), "spin256", 4, (64, 8), "int8", 1024,
+                                                  5104128, 1224736768.0, 2415919104.0, 2),
+}
+
+
+def _align256(n):
+    return (n + 255) // 256 * 256
+
+
+@pytest.mark.parametrize("config,options", sorted(_MMD_PLANS))
+def test_benchmark_mmd_shapes_take_the_pinned_kernel_forms(config, options):
+    import ctypes
+
+    from image_generation_amd import _lib, dev
+    L = _lib.lib()
+    nx, ny, d = _MMD_SHAPES[config]
+    pair, params, pair_grid, gated, dist, dist_ns, dist_grid, gram, final_grid, ws, i8, b16, terms = _MMD_PLANS[(config, options)]
+    _lib.check(L.dvg_reset_options(), "dvg_reset_options")
+    with _lib.option_scope(**dict(options)):
+        p = dev.mmd_plan(nx, ny, d)
+        assert (p["pair"], p["pair_params"], p["pair_grid"]) == (pair, params, pair_grid)
+        assert (p["gated_f32"], p["gated_nfb"], p["gated_grid"]) == ((True,) + gated if gated else (False, 0, 0))
+        assert (p["dist"], p["dist_ns"], p["dist_grid"]) == (dist, dist_ns, dist_grid)
+        assert p["gram"] == gram and p["final_grid"] == final_grid
+        assert (p["splits"], p["slices"]) == pair_grid[1:] and p["dist_splits"] == dist_grid[1]
+        # the priced work comes out of the same plan
+        f8, f16, t = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+        _lib.check(L.dvg_mmd_spin_flops(nx, ny, d, ctypes.byref(f8), ctypes.byref(f16), ctypes.byref(t)), "dvg_mmd_spin_flops")
+        assert (f8.value, f16.value, t.value) == (i8, b16, terms)
+        assert (p["gram_passes"], p["bf16_terms"]) == (pair_grid[2] if pair == "w128" else 1, terms)
+        # ... and so does the workspace: the total is dvg_mmd_workspace_bytes, and the layout rebuilt from the plan's counts
+        # (loss partials among them; at these shapes the gradient slabs are the pair form's splits) gives the same total
+        assert p["workspace_bytes"] == ws == L.dvg_mmd_workspace_bytes(nx, ny, d)
+        rows32 = -(-nx // 128) * 4 + -(-ny // 128) * 4  # 32-row blocks of the transposed copy: whole 128-row tiles
+        segments = [4 * (nx + ny), 4 * 16, 8 * dist_grid[0] * dist_grid[1], 8 * 3 * p["loss_parts"],
+                    4 * p["splits"] * nx * d if p["splits"] > 1 else 0, 4, (nx + ny) * d, rows32 * d * 32 * 2, 2 * (d + 1) * 16,
+                    (nx + ny) * d // 2 if d in (256, 512) else 0]
+        assert sum(_align256(s) for s in segments) == ws
