@@ -63,8 +63,11 @@ def _rel_l2(got, want):
     return float((got - want).norm() / (want.norm() + 1e-300))
 
 
-def _check_step_against_float64(tmp_path, cfg, grad_bar):
+def _check_step_against_float64(tmp_path, cfg, grad_bar, prepare=None):
+    """``prepare(model)``: called on the fresh model before anything is read from it (e.g. to load a checkpoint into it)."""
     m, imgs = _model(tmp_path, cfg, 1)
+    if prepare is not None:
+        prepare(m)
     gumbels, masks = _noise(cfg, 5)
     snap, meta = ho.snapshot(m), ho.meta_of(m)
     osampler = ho.oracle_sampler_like(m)
