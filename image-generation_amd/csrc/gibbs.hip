@@ -9,6 +9,7 @@
 // them simultaneously; classes are separated by a wavefront-level fence only (no
 // workgroup barrier: chains never interact).
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
 #include "common.h"
@@ -33,6 +34,34 @@ struct GibbsArgs {
   const uint32_t* sweep0_dev;  // non-null: read the first-sweep index from device memory (graph replay)
   int n_sweeps, init;
 };
+
+// Conditional draws (dvg_gibbs_sample_clamped): some spins of a chain are HELD at the value they have in `state` -- left
+// out of their colour class, nothing else changed (they still feed their neighbours' field sums).  The kernels carry the
+// held path as a compile-time variant, HELD, whose argument block is the plain one plus the flags: the instantiations
+// of the plain draw keep their arguments and their code.
+struct GibbsHeldArgs : GibbsArgs {
+  const uint8_t* clamp;   // [n_chains or 1][n]: nonzero = held
+  int64_t clamp_stride;   // n (a row per chain) or 0 (one row for all chains)
+};
+template <bool HELD>
+using GibbsArgsT = std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>;
+
+// a conditional draw's start state: held spins from `state` always, free ones from the INIT stream (init) or from `state`
+template <int LPC>
+__device__ __forceinline__ void gibbs_load_chain_held(const GibbsHeldArgs& a, _Float16* st, int chain, int l, uint32_t cid,
+                                                      uint32_t sweep0) {
+  const int n = a.n;
+  const int8_t* src = a.state + (size_t)chain * n;
+  const uint8_t* held = a.clamp + (int64_t)chain * a.clamp_stride;
+  for (int i = l; i < n; i += LPC) {
+    if (a.init && held[i] == 0) {
+      u32x4 r = philox4x32_10((uint32_t)i, cid, sweep0, STREAM_INIT, a.k0, a.k1);
+      st[i] = (r.x >> 31) ? (_Float16)1.0f : (_Float16)-1.0f;
+    } else {
+      st[i] = (_Float16)(float)src[i];
+    }
+  }
+}
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
@@ -151,9 +180,14 @@ __device__ __forceinline__ _Float16 gibbs_decide(float f, float two_beta, uint32
   return (b < 1.0f) ? (_Float16)1.0f : (_Float16)-1.0f;
 }
 
+// words of one chain's row of held flags in LDS (the rolled schedule of a conditional draw), one bit per spin
+__host__ __device__ __forceinline__ int gibbs_held_words(int n) { return (n + 31) >> 5; }
+
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
-template <int LPC, int WAVES>
-__global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgs a) {
+// HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
+// passed over in its class.
+template <int LPC, int WAVES, bool HELD = false>
+__global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD> a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n;
   const GibbsLds L = gibbs_carve(smem, n, a.n_batches, a.n_colours);
@@ -168,12 +202,25 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgs a) {
   const bool valid = chain < a.n_chains;
   _Float16* st = L.state + (size_t)(wave * CPW + sub) * n_pad;
   const uint32_t cid = a.chain_id0 + (uint32_t)chain;
+  // HELD: bit (i & 31) of word (i >> 5) of the chain's row of flags
+  [[maybe_unused]] uint32_t* hb = nullptr;
+  if constexpr (HELD)
+    hb = reinterpret_cast<uint32_t*>(L.state + (size_t)WAVES * CPW * n_pad) + (size_t)(wave * CPW + sub) * gibbs_held_words(n);
 
   // (read before the chains start: a fresh chain's start configuration is keyed by the sweep index it starts at, so
   // non-persistent draws do not all restart from one configuration)
   const uint32_t sweep0 = a.sweep0_dev ? *a.sweep0_dev : a.sweep0;
   if (valid) {
-    if (a.init) {
+    if constexpr (HELD) {
+      gibbs_load_chain_held<LPC>(a, st, chain, l, cid, sweep0);
+      // (a lane packs whole words: 32 consecutive flags each)
+      const uint8_t* held = a.clamp + (int64_t)chain * a.clamp_stride;
+      for (int w = l; w < gibbs_held_words(n); w += LPC) {
+        uint32_t bits = 0u;
+        for (int b = 0; b < 32 && 32 * w + b < n; ++b) bits |= (held[32 * w + b] != 0 ? 1u : 0u) << b;
+        hb[w] = bits;
+      }
+    } else if (a.init) {
       for (int i = l; i < n; i += LPC) {
         u32x4 r = philox4x32_10((uint32_t)i, cid, sweep0, STREAM_INIT, a.k0, a.k1);
         st[i] = (r.x >> 31) ? (_Float16)1.0f : (_Float16)-1.0f;
@@ -193,6 +240,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgs a) {
         const int lo = L.cls[k], hi = L.cls[k + 1];
         for (int p = lo + l; p < hi; p += LPC) {
           const int i = L.order[p];
+          if constexpr (HELD) {
+            if ((hb[i >> 5] >> (i & 31)) & 1u) continue;
+          }
           const float f = gibbs_field(L.hs[i], L.row[i], L, st, a.n_batches, a.max_batches);
           const u32x4 r = philox4x32_10((uint32_t)i, cid, tq, STREAM_GIBBS, a.k0, a.k1);
           st[i] = gibbs_decide(f, a.two_beta, pick(r, tw));
@@ -460,8 +510,10 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
   }
 }
 
-template <int LPC, int WAVES, int MB, int NR, int MAXS>
-__global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgs a) {
+// HELD: the conditional draw -- a lane owns the same spin in a slot for the whole draw, so its held flags are one bit
+// per slot in a register; a held slot draws no random word and stores to the sink.
+template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false>
+__global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD> a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n, n_pad = (n + 15) & ~15;
   const int n_rows = a.n_rows;
@@ -503,7 +555,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgs a) {
   // non-persistent draws do not all restart from one configuration)
   const uint32_t sweep0 = a.sweep0_dev ? *a.sweep0_dev : a.sweep0;
   if (valid) {
-    if (a.init) {
+    if constexpr (HELD) {
+      gibbs_load_chain_held<LPC>(a, st, chain, l, cid, sweep0);
+    } else if (a.init) {
       for (int i = l; i < n; i += LPC) {
         u32x4 r = philox4x32_10((uint32_t)i, cid, sweep0, STREAM_INIT, a.k0, a.k1);
         st[i] = (r.x >> 31) ? (_Float16)1.0f : (_Float16)-1.0f;
@@ -516,10 +570,14 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgs a) {
   // this lane's spin in each row (-1: none) and its clamped field offset
   int sp[MAXS];
   float hs[MAXS];
+  [[maybe_unused]] uint32_t held = 0u;  // HELD: bit k = the spin of slot k is held in this lane's chain
 #pragma unroll
   for (int k = 0; k < MAXS; ++k) {
     sp[k] = (valid && k < n_rows) ? a.lane_spin[k * LPC + l] : -1;
     hs[k] = sp[k] >= 0 ? clampf(__fmul_rn(a.prefactor, a.linear[sp[k]]), a.h_lo, a.h_hi) : 0.f;
+    if constexpr (HELD) {
+      if (sp[k] >= 0 && a.clamp[(int64_t)chain * a.clamp_stride + sp[k]] != 0) held |= 1u << k;
+    }
   }
   __syncthreads();  // the tables are staged
   if (!valid) return;
@@ -530,6 +588,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgs a) {
   const unsigned char* wl = smem + (size_t)l * 16;
   const unsigned char* ol = smem + (size_t)n_rows * MB * LPC * 16 + (size_t)l * 8;
   const unsigned char* stb = reinterpret_cast<const unsigned char*>(st);
+  // the lane updates a spin in slot K (else its decision goes to the sink)
+#define DVG_GIBBS_FREE(K) (HELD ? (sp[K] >= 0 && ((held >> (K)) & 1u) == 0u) : sp[K] >= 0)
   u32x4 rr[MAXS];
 #pragma unroll
   for (int k = 0; k < MAXS; ++k) rr[k] = u32x4{0u, 0u, 0u, 0u};
@@ -544,7 +604,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgs a) {
     if (t == sweep0 || tw == 0u) {
 #pragma unroll
       for (int k = 0; k < MAXS; ++k)
-        if (sp[k] >= 0) rr[k] = philox4x32_10((uint32_t)sp[k], cid, tq, STREAM_GIBBS, a.k0, a.k1);
+        if (DVG_GIBBS_FREE(k)) rr[k] = philox4x32_10((uint32_t)sp[k], cid, tq, STREAM_GIBBS, a.k0, a.k1);
     }
     // word tw of a slot's four, as two bit-selects under wave-uniform masks (a uniform `?:` becomes scalar branches,
     // four per slot and sweep)
@@ -565,12 +625,12 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgs a) {
         gibbs_lane_class<MB, LPC, NR, NR>(f, o, wlk, ol_next, stb);
         const _Float16 s0 = gibbs_decide(f[0], a.two_beta, DVG_GIBBS_WORD(k0));
         const _Float16 s1 = gibbs_decide(f[NR - 1], a.two_beta, DVG_GIBBS_WORD(k1));
-        *(sp[k0] >= 0 ? st + sp[k0] : sink) = s0;
-        *(sp[k1] >= 0 ? st + sp[k1] : sink) = s1;
+        *(DVG_GIBBS_FREE(k0) ? st + sp[k0] : sink) = s0;
+        *(DVG_GIBBS_FREE(k1) ? st + sp[k1] : sink) = s1;
       } else {  // one row (NR = 2: the step's second row is empty for the whole wave)
         gibbs_lane_class<MB, LPC, NR, 1>(f, o, wlk, ol_next, stb);
         const _Float16 s0 = gibbs_decide(f[0], a.two_beta, DVG_GIBBS_WORD(k0));
-        *(sp[k0] >= 0 ? st + sp[k0] : sink) = s0;
+        *(DVG_GIBBS_FREE(k0) ? st + sp[k0] : sink) = s0;
       }
       // the next class reads what this one wrote (same wave): order LDS traffic.  (Passes of one class are independent
       // of each other, so a fence between them is harmless.)
@@ -579,6 +639,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgs a) {
     }
   }
 #undef DVG_GIBBS_WORD
+#undef DVG_GIBBS_FREE
   int8_t* dst = a.state + (size_t)chain * n;
   for (int i = l; i < n; i += LPC) {
     const float v = (float)st[i];
@@ -596,17 +657,20 @@ static size_t gibbs_lds_bytes(int n, int n_batches, int n_colours, int chains_pe
 struct GibbsProbe { int workgroups; int threads; size_t lds; };
 static thread_local GibbsProbe* g_gibbs_probe = nullptr;
 
-template <int LPC, int WAVES>
-static int launch_gibbs(GibbsArgs a, hipStream_t s) {
+template <int LPC, int WAVES, bool HELD = false>
+static int launch_gibbs(GibbsArgsT<HELD> a, hipStream_t s) {
   constexpr int CPB = WAVES * (64 / LPC);
-  const size_t lds = gibbs_lds_bytes(a.n, a.n_batches, a.n_colours, CPB);
+  // (HELD: a row of flag bits per chain behind the state rows)
+  const size_t lds = gibbs_lds_bytes(a.n, a.n_batches, a.n_colours, CPB) +
+                     (HELD ? sizeof(uint32_t) * (size_t)CPB * gibbs_held_words(a.n) : 0);
   if (lds > 160 * 1024) {
-    set_error("gibbs: graph (n=%d, %d neighbour batches) needs %zu B of LDS > 160 KiB", a.n, a.n_batches, lds);
+    set_error("gibbs: graph (n=%d, %d neighbour batches) needs %zu B of LDS%s > 160 KiB", a.n, a.n_batches, lds,
+              HELD ? " (the held flags of a conditional draw included)" : "");
     return DVG_E_UNSUPPORTED;
   }
   const int grid = (int)ceil_div(a.n_chains, CPB);
   if (g_gibbs_probe) { *g_gibbs_probe = GibbsProbe{grid, WAVES * 64, lds}; return DVG_OK; }
-  auto kern = gibbs_kernel<LPC, WAVES>;
+  auto kern = gibbs_kernel<LPC, WAVES, HELD>;
   if (lds > 64 * 1024)
     DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // work = spin updates of the draw (bench.py's sampler roofline)
@@ -652,8 +716,8 @@ static int launch_gibbs_slots(GibbsArgs a, const GibbsSlots& sl, hipStream_t s) 
   return DVG_OK;
 }
 
-template <int LPC, int WAVES, int MB, int NR, int MAXS>
-static int launch_gibbs_fast(GibbsArgs a, hipStream_t s) {
+template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false>
+static int launch_gibbs_fast(GibbsArgsT<HELD> a, hipStream_t s) {
   constexpr int CPB = WAVES * (64 / LPC);
   const size_t lds = gibbs_lane_lds_bytes(a.n_rows, MB, LPC, a.n, CPB);
   if (lds > 160 * 1024) {
@@ -662,7 +726,7 @@ static int launch_gibbs_fast(GibbsArgs a, hipStream_t s) {
   }
   const int grid = (int)ceil_div(a.n_chains, CPB);
   if (g_gibbs_probe) { *g_gibbs_probe = GibbsProbe{grid, WAVES * 64, lds}; return DVG_OK; }
-  auto kern = gibbs_fast_kernel<LPC, WAVES, MB, NR, MAXS>;
+  auto kern = gibbs_fast_kernel<LPC, WAVES, MB, NR, MAXS, HELD>;
   if (lds > 64 * 1024)
     DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   DVG_LAUNCH_WORK(K_GIBBS, (double)a.n_chains * a.n * a.n_sweeps, kern, dim3(grid), dim3(WAVES * 64), lds, s, a);
@@ -673,17 +737,13 @@ static int launch_gibbs_fast(GibbsArgs a, hipStream_t s) {
 
 using namespace dvg;
 
-static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgs& a, int n_chains, hipStream_t s);
+template <bool HELD>
+static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD>& a, int n_chains, hipStream_t s);
 
-extern "C" int dvg_gibbs_sample(const dvg_graph_t* g, const float* linear, const float* quadratic,
-                                float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
-                                float beta, int8_t* state, int n_chains, uint32_t chain_id0,
-                                uint64_t seed, uint32_t sweep0, int n_sweeps, int init,
-                                float* samples_out, const dvg_step_state_t* dyn, dvg_stream_t stream) {
-  DVG_REQUIRE(g && linear && quadratic && state, "gibbs: null argument");
-  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 0, "gibbs: n_chains=%d n_sweeps=%d", n_chains, n_sweeps);
-  DVG_REQUIRE(g->n <= 32767, "gibbs: graph too large (n=%d: 16-bit state offsets)", g->n);
-  GibbsArgs a;
+static void gibbs_fill_args(GibbsArgs& a, const dvg_graph_t* g, const float* linear, const float* quadratic, float prefactor,
+                            float h_lo, float h_hi, float j_lo, float j_hi, float beta, int8_t* state, int n_chains,
+                            uint32_t chain_id0, uint64_t seed, uint32_t sweep0, int n_sweeps, int init, float* samples_out,
+                            const dvg_step_state_t* dyn) {
   a.order = g->order; a.class_ptr = g->class_ptr;
   a.adj_idx = g->adj_idx; a.adj_eid = g->adj_eid; a.adj_row = g->adj_row; a.adj_src4 = g->adj_src4;
   a.linear = linear; a.quadratic = quadratic;
@@ -695,7 +755,41 @@ extern "C" int dvg_gibbs_sample(const dvg_graph_t* g, const float* linear, const
   a.sweep0 = sweep0; a.n_sweeps = n_sweeps; a.init = init;
   a.sweep0_dev = dyn ? &dyn->sweep0 : nullptr;
   a.lane_spin = nullptr; a.lane_eid = nullptr; a.lane_off = nullptr; a.n_rows = 0;
-  return gibbs_dispatch(g, a, n_chains, (hipStream_t)stream);
+}
+
+extern "C" int dvg_gibbs_sample(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                float beta, int8_t* state, int n_chains, uint32_t chain_id0,
+                                uint64_t seed, uint32_t sweep0, int n_sweeps, int init,
+                                float* samples_out, const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  DVG_REQUIRE(g && linear && quadratic && state, "gibbs: null argument");
+  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 0, "gibbs: n_chains=%d n_sweeps=%d", n_chains, n_sweeps);
+  DVG_REQUIRE(g->n <= 32767, "gibbs: graph too large (n=%d: 16-bit state offsets)", g->n);
+  GibbsArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, beta, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, dyn);
+  return gibbs_dispatch<false>(g, a, n_chains, (hipStream_t)stream);
+}
+
+// The conditional draw: spins with a nonzero flag in `clamp` are held at their value in `state` (include/dvg.h).
+extern "C" int dvg_gibbs_sample_clamped(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                        float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                        float beta, int8_t* state, int n_chains, uint32_t chain_id0,
+                                        uint64_t seed, uint32_t sweep0, int n_sweeps, int init,
+                                        const uint8_t* clamp, int64_t clamp_chain_stride,
+                                        float* samples_out, const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  DVG_REQUIRE(g && linear && quadratic && state, "gibbs_clamped: null argument");
+  DVG_REQUIRE(clamp, "gibbs_clamped: null clamp (a draw that holds nothing is dvg_gibbs_sample)");
+  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 0, "gibbs_clamped: n_chains=%d n_sweeps=%d", n_chains, n_sweeps);
+  DVG_REQUIRE(g->n <= 32767, "gibbs_clamped: graph too large (n=%d: 16-bit state offsets)", g->n);
+  DVG_REQUIRE(clamp_chain_stride == 0 || clamp_chain_stride == g->n,
+              "gibbs_clamped: clamp_chain_stride=%lld is neither 0 (one shared row) nor n=%d (a row per chain)",
+              (long long)clamp_chain_stride, g->n);
+  GibbsHeldArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, beta, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, dyn);
+  a.clamp = clamp; a.clamp_stride = clamp_chain_stride;
+  return gibbs_dispatch<true>(g, a, n_chains, (hipStream_t)stream);
 }
 
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,
@@ -707,7 +801,7 @@ extern "C" int dvg_gibbs_launch_info(const dvg_graph_t* g, int n_chains, int* wo
   a.n = g->n; a.n_batches = g->n_batches; a.max_batches = g->max_batches; a.n_colours = g->n_colours; a.n_chains = n_chains;
   GibbsProbe pr{0, 0, 0};
   g_gibbs_probe = &pr;
-  const int rc = gibbs_dispatch(g, a, n_chains, nullptr);
+  const int rc = gibbs_dispatch<false>(g, a, n_chains, nullptr);
   g_gibbs_probe = nullptr;
   DVG_TRY(rc);
   if (workgroups) *workgroups = pr.workgroups;
@@ -716,18 +810,23 @@ extern "C" int dvg_gibbs_launch_info(const dvg_graph_t* g, int n_chains, int* wo
   return DVG_OK;
 }
 
-static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgs& a, int n_chains, hipStream_t s) {
+// HELD (the conditional draw) takes the plain draw's choices, with two exceptions: it has no chains-side-by-side form, so the
+// large graphs' many-chain draws run the rolled kernel in 16-wave workgroups, and the A/B forms 3 and 4 count as 0.
+template <bool HELD>
+static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD>& a, int n_chains, hipStream_t s) {
   // (option gibbs_generic = 1 forces the rolled reference schedule: A/B runs and the bit-exactness test of the fast one;
   // 2 = the fast schedule without its two-passes-side-by-side form)
-  const int64_t form = opt(OPT_GIBBS_GENERIC);
+  const int64_t form = (HELD && opt(OPT_GIBBS_GENERIC) >= 3) ? 0 : opt(OPT_GIBBS_GENERIC);
   // Graphs of more than 12 rows per lane (1024 spins: ~140 KB of tables, one 4-chain workgroup per CU) take the fast
   // schedule only for draws of at most 512 chains: it is the LATENCY form (c5-size graph, 2048 chains x 50 sweeps: 0.59 ms
   // alone against the rolled 16-wave form's 1.20) and costs the same CU-time -- but it takes every CU's LDS while it
   // runs, and the c5 step, whose encoder AND decoder forward hide behind a 1.2 ms draw on half the chip, got slower
   // with it (2.88 -> 3.01 ms: `profiles/r05_gibbs_c5_forms.txt`).
-  if (form == 4) {  // (4: the chains-side-by-side schedule in 8-chain workgroups whatever the size: A/B runs)
-    GibbsSlots sl8;
-    if (gibbs_make_slots(g, 8, &sl8)) return launch_gibbs_slots<8>(a, sl8, s);
+  if constexpr (!HELD) {
+    if (form == 4) {  // (4: the chains-side-by-side schedule in 8-chain workgroups whatever the size: A/B runs)
+      GibbsSlots sl8;
+      if (gibbs_make_slots(g, 8, &sl8)) return launch_gibbs_slots<8>(a, sl8, s);
+    }
   }
   bool lane_ok = g->lane_eid && (g->lane_rows <= 12 || n_chains <= 512 || form == 3);  // (3: the fast schedule whatever the size: A/B runs)
   if (lane_ok) {
@@ -754,7 +853,7 @@ static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgs& a, int n_chains, hipS
     const int nr = form == 2 ? 1 : g->lane_nr;  // (2: a two-row image walked one row at a time -- empty rows and all)
     const bool small = gibbs_lane_lds_bytes(rows, mb, lpc, g->n, 0) <= 16 * 1024 && n_chains <= 1024 && rows <= 12;
 #define DVG_GIBBS_FAST(LPC, W, MB, NR, MAXS) \
-  if (lpc == LPC && mb == MB && nr == NR && rows <= MAXS && (W == 1) == small) return launch_gibbs_fast<LPC, W, MB, NR, MAXS>(a, s);
+  if (lpc == LPC && mb == MB && nr == NR && rows <= MAXS && (W == 1) == small) return launch_gibbs_fast<LPC, W, MB, NR, MAXS, HELD>(a, s);
     DVG_GIBBS_FAST(16, 1, 4, 1, 12) DVG_GIBBS_FAST(16, 4, 4, 1, 12) DVG_GIBBS_FAST(16, 1, 5, 1, 12) DVG_GIBBS_FAST(16, 4, 5, 1, 12)
     DVG_GIBBS_FAST(32, 1, 4, 1, 12) DVG_GIBBS_FAST(32, 4, 4, 1, 12) DVG_GIBBS_FAST(32, 1, 5, 1, 12) DVG_GIBBS_FAST(32, 4, 5, 1, 12)
     DVG_GIBBS_FAST(64, 1, 4, 1, 12) DVG_GIBBS_FAST(64, 4, 4, 1, 12) DVG_GIBBS_FAST(64, 1, 5, 1, 12) DVG_GIBBS_FAST(64, 4, 5, 1, 12)
@@ -772,12 +871,14 @@ static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgs& a, int n_chains, hipS
   if (gibbs_lds_bytes(g->n, g->n_batches, g->n_colours, 4) > 72 * 1024) {
     // ... with static (class, pass) slots when the classes make at most 20 of them (gibbs_slot_kernel; option
     // gibbs_generic = 1 keeps the plain rolled kernel: the reference of the bit-exactness tests)
-    GibbsSlots sl;
-    if (form != 1 && gibbs_make_slots(g, 16, &sl)) return launch_gibbs_slots<16>(a, sl, s);
-    return launch_gibbs<64, 16>(a, s);
+    if constexpr (!HELD) {
+      GibbsSlots sl;
+      if (form != 1 && gibbs_make_slots(g, 16, &sl)) return launch_gibbs_slots<16>(a, sl, s);
+    }
+    return launch_gibbs<64, 16, HELD>(a, s);
   }
   const bool small = gibbs_lds_bytes(g->n, g->n_batches, g->n_colours, 0) <= 16 * 1024 && n_chains <= 1024;
-#define DVG_GIBBS_DISPATCH(LPC) return small ? launch_gibbs<LPC, 1>(a, s) : launch_gibbs<LPC, 4>(a, s);
+#define DVG_GIBBS_DISPATCH(LPC) return small ? launch_gibbs<LPC, 1, HELD>(a, s) : launch_gibbs<LPC, 4, HELD>(a, s);
   if (mc <= 16) { DVG_GIBBS_DISPATCH(16) }
   if (mc <= 32) { DVG_GIBBS_DISPATCH(32) }
   DVG_GIBBS_DISPATCH(64)

@@ -848,6 +848,43 @@ class ModelWrapper:
         return images, samples
 
     @torch.no_grad()
+    def generate_variations(self, images: torch.Tensor, n_variations: int = 8, keep: float = 0.5,
+                            sweeps: Optional[int] = None, sharpen: bool = False, lower: float = LOWER_THRESHOLD,
+                            upper: float = UPPER_THRESHOLD, mask_seed: int = 0, return_latents: bool = False):
+        """Variations of given images: encode -> hard spins (heaviside, H(0) = 0) -> hold ``round(keep n)`` of each
+        image's spins and let the prior redraw the others (a conditional block-Gibbs draw, ``n_variations`` chains per
+        image, free spins started from the INIT stream) -> decoder -> clip [-> sharpen as ``generate_images`` does].
+
+        The held set of an image is drawn with a ``torch.Generator`` seeded by ``mask_seed`` and is the same for all of
+        its variations.  Returns (B, n_variations, 1, 32, 32) on the device; with ``return_latents`` also the
+        (B n_variations, n) spins and the (B, n) bool mask.  Rank-local, like ``generate_images``."""
+        self._dvae.eval()
+        self._grbm.eval()
+        images = images.to(self._device)
+        B, V = int(images.shape[0]), int(n_variations)
+        if V < 1 or not 0.0 <= keep <= 1.0:
+            raise ValueError(f"n_variations={n_variations} keep={keep}")
+        spins = F.heaviside_latent_to_discrete(self._dvae.encoder(images)).squeeze(1)  # (B, n) +-1
+        n = int(spins.shape[1])
+        gen = torch.Generator().manual_seed(int(mask_seed))
+        held = torch.zeros((B, n), dtype=torch.bool)
+        n_held = int(round(keep * n))
+        for b in range(B):
+            held[b, torch.randperm(n, generator=gen)[:n_held]] = True
+        held = held.to(self._device)
+        start = spins.repeat_interleave(V, dim=0)
+        samples = self._grbm.sample_conditional(self.sampler, start, held.repeat_interleave(V, dim=0),
+                                                prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                                quadratic_range=self.quadratic_range, sweeps=sweeps)
+        out = self._dvae.decoder(samples.unsqueeze(1)).squeeze(1).clip(0.0, 1.0)
+        if sharpen:
+            over = (out > upper).to(out.dtype)
+            under = (out > lower).to(out.dtype)
+            out = (over + (1 - over) * out) * under
+        out = out.reshape(B, V, *out.shape[1:])
+        return (out, samples, held) if return_latents else out
+
+    @torch.no_grad()
     def reconstruct_images(self, batch: Optional[torch.Tensor] = None, sharpen: bool = False,
                            lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD) -> torch.Tensor:
         """Eval-mode encode -> discretise -> decode of one batch of training images, interleaved with the originals:

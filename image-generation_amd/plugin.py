@@ -166,6 +166,17 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         ss = sampler.sample_ising(h, J, **sample_params)
         return self.sampleset_to_tensor(ss, device) if as_tensor else ss
 
+    def sample_conditional(self, sampler, start: torch.Tensor, clamp: torch.Tensor, *, prefactor: float,
+                           linear_range=None, quadratic_range=None, sweeps: Optional[int] = None) -> torch.Tensor:
+        """Draw from the model with the spins flagged in ``clamp`` held at their value in ``start`` (one chain per row
+        of ``start``; :meth:`GibbsSampler.sample_conditional`, free spins started from the INIT stream).  The local
+        :class:`GibbsSampler` only: a ``sample_ising``-style sampler has no conditional form."""
+        if not (isinstance(sampler, GibbsSampler) and list(sampler.nodes) == self._nodes):
+            raise TypeError("sample_conditional needs the local GibbsSampler built on this model's nodes, got "
+                            f"{type(sampler).__name__}")
+        return sampler.sample_conditional(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, start,
+                                          clamp, sweeps=sweeps, init_free=True)
+
 
 class GaussianKernel(torch.nn.Module):
     """Multi-bandwidth RBF kernel configuration (/root/reference/src/model_wrapper.py:273).

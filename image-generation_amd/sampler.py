@@ -112,6 +112,10 @@ class GibbsSampler:
         self._state: Optional[torch.Tensor] = None
         self.sweep_count = 0
         self.calls = 0
+        # conditional draws (sample_conditional) run under a key and a sweep counter of their own: they never share a
+        # random word with the training draws, and interleaving them leaves the training stream as it was
+        self.cond_seed = self.seed ^ 0x636F6E64
+        self.cond_sweep_count = 0
 
     # -- native fast path ------------------------------------------------------------------
     @property
@@ -123,6 +127,7 @@ class GibbsSampler:
     def reset(self):
         self._state = None
         self.sweep_count = 0
+        self.cond_sweep_count = 0
 
     def launch_info(self, num_reads: int) -> dict:
         """Launch geometry of one draw of ``num_reads`` chains (``dvg_gibbs_launch_info``: nothing is launched):
@@ -163,6 +168,59 @@ class GibbsSampler:
             )
         self.sweep_count += self.sweeps
         self.calls += 1
+        return out
+
+    def sample_conditional(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float,
+                           linear_range, quadratic_range, start: torch.Tensor, clamp: torch.Tensor, *,
+                           sweeps: Optional[int] = None, init_free: bool = True) -> torch.Tensor:
+        """A conditional draw (``dvg_gibbs_sample_clamped``): the spins flagged in ``clamp`` are held at their value in
+        ``start``, the others are redrawn from their conditionals under the same ``(h, J)``.
+
+        ``start``: (C, n) float32 or int8; its values must be +-1 (not checked: that would be a host sync).  ``clamp``: (C, n), or (n,) for one held set shared by all chains, bool or
+        uint8.  ``init_free``: the free spins start from the INIT stream (else from ``start``).  Returns (C, n) float32
+        +-1 on the device; no host sync.
+
+        Apart from the graph handle it shares nothing with the training draws: it leaves the persistent chains,
+        ``sweep_count`` and ``calls`` alone, counts its sweeps in ``cond_sweep_count`` and draws its random words under
+        its own key ``cond_seed``; chain ids are ``chain_offset + arange(C)``."""
+        L = _lib.lib()
+        lin = _lib.require_cuda(linear.detach(), "linear")
+        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
+        n = self.plan.n
+        if lin.numel() != n or quad.numel() != self.plan.n_edges:
+            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
+        for name, t in (("start", start), ("clamp", clamp)):
+            if not t.is_cuda:
+                raise _lib.DvgError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
+            if t.device != lin.device:
+                raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
+        if start.dtype not in (torch.float32, torch.int8):
+            raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
+        if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1:
+            raise _lib.DvgError(f"start must be (chains, {n}), got {tuple(start.shape)}")
+        C = int(start.shape[0])
+        if tuple(clamp.shape) not in ((C, n), (n,)):
+            raise _lib.DvgError(f"clamp must be ({C}, {n}) or ({n},), got {tuple(clamp.shape)}")
+        if clamp.dtype not in (torch.bool, torch.uint8):
+            raise _lib.DvgError(f"clamp must be bool or uint8, got {clamp.dtype}")
+        state = start.detach().to(torch.int8, copy=True).contiguous()  # the call's own chains, never the persistent ones
+        flags = clamp.detach().to(torch.uint8).contiguous()
+        stride = n if flags.dim() == 2 else 0
+        n_sweeps = self.sweeps if sweeps is None else int(sweeps)
+        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
+        inf = float("inf")
+        hl, hh = linear_range if linear_range is not None else (-inf, inf)
+        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+        with torch.cuda.device(lin.device):
+            _lib.check(
+                L.dvg_gibbs_sample_clamped(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
+                                           float(hh), float(jl), float(jh), self.beta, state.data_ptr(), C,
+                                           self.chain_offset & 0xFFFFFFFF, self.cond_seed,
+                                           self.cond_sweep_count & 0xFFFFFFFF, n_sweeps, int(bool(init_free)),
+                                           flags.data_ptr(), stride, out.data_ptr(), None, _lib.stream_ptr(lin.device)),
+                "dvg_gibbs_sample_clamped",
+            )
+        self.cond_sweep_count += n_sweeps
         return out
 
     # -- dimod-style entry point -----------------------------------------------------------

@@ -116,6 +116,25 @@ int dvg_gibbs_sample(const dvg_graph_t *g, const float *linear, const float *qua
                      int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
                      uint32_t sweep0, int n_sweeps, int init, float *samples_out,
                      const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The conditional draw: dvg_gibbs_sample with some spins of a chain HELD and the others redrawn from their conditionals
+ * under the same (h, J).  By definition a held spin is left out of its colour class ("DVG block-Gibbs v1" keys every
+ * random word by (spin, chain id, sweep), so nothing else moves): oracle/gibbs.py::gibbs_sweeps called with the held
+ * spins filtered out of `order` / `class_ptr` is the draw, bit for bit.
+ *   clamp: DEVICE pointer, uint8; a nonzero entry holds that spin of that chain.  clamp_chain_stride = n: one row of n
+ *     flags per chain; = 0: one row shared by all chains; anything else, or clamp == NULL, is DVG_E_INVALID (a draw
+ *     that holds nothing is dvg_gibbs_sample).
+ *   A held spin keeps the value it has in `state` on entry, enters its neighbours' field sums as any spin does (same CSR
+ *     order, same single-rounded adds) and is written back unchanged to `state` and `samples_out`.
+ *   init != 0 draws the INIT-stream start value of the FREE spins only; held spins still come from `state`.
+ *   For a free spin every operation and every Philox counter is dvg_gibbs_sample's; with no flag set the two agree bit
+ *     for bit.  Every other argument as for dvg_gibbs_sample; a graph whose image does not fit the LDS with the flags
+ *     beside it is DVG_E_UNSUPPORTED. */
+int dvg_gibbs_sample_clamped(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                             float prefactor, float h_lo, float h_hi, float j_lo, float j_hi, float beta,
+                             int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                             uint32_t sweep0, int n_sweeps, int init,
+                             const uint8_t *clamp, int64_t clamp_chain_stride, float *samples_out,
+                             const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and

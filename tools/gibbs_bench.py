@@ -1,6 +1,9 @@
 """The block-Gibbs draw ALONE (nothing else on the chip): `python tools/gibbs_bench.py [n chains sweeps]` on an MI355X.
 Prints the draw time per kernel form -- inside a training step the same draw shares its CUs
-with the encoder's GEMMs and takes longer (bench.py's `sampler` entry is that in-situ number)."""
+with the encoder's GEMMs and takes longer (bench.py's `sampler` entry is that in-situ number).
+`clamped`: also the conditional draw (per-chain masks) at held fractions 0, 0.5 and 0.9 -- timed as the call
+GibbsSampler.sample_conditional with int8 / uint8 tensors: the kernel plus the call's own copy of the start state (a
+(chains, n) int8 device copy), where the plain rows time the kernel on the sampler's persistent chains."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -32,3 +35,19 @@ for name, opts in forms[:1] if only_default else forms:
         e1.record(); torch.cuda.synchronize()
         t = e0.elapsed_time(e1) / 5
         print(f"  {name:26s} {t*1e3:9.1f} us per draw  {C*n*sweeps/t/1e6:8.2f} G spin updates/s  checksum {float(out.sum()):.0f}")
+if "clamped" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    start = torch.from_numpy(np.where(rng.uniform(size=(C, n)) < 0.5, -1, 1).astype(np.int8)).cuda()
+    for frac in (0.0, 0.5, 0.9):
+        clamp = torch.from_numpy((rng.uniform(size=(C, n)) < frac).astype(np.uint8)).cuda()
+        s.sample_conditional(lin, quad, 0.05, (-4, 4), (-1, 1), start, clamp)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            out = s.sample_conditional(lin, quad, 0.05, (-4, 4), (-1, 1), start, clamp)
+        e1.record(); torch.cuda.synchronize()
+        t = e0.elapsed_time(e1) / 5
+        free = C * n - int(clamp.sum())
+        print(f"  {'cond. call, %.0f %% held' % (100 * frac):26s} {t*1e3:9.1f} us per draw  {free*sweeps/t/1e6:8.2f} G spin updates/s  "
+              f"checksum {float(out.sum()):.0f}")
