@@ -43,8 +43,15 @@ struct GibbsHeldArgs : GibbsArgs {
   const uint8_t* clamp;   // [n_chains or 1][n]: nonzero = held
   int64_t clamp_stride;   // n (a row per chain) or 0 (one row for all chains)
 };
-template <bool HELD>
-using GibbsArgsT = std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>;
+// Annealed draws (dvg_gibbs_sample_annealed): the inverse temperature of a sweep is looked up in a device table, by the
+// sweep's index within the call and, with a row per chain, by the chain.  A second compile-time variant, SCHED, carried
+// the same way: the plain block plus the table.  (HELD with SCHED: no such draw.)
+struct GibbsSchedArgs : GibbsArgs {
+  const float* betas;   // [n_chains or 1][n_sweeps]: beta of sweep k of the call (finite, >= 0: not checked)
+  int64_t beta_stride;  // n_sweeps (a row per chain) or 0 (one row for all chains)
+};
+template <bool HELD, bool SCHED = false>
+using GibbsArgsT = std::conditional_t<SCHED, GibbsSchedArgs, std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>;
 
 // a conditional draw's start state: held spins from `state` always, free ones from the INIT stream (init) or from `state`
 template <int LPC>
@@ -185,9 +192,10 @@ __host__ __device__ __forceinline__ int gibbs_held_words(int n) { return (n + 31
 
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
 // HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
-// passed over in its class.
-template <int LPC, int WAVES, bool HELD = false>
-__global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD> a) {
+// passed over in its class.  SCHED: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead.
+template <int LPC, int WAVES, bool HELD = false, bool SCHED = false>
+__global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
+  static_assert(!(HELD && SCHED), "no annealed conditional draw");
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n;
   const GibbsLds L = gibbs_carve(smem, n, a.n_batches, a.n_colours);
@@ -234,8 +242,23 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD> a) {
   __builtin_amdgcn_wave_barrier();
 
   if (valid) {
+    // SCHED: this chain's row of the table; the entry of the coming sweep, read a sweep ahead of its first use
+    [[maybe_unused]] const float* bt = nullptr;
+    [[maybe_unused]] float beta_next = 0.0f;
+    if constexpr (SCHED) {
+      bt = a.betas + (int64_t)chain * a.beta_stride;
+      beta_next = bt[0];
+    }
     for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
       const uint32_t tq = t >> 2, tw = t & 3u;
+      float two_beta;
+      if constexpr (SCHED) {
+        two_beta = __fmul_rn(2.0f, beta_next);
+        const uint32_t kn = t - sweep0 + 1u;
+        if (kn < (uint32_t)a.n_sweeps) beta_next = bt[kn];
+      } else {
+        two_beta = a.two_beta;
+      }
       for (int k = 0; k < a.n_colours; ++k) {
         const int lo = L.cls[k], hi = L.cls[k + 1];
         for (int p = lo + l; p < hi; p += LPC) {
@@ -245,7 +268,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD> a) {
           }
           const float f = gibbs_field(L.hs[i], L.row[i], L, st, a.n_batches, a.max_batches);
           const u32x4 r = philox4x32_10((uint32_t)i, cid, tq, STREAM_GIBBS, a.k0, a.k1);
-          st[i] = gibbs_decide(f, a.two_beta, pick(r, tw));
+          st[i] = gibbs_decide(f, two_beta, pick(r, tw));
         }
         // the next class reads what this one wrote (same wave): order LDS traffic
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -512,8 +535,11 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
 
 // HELD: the conditional draw -- a lane owns the same spin in a slot for the whole draw, so its held flags are one bit
 // per slot in a register; a held slot draws no random word and stores to the sink.
-template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false>
-__global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD> a) {
+// SCHED: the annealed draw -- two_beta is the lane's chain's table entry of the sweep, read one sweep ahead (one load per
+// sweep and lane; with the shared row every lane of a wave reads one address, with a row per chain the LPC lanes of a chain).
+template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, bool SCHED = false>
+__global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
+  static_assert(!(HELD && SCHED), "no annealed conditional draw");
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n, n_pad = (n + 15) & ~15;
   const int n_rows = a.n_rows;
@@ -599,8 +625,22 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD>
 #pragma unroll
     for (int j = 0; j < MB; ++j) o[r][j] = *reinterpret_cast<const gu32x2*>(ol + (size_t)(r * MB + j) * LPC * 8);
   }
+  [[maybe_unused]] const float* bt = nullptr;
+  [[maybe_unused]] float beta_next = 0.0f;
+  if constexpr (SCHED) {
+    bt = a.betas + (int64_t)chain * a.beta_stride;
+    beta_next = bt[0];
+  }
   for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
     const uint32_t tq = t >> 2, tw = t & 3u;
+    float two_beta;
+    if constexpr (SCHED) {
+      two_beta = __fmul_rn(2.0f, beta_next);
+      const uint32_t kn = t - sweep0 + 1u;
+      if (kn < (uint32_t)a.n_sweeps) beta_next = bt[kn];
+    } else {
+      two_beta = a.two_beta;
+    }
     if (t == sweep0 || tw == 0u) {
 #pragma unroll
       for (int k = 0; k < MAXS; ++k)
@@ -623,13 +663,13 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD>
       if constexpr (NR == 2) both = __builtin_amdgcn_ballot_w64(sp[k1] >= 0) != 0;
       if (both) {
         gibbs_lane_class<MB, LPC, NR, NR>(f, o, wlk, ol_next, stb);
-        const _Float16 s0 = gibbs_decide(f[0], a.two_beta, DVG_GIBBS_WORD(k0));
-        const _Float16 s1 = gibbs_decide(f[NR - 1], a.two_beta, DVG_GIBBS_WORD(k1));
+        const _Float16 s0 = gibbs_decide(f[0], two_beta, DVG_GIBBS_WORD(k0));
+        const _Float16 s1 = gibbs_decide(f[NR - 1], two_beta, DVG_GIBBS_WORD(k1));
         *(DVG_GIBBS_FREE(k0) ? st + sp[k0] : sink) = s0;
         *(DVG_GIBBS_FREE(k1) ? st + sp[k1] : sink) = s1;
       } else {  // one row (NR = 2: the step's second row is empty for the whole wave)
         gibbs_lane_class<MB, LPC, NR, 1>(f, o, wlk, ol_next, stb);
-        const _Float16 s0 = gibbs_decide(f[0], a.two_beta, DVG_GIBBS_WORD(k0));
+        const _Float16 s0 = gibbs_decide(f[0], two_beta, DVG_GIBBS_WORD(k0));
         *(DVG_GIBBS_FREE(k0) ? st + sp[k0] : sink) = s0;
       }
       // the next class reads what this one wrote (same wave): order LDS traffic.  (Passes of one class are independent
@@ -657,8 +697,8 @@ static size_t gibbs_lds_bytes(int n, int n_batches, int n_colours, int chains_pe
 struct GibbsProbe { int workgroups; int threads; size_t lds; };
 static thread_local GibbsProbe* g_gibbs_probe = nullptr;
 
-template <int LPC, int WAVES, bool HELD = false>
-static int launch_gibbs(GibbsArgsT<HELD> a, hipStream_t s) {
+template <int LPC, int WAVES, bool HELD = false, bool SCHED = false>
+static int launch_gibbs(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
   constexpr int CPB = WAVES * (64 / LPC);
   // (HELD: a row of flag bits per chain behind the state rows)
   const size_t lds = gibbs_lds_bytes(a.n, a.n_batches, a.n_colours, CPB) +
@@ -670,7 +710,7 @@ static int launch_gibbs(GibbsArgsT<HELD> a, hipStream_t s) {
   }
   const int grid = (int)ceil_div(a.n_chains, CPB);
   if (g_gibbs_probe) { *g_gibbs_probe = GibbsProbe{grid, WAVES * 64, lds}; return DVG_OK; }
-  auto kern = gibbs_kernel<LPC, WAVES, HELD>;
+  auto kern = gibbs_kernel<LPC, WAVES, HELD, SCHED>;
   if (lds > 64 * 1024)
     DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // work = spin updates of the draw (bench.py's sampler roofline)
@@ -716,8 +756,8 @@ static int launch_gibbs_slots(GibbsArgs a, const GibbsSlots& sl, hipStream_t s) 
   return DVG_OK;
 }
 
-template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false>
-static int launch_gibbs_fast(GibbsArgsT<HELD> a, hipStream_t s) {
+template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, bool SCHED = false>
+static int launch_gibbs_fast(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
   constexpr int CPB = WAVES * (64 / LPC);
   const size_t lds = gibbs_lane_lds_bytes(a.n_rows, MB, LPC, a.n, CPB);
   if (lds > 160 * 1024) {
@@ -726,7 +766,7 @@ static int launch_gibbs_fast(GibbsArgsT<HELD> a, hipStream_t s) {
   }
   const int grid = (int)ceil_div(a.n_chains, CPB);
   if (g_gibbs_probe) { *g_gibbs_probe = GibbsProbe{grid, WAVES * 64, lds}; return DVG_OK; }
-  auto kern = gibbs_fast_kernel<LPC, WAVES, MB, NR, MAXS, HELD>;
+  auto kern = gibbs_fast_kernel<LPC, WAVES, MB, NR, MAXS, HELD, SCHED>;
   if (lds > 64 * 1024)
     DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   DVG_LAUNCH_WORK(K_GIBBS, (double)a.n_chains * a.n * a.n_sweeps, kern, dim3(grid), dim3(WAVES * 64), lds, s, a);
@@ -737,8 +777,8 @@ static int launch_gibbs_fast(GibbsArgsT<HELD> a, hipStream_t s) {
 
 using namespace dvg;
 
-template <bool HELD>
-static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD>& a, int n_chains, hipStream_t s);
+template <bool HELD, bool SCHED = false>
+static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, int n_chains, hipStream_t s);
 
 static void gibbs_fill_args(GibbsArgs& a, const dvg_graph_t* g, const float* linear, const float* quadratic, float prefactor,
                             float h_lo, float h_hi, float j_lo, float j_hi, float beta, int8_t* state, int n_chains,
@@ -792,6 +832,28 @@ extern "C" int dvg_gibbs_sample_clamped(const dvg_graph_t* g, const float* linea
   return gibbs_dispatch<true>(g, a, n_chains, (hipStream_t)stream);
 }
 
+// The annealed draw: sweep k of the call on chain c runs at betas[c * beta_chain_stride + k] (include/dvg.h).
+extern "C" int dvg_gibbs_sample_annealed(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                         float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                         const float* betas, int64_t beta_chain_stride,
+                                         int8_t* state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                                         uint32_t sweep0, int n_sweeps, int init, float* samples_out,
+                                         const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  DVG_REQUIRE(g && linear && quadratic && state, "gibbs_annealed: null argument");
+  DVG_REQUIRE(betas, "gibbs_annealed: null betas (a draw at one fixed beta is dvg_gibbs_sample)");
+  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 1, "gibbs_annealed: n_chains=%d n_sweeps=%d (the table has an entry per sweep: at least one)",
+              n_chains, n_sweeps);
+  DVG_REQUIRE(g->n <= 32767, "gibbs_annealed: graph too large (n=%d: 16-bit state offsets)", g->n);
+  DVG_REQUIRE(beta_chain_stride == 0 || beta_chain_stride == n_sweeps,
+              "gibbs_annealed: beta_chain_stride=%lld is neither 0 (one shared row) nor n_sweeps=%d (a row per chain)",
+              (long long)beta_chain_stride, n_sweeps);
+  GibbsSchedArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, dyn);
+  a.betas = betas; a.beta_stride = beta_chain_stride;
+  return gibbs_dispatch<false, true>(g, a, n_chains, (hipStream_t)stream);
+}
+
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,
 // threads per workgroup, LDS bytes per workgroup.  The host side sizes what runs BESIDE the draw with it (the encoder
 // forward's Winograd launches take whole CUs: ModelWrapper leaves the draw's CUs out of their persistent grid).
@@ -812,17 +874,19 @@ extern "C" int dvg_gibbs_launch_info(const dvg_graph_t* g, int n_chains, int* wo
 
 // HELD (the conditional draw) takes the plain draw's choices, with two exceptions: it has no chains-side-by-side form, so the
 // large graphs' many-chain draws run the rolled kernel in 16-wave workgroups, and the A/B forms 3 and 4 count as 0.
-template <bool HELD>
-static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD>& a, int n_chains, hipStream_t s) {
+// SCHED (the annealed draw): the same two exceptions.
+template <bool HELD, bool SCHED>
+static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, int n_chains, hipStream_t s) {
+  constexpr bool VARIANT = HELD || SCHED;
   // (option gibbs_generic = 1 forces the rolled reference schedule: A/B runs and the bit-exactness test of the fast one;
   // 2 = the fast schedule without its two-passes-side-by-side form)
-  const int64_t form = (HELD && opt(OPT_GIBBS_GENERIC) >= 3) ? 0 : opt(OPT_GIBBS_GENERIC);
+  const int64_t form = (VARIANT && opt(OPT_GIBBS_GENERIC) >= 3) ? 0 : opt(OPT_GIBBS_GENERIC);
   // Graphs of more than 12 rows per lane (1024 spins: ~140 KB of tables, one 4-chain workgroup per CU) take the fast
   // schedule only for draws of at most 512 chains: it is the LATENCY form (c5-size graph, 2048 chains x 50 sweeps: 0.59 ms
   // alone against the rolled 16-wave form's 1.20) and costs the same CU-time -- but it takes every CU's LDS while it
   // runs, and the c5 step, whose encoder AND decoder forward hide behind a 1.2 ms draw on half the chip, got slower
   // with it (2.88 -> 3.01 ms: `profiles/r05_gibbs_c5_forms.txt`).
-  if constexpr (!HELD) {
+  if constexpr (!VARIANT) {
     if (form == 4) {  // (4: the chains-side-by-side schedule in 8-chain workgroups whatever the size: A/B runs)
       GibbsSlots sl8;
       if (gibbs_make_slots(g, 8, &sl8)) return launch_gibbs_slots<8>(a, sl8, s);
@@ -853,7 +917,7 @@ static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD>& a, int n_chain
     const int nr = form == 2 ? 1 : g->lane_nr;  // (2: a two-row image walked one row at a time -- empty rows and all)
     const bool small = gibbs_lane_lds_bytes(rows, mb, lpc, g->n, 0) <= 16 * 1024 && n_chains <= 1024 && rows <= 12;
 #define DVG_GIBBS_FAST(LPC, W, MB, NR, MAXS) \
-  if (lpc == LPC && mb == MB && nr == NR && rows <= MAXS && (W == 1) == small) return launch_gibbs_fast<LPC, W, MB, NR, MAXS, HELD>(a, s);
+  if (lpc == LPC && mb == MB && nr == NR && rows <= MAXS && (W == 1) == small) return launch_gibbs_fast<LPC, W, MB, NR, MAXS, HELD, SCHED>(a, s);
     DVG_GIBBS_FAST(16, 1, 4, 1, 12) DVG_GIBBS_FAST(16, 4, 4, 1, 12) DVG_GIBBS_FAST(16, 1, 5, 1, 12) DVG_GIBBS_FAST(16, 4, 5, 1, 12)
     DVG_GIBBS_FAST(32, 1, 4, 1, 12) DVG_GIBBS_FAST(32, 4, 4, 1, 12) DVG_GIBBS_FAST(32, 1, 5, 1, 12) DVG_GIBBS_FAST(32, 4, 5, 1, 12)
     DVG_GIBBS_FAST(64, 1, 4, 1, 12) DVG_GIBBS_FAST(64, 4, 4, 1, 12) DVG_GIBBS_FAST(64, 1, 5, 1, 12) DVG_GIBBS_FAST(64, 4, 5, 1, 12)
@@ -871,14 +935,14 @@ static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD>& a, int n_chain
   if (gibbs_lds_bytes(g->n, g->n_batches, g->n_colours, 4) > 72 * 1024) {
     // ... with static (class, pass) slots when the classes make at most 20 of them (gibbs_slot_kernel; option
     // gibbs_generic = 1 keeps the plain rolled kernel: the reference of the bit-exactness tests)
-    if constexpr (!HELD) {
+    if constexpr (!VARIANT) {
       GibbsSlots sl;
       if (form != 1 && gibbs_make_slots(g, 16, &sl)) return launch_gibbs_slots<16>(a, sl, s);
     }
-    return launch_gibbs<64, 16, HELD>(a, s);
+    return launch_gibbs<64, 16, HELD, SCHED>(a, s);
   }
   const bool small = gibbs_lds_bytes(g->n, g->n_batches, g->n_colours, 0) <= 16 * 1024 && n_chains <= 1024;
-#define DVG_GIBBS_DISPATCH(LPC) return small ? launch_gibbs<LPC, 1, HELD>(a, s) : launch_gibbs<LPC, 4, HELD>(a, s);
+#define DVG_GIBBS_DISPATCH(LPC) return small ? launch_gibbs<LPC, 1, HELD, SCHED>(a, s) : launch_gibbs<LPC, 4, HELD, SCHED>(a, s);
   if (mc <= 16) { DVG_GIBBS_DISPATCH(16) }
   if (mc <= 32) { DVG_GIBBS_DISPATCH(32) }
   DVG_GIBBS_DISPATCH(64)

@@ -25,7 +25,7 @@ from .optim import FlatAdam
 from .persistent_sampler import PersistentQPUSampleHelper
 from .plugin import (DiscreteVariationalAutoencoder, GaussianKernel, GraphRestrictedBoltzmannMachine,
                      maximum_mean_discrepancy_loss, maximum_mean_discrepancy_loss_and_grad)
-from .sampler import get_sampler_and_sampler_kwargs
+from .sampler import beta_schedule, get_sampler_and_sampler_kwargs
 from .viz import LOWER_THRESHOLD, UPPER_THRESHOLD  # /root/reference/demo_configs.py:62-63
 
 _DEFAULT_YAML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "training_parameters.yaml")
@@ -175,7 +175,9 @@ class ModelWrapper:
                 self._dvae_optimizer.exp_avg.data_ptr(), self._dvae_optimizer.exp_avg_sq.data_ptr(),
                 self._grbm._linear.data_ptr(), self._grbm._quadratic.data_ptr(),
                 0 if (s._state is None or not s.persistent) else s._state.data_ptr(),  # (restarted chains: a fresh tensor per draw)
-                0 if self._dyn is None else self._dyn.ptr)
+                0 if self._dyn is None else self._dyn.ptr,
+                # (a changed beta schedule: another number of sweeps per draw -- baked in -- or a new table)
+                int(s.sweeps), 0 if getattr(s, "_betas", None) is None else s._betas.data_ptr())
 
     # -- exact resume: an EXTRA file next to the reference-schema checkpoint, never read by the UI
     def save_training_state(self, file_path) -> None:
@@ -227,9 +229,12 @@ class ModelWrapper:
         n = self.n_latents
         plan = build_plan(n, ei, ej)
         old = self.sampler
-        self.sampler = GibbsSampler(plan, list(range(n)), beta=old.beta, sweeps=old.sweeps, seed=old.seed,
+        betas = getattr(old, "_betas", None)  # (with a schedule set, old.sweeps is the schedule's length)
+        self.sampler = GibbsSampler(plan, list(range(n)), beta=old.beta, sweeps=old.sweeps if betas is None else old._fixed_sweeps, seed=old.seed,
                                     persistent=old.persistent, device=self._device, chain_offset=old.chain_offset,
                                     h_range=tuple(old.properties["h_range"]), j_range=tuple(old.properties["j_range"]))
+        if betas is not None:
+            self.sampler.set_beta_schedule(betas)
         grbm = GraphRestrictedBoltzmannMachine(list(range(n)), list(zip(ei.tolist(), ej.tolist())))
         self._grbm = grbm.to(self._device)
         self._make_optimizers()
@@ -266,6 +271,12 @@ class ModelWrapper:
             device=self._device,
             chain_offset=rank * num_reads,  # chains are globally numbered: G GPUs sample G*num_reads distinct chains
         )
+        # GIBBS_BETA_START (optional): every draw anneals from that beta to the sampler's own over its GIBBS_SWEEPS sweeps,
+        # spaced as GIBBS_BETA_SCHEDULE says ("geometric", the default, or "linear")
+        beta_start = self._params.get("GIBBS_BETA_START")
+        if beta_start is not None:
+            kind = str(self._params.get("GIBBS_BETA_SCHEDULE", "geometric"))
+            self.sampler.set_beta_schedule(beta_schedule(float(beta_start), self.sampler.beta, self.sampler.sweeps, kind))
         grbm = GraphRestrictedBoltzmannMachine(graph.nodes, graph.edges)
         self._grbm = grbm.to(self._device)
         self._dvae.gumbel_seed = int(self.RANDOM_SEED) + 7919 * rank
@@ -826,20 +837,28 @@ class ModelWrapper:
 
     # ------------------------------------------------------------------ generation (tensor-returning core)
     @torch.no_grad()
-    def generate_images(self, sharpen: bool = False, lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD) -> torch.Tensor:
+    def generate_images(self, sharpen: bool = False, lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD,
+                        betas=None) -> torch.Tensor:
         """Sampler -> decoder -> clip, the compute of /root/reference/src/model_wrapper.py:355-385
-        (plotting left to the caller).  Returns (NUM_READS, 1, 32, 32) on the device."""
-        images, _samples = self._generate(sharpen, lower, upper)
+        (plotting left to the caller).  Returns (NUM_READS, 1, 32, 32) on the device.  ``betas``: a (S,) or
+        (NUM_READS, S) schedule -- generate from FRESH annealed chains (``GibbsSampler.sample_annealed``) instead of the
+        sampler's own draw."""
+        images, _samples = self._generate(sharpen, lower, upper, betas)
         return images
 
     @torch.no_grad()
-    def _generate(self, sharpen: bool, lower: float, upper: float):
+    def _generate(self, sharpen: bool, lower: float, upper: float, betas=None):
         # (rank-local, like save(): data-parallel callers run sync_buffers() on every rank first)
         self._dvae.eval()
         self._grbm.eval()
-        samples = self._grbm.sample(self.sampler, prefactor=self.PREFACTOR, device=self._device,
-                                    linear_range=self.linear_range, quadratic_range=self.quadratic_range,
-                                    sample_params=self.sampler_kwargs)
+        if betas is None:
+            samples = self._grbm.sample(self.sampler, prefactor=self.PREFACTOR, device=self._device,
+                                        linear_range=self.linear_range, quadratic_range=self.quadratic_range,
+                                        sample_params=self.sampler_kwargs)
+        else:
+            samples = self.sampler.sample_annealed(self._grbm._linear, self._grbm._quadratic, self.PREFACTOR,
+                                                   self.linear_range, self.quadratic_range, betas,
+                                                   num_reads=int(self.sampler_kwargs.get("num_reads", 1)))
         images = self._dvae.decoder(samples.unsqueeze(1)).squeeze(1).clip(0.0, 1.0)
         if sharpen:
             over = (images > upper).to(images.dtype)   # heaviside(x, 0): strict

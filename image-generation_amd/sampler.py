@@ -52,6 +52,74 @@ class GraphHandle:
             pass
 
 
+def beta_schedule(beta_start: float, beta_end: float, num_sweeps: int, kind: str = "geometric") -> np.ndarray:
+    """The inverse temperature of each sweep of an annealed draw, ``num_sweeps`` float32 values from ``beta_start`` (hot)
+    to ``beta_end`` (the target), as ``neal.SimulatedAnnealingSampler`` spaces them: ``kind`` "geometric" (both ends > 0)
+    or "linear".  The points are computed in float64 (``np.geomspace`` / ``np.linspace``) and rounded to float32; the
+    first entry is ``float32(beta_start)``, the last ``float32(beta_end)``; ``num_sweeps == 1`` gives ``[beta_end]``."""
+    if kind not in ("geometric", "linear"):
+        raise ValueError(f"beta schedule kind must be 'geometric' or 'linear', got {kind!r}")
+    if isinstance(num_sweeps, bool) or int(num_sweeps) != num_sweeps or int(num_sweeps) < 1:
+        raise ValueError(f"num_sweeps must be an integer >= 1, got {num_sweeps!r}")
+    num_sweeps = int(num_sweeps)
+    b0, b1 = float(beta_start), float(beta_end)
+    if not (np.isfinite(b0) and np.isfinite(b1)) or b0 < 0.0 or b1 < 0.0:
+        raise ValueError(f"beta_start={beta_start!r}, beta_end={beta_end!r}: both must be finite and >= 0")
+    if kind == "geometric" and not (b0 > 0.0 and b1 > 0.0):
+        raise ValueError(f"a geometric schedule needs both ends > 0, got beta_start={b0}, beta_end={b1}")
+    if num_sweeps == 1:
+        return np.array([b1], dtype=np.float32)
+    pts = np.geomspace(b0, b1, num_sweeps) if kind == "geometric" else np.linspace(b0, b1, num_sweeps)
+    out = pts.astype(np.float32)
+    out[0], out[-1] = np.float32(b0), np.float32(b1)
+    return out
+
+
+_make_beta_schedule = beta_schedule  # (sample_ising has a keyword of that name)
+
+
+def _check_beta_table(betas, what: str, rows: Optional[int] = None):
+    """The host-side checks of a table of betas, no device work: shape (S,) or (rows, S) with S >= 1; a CUDA tensor must
+    be float32 (its values are the caller's business: looking would be a host sync); host values -- a sequence, an
+    array, a CPU tensor -- must be finite and >= 0 once rounded to float32.  Returns the float32 host array, or None
+    for a CUDA tensor."""
+    on_device = torch.is_tensor(betas) and betas.is_cuda
+    if on_device:
+        if betas.dtype != torch.float32:
+            raise _lib.DvgError(f"{what}: a device table must be float32, got {betas.dtype}")
+        host, shape = None, tuple(betas.shape)
+    else:
+        try:
+            host = np.asarray(betas.detach().numpy() if torch.is_tensor(betas) else betas, dtype=np.float64)
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"{what}: not a numeric table ({exc})") from None
+        with np.errstate(over="ignore"):
+            host = host.astype(np.float32)
+        shape = host.shape  # (before ascontiguousarray: it makes a scalar one-dimensional)
+        host = np.ascontiguousarray(host)
+    want = "(sweeps,)" if rows is None else f"(sweeps,) or ({rows}, sweeps)"
+    if len(shape) not in (1, 2) or int(np.prod(shape)) == 0 or (len(shape) == 2 and (rows is None or int(shape[0]) != rows)):
+        raise _lib.DvgError(f"{what} must be {want} with at least one sweep, got {tuple(shape)}")
+    if host is not None and not (np.isfinite(host).all() and (host >= 0).all()):
+        raise ValueError(f"{what}: every beta must be finite and >= 0")
+    return host
+
+
+def _beta_table(betas, device, what: str, rows: Optional[int] = None, own: bool = False) -> torch.Tensor:
+    """``betas``, checked (:func:`_check_beta_table`), as a contiguous float32 tensor on ``device``: host values are
+    uploaded, a CUDA tensor is used as it is (``own``: copied)."""
+    host = _check_beta_table(betas, what, rows)
+    device = torch.device(device)
+    if host is None:
+        if device.type == "cuda" and device.index is not None and betas.device != device:
+            raise _lib.DvgError(f"{what} is on {betas.device}, expected {device}")
+        table = betas.detach().contiguous()
+        return table.clone() if own and table.data_ptr() == betas.data_ptr() else table
+    if device.type != "cuda":
+        raise _lib.DvgError(f"{what}: the sampler's device is {device}; the HIP path has no CPU fallback")
+    return torch.from_numpy(host).to(device)
+
+
 class _Record:
     def __init__(self, sample, energy):
         self.sample = sample
@@ -65,17 +133,21 @@ class SampleSet:
     ``device_tensor`` keeps the float32 samples on the GPU so ``sampleset_to_tensor``
     needs no host round trip."""
 
-    def __init__(self, samples: np.ndarray, variables: Sequence, energy=None, vartype="SPIN", device_tensor=None):
+    def __init__(self, samples: np.ndarray, variables: Sequence, energy=None, vartype="SPIN", device_tensor=None,
+                 device_energy=None):
         self._samples = samples
         self._energy = energy
         self.variables = list(variables)
         self.vartype = vartype
         self.device_tensor = device_tensor
+        self.device_energy = device_energy  # (reads,) float32 on the GPU: the per-read energy, not yet on the host
 
     @property
     def record(self):
         if self._samples is None:  # lazily materialise on the host
             self._samples = self.device_tensor.to(torch.int8).cpu().numpy()
+        if self._energy is None and self.device_energy is not None:
+            self._energy = self.device_energy.cpu().numpy()
         return _Record(self._samples, self._energy)
 
     def __len__(self):
@@ -116,6 +188,12 @@ class GibbsSampler:
         # random word with the training draws, and interleaving them leaves the training stream as it was
         self.cond_seed = self.seed ^ 0x636F6E64
         self.cond_sweep_count = 0
+        # ... and so do the one-off annealed draws (sample_annealed)
+        self.anneal_seed = self.seed ^ 0x616E6E6C
+        self.anneal_sweep_count = 0
+        # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
+        self._betas: Optional[torch.Tensor] = None
+        self._fixed_sweeps = self.sweeps
 
     # -- native fast path ------------------------------------------------------------------
     @property
@@ -128,6 +206,23 @@ class GibbsSampler:
         self._state = None
         self.sweep_count = 0
         self.cond_sweep_count = 0
+        self.anneal_sweep_count = 0
+
+    def set_beta_schedule(self, betas) -> None:
+        """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
+        (S,) schedule for every chain and every draw (``dvg_gibbs_sample_annealed``, shared row).  Sets ``sweeps = S``;
+        the key, ``sweep_count``, ``init`` and persistence are those of the fixed-beta draw.  ``betas``: a host sequence,
+        array or CPU tensor (checked: finite, >= 0) or a CUDA float32 tensor; it is copied into a device tensor of the
+        sampler's own (a new one per call: a captured training step notices and is captured again).  ``None`` restores
+        the fixed-beta draw (``dvg_gibbs_sample`` at ``beta``) and the sweeps per draw it had."""
+        if betas is None:
+            if self._betas is not None:
+                self._betas, self.sweeps = None, self._fixed_sweeps
+            return
+        table = _beta_table(betas, self.device, "betas", own=True)
+        if self._betas is None:
+            self._fixed_sweeps = self.sweeps
+        self._betas, self.sweeps = table, int(table.shape[0])
 
     def launch_info(self, num_reads: int) -> dict:
         """Launch geometry of one draw of ``num_reads`` chains (``dvg_gibbs_launch_info``: nothing is launched):
@@ -158,14 +253,28 @@ class GibbsSampler:
         inf = float("inf")
         hl, hh = linear_range if linear_range is not None else (-inf, inf)
         jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+        betas = self._betas
+        if betas is not None and (betas.device != lin.device or int(betas.shape[0]) != self.sweeps):
+            raise _lib.DvgError(f"the beta schedule ({tuple(betas.shape)} on {betas.device}) does not match the draw "
+                                f"({self.sweeps} sweeps on {lin.device}); set it again with set_beta_schedule")
         with torch.cuda.device(lin.device):
-            _lib.check(
-                L.dvg_gibbs_sample(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
-                                   float(hh), float(jl), float(jh), self.beta, self._state.data_ptr(), num_reads,
-                                   self.chain_offset & 0xFFFFFFFF, self.seed, self.sweep_count & 0xFFFFFFFF,
-                                   self.sweeps, init, out.data_ptr(), _lib.DYN, _lib.stream_ptr(lin.device)),
-                "dvg_gibbs_sample",
-            )
+            if betas is None:
+                _lib.check(
+                    L.dvg_gibbs_sample(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
+                                       float(hh), float(jl), float(jh), self.beta, self._state.data_ptr(), num_reads,
+                                       self.chain_offset & 0xFFFFFFFF, self.seed, self.sweep_count & 0xFFFFFFFF,
+                                       self.sweeps, init, out.data_ptr(), _lib.DYN, _lib.stream_ptr(lin.device)),
+                    "dvg_gibbs_sample",
+                )
+            else:
+                _lib.check(
+                    L.dvg_gibbs_sample_annealed(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor),
+                                                float(hl), float(hh), float(jl), float(jh), betas.data_ptr(), 0,
+                                                self._state.data_ptr(), num_reads, self.chain_offset & 0xFFFFFFFF,
+                                                self.seed, self.sweep_count & 0xFFFFFFFF, self.sweeps, init,
+                                                out.data_ptr(), _lib.DYN, _lib.stream_ptr(lin.device)),
+                    "dvg_gibbs_sample_annealed",
+                )
         self.sweep_count += self.sweeps
         self.calls += 1
         return out
@@ -223,14 +332,119 @@ class GibbsSampler:
         self.cond_sweep_count += n_sweeps
         return out
 
+    def sample_annealed(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
+                        quadratic_range, betas, *, num_reads: Optional[int] = None,
+                        start: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A one-off annealed draw (``dvg_gibbs_sample_annealed``): sweep k runs at ``betas[k]`` -- ``betas`` of shape
+        (S,), one schedule for all chains -- or at ``betas[c, k]`` on chain c -- shape (C, S), a temperature ladder.
+        ``betas``: a host sequence, array or CPU tensor (checked here: finite, >= 0; then uploaded) or a CUDA float32
+        tensor, used as it is.  ``start=None``: ``num_reads`` fresh chains from the INIT stream (with a (C, S) table
+        ``num_reads`` defaults to C); ``start`` (C, n) int8 or float32 +-1 on the device: the chains begin there.
+        Returns (C, n) float32 +-1 on the device; no host sync.
+
+        Apart from the graph handle it shares nothing with the training draws: it leaves the persistent chains,
+        ``sweep_count``, ``calls`` and any schedule set with :meth:`set_beta_schedule` alone, counts its sweeps in
+        ``anneal_sweep_count`` and draws its random words under its own key ``anneal_seed``; chain ids are
+        ``chain_offset + arange(C)``."""
+        n = self.plan.n
+        # every argument check comes before the first library call (the table's upload included)
+        if start is not None:
+            if not torch.is_tensor(start):
+                raise _lib.DvgError(f"start must be a tensor, got {type(start).__name__}")
+            if start.dtype not in (torch.float32, torch.int8):
+                raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
+            if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1:
+                raise _lib.DvgError(f"start must be (chains, {n}), got {tuple(start.shape)}")
+            if not start.is_cuda:
+                raise _lib.DvgError(f"start must live on the GPU (got {start.device}); the HIP path has no CPU fallback")
+            if num_reads is not None and num_reads != int(start.shape[0]):
+                raise _lib.DvgError(f"num_reads={num_reads!r} but start has {int(start.shape[0])} chains")
+            C = int(start.shape[0])
+        elif num_reads is not None:
+            if isinstance(num_reads, bool) or int(num_reads) != num_reads or int(num_reads) < 1:
+                raise ValueError(f"num_reads must be an integer >= 1, got {num_reads!r}")
+            C = int(num_reads)
+        else:
+            try:
+                shape = tuple(betas.shape) if hasattr(betas, "shape") else np.shape(betas)
+            except ValueError:
+                shape = ()
+            if len(shape) != 2 or int(shape[0]) < 1:
+                raise ValueError("sample_annealed needs num_reads, start or a (chains, sweeps) table to know how many chains to draw")
+            C = int(shape[0])
+        _check_beta_table(betas, "betas", rows=C)
+        lin = _lib.require_cuda(linear.detach(), "linear")
+        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
+        if lin.numel() != n or quad.numel() != self.plan.n_edges:
+            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
+        for name, t in (("start", start), ("betas", betas)):
+            if torch.is_tensor(t) and t.is_cuda and t.device != lin.device:
+                raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
+        table = _beta_table(betas, lin.device, "betas", rows=C)
+        S = int(table.shape[-1])
+        stride = S if table.dim() == 2 else 0
+        if start is None:
+            state, init = torch.empty((C, n), dtype=torch.int8, device=lin.device), 1
+        else:
+            state, init = start.detach().to(torch.int8, copy=True).contiguous(), 0  # the call's own chains
+        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
+        inf = float("inf")
+        hl, hh = linear_range if linear_range is not None else (-inf, inf)
+        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+        with torch.cuda.device(lin.device):
+            _lib.check(
+                _lib.lib().dvg_gibbs_sample_annealed(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor),
+                                                     float(hl), float(hh), float(jl), float(jh), table.data_ptr(), stride,
+                                                     state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF, self.anneal_seed,
+                                                     self.anneal_sweep_count & 0xFFFFFFFF, S, init, out.data_ptr(), None,
+                                                     _lib.stream_ptr(lin.device)),
+                "dvg_gibbs_sample_annealed",
+            )
+        self.anneal_sweep_count += S
+        return out
+
     # -- dimod-style entry point -----------------------------------------------------------
     def sample_ising(self, h: Dict, J: Dict, num_reads: int = 1, answer_mode: str = "raw", auto_scale: bool = False,
-                     annealing_time: float = 1.0, label: str = "", **_unused) -> SampleSet:
+                     annealing_time: float = 1.0, label: str = "", beta_schedule=None, beta_range=None,
+                     num_sweeps: Optional[int] = None, beta_schedule_type: str = "geometric", **_unused) -> SampleSet:
         """Same call the reference makes on its QPU sampler (kwargs built at
         /root/reference/src/utils/common.py:130-138).  ``h``/``J`` are already
-        scaled by the prefactor and clamped by the caller (plugin ``to_ising``)."""
+        scaled by the prefactor and clamped by the caller (plugin ``to_ising``).
+
+        Annealed reads, under ``neal.SimulatedAnnealingSampler``'s names: ``beta_range=(hot, target)`` with
+        ``num_sweeps`` (default: the sampler's ``sweeps``) and ``beta_schedule_type`` "geometric" / "linear", or an
+        explicit ``beta_schedule`` ((S,) or (num_reads, S); ``beta_schedule_type`` may then be "custom").  Either one
+        draws ``num_reads`` FRESH chains through :meth:`sample_annealed` (its key and counter; the persistent chains
+        are left alone).  ``annealing_time`` is accepted, as the reference passes it, and unused: nothing maps a QPU's
+        microseconds to a schedule.
+
+        The returned set carries the per-read Ising energy ``h.s + sum J s_i s_j`` of the ``(h, J)`` given, computed on
+        the device (``dvg_grbm_energy``) and brought to the host when ``.record`` is read."""
         if auto_scale:
             raise ValueError("auto_scale=True is not supported: the sampler draws from the distribution it is given")
+        betas = None
+        if beta_schedule is not None:
+            if beta_range is not None:
+                raise ValueError("give beta_schedule or beta_range, not both")
+            if beta_schedule_type not in ("custom", "geometric", "linear"):
+                raise ValueError(f"beta_schedule_type must be 'geometric', 'linear' or 'custom', got {beta_schedule_type!r}")
+            betas = beta_schedule
+        elif beta_range is not None:
+            if beta_schedule_type not in ("geometric", "linear"):
+                raise ValueError(f"beta_schedule_type must be 'geometric' or 'linear' with beta_range, got {beta_schedule_type!r}")
+            try:
+                b0, b1 = beta_range
+            except (TypeError, ValueError):
+                raise ValueError(f"beta_range must be (beta_start, beta_end), got {beta_range!r}") from None
+            betas = _make_beta_schedule(b0, b1, self.sweeps if num_sweeps is None else num_sweeps, beta_schedule_type)
+        elif num_sweeps is not None:
+            raise ValueError("num_sweeps needs beta_range (or a beta_schedule): a fixed-beta draw runs the sampler's own sweeps")
+        if betas is not None:
+            if isinstance(num_reads, bool) or int(num_reads) != num_reads or int(num_reads) < 1:
+                raise ValueError(f"num_reads must be an integer >= 1, got {num_reads!r}")
+            _check_beta_table(betas, "beta_schedule", rows=int(num_reads))  # (before anything is built or uploaded)
+            if num_sweeps is not None and beta_schedule is not None and int(num_sweeps) != int(np.shape(betas)[-1]):
+                raise ValueError(f"num_sweeps={num_sweeps} does not match the beta_schedule given ({np.shape(betas)[-1]} sweeps)")
         idx = {v: k for k, v in enumerate(self.nodes)}
         lin = torch.zeros(self.plan.n, dtype=torch.float32)
         for v, val in h.items():
@@ -244,8 +458,16 @@ class GibbsSampler:
                 raise ValueError(f"coupler {(a, b)} is not an edge of the sampler's graph")
             quad[edge_pos[key]] = float(val)
         dev = self.device
-        t = self.sample_native(lin.to(dev), quad.to(dev), 1.0, None, None, num_reads)
-        return SampleSet(None, self.nodes, energy=None, device_tensor=t)
+        lin, quad = lin.to(dev), quad.to(dev)
+        if betas is None:
+            t = self.sample_native(lin, quad, 1.0, None, None, num_reads)
+        else:
+            t = self.sample_annealed(lin, quad, 1.0, None, None, betas, num_reads=num_reads)
+        from . import functional as F  # (functional imports this module)
+
+        with torch.no_grad():
+            energy = F.grbm_energy(t, lin, quad, self.graph)
+        return SampleSet(None, self.nodes, energy=None, device_tensor=t, device_energy=energy)
 
 
 def get_sampler_and_sampler_kwargs(num_reads: int, annealing_time: float, n_latents: int, random_seed: int, qpu: str,

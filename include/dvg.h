@@ -135,6 +135,26 @@ int dvg_gibbs_sample_clamped(const dvg_graph_t *g, const float *linear, const fl
                              uint32_t sweep0, int n_sweeps, int init,
                              const uint8_t *clamp, int64_t clamp_chain_stride, float *samples_out,
                              const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The annealed draw: dvg_gibbs_sample with beta looked up per sweep, and optionally per chain, as
+ * neal.SimulatedAnnealingSampler's beta_range / num_sweeps / beta_schedule_type offer it.  Sweep k of the call (global
+ * index sweep0 + k) on chain c runs at  beta = betas[c * beta_chain_stride + k];  everything else is "DVG block-Gibbs v1"
+ * unchanged -- the field sum, z = clamp(rn(two_beta * f), -87, 87) with two_beta = 2 * beta (exact), spec_exp, the Philox
+ * counter (spin, chain id, sweep >> 2, STREAM_GIBBS), the decision, the INIT stream.  So oracle/gibbs.py::gibbs_sweeps called
+ * once per sweep (that sweep's beta, sweep0 + k, one sweep) on the chains that share a table row is the draw, bit for bit.
+ *   betas: DEVICE pointer, float32.  beta_chain_stride = 0: one row of n_sweeps entries shared by all chains; = n_sweeps:
+ *     a row per chain (temperature ladders: chains of one model at different temperatures in one launch); anything else,
+ *     betas == NULL or n_sweeps < 1 is DVG_E_INVALID.  The values must be finite and >= 0; they are NOT checked on the
+ *     device (beta = 0: every spin a fair coin).
+ *   dyn: as for dvg_gibbs_sample (the sweep index comes from the device); the table index is always relative to the
+ *     call's first sweep.
+ *   Every other argument as for dvg_gibbs_sample; with every entry equal to `beta` the two agree bit for bit.  No
+ *     annealed form of dvg_gibbs_sample_clamped. */
+int dvg_gibbs_sample_annealed(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                              float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                              const float *betas, int64_t beta_chain_stride,
+                              int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                              uint32_t sweep0, int n_sweeps, int init, float *samples_out,
+                              const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and

@@ -3,7 +3,11 @@ Prints the draw time per kernel form -- inside a training step the same draw sha
 with the encoder's GEMMs and takes longer (bench.py's `sampler` entry is that in-situ number).
 `clamped`: also the conditional draw (per-chain masks) at held fractions 0, 0.5 and 0.9 -- timed as the call
 GibbsSampler.sample_conditional with int8 / uint8 tensors: the kernel plus the call's own copy of the start state (a
-(chains, n) int8 device copy), where the plain rows time the kernel on the sampler's persistent chains."""
+(chains, n) int8 device copy), where the plain rows time the kernel on the sampler's persistent chains.
+`annealed`: also the annealed draw (dvg_gibbs_sample_annealed) on the sampler's persistent chains, as the plain rows are
+timed: a geometric schedule 0.05 -> 20 shared by all chains (GibbsSampler.set_beta_schedule), and the same kernel with a
+table row per chain (a ladder: chain c ends at beta 20 (c + 1) / chains).
+`repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -21,33 +25,63 @@ quad = torch.from_numpy((5.0 * rng.uniform(-1, 1, plan.n_edges)).astype(np.float
 print(f"n={n} chains={C} sweeps={sweeps} colours={plan.n_colours} max class={max(np.diff(plan.class_ptr))} "
       f"max degree={int(np.diff(plan.adj_ptr).max())}")
 only_default = "default" in sys.argv  # (PMC passes: the product's form only)
+repeat = max([int(a.split("=")[1]) for a in sys.argv if a.startswith("repeat=")] + [1])
+
+
+def timed(draw):
+    """us per draw, five draws per timing, `repeat` timings after one warm-up draw; the last draw's output"""
+    out = draw()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(repeat):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            out = draw()
+        e1.record(); torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) / 5 * 1e3)
+    return ts, out
+
+
+def row(name, ts, updates, out):
+    t = float(np.median(ts))
+    spread = f"  (median of {len(ts)}: min {min(ts):.1f} max {max(ts):.1f})" if len(ts) > 1 else ""
+    print(f"  {name:26s} {t:9.1f} us per draw  {updates/t/1e3:8.2f} G spin updates/s  checksum {float(out.sum()):.0f}{spread}")
+
+
 forms = (("default", dict()), ("one row at a time", dict(gibbs_generic=2)), ("rolled reference", dict(gibbs_generic=1)),
          ("chains side by side, 8-chain workgroups", dict(gibbs_generic=4)))
 for name, opts in forms[:1] if only_default else forms:
     with _lib.option_scope(**opts):
         s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
-        s.sample_native(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            out = s.sample_native(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)
-        e1.record(); torch.cuda.synchronize()
-        t = e0.elapsed_time(e1) / 5
-        print(f"  {name:26s} {t*1e3:9.1f} us per draw  {C*n*sweeps/t/1e6:8.2f} G spin updates/s  checksum {float(out.sum()):.0f}")
+        ts, out = timed(lambda: s.sample_native(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C))
+        row(name, ts, C * n * sweeps, out)
 if "clamped" in sys.argv:
     s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
     start = torch.from_numpy(np.where(rng.uniform(size=(C, n)) < 0.5, -1, 1).astype(np.int8)).cuda()
     for frac in (0.0, 0.5, 0.9):
         clamp = torch.from_numpy((rng.uniform(size=(C, n)) < frac).astype(np.uint8)).cuda()
-        s.sample_conditional(lin, quad, 0.05, (-4, 4), (-1, 1), start, clamp)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            out = s.sample_conditional(lin, quad, 0.05, (-4, 4), (-1, 1), start, clamp)
-        e1.record(); torch.cuda.synchronize()
-        t = e0.elapsed_time(e1) / 5
-        free = C * n - int(clamp.sum())
-        print(f"  {'cond. call, %.0f %% held' % (100 * frac):26s} {t*1e3:9.1f} us per draw  {free*sweeps/t/1e6:8.2f} G spin updates/s  "
-              f"checksum {float(out.sum()):.0f}")
+        ts, out = timed(lambda: s.sample_conditional(lin, quad, 0.05, (-4, 4), (-1, 1), start, clamp))
+        row("cond. call, %.0f %% held" % (100 * frac), ts, (C * n - int(clamp.sum())) * sweeps, out)
+if "annealed" in sys.argv:
+    shared = smp.beta_schedule(0.05, 20.0, sweeps)
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    s.set_beta_schedule(shared)
+    ts, out = timed(lambda: s.sample_native(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C))
+    row("annealed, shared table", ts, C * n * sweeps, out)
+    # a row per chain, on persistent chains like the rows above: the raw call (sample_annealed draws one-off chains)
+    ladder = torch.from_numpy(np.stack([smp.beta_schedule(0.05, 20.0 * (c + 1) / C, sweeps) for c in range(C)])).cuda()
+    state = torch.empty((C, n), dtype=torch.int8, device="cuda")
+    out = torch.empty((C, n), dtype=torch.float32, device="cuda")
+    at = [0]
+
+    def per_chain():
+        _lib.check(_lib.lib().dvg_gibbs_sample_annealed(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0,
+                                                        ladder.data_ptr(), sweeps, state.data_ptr(), C, 0, seed, at[0], sweeps,
+                                                        int(at[0] == 0), out.data_ptr(), None, _lib.stream_ptr()),
+                   "dvg_gibbs_sample_annealed")
+        at[0] += sweeps
+        return out
+
+    ts, out = timed(per_chain)
+    row("annealed, table per chain", ts, C * n * sweeps, out)
