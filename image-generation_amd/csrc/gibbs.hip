@@ -50,8 +50,19 @@ struct GibbsSchedArgs : GibbsArgs {
   const float* betas;   // [n_chains or 1][n_sweeps]: beta of sweep k of the call (finite, >= 0: not checked)
   int64_t beta_stride;  // n_sweeps (a row per chain) or 0 (one row for all chains)
 };
-template <bool HELD, bool SCHED = false>
-using GibbsArgsT = std::conditional_t<SCHED, GibbsSchedArgs, std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>;
+// AIS draws (dvg_gibbs_sample_ais): the annealed draw, weighed -- per chain the energy of its state under the scaled, clamped
+// (h, J), carried along from the local fields the updates compute anyway, and the log importance weight
+// -sum_k (beta_k - beta_{k-1}) E^(k) of annealed importance sampling ("DVG AIS v1", include/dvg.h).  SCHED is a mode: 0 fixed
+// beta, GIBBS_TABLE the table, GIBBS_WEIGH the table and the two float64 accumulators.  The spins are the annealed draw's.
+struct GibbsAisArgs : GibbsSchedArgs {
+  float beta_from;         // beta_{-1}: the inverse temperature the start states are a sample of
+  double* log_weight_out;  // [n_chains]
+  double* energy_out;      // [n_chains] or null
+};
+constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2;
+template <bool HELD, int SCHED = 0>
+using GibbsArgsT = std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
+                                      std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs, std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>;
 
 // a conditional draw's start state: held spins from `state` always, free ones from the INIT stream (init) or from `state`
 template <int LPC>
@@ -187,15 +198,34 @@ __device__ __forceinline__ _Float16 gibbs_decide(float f, float two_beta, uint32
   return (b < 1.0f) ? (_Float16)1.0f : (_Float16)-1.0f;
 }
 
+// AIS: one spin's addend of the start energy, 1/2 s (hs + f) -- exact in float64
+__device__ __forceinline__ double gibbs_start_energy(_Float16 s, float hs, float f) {
+  return 0.5 * (double)(float)s * ((double)hs + (double)f);
+}
+// AIS: the energy change of an update decided on the field f, (s_new - s_old) f = +-2 f or 0 -- exact in float32
+__device__ __forceinline__ double gibbs_energy_step(float s_new, float s_old, float f) {
+  return (double)__fmul_rn(__fsub_rn(s_new, s_old), f);
+}
+// AIS: sum of a chain's LPC lane shares, in every lane of the chain (its lanes are active together)
+template <int LPC>
+__device__ __forceinline__ double gibbs_chain_sum(double v) {
+#pragma unroll
+  for (int m = LPC / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, LPC);
+  return v;
+}
+
 // words of one chain's row of held flags in LDS (the rolled schedule of a conditional draw), one bit per spin
 __host__ __device__ __forceinline__ int gibbs_held_words(int n) { return (n + 31) >> 5; }
 
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
 // HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
 // passed over in its class.  SCHED: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead.
-template <int LPC, int WAVES, bool HELD = false, bool SCHED = false>
+// SCHED == GIBBS_WEIGH: a lane also keeps its share `e` of the chain's energy (the start addends of spins l, l + LPC, ...,
+// then every update it makes) and its share `lw` of the log weight; lane 0 of the chain stores the sums.
+template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
+  constexpr bool AIS = SCHED == GIBBS_WEIGH;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n;
   const GibbsLds L = gibbs_carve(smem, n, a.n_batches, a.n_colours);
@@ -249,11 +279,24 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
       bt = a.betas + (int64_t)chain * a.beta_stride;
       beta_next = bt[0];
     }
+    [[maybe_unused]] double e = 0.0, lw = 0.0;
+    [[maybe_unused]] float beta_prev = 0.0f;
+    if constexpr (AIS) {
+      beta_prev = a.beta_from;
+      for (int i = l; i < n; i += LPC) {
+        const float hsi = L.hs[i];
+        e += gibbs_start_energy(st[i], hsi, gibbs_field(hsi, L.row[i], L, st, a.n_batches, a.max_batches));
+      }
+    }
     for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
       const uint32_t tq = t >> 2, tw = t & 3u;
       float two_beta;
       if constexpr (SCHED) {
         two_beta = __fmul_rn(2.0f, beta_next);
+        if constexpr (AIS) {
+          lw -= ((double)beta_next - (double)beta_prev) * e;
+          beta_prev = beta_next;
+        }
         const uint32_t kn = t - sweep0 + 1u;
         if (kn < (uint32_t)a.n_sweeps) beta_next = bt[kn];
       } else {
@@ -268,7 +311,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
           }
           const float f = gibbs_field(L.hs[i], L.row[i], L, st, a.n_batches, a.max_batches);
           const u32x4 r = philox4x32_10((uint32_t)i, cid, tq, STREAM_GIBBS, a.k0, a.k1);
-          st[i] = gibbs_decide(f, two_beta, pick(r, tw));
+          const _Float16 s_new = gibbs_decide(f, two_beta, pick(r, tw));
+          if constexpr (AIS) e += gibbs_energy_step((float)s_new, (float)st[i], f);
+          st[i] = s_new;
         }
         // the next class reads what this one wrote (same wave): order LDS traffic
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -280,6 +325,14 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
       const float v = (float)st[i];
       dst[i] = (int8_t)v;
       if (a.samples_out) a.samples_out[(size_t)chain * n + i] = v;
+    }
+    if constexpr (AIS) {
+      e = gibbs_chain_sum<LPC>(e);
+      lw = gibbs_chain_sum<LPC>(lw);
+      if (l == 0) {
+        a.log_weight_out[chain] = lw;
+        if (a.energy_out) a.energy_out[chain] = e;
+      }
     }
   }
 }
@@ -537,9 +590,13 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
 // per slot in a register; a held slot draws no random word and stores to the sink.
 // SCHED: the annealed draw -- two_beta is the lane's chain's table entry of the sweep, read one sweep ahead (one load per
 // sweep and lane; with the shared row every lane of a wave reads one address, with a row per chain the LPC lanes of a chain).
-template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, bool SCHED = false>
+// SCHED == GIBBS_WEIGH: the AIS draw -- one walk over the steps before the first sweep for the start energy (the fields of
+// the start state; no decision, no store), then one convert and one float64 add per update; the value a slot's spin has
+// is one bit per slot in a register, like `held`.
+template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
+  constexpr bool AIS = SCHED == GIBBS_WEIGH;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n, n_pad = (n + 15) & ~15;
   const int n_rows = a.n_rows;
@@ -631,11 +688,52 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
     bt = a.betas + (int64_t)chain * a.beta_stride;
     beta_next = bt[0];
   }
+  [[maybe_unused]] double e = 0.0, lw = 0.0;
+  [[maybe_unused]] float beta_prev = 0.0f;
+  [[maybe_unused]] uint32_t up = 0u;  // AIS: bit k = the spin of slot k is +1
+  if constexpr (AIS) {
+    beta_prev = a.beta_from;
+    // the sweep loop's walk over the steps, on the start state (it leaves `o` at step 0's offsets again)
+#pragma unroll
+    for (int c = 0; c < MAXS / NR; ++c) {
+      const int k0 = NR * c, k1 = k0 + NR - 1;
+      if (k0 >= n_rows) continue;
+      const unsigned char* wlk = wl + (size_t)k0 * MB * LPC * 16;
+      const unsigned char* ol_next = ol + (size_t)(k0 + NR < n_rows ? k0 + NR : 0) * MB * LPC * 8;
+      float f[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) f[r] = hs[k0 + r];
+      bool both = false;
+      if constexpr (NR == 2) both = __builtin_amdgcn_ballot_w64(sp[k1] >= 0) != 0;
+      if (both) gibbs_lane_class<MB, LPC, NR, NR>(f, o, wlk, ol_next, stb);
+      else gibbs_lane_class<MB, LPC, NR, 1>(f, o, wlk, ol_next, stb);
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {  // (a row the step left out has no spin in any lane of the wave)
+        if (sp[k0 + r] >= 0) {
+          const _Float16 s = st[sp[k0 + r]];
+          e += gibbs_start_energy(s, hs[k0 + r], f[r]);
+          if ((float)s > 0.0f) up |= 1u << (k0 + r);
+        }
+      }
+    }
+  }
+  // AIS: slot K's decision S on the field F goes into the lane's energy share; lanes that update no spin there add 0
+#define DVG_GIBBS_WEIGH(K, S, F)                                                                            \
+  if constexpr (AIS) {                                                                                      \
+    const bool fr = DVG_GIBBS_FREE(K);                                                                      \
+    const float sn = (float)(S), so = ((up >> (K)) & 1u) ? 1.0f : -1.0f;                                    \
+    e += gibbs_energy_step(fr ? sn : so, so, F);                                                            \
+    if (fr) up = (up & ~(1u << (K))) | (sn > 0.0f ? 1u << (K) : 0u);                                        \
+  }
   for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
     const uint32_t tq = t >> 2, tw = t & 3u;
     float two_beta;
     if constexpr (SCHED) {
       two_beta = __fmul_rn(2.0f, beta_next);
+      if constexpr (AIS) {
+        lw -= ((double)beta_next - (double)beta_prev) * e;
+        beta_prev = beta_next;
+      }
       const uint32_t kn = t - sweep0 + 1u;
       if (kn < (uint32_t)a.n_sweeps) beta_next = bt[kn];
     } else {
@@ -653,7 +751,10 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
 #pragma unroll
     for (int c = 0; c < MAXS / NR; ++c) {
       const int k0 = NR * c, k1 = k0 + NR - 1;
-      if (k0 >= n_rows) break;
+      if (k0 >= n_rows) {  // (AIS: with the early exit the compiler left this loop rolled at 20 slots, the slot registers in scratch)
+        if constexpr (AIS) continue;
+        else break;
+      }
       const unsigned char* wlk = wl + (size_t)k0 * MB * LPC * 16;
       const unsigned char* ol_next = ol + (size_t)(k0 + NR < n_rows ? k0 + NR : 0) * MB * LPC * 8;
       float f[NR];
@@ -665,11 +766,14 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
         gibbs_lane_class<MB, LPC, NR, NR>(f, o, wlk, ol_next, stb);
         const _Float16 s0 = gibbs_decide(f[0], two_beta, DVG_GIBBS_WORD(k0));
         const _Float16 s1 = gibbs_decide(f[NR - 1], two_beta, DVG_GIBBS_WORD(k1));
+        DVG_GIBBS_WEIGH(k0, s0, f[0])
+        DVG_GIBBS_WEIGH(k1, s1, f[NR - 1])
         *(DVG_GIBBS_FREE(k0) ? st + sp[k0] : sink) = s0;
         *(DVG_GIBBS_FREE(k1) ? st + sp[k1] : sink) = s1;
       } else {  // one row (NR = 2: the step's second row is empty for the whole wave)
         gibbs_lane_class<MB, LPC, NR, 1>(f, o, wlk, ol_next, stb);
         const _Float16 s0 = gibbs_decide(f[0], two_beta, DVG_GIBBS_WORD(k0));
+        DVG_GIBBS_WEIGH(k0, s0, f[0])
         *(DVG_GIBBS_FREE(k0) ? st + sp[k0] : sink) = s0;
       }
       // the next class reads what this one wrote (same wave): order LDS traffic.  (Passes of one class are independent
@@ -679,12 +783,21 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
     }
   }
 #undef DVG_GIBBS_WORD
+#undef DVG_GIBBS_WEIGH
 #undef DVG_GIBBS_FREE
   int8_t* dst = a.state + (size_t)chain * n;
   for (int i = l; i < n; i += LPC) {
     const float v = (float)st[i];
     dst[i] = (int8_t)v;
     if (a.samples_out) a.samples_out[(size_t)chain * n + i] = v;
+  }
+  if constexpr (AIS) {
+    e = gibbs_chain_sum<LPC>(e);
+    lw = gibbs_chain_sum<LPC>(lw);
+    if (l == 0) {
+      a.log_weight_out[chain] = lw;
+      if (a.energy_out) a.energy_out[chain] = e;
+    }
   }
 }
 
@@ -697,7 +810,7 @@ static size_t gibbs_lds_bytes(int n, int n_batches, int n_colours, int chains_pe
 struct GibbsProbe { int workgroups; int threads; size_t lds; };
 static thread_local GibbsProbe* g_gibbs_probe = nullptr;
 
-template <int LPC, int WAVES, bool HELD = false, bool SCHED = false>
+template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 static int launch_gibbs(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
   constexpr int CPB = WAVES * (64 / LPC);
   // (HELD: a row of flag bits per chain behind the state rows)
@@ -756,7 +869,7 @@ static int launch_gibbs_slots(GibbsArgs a, const GibbsSlots& sl, hipStream_t s) 
   return DVG_OK;
 }
 
-template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, bool SCHED = false>
+template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 static int launch_gibbs_fast(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
   constexpr int CPB = WAVES * (64 / LPC);
   const size_t lds = gibbs_lane_lds_bytes(a.n_rows, MB, LPC, a.n, CPB);
@@ -777,7 +890,7 @@ static int launch_gibbs_fast(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
 
 using namespace dvg;
 
-template <bool HELD, bool SCHED = false>
+template <bool HELD, int SCHED = 0>
 static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, int n_chains, hipStream_t s);
 
 static void gibbs_fill_args(GibbsArgs& a, const dvg_graph_t* g, const float* linear, const float* quadratic, float prefactor,
@@ -851,7 +964,35 @@ extern "C" int dvg_gibbs_sample_annealed(const dvg_graph_t* g, const float* line
   gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
                   n_sweeps, init, samples_out, dyn);
   a.betas = betas; a.beta_stride = beta_chain_stride;
-  return gibbs_dispatch<false, true>(g, a, n_chains, (hipStream_t)stream);
+  return gibbs_dispatch<false, GIBBS_TABLE>(g, a, n_chains, (hipStream_t)stream);
+}
+
+// The AIS draw: the annealed draw plus, per chain, its log importance weight and its final energy (include/dvg.h).
+extern "C" int dvg_gibbs_sample_ais(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                    float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                    const float* betas, int64_t beta_chain_stride, float beta_from,
+                                    int8_t* state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                                    uint32_t sweep0, int n_sweeps, int init, float* samples_out,
+                                    double* log_weight_out, double* energy_out,
+                                    const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  DVG_REQUIRE(g && linear && quadratic && state, "gibbs_ais: null argument");
+  DVG_REQUIRE(betas, "gibbs_ais: null betas");
+  DVG_REQUIRE(log_weight_out, "gibbs_ais: null log_weight_out (a draw that is not weighed is dvg_gibbs_sample_annealed)");
+  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 1, "gibbs_ais: n_chains=%d n_sweeps=%d (the table has an entry per sweep: at least one)",
+              n_chains, n_sweeps);
+  DVG_REQUIRE(g->n <= 32767, "gibbs_ais: graph too large (n=%d: 16-bit state offsets)", g->n);
+  DVG_REQUIRE(beta_chain_stride == 0 || beta_chain_stride == n_sweeps,
+              "gibbs_ais: beta_chain_stride=%lld is neither 0 (one shared row) nor n_sweeps=%d (a row per chain)",
+              (long long)beta_chain_stride, n_sweeps);
+  DVG_REQUIRE(beta_from >= 0.0f && beta_from <= 3.4028234663852886e38f, "gibbs_ais: beta_from=%g must be finite and >= 0", (double)beta_from);
+  DVG_REQUIRE(init == 0 || beta_from == 0.0f,
+              "gibbs_ais: init=%d with beta_from=%g (fresh chains are uniform: a sample at beta 0 and at no other)", init, (double)beta_from);
+  GibbsAisArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, dyn);
+  a.betas = betas; a.beta_stride = beta_chain_stride;
+  a.beta_from = beta_from; a.log_weight_out = log_weight_out; a.energy_out = energy_out;
+  return gibbs_dispatch<false, GIBBS_WEIGH>(g, a, n_chains, (hipStream_t)stream);
 }
 
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,
@@ -874,10 +1015,10 @@ extern "C" int dvg_gibbs_launch_info(const dvg_graph_t* g, int n_chains, int* wo
 
 // HELD (the conditional draw) takes the plain draw's choices, with two exceptions: it has no chains-side-by-side form, so the
 // large graphs' many-chain draws run the rolled kernel in 16-wave workgroups, and the A/B forms 3 and 4 count as 0.
-// SCHED (the annealed draw): the same two exceptions.
-template <bool HELD, bool SCHED>
+// SCHED (the annealed draw, weighed or not): the same two exceptions.
+template <bool HELD, int SCHED>
 static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, int n_chains, hipStream_t s) {
-  constexpr bool VARIANT = HELD || SCHED;
+  constexpr bool VARIANT = HELD || SCHED != 0;
   // (option gibbs_generic = 1 forces the rolled reference schedule: A/B runs and the bit-exactness test of the fast one;
   // 2 = the fast schedule without its two-passes-side-by-side form)
   const int64_t form = (VARIANT && opt(OPT_GIBBS_GENERIC) >= 3) ? 0 : opt(OPT_GIBBS_GENERIC);

@@ -178,6 +178,40 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
                                           clamp, sweeps=sweeps, init_free=True)
 
 
+    def _need_local_sampler(self, sampler, what: str) -> None:
+        if not (isinstance(sampler, GibbsSampler) and list(sampler.nodes) == self._nodes):
+            raise TypeError(f"{what} needs the local GibbsSampler built on this model's nodes, got {type(sampler).__name__}")
+
+    def log_partition(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """The AIS estimate of ``log Z`` of the distribution ``sampler`` draws from -- ``exp(-beta E_s)`` with ``E_s`` the
+        energy under the prefactor-scaled, clamped ``(h, J)`` and ``beta = sampler.beta`` unless ``beta=`` says otherwise
+        (:meth:`GibbsSampler.log_partition`; ``num_sweeps``, ``num_reads``, ``schedule`` are passed on).  The local
+        :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "log_partition")
+        return sampler.log_partition(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, **kw)
+
+    @torch.no_grad()
+    def log_likelihood(self, x: torch.Tensor, sampler, *, prefactor: float, linear_range=None, quadratic_range=None,
+                       log_z=None, **kw) -> torch.Tensor:
+        """``log p(x) = -beta E_s(x) - log Z`` per row of ``x`` ((B, n) +-1 on the device) under the distribution
+        ``sampler`` draws from: ``E_s`` the energy under the scaled, clamped ``(h, J)`` (``dvg_grbm_energy``), ``beta =
+        sampler.beta``.  ``log_z``: a value from :meth:`log_partition` (at that beta); None: estimated here, ``**kw``
+        passed on.  With ``beta = 1 / prefactor`` and inactive clamps this is the GRBM's own ``log p(x)``.  Returns (B,)
+        float64 on the device.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "log_likelihood")
+        if log_z is None:
+            log_z = self.log_partition(sampler, prefactor=prefactor, linear_range=linear_range,
+                                       quadratic_range=quadratic_range, **kw).log_z
+        h = prefactor * self._linear.detach()
+        J = prefactor * self._quadratic.detach()
+        if linear_range is not None:
+            h = h.clamp(*linear_range)
+        if quadratic_range is not None:
+            J = J.clamp(*quadratic_range)
+        energy = F.grbm_energy(x, h, J, self.graph_handle(x.device))
+        return -float(sampler.beta) * energy.double() - log_z
+
+
 class GaussianKernel(torch.nn.Module):
     """Multi-bandwidth RBF kernel configuration (/root/reference/src/model_wrapper.py:273).
 

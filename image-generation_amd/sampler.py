@@ -154,6 +154,28 @@ class SampleSet:
         return int(self.device_tensor.shape[0]) if self.device_tensor is not None else len(self._samples)
 
 
+class LogPartition:
+    """What :meth:`GibbsSampler.log_partition` returns.  ``log_z``: float64 device scalar, ``n log 2 + logsumexp(log_weights)
+    - log C``; ``ess``: the effective sample size ``(sum w)^2 / sum w^2`` of the C weights; ``std_err``: the standard
+    error of ``log_z`` to first order, ``sqrt(1 / ess - 1 / C)`` (the relative standard error of the mean weight);
+    ``log_weights`` (C,) float64 and ``samples`` (C, n) float32: the chains."""
+
+    def __init__(self, log_z, ess, std_err, log_weights, samples):
+        self.log_z, self.ess, self.std_err, self.log_weights, self.samples = log_z, ess, std_err, log_weights, samples
+
+    @classmethod
+    def from_weights(cls, n: int, log_weights: torch.Tensor, samples=None, log_z_from: float = None) -> "LogPartition":
+        C = int(log_weights.shape[0])
+        lse = torch.logsumexp(log_weights, 0)
+        base = n * float(np.log(2.0)) if log_z_from is None else float(log_z_from)
+        ess = torch.exp(2.0 * lse - torch.logsumexp(2.0 * log_weights, 0))
+        std_err = torch.sqrt(torch.clamp(1.0 / ess - 1.0 / C, min=0.0))
+        return cls(lse + (base - float(np.log(C))), ess, std_err, log_weights, samples)
+
+    def __repr__(self):
+        return f"LogPartition(log_z={float(self.log_z):.6f}, ess={float(self.ess):.1f}, std_err={float(self.std_err):.4f})"
+
+
 class GibbsSampler:
     """``sample_ising``-compatible local solver running on the MI355X.
 
@@ -191,6 +213,9 @@ class GibbsSampler:
         # ... and so do the one-off annealed draws (sample_annealed)
         self.anneal_seed = self.seed ^ 0x616E6E6C
         self.anneal_sweep_count = 0
+        # ... and the weighed annealed draws (sample_ais, log_partition)
+        self.ais_seed = self.seed ^ 0x61697331
+        self.ais_sweep_count = 0
         # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
         self._betas: Optional[torch.Tensor] = None
         self._fixed_sweeps = self.sweeps
@@ -207,6 +232,7 @@ class GibbsSampler:
         self.sweep_count = 0
         self.cond_sweep_count = 0
         self.anneal_sweep_count = 0
+        self.ais_sweep_count = 0
 
     def set_beta_schedule(self, betas) -> None:
         """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
@@ -332,22 +358,20 @@ class GibbsSampler:
         self.cond_sweep_count += n_sweeps
         return out
 
-    def sample_annealed(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
-                        quadratic_range, betas, *, num_reads: Optional[int] = None,
-                        start: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """A one-off annealed draw (``dvg_gibbs_sample_annealed``): sweep k runs at ``betas[k]`` -- ``betas`` of shape
-        (S,), one schedule for all chains -- or at ``betas[c, k]`` on chain c -- shape (C, S), a temperature ladder.
-        ``betas``: a host sequence, array or CPU tensor (checked here: finite, >= 0; then uploaded) or a CUDA float32
-        tensor, used as it is.  ``start=None``: ``num_reads`` fresh chains from the INIT stream (with a (C, S) table
-        ``num_reads`` defaults to C); ``start`` (C, n) int8 or float32 +-1 on the device: the chains begin there.
-        Returns (C, n) float32 +-1 on the device; no host sync.
-
-        Apart from the graph handle it shares nothing with the training draws: it leaves the persistent chains,
-        ``sweep_count``, ``calls`` and any schedule set with :meth:`set_beta_schedule` alone, counts its sweeps in
-        ``anneal_sweep_count`` and draws its random words under its own key ``anneal_seed``; chain ids are
-        ``chain_offset + arange(C)``."""
+    def _annealed_arguments(self, linear, quadratic, linear_range, quadratic_range, betas, num_reads, start, beta_from=None):
+        """The argument checks and buffers :meth:`sample_annealed` and :meth:`sample_ais` share; every check comes before
+        the first library call.  Returns (lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh))."""
         n = self.plan.n
         # every argument check comes before the first library call (the table's upload included)
+        if beta_from is not None:  # (sample_ais)
+            bf = float(beta_from)
+            with np.errstate(over="ignore"):
+                finite = bool(np.isfinite(np.float32(bf)))
+            if not finite or bf < 0.0:
+                raise ValueError(f"beta_from={beta_from!r} must be finite and >= 0")
+            if start is None and np.float32(bf) != 0.0:
+                raise ValueError(f"beta_from={beta_from!r} with fresh chains: they are uniform, a sample at beta 0 and at no "
+                                 "other; give the chains' states as `start`")
         if start is not None:
             if not torch.is_tensor(start):
                 raise _lib.DvgError(f"start must be a tensor, got {type(start).__name__}")
@@ -370,7 +394,7 @@ class GibbsSampler:
             except ValueError:
                 shape = ()
             if len(shape) != 2 or int(shape[0]) < 1:
-                raise ValueError("sample_annealed needs num_reads, start or a (chains, sweeps) table to know how many chains to draw")
+                raise ValueError("an annealed draw needs num_reads, start or a (chains, sweeps) table to know how many chains to draw")
             C = int(shape[0])
         _check_beta_table(betas, "betas", rows=C)
         lin = _lib.require_cuda(linear.detach(), "linear")
@@ -391,6 +415,25 @@ class GibbsSampler:
         inf = float("inf")
         hl, hh = linear_range if linear_range is not None else (-inf, inf)
         jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+        return lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh)
+
+    def sample_annealed(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
+                        quadratic_range, betas, *, num_reads: Optional[int] = None,
+                        start: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A one-off annealed draw (``dvg_gibbs_sample_annealed``): sweep k runs at ``betas[k]`` -- ``betas`` of shape
+        (S,), one schedule for all chains -- or at ``betas[c, k]`` on chain c -- shape (C, S), a temperature ladder.
+        ``betas``: a host sequence, array or CPU tensor (checked here: finite, >= 0; then uploaded) or a CUDA float32
+        tensor, used as it is.  ``start=None``: ``num_reads`` fresh chains from the INIT stream (with a (C, S) table
+        ``num_reads`` defaults to C); ``start`` (C, n) int8 or float32 +-1 on the device: the chains begin there.
+        Returns (C, n) float32 +-1 on the device; no host sync.
+
+        Apart from the graph handle it shares nothing with the training draws: it leaves the persistent chains,
+        ``sweep_count``, ``calls`` and any schedule set with :meth:`set_beta_schedule` alone, counts its sweeps in
+        ``anneal_sweep_count`` and draws its random words under its own key ``anneal_seed``; chain ids are
+        ``chain_offset + arange(C)``."""
+        lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh) = self._annealed_arguments(
+            linear, quadratic, linear_range, quadratic_range, betas, num_reads, start)
+        C = int(out.shape[0])
         with torch.cuda.device(lin.device):
             _lib.check(
                 _lib.lib().dvg_gibbs_sample_annealed(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor),
@@ -402,6 +445,61 @@ class GibbsSampler:
             )
         self.anneal_sweep_count += S
         return out
+
+    def sample_ais(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                   betas, *, num_reads: Optional[int] = None, start: Optional[torch.Tensor] = None, beta_from: float = 0.0):
+        """An annealed draw, weighed (``dvg_gibbs_sample_ais``, "DVG AIS v1" in include/dvg.h): the chains of
+        :meth:`sample_annealed` with the same arguments plus, per chain, the log importance weight of annealed
+        importance sampling, ``-sum_k (betas[k] - betas[k-1]) E(state before sweep k)`` with ``betas[-1] = beta_from``, and
+        the energy of the returned state under the scaled, clamped ``(h, J)`` -- both accumulated inside the kernel.
+        ``log Z(betas[-1]) ~= log Z(beta_from) + logsumexp(log_weights) - log C`` (:meth:`log_partition`).
+
+        The argument rules are :meth:`sample_annealed`'s.  ``beta_from``: the inverse temperature ``start`` is a sample
+        of; fresh chains (``start=None``) are uniform, so they need ``beta_from == 0``.  Returns ``(samples, log_weights,
+        energies)``: (C, n) float32 +-1, (C,) float64, (C,) float64, on the device; no host sync.
+
+        Its own key ``ais_seed`` and counter ``ais_sweep_count``: the training, conditional and annealed streams are
+        left alone."""
+        lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh) = self._annealed_arguments(
+            linear, quadratic, linear_range, quadratic_range, betas, num_reads, start, beta_from=beta_from)
+        C = int(out.shape[0])
+        log_w = torch.empty((C,), dtype=torch.float64, device=lin.device)
+        energy = torch.empty((C,), dtype=torch.float64, device=lin.device)
+        with torch.cuda.device(lin.device):
+            _lib.check(
+                _lib.lib().dvg_gibbs_sample_ais(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
+                                                float(hh), float(jl), float(jh), table.data_ptr(), stride, float(beta_from),
+                                                state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF, self.ais_seed,
+                                                self.ais_sweep_count & 0xFFFFFFFF, S, init, out.data_ptr(),
+                                                log_w.data_ptr(), energy.data_ptr(), None, _lib.stream_ptr(lin.device)),
+                "dvg_gibbs_sample_ais",
+            )
+        self.ais_sweep_count += S
+        return out, log_w, energy
+
+    def log_partition(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                      *, beta: Optional[float] = None, num_sweeps: int = 1000, num_reads: int = 1024,
+                      schedule: str = "linear") -> "LogPartition":
+        """The AIS estimate of ``log Z(beta)`` of the scaled, clamped model (``beta=None``: the sampler's own):
+        ``num_reads`` fresh chains annealed from beta 0 -- where ``log Z = n log 2`` -- to ``beta`` over ``num_sweeps``
+        sweeps through :meth:`sample_ais`.  ``schedule`` "linear": ``linspace(0, beta, num_sweeps)``; "geometric": 0, then
+        ``geomspace(beta / num_sweeps, beta, num_sweeps - 1)``.  Returns a :class:`LogPartition`; its reductions are
+        plain torch ops on the device, no host sync."""
+        if schedule not in ("linear", "geometric"):
+            raise ValueError(f"schedule must be 'linear' or 'geometric', got {schedule!r}")
+        if isinstance(num_sweeps, bool) or int(num_sweeps) != num_sweeps or int(num_sweeps) < 2:
+            raise ValueError(f"num_sweeps must be an integer >= 2, got {num_sweeps!r}")
+        b = float(self.beta if beta is None else beta)
+        if not np.isfinite(b) or b <= 0.0:
+            raise ValueError(f"beta={beta!r} must be finite and > 0")
+        num_sweeps = int(num_sweeps)
+        if schedule == "linear":
+            betas = beta_schedule(0.0, b, num_sweeps, "linear")
+        else:
+            betas = np.concatenate([np.zeros(1, np.float32), beta_schedule(b / num_sweeps, b, num_sweeps - 1, "geometric")])
+        samples, log_w, _energy = self.sample_ais(linear, quadratic, prefactor, linear_range, quadratic_range, betas,
+                                                  num_reads=num_reads)
+        return LogPartition.from_weights(self.plan.n, log_w, samples)
 
     # -- dimod-style entry point -----------------------------------------------------------
     def sample_ising(self, h: Dict, J: Dict, num_reads: int = 1, answer_mode: str = "raw", auto_scale: bool = False,

@@ -155,6 +155,29 @@ int dvg_gibbs_sample_annealed(const dvg_graph_t *g, const float *linear, const f
                               int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
                               uint32_t sweep0, int n_sweeps, int init, float *samples_out,
                               const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The AIS draw ("DVG AIS v1"): dvg_gibbs_sample_annealed with the same arguments -- its spins, random words and betas, bit
+ * for bit -- plus, per chain, the log importance weight of annealed importance sampling and the energy of the returned
+ * state, accumulated inside the kernel from the local fields the updates compute anyway.  With hs, Js the scaled, clamped
+ * float32 fields, s^(k) the chain's state before sweep k of the call, beta_k = betas[c * beta_chain_stride + k] and
+ * beta_{-1} = beta_from, everything below in float64 unless marked:
+ *   f_i(s)   the float32 field exactly as v1 computes it (hs_i, then the CSR-order signed adds, each rounded);
+ *   E_0      = sum_i 1/2 s_i (hs_i + f_i(s^(0)))  (each addend exact; with exact fields: sum hs_i s_i + sum_e Js_e s_i s_j);
+ *   every update of spin i adds  (s_new - s_old) f_i,  f_i the float32 field the decision used (+-2 f_i or 0, exact);
+ *   E^(k)    = E_0 plus the updates of sweeps 0 .. k-1;
+ *   log_weight_out[c] = -sum_{k=0}^{n_sweeps-1} (beta_k - beta_{k-1}) E^(k)   (the differences of float32 values: exact);
+ *   energy_out[c]     = E^(n_sweeps), the energy of the returned state (may be NULL).
+ * Only the order of the float64 additions is the implementation's.  The estimate:  log Z(beta_last) ~= log Z(beta_from)
+ * + logsumexp_c(log_weight) - log n_chains,  with log Z(0) = n log 2.  Fresh chains (init != 0) come from the INIT stream,
+ * uniform +-1, which is the beta = 0 distribution and no other: init != 0 needs beta_from == 0.  DVG_E_INVALID, before any
+ * launch: what dvg_gibbs_sample_annealed rejects, log_weight_out == NULL, init != 0 with beta_from != 0, beta_from negative
+ * or not finite.  Both outputs are DEVICE pointers, float64, [n_chains].  No weighed form of dvg_gibbs_sample_clamped. */
+int dvg_gibbs_sample_ais(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                         float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                         const float *betas, int64_t beta_chain_stride, float beta_from,
+                         int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                         uint32_t sweep0, int n_sweeps, int init, float *samples_out,
+                         double *log_weight_out, double *energy_out,
+                         const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and

@@ -1,0 +1,251 @@
+"""CPU-side checks of the weighed annealed draw ("DVG AIS v1", ``dvg_gibbs_sample_ais`` in include/dvg.h): the definition
+itself (``tests/ais_oracle.py``) against float64 energies and against enumeration, the symbol, and every argument error of
+the Python surface -- raised before the library is touched."""
+import ctypes
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ais_oracle  # noqa: E402
+from image_generation_amd import _lib, graphs, sampler as smp  # noqa: E402
+from oracle import gibbs  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME = "dvg_gibbs_sample_ais"
+SEED = 775321899904
+
+
+def _zephyr(n):
+    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, graphs.zephyr_graph(12)))
+    nodes, ei, ej = graphs.edges_of(mg)
+    return graphs.build_plan(n, ei, ej), nodes
+
+
+# ------------------------------------------------------------------------------------------------ (a) float32 fields
+def test_float32_field_energy_is_the_float64_energy_within_the_bound_of_v1s_arithmetic():
+    """Zephyr 128 with the annealed GPU test's recipe, 7 sweeps to beta = 20.  The definition's running energy (start
+    energy from float32 fields, then (s_new - s_old) f per update) against ``oracle.gibbs.energy`` of the same state, before
+    every sweep and at the end; and its log weight against the direct ``-sum_k dbeta_k energy(s^(k))``.
+
+    Bound: a field of degree d is d rounded float32 adds, off by at most g_i = gamma_d (|hs_i| + sum_j |Js_ij|) with
+    gamma_d = d u / (1 - d u), u = 2^-24.  The start energy sums 1/2 s_i (hs_i + f_i): off by at most 1/2 sum_i g_i.  An
+    update that flips spin i adds +-2 f_i: off by at most 2 g_i.  So E^(k) is off by at most B_k = 1/2 sum_i g_i + 2 (sum
+    of g_i over the chain's flips before sweep k), and log_w by at most sum_k |dbeta_k| B_k.  (The float64 additions of
+    both sides: N addends of absolute sum A, 2 N 2^-53 A each way -- four orders below.)"""
+    plan, _nodes = _zephyr(128)
+    C = 5
+    rng = np.random.default_rng(plan.n + C)
+    h = (0.05 * rng.uniform(-1, 1, plan.n)).astype(np.float32)
+    J = (5.0 * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)
+    hs, Js = gibbs.scaled_fields(h, J, 0.05, (-4, 4), (-1, 1))
+    ids = np.arange(C, dtype=np.uint32) + 1000
+    betas = np.linspace(0.0, 20.0, 8)[1:].astype(np.float32)
+    r = ais_oracle.ais(plan, hs, Js, betas, ids, SEED, 6, trace=True)
+    S = betas.size
+    assert r.N == plan.n + plan.n * S + S and r.states.shape == (S + 1, C, plan.n)
+
+    adj_ptr = np.asarray(plan.adj_ptr)
+    deg = np.diff(adj_ptr).astype(np.float64)
+    u = 2.0 ** -24
+    gamma = deg * u / (1.0 - deg * u)
+    absrow = np.add.reduceat(np.abs(Js.astype(np.float64))[np.asarray(plan.adj_eid)], adj_ptr[:-1]) * (deg > 0)
+    g = gamma * (np.abs(hs.astype(np.float64)) + absrow)
+    ei, ej = np.asarray(plan.edge_i), np.asarray(plan.edge_j)
+
+    slack = 4.0 * r.N * 2.0 ** -53 * r.A
+    flipped = np.zeros(C)
+    direct, direct_bound = np.zeros(C), np.zeros(C)
+    prev = 0.0
+    worst_e = 0.0
+    for k in range(S + 1):
+        bound_k = 0.5 * g.sum() + 2.0 * flipped
+        err = np.abs(r.energies[k] - gibbs.energy(r.states[k], hs, Js, ei, ej))
+        worst_e = max(worst_e, float(err.max()))
+        assert (err <= bound_k + slack).all(), (k, err, bound_k)
+        if k < S:
+            db = float(betas[k]) - prev
+            prev = float(betas[k])
+            direct -= db * gibbs.energy(r.states[k], hs, Js, ei, ej)
+            direct_bound += abs(db) * bound_k
+            flipped += ((r.states[k + 1] != r.states[k]) * g[None, :]).sum(axis=1)
+    assert np.array_equal(r.energies[S], r.energy) and np.array_equal(r.states[S], r.spins)
+    err_w = np.abs(r.log_w - direct)
+    print(f"energy: worst error {worst_e:.3e} (bound at the end {float((0.5 * g.sum() + 2 * flipped).max()):.3e}); "
+          f"log_w ~ {float(np.abs(r.log_w).max()):.1f}: worst error {float(err_w.max()):.3e} (bound {float(direct_bound.max()):.3e})")
+    assert flipped.min() > 0 and (err_w <= direct_bound + float(np.abs(betas).max()) * slack).all(), (err_w, direct_bound)
+
+
+# ------------------------------------------------------------------------------------------------ (b) enumeration
+def zephyr16_case(beta):
+    """The 16-spin case of the issue: graph, scaled fields, table, chain ids, key, first sweep."""
+    plan, nodes = _zephyr(16)
+    assert plan.n_edges == 72
+    rng = np.random.default_rng(16)
+    h = (0.5 * rng.uniform(-1, 1, plan.n)).astype(np.float32)
+    J = rng.uniform(-1, 1, plan.n_edges).astype(np.float32)
+    hs, Js = gibbs.scaled_fields(h, J, 1.0, (-4, 4), (-1, 1))
+    betas = np.linspace(0.0, beta, 65)[1:].astype(np.float32)
+    ids = np.arange(1024, dtype=np.uint32) + 11
+    return plan, nodes, h, J, hs, Js, betas, ids, SEED ^ 0x616E6E6C, 5
+
+
+@pytest.mark.parametrize("beta,known", [(1.0, 24.417731), (2.0, None)])
+def test_the_estimator_against_enumeration(beta, known):
+    """1024 fresh chains, 64 sweeps on a linear schedule: the definition's estimate of log Z lies within 3 standard errors
+    of the sum over all 2^16 states."""
+    plan, _nodes, _h, _J, hs, Js, betas, ids, key, sweep0 = zephyr16_case(beta)
+    exact = ais_oracle.exact_log_z(plan.n, hs, Js, np.asarray(plan.edge_i), np.asarray(plan.edge_j), float(betas[-1]))
+    if known is not None:
+        assert abs(exact - known) < 1e-6, exact
+    r = ais_oracle.ais(plan, hs, Js, betas, ids, key, sweep0)
+    est, ess, std_err = ais_oracle.log_z_estimate(plan.n, r.log_w)
+    print(f"beta {beta}: exact {exact:.6f}, estimate {est:.6f}, off by {abs(est - exact):.4f}, ESS {ess:.0f}, 3 std_err {3 * std_err:.3f}")
+    assert abs(est - exact) <= 3.0 * std_err
+
+
+def test_log_partition_reductions_match_the_helper():
+    """``LogPartition.from_weights`` (plain torch ops) against the helper's numpy on arbitrary weights."""
+    rng = np.random.default_rng(0)
+    lw = rng.normal(700.0, 3.0, size=257)
+    est, ess, std_err = ais_oracle.log_z_estimate(16, lw)
+    res = smp.LogPartition.from_weights(16, torch.from_numpy(lw))
+    assert res.log_z.dtype == torch.float64 and res.log_z.dim() == 0
+    assert abs(float(res.log_z) - est) < 1e-9 and abs(float(res.ess) - ess) < 1e-6 * ess and abs(float(res.std_err) - std_err) < 1e-9
+    one = smp.LogPartition.from_weights(4, torch.zeros(8, dtype=torch.float64))  # equal weights: ESS = C, no error
+    assert abs(float(one.log_z) - 4 * np.log(2.0)) < 1e-12 and abs(float(one.ess) - 8.0) < 1e-9 and float(one.std_err) < 1e-6
+
+
+# ------------------------------------------------------------------------------------------------ the symbol and its checks
+def test_symbol_is_declared_bound_and_exported():
+    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
+    assert NAME in _lib.SIGNATURES
+    _lib.build()
+    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+
+
+def _call(g, lin, quad, state, betas, stride, n_sweeps, log_w, beta_from=0.0, init=1, n_chains=4):
+    L = _lib.lib()
+    rc = L.dvg_gibbs_sample_ais(g, lin, quad, 1.0, -1, 1, -1, 1, betas, stride, beta_from, state, n_chains, 0, 0, 0, n_sweeps,
+                                init, None, log_w, None, None, None)
+    return rc, L.dvg_last_error()
+
+
+def test_argument_validation_without_gpu():
+    """What ``dvg_gibbs_sample_annealed`` rejects, a null ``log_weight_out``, fresh chains with a nonzero ``beta_from`` and a
+    negative or non-finite ``beta_from`` are DVG_E_INVALID (-1) with a message, before any HIP call."""
+    rc, msg = _call(None, None, None, None, None, 0, 3, None)
+    assert rc == -1 and b"null" in msg
+    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first field: the spin count)
+    ctypes.c_int32.from_buffer(graph).value = 64
+    g = ctypes.cast(graph, ctypes.c_void_p)
+    dummy = ctypes.create_string_buffer(16)
+    p = ctypes.cast(dummy, ctypes.c_void_p)
+    rc, msg = _call(g, p, p, p, None, 0, 3, p)
+    assert rc == -1 and b"betas" in msg
+    rc, msg = _call(g, p, p, p, p, 0, 3, None)
+    assert rc == -1 and b"log_weight_out" in msg
+    for stride in (3, 1, 6, 8, -7, 64):
+        rc, msg = _call(g, p, p, p, p, stride, 7, p)
+        assert rc == -1 and b"beta_chain_stride" in msg, (stride, rc, msg)
+    for n_sweeps in (0, -1):
+        rc, msg = _call(g, p, p, p, p, 0, n_sweeps, p)
+        assert rc == -1 and b"n_sweeps" in msg
+    rc, msg = _call(g, p, p, p, p, 0, 3, p, n_chains=0)
+    assert rc == -1 and b"n_chains" in msg
+    rc, msg = _call(g, p, p, p, p, 0, 3, p, beta_from=0.3, init=1)
+    assert rc == -1 and b"init" in msg and b"beta_from" in msg
+    for bad in (-0.5, float("nan"), float("inf"), -float("inf")):
+        for init in (0, 1):
+            rc, msg = _call(g, p, p, p, p, 0, 3, p, beta_from=bad, init=init)
+            assert rc == -1 and b"beta_from" in msg, (bad, init, rc, msg)
+
+
+# ------------------------------------------------------------------------------------------------ (c) the Python surface
+@pytest.fixture
+def untouched(monkeypatch):
+    """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
+    def boom(*_a, **_k):
+        raise AssertionError("the library was touched before the argument error was raised")
+
+    monkeypatch.setattr(_lib, "lib", boom)
+    n = 12
+    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
+    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
+    lin, quad = torch.zeros(n), torch.zeros(plan.n_edges)
+    return s, lin, quad
+
+
+BAD_TABLES = [
+    ([0.1, -0.5, 1.0], ValueError), ([0.1, float("nan")], ValueError), ([0.1, float("inf")], ValueError),
+    (np.array([1e39, 1.0]), ValueError), (torch.tensor([0.5, -1.0]), ValueError), ([], _lib.DvgError),
+    (np.zeros((2, 0)), _lib.DvgError), (np.ones((2, 2, 2)), _lib.DvgError), (3.0, _lib.DvgError), (["a", "b"], ValueError),
+    (np.ones((3, 5)), _lib.DvgError),  # a row per chain, but three rows for four chains
+]
+
+
+@pytest.mark.parametrize("betas,exc", BAD_TABLES)
+def test_sample_ais_rejects_bad_tables(untouched, betas, exc):
+    s, lin, quad = untouched
+    with pytest.raises(exc):
+        s.sample_ais(lin, quad, 1.0, None, None, betas, num_reads=4)
+    assert s.ais_sweep_count == 0
+
+
+def test_sample_ais_rejects_beta_from_with_fresh_chains_and_bad_values(untouched):
+    s, lin, quad = untouched
+    n, ok = s.plan.n, [0.1, 1.0, 2.0]
+    call = lambda **kw: s.sample_ais(lin, quad, 1.0, None, None, ok, **kw)  # noqa: E731
+    with pytest.raises(ValueError, match="fresh chains"):
+        call(num_reads=4, beta_from=0.3)
+    for bad in (-0.1, float("nan"), float("inf"), 1e39):
+        with pytest.raises(ValueError, match="beta_from"):
+            call(num_reads=4, beta_from=bad)
+        with pytest.raises(ValueError, match="beta_from"):
+            call(start=torch.ones((4, n), dtype=torch.int8), beta_from=bad)  # (checked before the start's device)
+    with pytest.raises(ValueError, match="num_reads"):
+        call()  # how many chains?
+    with pytest.raises(_lib.DvgError, match="GPU"):
+        call(start=torch.ones((4, n), dtype=torch.int8), beta_from=0.3)  # a CPU start state
+    with pytest.raises(_lib.DvgError):  # valid arguments, CPU parameters: the HIP path has no CPU fallback
+        call(num_reads=4)
+    assert (s.ais_sweep_count, s.anneal_sweep_count, s.sweep_count, s.calls, s.cond_sweep_count) == (0, 0, 0, 0, 0)
+
+
+@pytest.mark.parametrize("kw", [dict(schedule="cosine"), dict(schedule=None), dict(num_sweeps=1), dict(num_sweeps=0),
+                                dict(num_sweeps=2.5), dict(beta=0.0), dict(beta=-1.0), dict(beta=float("nan")),
+                                dict(num_reads=0), dict(num_reads=2.5)])
+def test_log_partition_rejects(untouched, kw):
+    s, lin, quad = untouched
+    with pytest.raises(ValueError):
+        s.log_partition(lin, quad, 1.0, None, None, **kw)
+    assert s.ais_sweep_count == 0
+
+
+def test_ais_draws_have_their_own_key_and_counter(untouched):
+    s, _lin, _quad = untouched
+    assert s.ais_seed == 3 ^ 0x61697331 and s.ais_seed not in (s.seed, s.cond_seed, s.anneal_seed) and s.ais_sweep_count == 0
+    s.ais_sweep_count, s.anneal_sweep_count, s.sweep_count = 5, 6, 7
+    s.reset()
+    assert (s.ais_sweep_count, s.anneal_sweep_count, s.sweep_count) == (0, 0, 0)
+
+
+def test_grbm_likelihood_takes_the_local_sampler_only(untouched):
+    from image_generation_amd.plugin import GraphRestrictedBoltzmannMachine
+
+    s, _lin, _quad = untouched
+    nodes = list(range(12))
+    grbm = GraphRestrictedBoltzmannMachine(nodes, [(i, (i + 1) % 12) for i in range(12)])
+    x = torch.ones((2, 12))
+    for other in (object(), smp.GibbsSampler(s.plan, [f"q{i}" for i in range(12)], beta=2.0, sweeps=5, seed=3, device="cuda")):
+        with pytest.raises(TypeError):
+            grbm.log_partition(other, prefactor=1.0)
+        with pytest.raises(TypeError):
+            grbm.log_likelihood(x, other, prefactor=1.0)

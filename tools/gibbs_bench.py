@@ -7,6 +7,9 @@ GibbsSampler.sample_conditional with int8 / uint8 tensors: the kernel plus the c
 `annealed`: also the annealed draw (dvg_gibbs_sample_annealed) on the sampler's persistent chains, as the plain rows are
 timed: a geometric schedule 0.05 -> 20 shared by all chains (GibbsSampler.set_beta_schedule), and the same kernel with a
 table row per chain (a ladder: chain c ends at beta 20 (c + 1) / chains).
+`ais`: also the weighed annealed draw (dvg_gibbs_sample_ais: the annealed draw plus each chain's log importance weight and
+energy, accumulated in the kernel), timed as the annealed rows are -- the raw call on persistent chains, the same shared
+schedule and the same ladder; a second line gives the sums of the last draw's log weights and energies.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -85,3 +88,28 @@ if "annealed" in sys.argv:
 
     ts, out = timed(per_chain)
     row("annealed, table per chain", ts, C * n * sweeps, out)
+if "ais" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    shared = torch.from_numpy(smp.beta_schedule(0.05, 20.0, sweeps)).cuda()
+    ladder = torch.from_numpy(np.stack([smp.beta_schedule(0.05, 20.0 * (c + 1) / C, sweeps) for c in range(C)])).cuda()
+    for name, table, stride in (("ais, shared table", shared, 0), ("ais, table per chain", ladder, sweeps)):
+        state = torch.empty((C, n), dtype=torch.int8, device="cuda")
+        out = torch.empty((C, n), dtype=torch.float32, device="cuda")
+        log_w = torch.empty((C,), dtype=torch.float64, device="cuda")
+        energy = torch.empty((C,), dtype=torch.float64, device="cuda")
+        at = [0]
+
+        def weighed():
+            # (the first draw starts fresh chains, at beta 0; the later ones go on from the chains' states, each a sample at
+            # its table's last entry or near it: the weights of those draws are timed, not used)
+            _lib.check(_lib.lib().dvg_gibbs_sample_ais(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0,
+                                                       table.data_ptr(), stride, 0.0 if at[0] == 0 else 20.0, state.data_ptr(), C, 0,
+                                                       seed, at[0], sweeps, int(at[0] == 0), out.data_ptr(), log_w.data_ptr(),
+                                                       energy.data_ptr(), None, _lib.stream_ptr()),
+                       "dvg_gibbs_sample_ais")
+            at[0] += sweeps
+            return out
+
+        ts, out = timed(weighed)
+        row(name, ts, C * n * sweeps, out)
+        print(f"  {'':26s} sum of log weights {float(log_w.sum()):.6e}  sum of energies {float(energy.sum()):.6e}")
