@@ -1,5 +1,6 @@
 // Development hooks (include/dvg_dev.h): direct launches of the MFMA GEMM kernels for unit tests / micro-benchmarks.
 #include "conv_plan.h"
+#include "gibbs_plan.h"
 #include "mmd_plan.h"
 #include "../../include/dvg_dev.h"
 using namespace dvg;
@@ -71,6 +72,20 @@ extern "C" int dvg_dev_mmd_plan(int64_t nx, int64_t ny, int dim, int64_t out[24]
                          p.pair_launch.grid[0], p.pair_launch.grid[1], p.pair_launch.grid[2], p.distsum.grid[0], p.distsum.grid[1],
                          p.gated_nfb ? (int64_t)p.gated.grid[0] : 0, p.final_grad.grid[0]};
   for (int i = 0; i < 24; ++i) out[i] = v[i];
+  return DVG_OK;
+}
+// The plan of a Gibbs draw under the current option gibbs_generic (gibbs_plan.h); reads host arrays only, needs no device.
+extern "C" int dvg_dev_gibbs_draw_plan(int n, int n_colours, const int32_t* class_ptr, const int32_t* adj_ptr, int n_chains,
+                                       int kind, int64_t out[19]) {
+  DVG_REQUIRE(out && class_ptr && adj_ptr && n > 0 && n_colours > 0 && n_colours <= 64 && n_chains > 0 && kind >= GK_PLAIN &&
+                  kind <= GK_WEIGH,
+              "dev_gibbs_draw_plan: bad argument");
+  const GibbsGraphShape g = gibbs_graph_shape(n, n_colours, class_ptr, adj_ptr);
+  GibbsDrawPlan p;
+  DVG_TRY(gibbs_draw_plan(g, n_chains, (GibbsDrawKind)kind, opt(OPT_GIBBS_GENERIC), &p));
+  const int64_t v[19] = {p.form, p.lpc, p.waves, p.mb, p.nr, p.maxs, p.ch, p.fix, p.slots.n, p.chains_per_block, p.grid, p.threads,
+                         (int64_t)p.lds, g.lane_has, g.lane_lpc, g.lane_mb, g.lane_nr, g.lane_rows, g.n_batches};
+  for (int i = 0; i < 19; ++i) out[i] = v[i];
   return DVG_OK;
 }
 extern "C" int dvg_dev_conv_wino_stats_blocks(int64_t M, int Cout) { return conv_wino_stats_blocks(M, Cout); }

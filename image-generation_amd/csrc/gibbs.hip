@@ -13,6 +13,7 @@
 #include <utility>
 
 #include "common.h"
+#include "gibbs_plan.h"
 #include "graph.h"
 #include "philox.h"
 
@@ -64,23 +65,32 @@ template <bool HELD, int SCHED = 0>
 using GibbsArgsT = std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
                                       std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs, std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>;
 
-// a conditional draw's start state: held spins from `state` always, free ones from the INIT stream (init) or from `state`
-template <int LPC>
-__device__ __forceinline__ void gibbs_load_chain_held(const GibbsHeldArgs& a, _Float16* st, int chain, int l, uint32_t cid,
-                                                      uint32_t sweep0) {
+// A chain's start state, its LPC lanes each taking spins l, l + LPC, ...: from the INIT stream (init) or from `state`.
+// HELD (a conditional draw): held spins from `state` always, free ones as above.
+template <int LPC, bool HELD, typename Args>
+__device__ __forceinline__ void gibbs_load_chain(const Args& a, _Float16* st, int chain, int l, uint32_t cid, uint32_t sweep0) {
   const int n = a.n;
-  const int8_t* src = a.state + (size_t)chain * n;
-  const uint8_t* held = a.clamp + (int64_t)chain * a.clamp_stride;
-  for (int i = l; i < n; i += LPC) {
-    if (a.init && held[i] == 0) {
+  if constexpr (HELD) {
+    const int8_t* src = a.state + (size_t)chain * n;
+    const uint8_t* held = a.clamp + (int64_t)chain * a.clamp_stride;
+    for (int i = l; i < n; i += LPC) {
+      if (a.init && held[i] == 0) {
+        u32x4 r = philox4x32_10((uint32_t)i, cid, sweep0, STREAM_INIT, a.k0, a.k1);
+        st[i] = (r.x >> 31) ? (_Float16)1.0f : (_Float16)-1.0f;
+      } else {
+        st[i] = (_Float16)(float)src[i];
+      }
+    }
+  } else if (a.init) {
+    for (int i = l; i < n; i += LPC) {
       u32x4 r = philox4x32_10((uint32_t)i, cid, sweep0, STREAM_INIT, a.k0, a.k1);
       st[i] = (r.x >> 31) ? (_Float16)1.0f : (_Float16)-1.0f;
-    } else {
-      st[i] = (_Float16)(float)src[i];
     }
+  } else {
+    const int8_t* src = a.state + (size_t)chain * n;
+    for (int i = l; i < n; i += LPC) st[i] = (_Float16)(float)src[i];
   }
 }
-
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 // ---------------------------------------------------------------- the LDS image and the neighbour sum (round 4)
@@ -97,7 +107,6 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fm
 //     round are one straight line: 2 NB reads, then 4 NB state reads, then 4 NB dependent fmas.
 typedef float gf32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t gu32x2 __attribute__((ext_vector_type(2)));
-constexpr int GIBBS_NB = 5;
 
 struct GibbsLds {
   float* hs;         // [n]  clamped prefactor * h
@@ -108,18 +117,7 @@ struct GibbsLds {
   uint16_t* order;   // [n]
   _Float16* state;   // [chains][n_pad]
 };
-__host__ __device__ __forceinline__ size_t gibbs_lds_layout(int n, int n_batches, int n_colours, size_t off[7]) {
-  size_t b = 0;
-  off[0] = b; b += sizeof(float) * (size_t)((n + 3) & ~3);
-  off[1] = b; b += sizeof(float) * 4 * (size_t)(n_batches + 1);
-  off[2] = b; b += sizeof(uint32_t) * (size_t)n;
-  off[3] = b; b += sizeof(int32_t) * (size_t)(n_colours + 1);
-  b = (b + 7) & ~(size_t)7;
-  off[4] = b; b += sizeof(uint16_t) * 4 * (size_t)(n_batches + 1);
-  off[5] = b; b += sizeof(uint16_t) * (size_t)((n + 1) & ~1);
-  off[6] = b;
-  return b;
-}
+// (gibbs_lds_layout: gibbs_plan.h)
 __device__ __forceinline__ GibbsLds gibbs_carve(unsigned char* smem, int n, int n_batches, int n_colours) {
   size_t o[7];
   gibbs_lds_layout(n, n_batches, n_colours, o);
@@ -158,17 +156,21 @@ __device__ __forceinline__ float gibbs_signed_add(_Float16 s, float w, float f) 
   return __builtin_fmaf((float)s, w, f);
 }
 
-// f + (the row's signed couplings, in row order); max_batches is uniform (the graph's longest row)
-__device__ __forceinline__ float gibbs_field(float f, uint32_t rowinfo, const GibbsLds& L, const _Float16* st,
-                                             int zero_batch, int max_batches) {
-  const int first = (int)(rowinfo >> 8), nb = (int)(rowinfo & 255u);
+// f + (the row's signed couplings, in row order); max_batches is uniform (the graph's longest row).  `st`: the chain's
+// state -- its row, or with the state stored [spin][chains] (gibbs_slot_kernel, which stages the offsets as 2 x chains x
+// spin) the lane's chain column.
+// (FIX: the image holds exactly GIBBS_NB batches per spin, spin i's at GIBBS_NB i -- rowinfo = that index; no per-batch select)
+template <bool FIX = false>
+__device__ __forceinline__ float gibbs_field(float f, uint32_t rowinfo, const GibbsLds& L, const void* st, int zero_batch,
+                                             int max_batches) {
+  const int first = FIX ? (int)rowinfo : (int)(rowinfo >> 8), nb = FIX ? GIBBS_NB : (int)(rowinfo & 255u);
   const unsigned char* stb = reinterpret_cast<const unsigned char*>(st);
-  for (int b0 = 0; b0 < max_batches; b0 += GIBBS_NB) {
+  for (int b0 = 0; b0 < (FIX ? GIBBS_NB : max_batches); b0 += GIBBS_NB) {
     gf32x4 w[GIBBS_NB];
     gu32x2 o[GIBBS_NB];
 #pragma unroll
     for (int j = 0; j < GIBBS_NB; ++j) {
-      const int bi = b0 + j < nb ? first + b0 + j : zero_batch;
+      const int bi = (FIX || b0 + j < nb) ? first + b0 + j : zero_batch;
       w[j] = *reinterpret_cast<const gf32x4*>(L.w + 4 * bi);
       o[j] = *reinterpret_cast<const gu32x2*>(L.off + 4 * bi);
     }
@@ -214,9 +216,6 @@ __device__ __forceinline__ double gibbs_chain_sum(double v) {
   return v;
 }
 
-// words of one chain's row of held flags in LDS (the rolled schedule of a conditional draw), one bit per spin
-__host__ __device__ __forceinline__ int gibbs_held_words(int n) { return (n + 31) >> 5; }
-
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
 // HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
 // passed over in its class.  SCHED: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead.
@@ -249,8 +248,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
   // non-persistent draws do not all restart from one configuration)
   const uint32_t sweep0 = a.sweep0_dev ? *a.sweep0_dev : a.sweep0;
   if (valid) {
+    gibbs_load_chain<LPC, HELD>(a, st, chain, l, cid, sweep0);
     if constexpr (HELD) {
-      gibbs_load_chain_held<LPC>(a, st, chain, l, cid, sweep0);
       // (a lane packs whole words: 32 consecutive flags each)
       const uint8_t* held = a.clamp + (int64_t)chain * a.clamp_stride;
       for (int w = l; w < gibbs_held_words(n); w += LPC) {
@@ -258,14 +257,6 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
         for (int b = 0; b < 32 && 32 * w + b < n; ++b) bits |= (held[32 * w + b] != 0 ? 1u : 0u) << b;
         hb[w] = bits;
       }
-    } else if (a.init) {
-      for (int i = l; i < n; i += LPC) {
-        u32x4 r = philox4x32_10((uint32_t)i, cid, sweep0, STREAM_INIT, a.k0, a.k1);
-        st[i] = (r.x >> 31) ? (_Float16)1.0f : (_Float16)-1.0f;
-      }
-    } else {
-      const int8_t* src = a.state + (size_t)chain * n;
-      for (int i = l; i < n; i += LPC) st[i] = (_Float16)(float)src[i];
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -347,42 +338,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
 // half the time.  Here a wave's lanes are 4 spins x 16 chains, and the state is stored [spin][chain]: a neighbour read is
 // four runs of sixteen consecutive halfwords (8 banks each), the table reads four addresses broadcast to sixteen lanes.
 // All 16 waves now work on the same 16 chains, so a colour class ends in a workgroup barrier instead of a wave fence
-// (5 per sweep).  A lane's (class, pass) slots are static (the host lists them: GibbsSlots), the slot loop unrolled.
-struct GibbsSlots { int n; uint32_t last_mask; int16_t lo[20], hi[20]; };
-
-// f + (the row's signed couplings, in row order) with the state stored [spin][16 chains]: `stc` = the lane's chain column
-// (FIX: the image holds exactly GIBBS_NB batches per spin, spin i's at GIBBS_NB i -- rowinfo = that index; no per-batch select)
-template <bool FIX>
-__device__ __forceinline__ float gibbs_field_cm(float f, uint32_t rowinfo, const GibbsLds& L, const unsigned char* stc,
-                                                int zero_batch, int max_batches) {
-  const int first = FIX ? (int)rowinfo : (int)(rowinfo >> 8), nb = FIX ? GIBBS_NB : (int)(rowinfo & 255u);
-  for (int b0 = 0; b0 < (FIX ? GIBBS_NB : max_batches); b0 += GIBBS_NB) {
-    gf32x4 w[GIBBS_NB];
-    gu32x2 o[GIBBS_NB];
-#pragma unroll
-    for (int j = 0; j < GIBBS_NB; ++j) {
-      const int bi = (FIX || b0 + j < nb) ? first + b0 + j : zero_batch;
-      w[j] = *reinterpret_cast<const gf32x4*>(L.w + 4 * bi);
-      o[j] = *reinterpret_cast<const gu32x2*>(L.off + 4 * bi);
-    }
-    _Float16 h[GIBBS_NB][4];
-#pragma unroll
-    for (int j = 0; j < GIBBS_NB; ++j) {  // (this kernel stages the offsets as 32 x spin: gibbs_stage<.., 32>)
-      h[j][0] = *reinterpret_cast<const _Float16*>(stc + (o[j][0] & 0xffffu));
-      h[j][1] = *reinterpret_cast<const _Float16*>(stc + (o[j][0] >> 16));
-      h[j][2] = *reinterpret_cast<const _Float16*>(stc + (o[j][1] & 0xffffu));
-      h[j][3] = *reinterpret_cast<const _Float16*>(stc + (o[j][1] >> 16));
-    }
-#pragma unroll
-    for (int j = 0; j < GIBBS_NB; ++j) {
-      f = gibbs_signed_add(h[j][0], w[j][0], f);
-      f = gibbs_signed_add(h[j][1], w[j][1], f);
-      f = gibbs_signed_add(h[j][2], w[j][2], f);
-      f = gibbs_signed_add(h[j][3], w[j][3], f);
-    }
-  }
-  return f;
-}
+// (5 per sweep).  A lane's (class, pass) slots are static (the host lists them: GibbsSlots, gibbs_plan.h), the slot loop unrolled.
 
 template <int K, int MAXS, int SB, bool FIX>  // SB: bytes between two spins in the state image (2 x chains per workgroup)
 struct GibbsSlotLoop {
@@ -399,7 +355,7 @@ struct GibbsSlotLoop {
       uint32_t irk = desc;
       asm volatile("" : "+v"(irk));
       const int i = FIX ? (int)irk : (int)(irk >> 21);
-      const float f = gibbs_field_cm<FIX>(L.hs[i], FIX ? (uint32_t)(GIBBS_NB * i) : (irk & 0x1fffffu), L, stc, a.n_batches, a.max_batches);
+      const float f = gibbs_field<FIX>(L.hs[i], FIX ? (uint32_t)(GIBBS_NB * i) : (irk & 0x1fffffu), L, stc, a.n_batches, a.max_batches);
       // the four words of a (spin, sweep >> 2) counter serve four sweeps: drawn once, three kept (with the LDS gathers out
       // of the way the kernel is bound by its vector instructions, and a Philox call is 100 of an update's 190)
       uint32_t word;
@@ -422,17 +378,6 @@ struct GibbsSlotLoop<MAXS, MAXS, SB, FIX> {
                                              uint32_t, uint32_t, bool, const uint32_t (&)[MAXS], uint32_t (&)[MAXS],
                                              uint32_t (&)[MAXS], uint32_t (&)[MAXS]) {}
 };
-
-// LDS of the fixed-row image (FIX): h [n] | couplings [n][20] | state offsets [n][20] | order [n] | state [n_pad][CH]
-__host__ __device__ __forceinline__ size_t gibbs_fix_layout(int n, size_t off[5]) {
-  size_t b = 0;
-  off[0] = b; b += sizeof(float) * (size_t)((n + 3) & ~3);
-  off[1] = b; b += sizeof(float) * 20 * (size_t)n;
-  off[2] = b; b += sizeof(uint16_t) * 20 * (size_t)n;
-  off[3] = b; b += sizeof(uint16_t) * (size_t)((n + 7) & ~7);
-  off[4] = b;
-  return b;
-}
 
 // CH chains per workgroup (16; 8: the draws of few chains -- twice the workgroups, runs of 4 banks).  FIX: graphs of at most
 // 20 neighbours per spin whose image fits with every spin's row padded to five batches (c5's do, with 2 KB to spare): the
@@ -538,11 +483,7 @@ __global__ __launch_bounds__(1024) void gibbs_slot_kernel(GibbsArgs a, GibbsSlot
 // 0.73; two passes side by side 0.68; offsets one step ahead + straight-line steps 0.54.  Forms that lost: two waves
 // per chain with 4-wave workgroups (faster alone, twice the workgroups beside the encoder: slower step); a wave PAIR per
 // chain in 8-wave workgroups meeting at a barrier per class (0.61 ms); 8 or 2 waves per workgroup (step +0.2 ms).)
-__host__ __device__ __forceinline__ size_t gibbs_lane_lds_bytes(int slots, int mb, int lpc, int n, int chains) {
-  // tables | one state row per chain | a 64-entry sink per wave (where lanes without a spin in a slot store)
-  return (size_t)slots * mb * lpc * 24 + sizeof(_Float16) * (size_t)chains * ((n + 15) & ~15) +
-         sizeof(_Float16) * 64 * (size_t)((chains * lpc + 63) / 64);
-}
+// (LDS: gibbs_lane_lds_bytes, gibbs_plan.h)
 
 // One colour-class step of the fast schedule: NRUN rows (slots k, k + 1) side by side -- per row the same reads and
 // the same adds, in row order.  The rows' state offsets `o` were read one step AHEAD (they do not depend on the state);
@@ -638,8 +579,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   // non-persistent draws do not all restart from one configuration)
   const uint32_t sweep0 = a.sweep0_dev ? *a.sweep0_dev : a.sweep0;
   if (valid) {
+    // (gibbs_load_chain, spelled out for the plain start: as one call it changes this kernel's register allocation)
     if constexpr (HELD) {
-      gibbs_load_chain_held<LPC>(a, st, chain, l, cid, sweep0);
+      gibbs_load_chain<LPC, true>(a, st, chain, l, cid, sweep0);
     } else if (a.init) {
       for (int i = l; i < n; i += LPC) {
         u32x4 r = philox4x32_10((uint32_t)i, cid, sweep0, STREAM_INIT, a.k0, a.k1);
@@ -801,88 +743,42 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   }
 }
 
-static size_t gibbs_lds_bytes(int n, int n_batches, int n_colours, int chains_per_block) {
-  size_t o[7];
-  return gibbs_lds_layout(n, n_batches, n_colours, o) + sizeof(_Float16) * (size_t)chains_per_block * ((n + 15) & ~15);
+// ---------------------------------------------------------------- host: plan (gibbs_plan.h), fill arguments, launch
+template <bool HELD, int SCHED>
+using GibbsKernelT = void (*)(GibbsArgsT<HELD, SCHED>);
+
+// the instantiation a plan names; null: it has none.  The tables expand from the lists the plan chose from.
+template <bool HELD, int SCHED>
+static GibbsKernelT<HELD, SCHED> gibbs_kernel_of(const GibbsDrawPlan& p) {
+#define DVG_GIBBS_LANE_ENTRY(LPC, W, MB, NR, MAXS)                                                      \
+  if (p.form == GF_LANE && p.lpc == LPC && p.waves == W && p.mb == MB && p.nr == NR && p.maxs == MAXS)  \
+    return gibbs_fast_kernel<LPC, W, MB, NR, MAXS, HELD, SCHED>;
+  DVG_GIBBS_LANE_KERNELS(DVG_GIBBS_LANE_ENTRY)
+#undef DVG_GIBBS_LANE_ENTRY
+#define DVG_GIBBS_ROLLED_ENTRY(LPC, W) \
+  if (p.form == GF_ROLLED && p.lpc == LPC && p.waves == W) return gibbs_kernel<LPC, W, HELD, SCHED>;
+  DVG_GIBBS_ROLLED_KERNELS(DVG_GIBBS_ROLLED_ENTRY)
+#undef DVG_GIBBS_ROLLED_ENTRY
+  return nullptr;
+}
+static void (*gibbs_slot_kernel_of(const GibbsDrawPlan& p))(GibbsArgs, GibbsSlots) {
+#define DVG_GIBBS_SLOT_ENTRY(MAXS, CH, FIX) \
+  if (p.form == GF_SLOTS && p.maxs == MAXS && p.ch == CH && p.fix == FIX) return gibbs_slot_kernel<MAXS, CH, FIX>;
+  DVG_GIBBS_SLOT_KERNELS(DVG_GIBBS_SLOT_ENTRY)
+#undef DVG_GIBBS_SLOT_ENTRY
+  return nullptr;
 }
 
-// dvg_gibbs_launch_info: the dispatch below runs with a probe set and reports its launch geometry instead of launching
-struct GibbsProbe { int workgroups; int threads; size_t lds; };
-static thread_local GibbsProbe* g_gibbs_probe = nullptr;
-
-template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
-static int launch_gibbs(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
-  constexpr int CPB = WAVES * (64 / LPC);
-  // (HELD: a row of flag bits per chain behind the state rows)
-  const size_t lds = gibbs_lds_bytes(a.n, a.n_batches, a.n_colours, CPB) +
-                     (HELD ? sizeof(uint32_t) * (size_t)CPB * gibbs_held_words(a.n) : 0);
-  if (lds > 160 * 1024) {
-    set_error("gibbs: graph (n=%d, %d neighbour batches) needs %zu B of LDS%s > 160 KiB", a.n, a.n_batches, lds,
-              HELD ? " (the held flags of a conditional draw included)" : "");
+template <typename... A>
+static int gibbs_launch(void (*kern)(A...), const GibbsDrawPlan& p, const GibbsArgs& a, hipStream_t s, A... args) {
+  if (!kern) {  // (a plan without an instantiation is an error, never another kernel)
+    set_error("gibbs: lane image (%d lanes per chain, %d batches, %d rows in steps of %d) has no kernel", p.lpc, p.mb, a.n_rows, p.nr);
     return DVG_E_UNSUPPORTED;
   }
-  const int grid = (int)ceil_div(a.n_chains, CPB);
-  if (g_gibbs_probe) { *g_gibbs_probe = GibbsProbe{grid, WAVES * 64, lds}; return DVG_OK; }
-  auto kern = gibbs_kernel<LPC, WAVES, HELD, SCHED>;
-  if (lds > 64 * 1024)
-    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (p.lds > 64 * 1024)
+    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
   // work = spin updates of the draw (bench.py's sampler roofline)
-  DVG_LAUNCH_WORK(K_GIBBS, (double)a.n_chains * a.n * a.n_sweeps, kern, dim3(grid), dim3(WAVES * 64), lds, s, a);
-  return DVG_OK;
-}
-
-// pass = 16 waves x (64 / ch) spins; false: more than 20 (class, pass) slots, or a graph beyond the slot registers' bit fields
-static bool gibbs_make_slots(const dvg_graph_t* g, int ch, GibbsSlots* sl) {
-  *sl = GibbsSlots{};
-  if (g->n_colours > 64 || g->n >= 2048 || g->n_batches >= 8192) return false;
-  const int pass = 16 * (64 / ch);
-  for (int k = 0; k < g->n_colours; ++k) {
-    const int lo = g->h_class_ptr[k], hi = g->h_class_ptr[k + 1];
-    for (int p = lo; p < hi; p += pass) {
-      if (sl->n >= 20) return false;
-      sl->lo[sl->n] = (int16_t)p; sl->hi[sl->n] = (int16_t)hi;
-      if (p + pass >= hi) sl->last_mask |= 1u << sl->n;
-      ++sl->n;
-    }
-  }
-  return sl->n > 0;
-}
-
-template <int CH>
-static int launch_gibbs_slots(GibbsArgs a, const GibbsSlots& sl, hipStream_t s) {
-  size_t fo[5];
-  const size_t lds_fix = gibbs_fix_layout(a.n, fo) + sizeof(_Float16) * (size_t)CH * ((a.n + 15) & ~15);
-  const bool fix = a.max_batches <= GIBBS_NB && lds_fix <= 160 * 1024;
-  const size_t lds = fix ? lds_fix : gibbs_lds_bytes(a.n, a.n_batches, a.n_colours, CH);
-  if (lds > 160 * 1024) {
-    set_error("gibbs: graph (n=%d, %d neighbour batches) needs %zu B of LDS > 160 KiB", a.n, a.n_batches, lds);
-    return DVG_E_UNSUPPORTED;
-  }
-  const int grid = (int)ceil_div(a.n_chains, CH);
-  if (g_gibbs_probe) { *g_gibbs_probe = GibbsProbe{grid, 1024, lds}; return DVG_OK; }
-  // (18 slots: c5's graphs; the word registers of two more slots are what spills at 128 registers per wave)
-  auto kern = fix ? (sl.n <= 18 ? gibbs_slot_kernel<18, CH, true> : gibbs_slot_kernel<20, CH, true>)
-                  : (sl.n <= 18 ? gibbs_slot_kernel<18, CH, false> : gibbs_slot_kernel<20, CH, false>);
-  if (lds > 64 * 1024)
-    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  DVG_LAUNCH_WORK(K_GIBBS, (double)a.n_chains * a.n * a.n_sweeps, kern, dim3(grid), dim3(1024), lds, s, a, sl);
-  return DVG_OK;
-}
-
-template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
-static int launch_gibbs_fast(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
-  constexpr int CPB = WAVES * (64 / LPC);
-  const size_t lds = gibbs_lane_lds_bytes(a.n_rows, MB, LPC, a.n, CPB);
-  if (lds > 160 * 1024) {
-    set_error("gibbs: graph (n=%d, %d rows per lane) needs %zu B of LDS > 160 KiB", a.n, a.n_rows, lds);
-    return DVG_E_UNSUPPORTED;
-  }
-  const int grid = (int)ceil_div(a.n_chains, CPB);
-  if (g_gibbs_probe) { *g_gibbs_probe = GibbsProbe{grid, WAVES * 64, lds}; return DVG_OK; }
-  auto kern = gibbs_fast_kernel<LPC, WAVES, MB, NR, MAXS, HELD, SCHED>;
-  if (lds > 64 * 1024)
-    DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  DVG_LAUNCH_WORK(K_GIBBS, (double)a.n_chains * a.n * a.n_sweeps, kern, dim3(grid), dim3(WAVES * 64), lds, s, a);
+  DVG_LAUNCH_WORK(K_GIBBS, (double)a.n_chains * a.n * a.n_sweeps, kern, dim3(p.grid), dim3(p.threads), p.lds, s, args...);
   return DVG_OK;
 }
 
@@ -891,7 +787,35 @@ static int launch_gibbs_fast(GibbsArgsT<HELD, SCHED> a, hipStream_t s) {
 using namespace dvg;
 
 template <bool HELD, int SCHED = 0>
-static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, int n_chains, hipStream_t s);
+static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStream_t s) {
+  constexpr GibbsDrawKind KIND = HELD ? GK_HELD : SCHED == GIBBS_WEIGH ? GK_WEIGH : SCHED == GIBBS_TABLE ? GK_TABLE : GK_PLAIN;
+  GibbsDrawPlan p;
+  DVG_TRY(gibbs_draw_plan(g->shape, a.n_chains, KIND, opt(OPT_GIBBS_GENERIC), &p));
+  if (p.form == GF_LANE) {
+    a.lane_spin = g->lane_spin; a.lane_eid = g->lane_eid; a.lane_off = g->lane_off; a.n_rows = g->shape.lane_rows;
+  }
+  if constexpr (KIND == GK_PLAIN) {
+    if (p.form == GF_SLOTS) return gibbs_launch(gibbs_slot_kernel_of(p), p, a, s, a, p.slots);
+  }
+  return gibbs_launch(gibbs_kernel_of<HELD, SCHED>(p), p, a, s, a);
+}
+
+// What every draw checks, under its entry point's name `who`.  `missing`: the entry point's own null argument, if any
+// (its message).  `table`: an annealed draw (an entry per sweep: at least one).  `stride`: the per-chain stride of the
+// entry point's [n_chains or 1][row] array and the names of the two in its signature (null: it has no such array).
+struct GibbsStride { const char* name; int64_t value; const char* row_name; int row; };
+static int gibbs_check(const char* who, const dvg_graph_t* g, bool tensors, const char* missing, int n_chains, int n_sweeps,
+                       bool table, const GibbsStride* stride) {
+  DVG_REQUIRE(g && tensors, "%s: null argument", who);
+  DVG_REQUIRE(!missing, "%s: %s", who, missing);
+  DVG_REQUIRE(n_chains > 0 && n_sweeps >= (table ? 1 : 0), "%s: n_chains=%d n_sweeps=%d%s", who, n_chains, n_sweeps,
+              table ? " (the table has an entry per sweep: at least one)" : "");
+  DVG_REQUIRE(g->n <= 32767, "%s: graph too large (n=%d: 16-bit state offsets)", who, g->n);
+  DVG_REQUIRE(!stride || stride->value == 0 || stride->value == stride->row,
+              "%s: %s=%lld is neither 0 (one shared row) nor %s=%d (a row per chain)", who, stride->name,
+              (long long)stride->value, stride->row_name, stride->row);
+  return DVG_OK;
+}
 
 static void gibbs_fill_args(GibbsArgs& a, const dvg_graph_t* g, const float* linear, const float* quadratic, float prefactor,
                             float h_lo, float h_hi, float j_lo, float j_hi, float beta, int8_t* state, int n_chains,
@@ -900,7 +824,7 @@ static void gibbs_fill_args(GibbsArgs& a, const dvg_graph_t* g, const float* lin
   a.order = g->order; a.class_ptr = g->class_ptr;
   a.adj_idx = g->adj_idx; a.adj_eid = g->adj_eid; a.adj_row = g->adj_row; a.adj_src4 = g->adj_src4;
   a.linear = linear; a.quadratic = quadratic;
-  a.n = g->n; a.n_batches = g->n_batches; a.max_batches = g->max_batches; a.n_colours = g->n_colours;
+  a.n = g->n; a.n_batches = g->shape.n_batches; a.max_batches = g->shape.max_batches; a.n_colours = g->n_colours;
   a.prefactor = prefactor; a.h_lo = h_lo; a.h_hi = h_hi; a.j_lo = j_lo; a.j_hi = j_hi;
   a.two_beta = 2.0f * beta;
   a.state = state; a.samples_out = samples_out; a.n_chains = n_chains;
@@ -915,13 +839,11 @@ extern "C" int dvg_gibbs_sample(const dvg_graph_t* g, const float* linear, const
                                 float beta, int8_t* state, int n_chains, uint32_t chain_id0,
                                 uint64_t seed, uint32_t sweep0, int n_sweeps, int init,
                                 float* samples_out, const dvg_step_state_t* dyn, dvg_stream_t stream) {
-  DVG_REQUIRE(g && linear && quadratic && state, "gibbs: null argument");
-  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 0, "gibbs: n_chains=%d n_sweeps=%d", n_chains, n_sweeps);
-  DVG_REQUIRE(g->n <= 32767, "gibbs: graph too large (n=%d: 16-bit state offsets)", g->n);
+  DVG_TRY(gibbs_check("gibbs", g, linear && quadratic && state, nullptr, n_chains, n_sweeps, false, nullptr));
   GibbsArgs a;
   gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, beta, state, n_chains, chain_id0, seed, sweep0,
                   n_sweeps, init, samples_out, dyn);
-  return gibbs_dispatch<false>(g, a, n_chains, (hipStream_t)stream);
+  return gibbs_draw<false>(g, a, (hipStream_t)stream);
 }
 
 // The conditional draw: spins with a nonzero flag in `clamp` are held at their value in `state` (include/dvg.h).
@@ -931,18 +853,14 @@ extern "C" int dvg_gibbs_sample_clamped(const dvg_graph_t* g, const float* linea
                                         uint64_t seed, uint32_t sweep0, int n_sweeps, int init,
                                         const uint8_t* clamp, int64_t clamp_chain_stride,
                                         float* samples_out, const dvg_step_state_t* dyn, dvg_stream_t stream) {
-  DVG_REQUIRE(g && linear && quadratic && state, "gibbs_clamped: null argument");
-  DVG_REQUIRE(clamp, "gibbs_clamped: null clamp (a draw that holds nothing is dvg_gibbs_sample)");
-  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 0, "gibbs_clamped: n_chains=%d n_sweeps=%d", n_chains, n_sweeps);
-  DVG_REQUIRE(g->n <= 32767, "gibbs_clamped: graph too large (n=%d: 16-bit state offsets)", g->n);
-  DVG_REQUIRE(clamp_chain_stride == 0 || clamp_chain_stride == g->n,
-              "gibbs_clamped: clamp_chain_stride=%lld is neither 0 (one shared row) nor n=%d (a row per chain)",
-              (long long)clamp_chain_stride, g->n);
+  const GibbsStride stride{"clamp_chain_stride", clamp_chain_stride, "n", g ? g->n : 0};
+  DVG_TRY(gibbs_check("gibbs_clamped", g, linear && quadratic && state,
+                      clamp ? nullptr : "null clamp (a draw that holds nothing is dvg_gibbs_sample)", n_chains, n_sweeps, false, &stride));
   GibbsHeldArgs a;
   gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, beta, state, n_chains, chain_id0, seed, sweep0,
                   n_sweeps, init, samples_out, dyn);
   a.clamp = clamp; a.clamp_stride = clamp_chain_stride;
-  return gibbs_dispatch<true>(g, a, n_chains, (hipStream_t)stream);
+  return gibbs_draw<true>(g, a, (hipStream_t)stream);
 }
 
 // The annealed draw: sweep k of the call on chain c runs at betas[c * beta_chain_stride + k] (include/dvg.h).
@@ -952,19 +870,14 @@ extern "C" int dvg_gibbs_sample_annealed(const dvg_graph_t* g, const float* line
                                          int8_t* state, int n_chains, uint32_t chain_id0, uint64_t seed,
                                          uint32_t sweep0, int n_sweeps, int init, float* samples_out,
                                          const dvg_step_state_t* dyn, dvg_stream_t stream) {
-  DVG_REQUIRE(g && linear && quadratic && state, "gibbs_annealed: null argument");
-  DVG_REQUIRE(betas, "gibbs_annealed: null betas (a draw at one fixed beta is dvg_gibbs_sample)");
-  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 1, "gibbs_annealed: n_chains=%d n_sweeps=%d (the table has an entry per sweep: at least one)",
-              n_chains, n_sweeps);
-  DVG_REQUIRE(g->n <= 32767, "gibbs_annealed: graph too large (n=%d: 16-bit state offsets)", g->n);
-  DVG_REQUIRE(beta_chain_stride == 0 || beta_chain_stride == n_sweeps,
-              "gibbs_annealed: beta_chain_stride=%lld is neither 0 (one shared row) nor n_sweeps=%d (a row per chain)",
-              (long long)beta_chain_stride, n_sweeps);
+  const GibbsStride stride{"beta_chain_stride", beta_chain_stride, "n_sweeps", n_sweeps};
+  DVG_TRY(gibbs_check("gibbs_annealed", g, linear && quadratic && state,
+                      betas ? nullptr : "null betas (a draw at one fixed beta is dvg_gibbs_sample)", n_chains, n_sweeps, true, &stride));
   GibbsSchedArgs a;
   gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
                   n_sweeps, init, samples_out, dyn);
   a.betas = betas; a.beta_stride = beta_chain_stride;
-  return gibbs_dispatch<false, GIBBS_TABLE>(g, a, n_chains, (hipStream_t)stream);
+  return gibbs_draw<false, GIBBS_TABLE>(g, a, (hipStream_t)stream);
 }
 
 // The AIS draw: the annealed draw plus, per chain, its log importance weight and its final energy (include/dvg.h).
@@ -975,15 +888,11 @@ extern "C" int dvg_gibbs_sample_ais(const dvg_graph_t* g, const float* linear, c
                                     uint32_t sweep0, int n_sweeps, int init, float* samples_out,
                                     double* log_weight_out, double* energy_out,
                                     const dvg_step_state_t* dyn, dvg_stream_t stream) {
-  DVG_REQUIRE(g && linear && quadratic && state, "gibbs_ais: null argument");
-  DVG_REQUIRE(betas, "gibbs_ais: null betas");
-  DVG_REQUIRE(log_weight_out, "gibbs_ais: null log_weight_out (a draw that is not weighed is dvg_gibbs_sample_annealed)");
-  DVG_REQUIRE(n_chains > 0 && n_sweeps >= 1, "gibbs_ais: n_chains=%d n_sweeps=%d (the table has an entry per sweep: at least one)",
-              n_chains, n_sweeps);
-  DVG_REQUIRE(g->n <= 32767, "gibbs_ais: graph too large (n=%d: 16-bit state offsets)", g->n);
-  DVG_REQUIRE(beta_chain_stride == 0 || beta_chain_stride == n_sweeps,
-              "gibbs_ais: beta_chain_stride=%lld is neither 0 (one shared row) nor n_sweeps=%d (a row per chain)",
-              (long long)beta_chain_stride, n_sweeps);
+  const GibbsStride stride{"beta_chain_stride", beta_chain_stride, "n_sweeps", n_sweeps};
+  DVG_TRY(gibbs_check("gibbs_ais", g, linear && quadratic && state,
+                      !betas ? "null betas"
+                      : !log_weight_out ? "null log_weight_out (a draw that is not weighed is dvg_gibbs_sample_annealed)" : nullptr,
+                      n_chains, n_sweeps, true, &stride));
   DVG_REQUIRE(beta_from >= 0.0f && beta_from <= 3.4028234663852886e38f, "gibbs_ais: beta_from=%g must be finite and >= 0", (double)beta_from);
   DVG_REQUIRE(init == 0 || beta_from == 0.0f,
               "gibbs_ais: init=%d with beta_from=%g (fresh chains are uniform: a sample at beta 0 and at no other)", init, (double)beta_from);
@@ -992,7 +901,7 @@ extern "C" int dvg_gibbs_sample_ais(const dvg_graph_t* g, const float* linear, c
                   n_sweeps, init, samples_out, dyn);
   a.betas = betas; a.beta_stride = beta_chain_stride;
   a.beta_from = beta_from; a.log_weight_out = log_weight_out; a.energy_out = energy_out;
-  return gibbs_dispatch<false, GIBBS_WEIGH>(g, a, n_chains, (hipStream_t)stream);
+  return gibbs_draw<false, GIBBS_WEIGH>(g, a, (hipStream_t)stream);
 }
 
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,
@@ -1000,92 +909,10 @@ extern "C" int dvg_gibbs_sample_ais(const dvg_graph_t* g, const float* linear, c
 // forward's Winograd launches take whole CUs: ModelWrapper leaves the draw's CUs out of their persistent grid).
 extern "C" int dvg_gibbs_launch_info(const dvg_graph_t* g, int n_chains, int* workgroups, int* threads, size_t* lds_bytes) {
   DVG_REQUIRE(g && n_chains > 0, "gibbs_launch_info: null graph / no chains");
-  GibbsArgs a{};
-  a.n = g->n; a.n_batches = g->n_batches; a.max_batches = g->max_batches; a.n_colours = g->n_colours; a.n_chains = n_chains;
-  GibbsProbe pr{0, 0, 0};
-  g_gibbs_probe = &pr;
-  const int rc = gibbs_dispatch<false>(g, a, n_chains, nullptr);
-  g_gibbs_probe = nullptr;
-  DVG_TRY(rc);
-  if (workgroups) *workgroups = pr.workgroups;
-  if (threads) *threads = pr.threads;
-  if (lds_bytes) *lds_bytes = pr.lds;
+  GibbsDrawPlan p;
+  DVG_TRY(gibbs_draw_plan(g->shape, n_chains, GK_PLAIN, opt(OPT_GIBBS_GENERIC), &p));
+  if (workgroups) *workgroups = p.grid;
+  if (threads) *threads = p.threads;
+  if (lds_bytes) *lds_bytes = p.lds;
   return DVG_OK;
-}
-
-// HELD (the conditional draw) takes the plain draw's choices, with two exceptions: it has no chains-side-by-side form, so the
-// large graphs' many-chain draws run the rolled kernel in 16-wave workgroups, and the A/B forms 3 and 4 count as 0.
-// SCHED (the annealed draw, weighed or not): the same two exceptions.
-template <bool HELD, int SCHED>
-static int gibbs_dispatch(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, int n_chains, hipStream_t s) {
-  constexpr bool VARIANT = HELD || SCHED != 0;
-  // (option gibbs_generic = 1 forces the rolled reference schedule: A/B runs and the bit-exactness test of the fast one;
-  // 2 = the fast schedule without its two-passes-side-by-side form)
-  const int64_t form = (VARIANT && opt(OPT_GIBBS_GENERIC) >= 3) ? 0 : opt(OPT_GIBBS_GENERIC);
-  // Graphs of more than 12 rows per lane (1024 spins: ~140 KB of tables, one 4-chain workgroup per CU) take the fast
-  // schedule only for draws of at most 512 chains: it is the LATENCY form (c5-size graph, 2048 chains x 50 sweeps: 0.59 ms
-  // alone against the rolled 16-wave form's 1.20) and costs the same CU-time -- but it takes every CU's LDS while it
-  // runs, and the c5 step, whose encoder AND decoder forward hide behind a 1.2 ms draw on half the chip, got slower
-  // with it (2.88 -> 3.01 ms: `profiles/r05_gibbs_c5_forms.txt`).
-  if constexpr (!VARIANT) {
-    if (form == 4) {  // (4: the chains-side-by-side schedule in 8-chain workgroups whatever the size: A/B runs)
-      GibbsSlots sl8;
-      if (gibbs_make_slots(g, 8, &sl8)) return launch_gibbs_slots<8>(a, sl8, s);
-    }
-  }
-  bool lane_ok = g->lane_eid && (g->lane_rows <= 12 || n_chains <= 512 || form == 3);  // (3: the fast schedule whatever the size: A/B runs)
-  if (lane_ok) {
-    // (a lane image the fast form cannot serve -- more than 160 KiB of LDS: 20 rows x 5 batches at n_pad > 1216;
-    // or a shape without an instantiation: two rows per step with a single small class -- falls through to the rolled
-    // schedule, which serves every graph, instead of failing the draw)
-    const int lpc = g->lane_lpc, mb = g->lane_mb, rows = g->lane_rows, nr = form == 2 ? 1 : g->lane_nr;
-    const bool small = gibbs_lane_lds_bytes(rows, mb, lpc, g->n, 0) <= 16 * 1024 && n_chains <= 1024 && rows <= 12;
-    const int waves = small ? 1 : 4;
-    const bool has_kernel = (lpc == 16 || lpc == 32 || lpc == 64) && (mb == 4 || mb == 5) && rows <= 20 &&
-                            (nr == 1 ? (rows <= 12 || (lpc == 64 && !small)) : (nr == 2 && lpc == 64 && !small));
-    if (!has_kernel || gibbs_lane_lds_bytes(rows, mb, lpc, g->n, waves * (64 / lpc)) > 160 * 1024) lane_ok = false;
-  }
-  if (lane_ok && form != 1) {
-    // Lanes per chain: the smallest of 16/32/64 that covers the largest colour class in one pass, else 64 (graph.cpp).
-    // Waves per workgroup.  Measured on the c2 step with the draw overlapped with the encoder forward: 4 -> 1.237 ms,
-    // 8 -> 1.273, 16 -> 1.391: the sweep loop does contend for issue slots, fatter workgroups do not pay for the CUs they
-    // free (round 5, c3: 8 or 2 waves instead of 4: step +0.2 ms).  Small graphs with few chains (c2: 128 spins, 256
-    // chains -> 32 four-wave workgroups on 256 CUs): one wave per workgroup spreads the draw over four times as many
-    // CUs at a few KB of tables each (c2 step 1.082 -> 1.060 ms).  Larger graphs keep four waves: every extra workgroup
-    // stages its own copy of the tables.
-    const int lpc = g->lane_lpc, mb = g->lane_mb, rows = g->lane_rows;
-    a.lane_spin = g->lane_spin; a.lane_eid = g->lane_eid; a.lane_off = g->lane_off; a.n_rows = rows;
-    const int nr = form == 2 ? 1 : g->lane_nr;  // (2: a two-row image walked one row at a time -- empty rows and all)
-    const bool small = gibbs_lane_lds_bytes(rows, mb, lpc, g->n, 0) <= 16 * 1024 && n_chains <= 1024 && rows <= 12;
-#define DVG_GIBBS_FAST(LPC, W, MB, NR, MAXS) \
-  if (lpc == LPC && mb == MB && nr == NR && rows <= MAXS && (W == 1) == small) return launch_gibbs_fast<LPC, W, MB, NR, MAXS, HELD, SCHED>(a, s);
-    DVG_GIBBS_FAST(16, 1, 4, 1, 12) DVG_GIBBS_FAST(16, 4, 4, 1, 12) DVG_GIBBS_FAST(16, 1, 5, 1, 12) DVG_GIBBS_FAST(16, 4, 5, 1, 12)
-    DVG_GIBBS_FAST(32, 1, 4, 1, 12) DVG_GIBBS_FAST(32, 4, 4, 1, 12) DVG_GIBBS_FAST(32, 1, 5, 1, 12) DVG_GIBBS_FAST(32, 4, 5, 1, 12)
-    DVG_GIBBS_FAST(64, 1, 4, 1, 12) DVG_GIBBS_FAST(64, 4, 4, 1, 12) DVG_GIBBS_FAST(64, 1, 5, 1, 12) DVG_GIBBS_FAST(64, 4, 5, 1, 12)
-    DVG_GIBBS_FAST(64, 4, 4, 1, 20) DVG_GIBBS_FAST(64, 4, 5, 1, 20)
-    DVG_GIBBS_FAST(64, 4, 4, 2, 12) DVG_GIBBS_FAST(64, 4, 5, 2, 12) DVG_GIBBS_FAST(64, 4, 4, 2, 20) DVG_GIBBS_FAST(64, 4, 5, 2, 20)
-#undef DVG_GIBBS_FAST
-    set_error("gibbs: lane image (%d lanes per chain, %d batches, %d rows in steps of %d) has no kernel", lpc, mb, rows, nr);
-    return DVG_E_UNSUPPORTED;
-  }
-  // The rolled schedule: graphs without a lane image (more than 20 rows per lane, more than 20 neighbours per spin).
-  const int mc = g->max_class;
-  // Large graphs (c5: 1024 spins, 2|E| = 16 K -> ~105 KB of tables): one workgroup per CU fits, so the workgroup must
-  // carry the CU's whole latency-hiding: 16 waves = 16 chains share one LDS copy of the graph (2 waves left 7/8 of
-  // the issue slots empty: 7.3 ms per 2048-chain, 50-sweep draw).
-  if (gibbs_lds_bytes(g->n, g->n_batches, g->n_colours, 4) > 72 * 1024) {
-    // ... with static (class, pass) slots when the classes make at most 20 of them (gibbs_slot_kernel; option
-    // gibbs_generic = 1 keeps the plain rolled kernel: the reference of the bit-exactness tests)
-    if constexpr (!VARIANT) {
-      GibbsSlots sl;
-      if (form != 1 && gibbs_make_slots(g, 16, &sl)) return launch_gibbs_slots<16>(a, sl, s);
-    }
-    return launch_gibbs<64, 16, HELD, SCHED>(a, s);
-  }
-  const bool small = gibbs_lds_bytes(g->n, g->n_batches, g->n_colours, 0) <= 16 * 1024 && n_chains <= 1024;
-#define DVG_GIBBS_DISPATCH(LPC) return small ? launch_gibbs<LPC, 1, HELD, SCHED>(a, s) : launch_gibbs<LPC, 4, HELD, SCHED>(a, s);
-  if (mc <= 16) { DVG_GIBBS_DISPATCH(16) }
-  if (mc <= 32) { DVG_GIBBS_DISPATCH(32) }
-  DVG_GIBBS_DISPATCH(64)
-#undef DVG_GIBBS_DISPATCH
 }

@@ -50,13 +50,7 @@ extern "C" int dvg_graph_create(int n, int n_edges, const int32_t* edge_i, const
   DVG_REQUIRE(g, "graph_create: out of host memory");
   memset(g, 0, sizeof(*g));
   g->n = n; g->n_edges = n_edges; g->n_colours = n_colours; g->n_adj = 2 * n_edges;
-  g->max_class = 0; g->max_degree = 0;
-  for (int k = 0; k < n_colours; ++k) {
-    int sz = class_ptr[k + 1] - class_ptr[k];
-    if (sz > g->max_class) g->max_class = sz;
-    g->h_class_ptr[k] = class_ptr[k];
-  }
-  g->h_class_ptr[n_colours] = class_ptr[n_colours];
+  g->shape = gibbs_graph_shape(n, n_colours, class_ptr, adj_ptr);
   for (int i = 0; i < n; ++i) {
     int d = adj_ptr[i + 1] - adj_ptr[i];
     if (d > g->max_degree) g->max_degree = d;
@@ -70,56 +64,44 @@ extern "C" int dvg_graph_create(int n, int n_edges, const int32_t* edge_i, const
     const int d = adj_ptr[i + 1] - adj_ptr[i], b = (d + 3) / 4;
     row[i] = (int32_t)(((uint32_t)nb << 8) | (uint32_t)(b > 255 ? 255 : b));
     for (int k = 0; k < 4 * b; ++k) src4[4 * (size_t)nb + k] = k < d ? adj_ptr[i] + k : -1;
-    if (b > g->max_batches) g->max_batches = b;
     nb += b;
   }
-  g->n_batches = nb;
   hipGetDevice(&g->device);
-  int rc = (g->max_batches > 255 || nb >= (1 << 24)) ? DVG_E_UNSUPPORTED : DVG_OK;
+  int rc = (g->shape.max_batches > 255 || nb >= (1 << 24)) ? DVG_E_UNSUPPORTED : DVG_OK;
   if (rc == DVG_OK) rc = upload(&g->adj_row, row, n);
   if (rc == DVG_OK) rc = upload(&g->adj_src4, src4, (size_t)4 * nb);
   delete[] row; delete[] src4;
-  if (rc == DVG_OK) {  // the lane-major image of the sampler's fast schedule (graph.h)
-    const int lpc = g->max_class <= 16 ? 16 : g->max_class <= 32 ? 32 : 64;
-    const int nr = g->max_class > lpc ? 2 : 1;
-    const int mb = g->max_batches <= 4 ? 4 : 5;
-    int rows = 0;
+  if (rc == DVG_OK && g->shape.lane_has) {  // the lane-major image of the sampler's fast schedule (graph.h)
+    const int lpc = g->shape.lane_lpc, nr = g->shape.lane_nr, mb = g->shape.lane_mb, rows = g->shape.lane_rows;
+    const size_t count = (size_t)rows * mb * lpc * 4;
+    int32_t* spin = new (std::nothrow) int32_t[(size_t)rows * lpc];
+    int32_t* eid = new (std::nothrow) int32_t[count];
+    uint16_t* off = new (std::nothrow) uint16_t[count];
+    if (!spin || !eid || !off) {
+      delete[] spin; delete[] eid; delete[] off; dvg_graph_destroy(g);
+      DVG_REQUIRE(false, "graph_create: out of host memory");
+    }
+    for (size_t q = 0; q < (size_t)rows * lpc; ++q) spin[q] = -1;
+    for (size_t q = 0; q < count; ++q) { eid[q] = -1; off[q] = 0; }
+    int k = 0;
     for (int c = 0; c < n_colours; ++c) {
-      const int passes = (class_ptr[c + 1] - class_ptr[c] + lpc - 1) / lpc;
-      rows += nr * ((passes + nr - 1) / nr);
-    }
-    if (rows <= (lpc == 64 ? 20 : 12) && g->max_batches <= 5 && n <= 32767) {
-      const size_t count = (size_t)rows * mb * lpc * 4;
-      int32_t* spin = new (std::nothrow) int32_t[(size_t)rows * lpc];
-      int32_t* eid = new (std::nothrow) int32_t[count];
-      uint16_t* off = new (std::nothrow) uint16_t[count];
-      if (!spin || !eid || !off) {
-        delete[] spin; delete[] eid; delete[] off; dvg_graph_destroy(g);
-        DVG_REQUIRE(false, "graph_create: out of host memory");
-      }
-      for (size_t q = 0; q < (size_t)rows * lpc; ++q) spin[q] = -1;
-      for (size_t q = 0; q < count; ++q) { eid[q] = -1; off[q] = 0; }
-      int k = 0;
-      for (int c = 0; c < n_colours; ++c) {
-        const int size = class_ptr[c + 1] - class_ptr[c], passes = (size + lpc - 1) / lpc;
-        for (int pass = 0; pass < passes; ++pass)
-          for (int l = 0; l < lpc && pass * lpc + l < size; ++l) {
-            const int i = order[class_ptr[c] + pass * lpc + l], d = adj_ptr[i + 1] - adj_ptr[i];
-            spin[(size_t)(k + pass) * lpc + l] = i;
-            for (int t = 0; t < d; ++t) {
-              const size_t q = (((size_t)(k + pass) * mb + t / 4) * lpc + l) * 4 + t % 4;
-              eid[q] = adj_eid[adj_ptr[i] + t];
-              off[q] = (uint16_t)(2 * adj_idx[adj_ptr[i] + t]);
-            }
+      const int size = class_ptr[c + 1] - class_ptr[c], passes = (size + lpc - 1) / lpc;
+      for (int pass = 0; pass < passes; ++pass)
+        for (int l = 0; l < lpc && pass * lpc + l < size; ++l) {
+          const int i = order[class_ptr[c] + pass * lpc + l], d = adj_ptr[i + 1] - adj_ptr[i];
+          spin[(size_t)(k + pass) * lpc + l] = i;
+          for (int t = 0; t < d; ++t) {
+            const size_t q = (((size_t)(k + pass) * mb + t / 4) * lpc + l) * 4 + t % 4;
+            eid[q] = adj_eid[adj_ptr[i] + t];
+            off[q] = (uint16_t)(2 * adj_idx[adj_ptr[i] + t]);
           }
-        k += nr * ((passes + nr - 1) / nr);
-      }
-      rc = upload(&g->lane_spin, spin, (size_t)rows * lpc);
-      if (rc == DVG_OK) rc = upload(&g->lane_eid, eid, count);
-      if (rc == DVG_OK) rc = upload(&g->lane_off, off, count);
-      delete[] spin; delete[] eid; delete[] off;
-      g->lane_lpc = lpc; g->lane_mb = mb; g->lane_nr = nr; g->lane_rows = rows;
+        }
+      k += nr * ((passes + nr - 1) / nr);
     }
+    rc = upload(&g->lane_spin, spin, (size_t)rows * lpc);
+    if (rc == DVG_OK) rc = upload(&g->lane_eid, eid, count);
+    if (rc == DVG_OK) rc = upload(&g->lane_off, off, count);
+    delete[] spin; delete[] eid; delete[] off;
   }
   if (rc != DVG_OK) {
     if (rc == DVG_E_UNSUPPORTED) set_error("graph_create: a spin with more than 1020 neighbours");

@@ -23,6 +23,8 @@ _SIGS = {
     "dvg_dev_conv_wino_ok": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_plan_forms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "dvg_dev_mmd_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
+    "dvg_dev_gibbs_draw_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(ctypes.c_int64)]),
     "dvg_dev_conv_wino_stats_blocks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int]),
     "dvg_dev_wgrad_slab_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_conv_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 +
@@ -125,6 +127,29 @@ def mmd_plan(nx, ny, d):
                 splits=o[9], slices=o[10], gated_f32=o[11] != 0, gated_nfb=o[11], loss_parts=o[12], workspace_bytes=o[13],
                 dist_splits=o[14], gram_passes=o[15], bf16_terms=o[16], pair_grid=(o[17], o[18], o[19]),
                 dist_grid=(o[20], o[21]), gated_grid=o[22], final_grid=o[23])
+
+
+GIBBS_FORMS = ("rolled", "lane", "slots")            # csrc/gibbs_plan.h: GibbsForm
+GIBBS_KINDS = ("plain", "held", "table", "weigh")    # GibbsDrawKind
+
+
+def gibbs_draw_plan(plan, n_chains, kind="plain"):
+    """The kernel form a Gibbs draw of ``n_chains`` chains takes on the graph of ``plan`` (a ``graphs.GibbsPlan``) under
+    the current option ``gibbs_generic`` (no device needed).  ``kind``: ``"plain"`` (``dvg_gibbs_sample``), ``"held"``
+    (``_clamped``), ``"table"`` (``_annealed``) or ``"weigh"`` (``_ais``).  ``form``: ``"rolled"`` (``gibbs_kernel``),
+    ``"lane"`` (``gibbs_fast_kernel``) or ``"slots"`` (``gibbs_slot_kernel``), ``params`` its template parameters;
+    ``workgroups``, ``threads``, ``lds_bytes``: the launch, what ``dvg_gibbs_launch_info`` reports for the plain kind;
+    ``lane_image``: the shape of the graph's lane-major image (csrc/graph.h), ``None`` for a graph that gets none."""
+    class_ptr = np.ascontiguousarray(plan.class_ptr, dtype=np.int32)
+    adj_ptr = np.ascontiguousarray(plan.adj_ptr, dtype=np.int32)
+    o = (ctypes.c_int64 * 19)()
+    _lib.check(lib().dvg_dev_gibbs_draw_plan(int(plan.n), int(plan.n_colours), class_ptr.ctypes.data, adj_ptr.ctypes.data,
+                                             int(n_chains), GIBBS_KINDS.index(kind), o), "dvg_dev_gibbs_draw_plan")
+    form = GIBBS_FORMS[o[0]]
+    params = {"rolled": dict(LPC=o[1], WAVES=o[2]), "lane": dict(LPC=o[1], WAVES=o[2], MB=o[3], NR=o[4], MAXS=o[5]),
+              "slots": dict(MAXS=o[5], CH=o[6], FIX=bool(o[7]))}[form]
+    return dict(form=form, params=params, slots=o[8], chains_per_workgroup=o[9], workgroups=o[10], threads=o[11],
+                lds_bytes=o[12], lane_image=dict(LPC=o[14], MB=o[15], NR=o[16], rows=o[17]) if o[13] else None, n_batches=o[18])
 
 
 def conv_wino(x_m, w, mode, M, Cin, Cout, L, bias=None, stats=False):

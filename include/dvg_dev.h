@@ -41,6 +41,18 @@ int dvg_dev_plan_forms(int network, int64_t rows, int n_latents, int training, i
  * launch, out[20..21] of the distance sum (when no bandwidth is given), out[22] of the gated launch, out[23] of the final
  * kernel when a gradient is asked for. */
 int dvg_dev_mmd_plan(int64_t nx, int64_t ny, int dim, int64_t out[24]);
+/* The kernel form a Gibbs draw of n_chains chains takes on a graph under the current option gibbs_generic
+ * (csrc/gibbs_plan.h; reads the host arrays of the graph's colouring and CSR only, needs no device).  kind: 0 plain
+ * (dvg_gibbs_sample), 1 held (_clamped), 2 table (_annealed), 3 weigh (_ais).  out[0] form: 0 rolled (gibbs_kernel<out[1],
+ * out[2], ..>), 1 lane-major (gibbs_fast_kernel<out[1], out[2], out[3], out[4], out[5], ..>), 2 chains side by side
+ * (gibbs_slot_kernel<out[5], out[6], out[7]>); out[1..7] = LPC, WAVES, MB, NR, MAXS, CH, FIX (0 where the form has no such
+ * parameter); out[8] the slots form's (class, pass) slots; out[9] chains per workgroup; out[10] workgroups, out[11] threads
+ * per workgroup, out[12] LDS bytes per workgroup (what dvg_gibbs_launch_info reports for kind 0); out[13] whether the
+ * graph gets a lane-major image, out[14..17] its lanes per chain, batches per row, rows per step and rows (csrc/graph.h);
+ * out[18] the padded-row image's batches.  DVG_E_UNSUPPORTED: the form the
+ * graph must take needs more than 160 KiB of LDS. */
+int dvg_dev_gibbs_draw_plan(int n, int n_colours, const int32_t *class_ptr, const int32_t *adj_ptr, int n_chains, int kind,
+                            int64_t out[19]);
 /* The same layer in the Winograd F(4x4,3x3) form (csrc/conv_wino4.hip: 36 position GEMMs per 4x4 output tile, 2.25 multiplies
  * per output where F(2x2,3x3) issues 4.0): `u` = scratch of 36*Cin*Cout floats, `stats` rows = M / 1024 (tile blocks of 64
  * tiles), cus = CUs the persistent grid is sized for (0 = 256).  Shapes: whole 1024-pixel blocks of 4x4 / 8x8 / 16x16 images. */

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from image_generation_amd import _lib, graphs, sampler as smp
+from image_generation_amd import _lib, dev, graphs, sampler as smp
 from oracle import cref, gibbs
 
 pytestmark = pytest.mark.gpu
@@ -18,6 +18,12 @@ def _plan(fam, n, seed=SEED):
     return graphs.build_plan(n, ei, ej), nodes
 
 
+def _takes(plan, C, form, **params):
+    """The plain draw's plan under the current options names this kernel form (and these template parameters of it)."""
+    p = dev.gibbs_draw_plan(plan, C, "plain")
+    assert p["form"] == form and all(p["params"][k] == v for k, v in params.items()), p
+
+
 def _model(plan, rng):
     h = (0.05 * rng.uniform(-1, 1, plan.n)).astype(np.float32)
     J = (5.0 * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)
@@ -26,8 +32,9 @@ def _model(plan, rng):
 
 @pytest.mark.parametrize("fam,n,C,sweeps", [("pegasus", 64, 37, 3), ("zephyr", 128, 256, 5), ("pegasus", 256, 130, 4),
                                              ("zephyr", 512, 64, 3), ("zephyr", 1024, 9, 2), ("pegasus", 128, 256, 50),
-                                             ("zephyr", 512, 33, 13), ("zephyr", 1024, 41, 5)])  # last: 16-wave workgroups, ragged last one
+                                             ("zephyr", 512, 33, 13), ("zephyr", 1024, 41, 5)])  # last: lane-major at 20 rows, ragged last workgroup
 def test_gibbs_bit_exact(fam, n, C, sweeps):
+    _takes(_plan(fam, n)[0], C, "lane", MAXS=20 if n == 1024 else 12)
     _bit_exact(fam, n, C, sweeps)
 
 
@@ -38,6 +45,10 @@ def test_gibbs_bit_exact_large_graph_many_chains(fam, n, C, sweeps, generic):
     (class, pass) slots and the Philox words of a counter kept for its four sweeps (gibbs_slot_kernel; draws of 5 and 7
     sweeps start off the multiples of four), with gibbs_generic = 1 the plain rolled kernel -- against the C oracle."""
     with _lib.option_scope(gibbs_generic=generic):
+        if generic == 0:
+            _takes(_plan(fam, n)[0], C, "slots", CH=16, FIX=True)
+        else:
+            _takes(_plan(fam, n)[0], C, "rolled", LPC=64, WAVES=16)
         _bit_exact(fam, n, C, sweeps)
 
 
@@ -46,6 +57,7 @@ def test_gibbs_bit_exact_chains_side_by_side_in_8_chain_workgroups(fam, n, C, sw
     """gibbs_generic = 4 (an A/B form: the chains-side-by-side schedule of the large graphs, gibbs_slot_kernel, in 8-chain
     workgroups on any graph whose classes make at most 20 slots) -- same bits as the oracle; ragged last workgroups."""
     with _lib.option_scope(gibbs_generic=4):
+        _takes(_plan(fam, n)[0], C, "slots", CH=8)
         _bit_exact(fam, n, C, sweeps)
 
 
@@ -54,6 +66,7 @@ def test_gibbs_bit_exact_one_row_at_a_time(fam, n, C, sweeps):
     """Graphs whose colour classes take two passes of 64 lanes run the passes side by side by default; option
     gibbs_generic = 2 keeps the same lane-major schedule one row at a time -- same bits."""
     with _lib.option_scope(gibbs_generic=2):
+        _takes(_plan(fam, n)[0], C, "lane", LPC=64, NR=1)
         _bit_exact(fam, n, C, sweeps)
 
 
@@ -99,6 +112,10 @@ def test_gibbs_bit_exact_on_arbitrary_graphs(n, p_edge, C, sweeps):
     lin = torch.from_numpy(h).cuda(); quad = torch.from_numpy(J).cuda()
     for generic in (0, 1, 2):
         with _lib.option_scope(gibbs_generic=generic):
+            if generic == 1 or p_edge > 0.1:  # (degrees beyond 20: no lane image)
+                _takes(plan, C, "rolled")
+            else:
+                _takes(plan, C, "lane")
             s = smp.GibbsSampler(plan, list(range(n)), beta=1.5, sweeps=sweeps, seed=SEED, persistent=True, chain_offset=7,
                                  h_range=(-4, 4), j_range=(-1, 1))
             want = cref.init_state(ids, n, SEED)
@@ -128,6 +145,10 @@ def test_gibbs_bit_exact_large_arbitrary_graph(generic):
     ids = np.arange(C, dtype=np.uint32) + 7
     lin = torch.from_numpy(h).cuda(); quad = torch.from_numpy(J).cuda()
     with _lib.option_scope(gibbs_generic=generic):
+        if generic == 0:
+            _takes(plan, C, "slots", CH=16, FIX=False)
+        else:
+            _takes(plan, C, "rolled", LPC=64, WAVES=16)
         s = smp.GibbsSampler(plan, list(range(n)), beta=1.5, sweeps=sweeps, seed=SEED, persistent=True, chain_offset=7,
                              h_range=(-4, 4), j_range=(-1, 1))
         want = cref.init_state(ids, n, SEED)
@@ -160,6 +181,11 @@ def test_gibbs_bit_exact_many_small_classes():
     lin = torch.from_numpy(h).cuda(); quad = torch.from_numpy(J).cuda()
     for generic in (0, 1):
         with _lib.option_scope(gibbs_generic=generic):
+            if generic == 0:
+                _takes(plan, C, "lane", LPC=64, WAVES=4, NR=1, MAXS=20)
+                assert dev.gibbs_draw_plan(plan, C)["lane_image"]["rows"] == 14
+            else:
+                _takes(plan, C, "rolled")
             s = smp.GibbsSampler(plan, list(range(n)), beta=1.2, sweeps=sweeps, seed=SEED, persistent=True, chain_offset=3,
                                  h_range=(-4, 4), j_range=(-1, 1))
             want = cref.init_state(ids, n, SEED)

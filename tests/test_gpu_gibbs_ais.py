@@ -22,7 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ais_oracle  # noqa: E402
-from image_generation_amd import _lib, graphs, sampler as smp  # noqa: E402
+from image_generation_amd import _lib, dev, graphs, sampler as smp  # noqa: E402
 from oracle import cref, gibbs  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -87,6 +87,18 @@ def _shape(name):
 
 SHAPES = ["pegasus64", "zephyr128", "zephyr512", "zephyr512-one-row", "zephyr512-rolled", "zephyr1024x41", "zephyr1024x530",
           "random77", "cliques"]
+# the kernel form each shape's draw takes (the module docstring), as the draw's plan names it: _setup asserts it
+FORMS = {
+    "pegasus64": ("lane", dict(LPC=32, WAVES=1, MB=4, NR=1, MAXS=12)),
+    "zephyr128": ("lane", dict(LPC=32, WAVES=4, MB=5, NR=1, MAXS=12)),
+    "zephyr512": ("lane", dict(LPC=64, WAVES=4, MB=5, NR=2, MAXS=12)),
+    "zephyr512-one-row": ("lane", dict(LPC=64, WAVES=4, MB=5, NR=1, MAXS=12)),
+    "zephyr512-rolled": ("rolled", dict(LPC=64, WAVES=4)),
+    "zephyr1024x41": ("lane", dict(LPC=64, WAVES=4, MB=5, NR=2, MAXS=20)),
+    "zephyr1024x530": ("rolled", dict(LPC=64, WAVES=16)),
+    "random77": ("rolled", dict(LPC=16, WAVES=1)),
+    "cliques": ("lane", dict(LPC=64, WAVES=4, MB=4, NR=1, MAXS=20)),
+}
 
 
 # ------------------------------------------------------------------------------------------------ the raw ABI
@@ -134,6 +146,9 @@ class _Draw:
 
 def _setup(name):
     plan, C, sweeps, generic, p = _shape(name)
+    with _lib.option_scope(gibbs_generic=generic):
+        got = dev.gibbs_draw_plan(plan, C, "weigh")
+    assert (got["form"], got["params"]) == FORMS[name], got
     rng = np.random.default_rng(plan.n + C)
     h = (p["h_scale"] * rng.uniform(-1, 1, plan.n)).astype(np.float32)
     J = (p["j_scale"] * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)

@@ -4,8 +4,9 @@ chains or a row per chain) against the oracle, bit for bit, and of the Python su
 The oracle is the existing one, unchanged: per distinct row of the table, ``cref.gibbs_sweeps`` called once per sweep --
 that sweep's beta, ``sweep0 + k``, one sweep -- on the chains that share the row IS the annealed draw.
 
-Dispatch each shape takes (gibbs_generic = 0): Pegasus 64, Zephyr 128 -- the lane-major form, one-wave workgroups, one row
-per step; Zephyr 512 -- lane-major, four waves, two rows side by side (gibbs_generic = 2: one at a time; 1: the rolled
+Dispatch each shape takes (gibbs_generic = 0; FORMS below, asserted against the draw's plan beside the bits): Pegasus 64
+-- the lane-major form, one-wave workgroups, one row per step; Zephyr 128 -- the same in four-wave workgroups (its tables
+are beyond the one-wave rule's 16 KiB); Zephyr 512 -- lane-major, four waves, two rows side by side (gibbs_generic = 2: one at a time; 1: the rolled
 kernel); Zephyr 1024 x 41 -- lane-major, four waves, 20 rows; Zephyr 1024 x 530 -- the rolled kernel in 16-wave workgroups
 (the plain draw runs its chains-side-by-side kernel there); the 77-spin random graph -- no lane image: rolled, one wave;
 the clique graph -- lane-major, one row per step, 14 rows.
@@ -20,7 +21,7 @@ import numpy as np
 import pytest
 import torch
 
-from image_generation_amd import _lib, graphs, sampler as smp
+from image_generation_amd import _lib, dev, graphs, sampler as smp
 from oracle import cref, gibbs
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +85,18 @@ def _shape(name):
 
 SHAPES = ["pegasus64", "zephyr128", "zephyr512", "zephyr512-one-row", "zephyr512-rolled", "zephyr1024x41", "zephyr1024x530",
           "random77", "cliques"]
+# the kernel form each shape's draw takes (the module docstring), as the draw's plan names it: _setup asserts it
+FORMS = {
+    "pegasus64": ("lane", dict(LPC=32, WAVES=1, MB=4, NR=1, MAXS=12)),
+    "zephyr128": ("lane", dict(LPC=32, WAVES=4, MB=5, NR=1, MAXS=12)),
+    "zephyr512": ("lane", dict(LPC=64, WAVES=4, MB=5, NR=2, MAXS=12)),
+    "zephyr512-one-row": ("lane", dict(LPC=64, WAVES=4, MB=5, NR=1, MAXS=12)),
+    "zephyr512-rolled": ("rolled", dict(LPC=64, WAVES=4)),
+    "zephyr1024x41": ("lane", dict(LPC=64, WAVES=4, MB=5, NR=2, MAXS=20)),
+    "zephyr1024x530": ("rolled", dict(LPC=64, WAVES=16)),
+    "random77": ("rolled", dict(LPC=16, WAVES=1)),
+    "cliques": ("lane", dict(LPC=64, WAVES=4, MB=4, NR=1, MAXS=20)),
+}
 
 
 # ------------------------------------------------------------------------------------------------ the oracle
@@ -144,6 +157,9 @@ class _Draw:
 
 def _setup(name):
     plan, C, sweeps, generic, p = _shape(name)
+    with _lib.option_scope(gibbs_generic=generic):
+        got = dev.gibbs_draw_plan(plan, C, "table")
+    assert (got["form"], got["params"]) == FORMS[name], got
     rng = np.random.default_rng(plan.n + C)
     h = (p["h_scale"] * rng.uniform(-1, 1, plan.n)).astype(np.float32)
     J = (p["j_scale"] * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)

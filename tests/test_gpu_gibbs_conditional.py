@@ -4,8 +4,9 @@ redrawn) against the oracle, bit for bit, and of the Python surface built on it.
 The oracle is the existing one, unchanged: a held spin is a spin left out of its colour class, so ``cref.gibbs_sweeps``
 called with the held spins filtered out of ``order`` / ``class_ptr`` (empty classes kept) IS the conditional draw.
 
-Dispatch each shape takes (gibbs_generic = 0): Pegasus 64, Zephyr 128 -- the lane-major form, one-wave workgroups, one row
-per step; Zephyr / Pegasus 512 -- lane-major, four waves, two rows side by side (gibbs_generic = 2: one at a time); Zephyr
+Dispatch each shape takes (gibbs_generic = 0; asserted against the draw's plan, dev.gibbs_draw_plan, beside the bits):
+Pegasus 64 -- the lane-major form, one-wave workgroups, one row per step; Zephyr 128 -- the same in four-wave workgroups
+(its tables are beyond the one-wave rule's 16 KiB); Zephyr / Pegasus 512 -- lane-major, four waves, two rows side by side (gibbs_generic = 2: one at a time); Zephyr
 1024 x 41 -- lane-major, four waves, 20 rows; Zephyr 1024 x 530 -- the rolled kernel in 16-wave workgroups (the plain draw
 runs its chains-side-by-side kernel there); the 77-spin random graph -- no lane image: rolled, one wave; the clique graph
 -- lane-major, one row per step, 14 rows.  gibbs_generic = 1 is the rolled kernel everywhere."""
@@ -16,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-from image_generation_amd import _lib, graphs, sampler as smp
+from image_generation_amd import _lib, dev, graphs, sampler as smp
 from oracle import cref, gibbs
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +57,23 @@ def _clique_plan(k=14, m=50):
     plan = graphs.build_plan(k * m, np.asarray(ei, np.int64), np.asarray(ej, np.int64))
     assert plan.n_colours == k and np.diff(plan.class_ptr).max() == m
     return plan
+
+
+def _takes(plan, C, kind, form, **params):
+    """The draw's plan under the current options names this kernel form (and these template parameters of it)."""
+    p = dev.gibbs_draw_plan(plan, C, kind)
+    assert p["form"] == form and all(p["params"][k] == v for k, v in params.items()), p
+
+
+# the form the module docstring claims for a solver graph's conditional draw: (n, more than 512 chains, gibbs_generic)
+def _solver_form(n, C, generic):
+    if n == 1024 and (generic == 1 or C > 512):
+        return "rolled", dict(LPC=64, WAVES=16)
+    if generic == 1:
+        return "rolled", {}
+    if n <= 128:
+        return "lane", dict(LPC=32, WAVES=1 if n == 64 else 4, NR=1, MAXS=12)
+    return "lane", dict(LPC=64, WAVES=4, NR=1 if generic == 2 else 2, MAXS=20 if n == 1024 else 12)
 
 
 # ------------------------------------------------------------------------------------------------ the oracle
@@ -167,6 +185,8 @@ SOLVER_CASES = [
 def test_conditional_bit_exact(fam, n, C, sweeps, generic, shared):
     plan, _nodes = _solver_plan(fam, n)
     with _lib.option_scope(gibbs_generic=generic):
+        form, params = _solver_form(n, C, generic)
+        _takes(plan, C, "held", form, **params)
         _bit_exact(plan, C, sweeps, h_scale=0.05, j_scale=5.0, prefactor=0.05, beta=20.0, id0=1000, shared=shared)
 
 
@@ -174,6 +194,7 @@ def test_conditional_bit_exact(fam, n, C, sweeps, generic, shared):
 def test_conditional_bit_exact_on_arbitrary_graph(generic):
     """77 spins at p = 0.35: degrees beyond 20 (two rounds of the neighbour sum), an isolated spin, an odd spin count."""
     with _lib.option_scope(gibbs_generic=generic):
+        _takes(_random_plan(77, 0.35), 19, "held", "rolled", LPC=16, WAVES=1)  # (no lane image)
         _bit_exact(_random_plan(77, 0.35), 19, 6, h_scale=0.5, j_scale=2.0, prefactor=0.3, beta=1.5, id0=7)
 
 
@@ -181,6 +202,11 @@ def test_conditional_bit_exact_on_arbitrary_graph(generic):
 def test_conditional_bit_exact_many_small_classes(generic):
     """50 disjoint 14-cliques: the lane-major schedule's one-row form at more than 12 rows."""
     with _lib.option_scope(gibbs_generic=generic):
+        if generic == 0:
+            _takes(_clique_plan(), 21, "held", "lane", LPC=64, WAVES=4, NR=1, MAXS=20)
+            assert dev.gibbs_draw_plan(_clique_plan(), 21, "held")["lane_image"]["rows"] == 14
+        else:
+            _takes(_clique_plan(), 21, "held", "rolled")
         _bit_exact(_clique_plan(), 21, 5, h_scale=0.5, j_scale=1.0, prefactor=0.4, beta=1.2, id0=3)
 
 
@@ -191,6 +217,9 @@ def test_nothing_held_is_the_plain_draw(n, C, init):
     """An all-zero mask gives the bits of dvg_gibbs_sample from the same state, seed and sweep index (1024 x 530: the plain
     draw runs the chains-side-by-side kernel, the conditional one the rolled kernel)."""
     plan, _nodes = _solver_plan("zephyr", n)
+    if n == 1024:
+        _takes(plan, C, "plain", "slots", CH=16)
+        _takes(plan, C, "held", "rolled", LPC=64, WAVES=16)
     rng = np.random.default_rng(n)
     h, J = _params(plan, rng, 0.05, 5.0)
     d = _Draw(plan, h, J, 0.05, 20.0)
