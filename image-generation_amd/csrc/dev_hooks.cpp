@@ -88,6 +88,22 @@ extern "C" int dvg_dev_gibbs_draw_plan(int n, int n_colours, const int32_t* clas
   for (int i = 0; i < 19; ++i) out[i] = v[i];
   return DVG_OK;
 }
+// ... and of an exchange draw (dvg_gibbs_sample_tempered) of n_ladders ladders of n_replicas chains: out[0..18] as above,
+// out[19] the ladders a workgroup holds
+extern "C" int dvg_dev_gibbs_exchange_plan(int n, int n_colours, const int32_t* class_ptr, const int32_t* adj_ptr, int n_ladders,
+                                           int n_replicas, int64_t out[20]) {
+  DVG_REQUIRE(out && class_ptr && adj_ptr && n > 0 && n_colours > 0 && n_colours <= 64 && n_ladders > 0 && n_replicas >= 2 &&
+                  n_replicas <= GIBBS_MAX_REPLICAS && (int64_t)n_ladders * n_replicas <= 0x7fffffff,
+              "dev_gibbs_exchange_plan: bad argument");
+  const GibbsGraphShape g = gibbs_graph_shape(n, n_colours, class_ptr, adj_ptr);
+  GibbsDrawPlan p;
+  int per_block = 0;
+  DVG_TRY(gibbs_exchange_plan(g, n_ladders, n_replicas, opt(OPT_GIBBS_GENERIC), &p, &per_block));
+  const int64_t v[20] = {p.form, p.lpc, p.waves, p.mb, p.nr, p.maxs, p.ch, p.fix, p.slots.n, p.chains_per_block, p.grid, p.threads,
+                         (int64_t)p.lds, g.lane_has, g.lane_lpc, g.lane_mb, g.lane_nr, g.lane_rows, g.n_batches, per_block};
+  for (int i = 0; i < 20; ++i) out[i] = v[i];
+  return DVG_OK;
+}
 extern "C" int dvg_dev_conv_wino_stats_blocks(int64_t M, int Cout) { return conv_wino_stats_blocks(M, Cout); }
 
 extern "C" size_t dvg_dev_conv_splitk_floats(int64_t M, int Cin, int Cout, int ntaps, int poolsum) {

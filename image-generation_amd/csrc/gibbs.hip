@@ -60,10 +60,23 @@ struct GibbsAisArgs : GibbsSchedArgs {
   double* log_weight_out;  // [n_chains]
   double* energy_out;      // [n_chains] or null
 };
-constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2;
+// Exchange draws (dvg_gibbs_sample_tempered, "DVG PT v1" in include/dvg.h): replica exchange.  The chains come in ladders of
+// n_replicas consecutive chains; a chain sweeps at the beta of the RUNG it holds, carries its energy as the AIS draw does, and
+// every swap_every sweeps neighbouring rungs of a ladder change hands on a Metropolis coin.  A fourth mode of SCHED,
+// GIBBS_EXCHANGE: the plain block plus the ladder and the three outputs.  A workgroup holds whole ladders (gibbs_exchange_plan).
+struct GibbsExchangeArgs : GibbsArgs {
+  const float* ladder;   // [n_replicas]: beta of rung r
+  int n_replicas, swap_every;
+  int32_t* rung;         // [n_chains] in/out: the rung chain c holds
+  double* energy_out;    // [n_chains] by rung, or null
+  uint32_t* accept_out;  // [n_chains]: element q R + r = accepted exchanges of the pair (r, r + 1) of ladder q; or null
+};
+constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3;
 template <bool HELD, int SCHED = 0>
-using GibbsArgsT = std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
-                                      std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs, std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>;
+using GibbsArgsT = std::conditional_t<
+    SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
+    std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
+                       std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs, std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>;
 
 // A chain's start state, its LPC lanes each taking spins l, l + LPC, ...: from the INIT stream (init) or from `state`.
 // HELD (a conditional draw): held spins from `state` always, free ones as above.
@@ -216,27 +229,99 @@ __device__ __forceinline__ double gibbs_chain_sum(double v) {
   return v;
 }
 
+// ---------------------------------------------------------------- the exchange step (GIBBS_EXCHANGE)
+// Which chain a workgroup's chain slot s = wave CPW + sub works on.  The other draws: chain b SLOTS + s in workgroup b,
+// SLOTS = WAVES CPW.  The exchange draw: a workgroup holds SLOTS / R whole ladders, slot s = (ladder lq of the workgroup,
+// replica j); the SLOTS % R slots behind the last ladder idle, as do the slots of ladders beyond the draw's.
+struct GibbsSlot { int chain; bool valid; int lq, j; };
+template <bool EXCH, int WAVES, int CPW, typename Args>
+__device__ __forceinline__ GibbsSlot gibbs_slot(const Args& a, int wave, int sub) {
+  GibbsSlot r{};
+  if constexpr (EXCH) {
+    constexpr int SLOTS = WAVES * CPW;
+    const int s = wave * CPW + sub;
+    const int R = a.n_replicas, per_block = SLOTS / R;
+    r.lq = s / R; r.j = s - r.lq * R;
+    const int q = (int)blockIdx.x * per_block + r.lq;
+    r.chain = q * R + r.j;
+    r.valid = r.lq < per_block && r.chain < a.n_chains;  // (n_chains is a multiple of R: whole ladders)
+  } else {
+    r.chain = (blockIdx.x * WAVES + wave) * CPW + sub;
+    r.valid = r.chain < a.n_chains;
+  }
+  return r;
+}
+struct GibbsExchangeLds { double* mail; uint32_t* acc; float* ladder; };
+__device__ __forceinline__ GibbsExchangeLds gibbs_exchange_carve(unsigned char* smem, size_t form_bytes, int slots) {
+  size_t o[3];
+  gibbs_exchange_lds_layout(form_bytes, slots, o);
+  return {reinterpret_cast<double*>(smem + o[0]), reinterpret_cast<uint32_t*>(smem + o[1]), reinterpret_cast<float*>(smem + o[2])};
+}
+// before the workgroup's first barrier: counters to zero, the ladder into LDS
+template <int NT, int SLOTS>
+__device__ __forceinline__ void gibbs_exchange_stage(const GibbsExchangeArgs& a, const GibbsExchangeLds& X, int tid) {
+  for (int i = tid; i < SLOTS; i += NT) X.acc[i] = 0u;
+  for (int i = tid; i < GIBBS_MAX_REPLICAS; i += NT) X.ladder[i] = i < a.n_replicas ? a.ladder[i] : 0.0f;
+}
+// Exchange number x, first half: the chain's energy (the sum of its lanes' shares) into mailbox x & 1 at (ladder, rung).  All
+// lanes of a valid chain call it together; a WORKGROUP BARRIER follows, reached by every wave of the workgroup.
+template <int LPC, int SLOTS>
+__device__ __forceinline__ void gibbs_exchange_post(const GibbsExchangeLds& X, int R, uint32_t x, int lq, int rung, int l, double e) {
+  const double E = gibbs_chain_sum<LPC>(e);
+  if (l == 0) X.mail[(x & 1u) * SLOTS + lq * R + rung] = E;
+}
+// ... second half, behind the barrier: the chain whose rung belongs to a pair (r, r + 1) of this exchange's parity reads both
+// energies and decides -- its partner evaluates the same expression on the same operands and decides the same.  Mailbox x & 1
+// is written again at exchange x + 2, behind barrier x + 1, which no wave passes before every reader of x has arrived.
+__device__ __forceinline__ void gibbs_exchange_decide(const GibbsExchangeArgs& a, const GibbsExchangeLds& X, int slots, int R, uint32_t x,
+                                                      int lq, uint32_t ladder_id, int l, int& rung, float& beta) {
+  const int par = (int)(x & 1u);
+  const bool lower = (rung & 1) == par && rung + 1 < R, upper = (rung & 1) != par && rung >= 1;
+  if (!(lower || upper)) return;
+  const int r = lower ? rung : rung - 1;
+  const double* m = X.mail + (x & 1u) * slots + lq * R;
+  const double ea = m[r], eb = m[r + 1];
+  const double db = (double)X.ladder[r + 1] - (double)X.ladder[r], de = eb - ea;
+  const double d = db * de;
+  const u32x4 w = philox4x32_10((uint32_t)r, ladder_id, x, STREAM_SWAP, a.k0, a.k1);
+  const bool accept = d >= 0.0 || (double)u32_to_unit(w.x) < exp(d);
+  if (accept) {
+    rung = lower ? r + 1 : r;
+    beta = X.ladder[rung];
+    if (lower && l == 0) X.acc[lq * R + r] += 1u;  // (this pair's only writer)
+  }
+}
+
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
 // HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
 // passed over in its class.  SCHED: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead.
 // SCHED == GIBBS_WEIGH: a lane also keeps its share `e` of the chain's energy (the start addends of spins l, l + LPC, ...,
 // then every update it makes) and its share `lw` of the log weight; lane 0 of the chain stores the sums.
+// SCHED == GIBBS_EXCHANGE: the energy share as above, beta the entry of the rung the chain holds; at an exchange the
+// workgroup meets at a barrier (gibbs_exchange_post / _decide).  EVERY wave runs the sweep loop and reaches every barrier --
+// lanes of an idle slot with empty classes; the exchanges are counted from (sweep0, n_sweeps, swap_every) alone.
 template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
-  constexpr bool AIS = SCHED == GIBBS_WEIGH;
+  constexpr bool AIS = SCHED == GIBBS_WEIGH, EXCH = SCHED == GIBBS_EXCHANGE, ENERGY = AIS || EXCH;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n;
   const GibbsLds L = gibbs_carve(smem, n, a.n_batches, a.n_colours);
   const int n_pad = (n + 15) & ~15;
   const int tid = threadIdx.x;
+  constexpr int CPW = 64 / LPC;  // chains per wave
+  [[maybe_unused]] GibbsExchangeLds X{};
+  if constexpr (EXCH) {
+    X = gibbs_exchange_carve(smem, gibbs_lds_bytes(n, a.n_batches, a.n_colours, WAVES * CPW), WAVES * CPW);
+    gibbs_exchange_stage<WAVES * 64, WAVES * CPW>(a, X, tid);
+  }
   gibbs_stage<WAVES * 64>(a, L, tid);
 
-  constexpr int CPW = 64 / LPC;  // chains per wave
   const int wave = tid >> 6, lane = tid & 63;
   const int sub = lane / LPC, l = lane % LPC;
-  const int chain = (blockIdx.x * WAVES + wave) * CPW + sub;
-  const bool valid = chain < a.n_chains;
+  const GibbsSlot slot = gibbs_slot<EXCH, WAVES, CPW>(a, wave, sub);
+  const int chain = slot.chain;
+  const bool valid = slot.valid;
   _Float16* st = L.state + (size_t)(wave * CPW + sub) * n_pad;
   const uint32_t cid = a.chain_id0 + (uint32_t)chain;
   // HELD: bit (i & 31) of word (i >> 5) of the chain's row of flags
@@ -262,19 +347,24 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   __builtin_amdgcn_wave_barrier();
 
-  if (valid) {
+  if (valid || EXCH) {
     // SCHED: this chain's row of the table; the entry of the coming sweep, read a sweep ahead of its first use
     [[maybe_unused]] const float* bt = nullptr;
     [[maybe_unused]] float beta_next = 0.0f;
-    if constexpr (SCHED) {
+    [[maybe_unused]] int rung = 0;  // EXCH: the rung the chain holds, and (beta_next) its beta
+    if constexpr (EXCH) {
+      const int R = a.n_replicas;
+      if (valid) rung = a.init ? slot.j : min(max(a.rung[chain], 0), R - 1);
+      beta_next = X.ladder[rung];
+    } else if constexpr (SCHED) {
       bt = a.betas + (int64_t)chain * a.beta_stride;
       beta_next = bt[0];
     }
     [[maybe_unused]] double e = 0.0, lw = 0.0;
     [[maybe_unused]] float beta_prev = 0.0f;
-    if constexpr (AIS) {
-      beta_prev = a.beta_from;
-      for (int i = l; i < n; i += LPC) {
+    if constexpr (AIS) beta_prev = a.beta_from;
+    if constexpr (ENERGY) {
+      for (int i = l; i < (valid ? n : 0); i += LPC) {
         const float hsi = L.hs[i];
         e += gibbs_start_energy(st[i], hsi, gibbs_field(hsi, L.row[i], L, st, a.n_batches, a.max_batches));
       }
@@ -282,7 +372,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
     for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
       const uint32_t tq = t >> 2, tw = t & 3u;
       float two_beta;
-      if constexpr (SCHED) {
+      if constexpr (EXCH) {
+        two_beta = __fmul_rn(2.0f, beta_next);
+      } else if constexpr (SCHED) {
         two_beta = __fmul_rn(2.0f, beta_next);
         if constexpr (AIS) {
           lw -= ((double)beta_next - (double)beta_prev) * e;
@@ -294,7 +386,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
         two_beta = a.two_beta;
       }
       for (int k = 0; k < a.n_colours; ++k) {
-        const int lo = L.cls[k], hi = L.cls[k + 1];
+        const int lo = L.cls[k], hi = (EXCH && !valid) ? lo : L.cls[k + 1];  // (an idle slot: every class empty)
         for (int p = lo + l; p < hi; p += LPC) {
           const int i = L.order[p];
           if constexpr (HELD) {
@@ -303,13 +395,42 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
           const float f = gibbs_field(L.hs[i], L.row[i], L, st, a.n_batches, a.max_batches);
           const u32x4 r = philox4x32_10((uint32_t)i, cid, tq, STREAM_GIBBS, a.k0, a.k1);
           const _Float16 s_new = gibbs_decide(f, two_beta, pick(r, tw));
-          if constexpr (AIS) e += gibbs_energy_step((float)s_new, (float)st[i], f);
+          if constexpr (ENERGY) e += gibbs_energy_step((float)s_new, (float)st[i], f);
           st[i] = s_new;
         }
         // the next class reads what this one wrote (same wave): order LDS traffic
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
       }
+      if constexpr (EXCH) {
+        // (t, swap_every: kernel arguments -- the same in every wave of every workgroup)
+        if ((t + 1u) % (uint32_t)a.swap_every == 0u) {
+          const uint32_t x = (t + 1u) / (uint32_t)a.swap_every;
+          if (valid) gibbs_exchange_post<LPC, WAVES * CPW>(X, a.n_replicas, x, slot.lq, rung, l, e);
+          __syncthreads();
+          if (valid)
+            gibbs_exchange_decide(a, X, WAVES * CPW, a.n_replicas, x, slot.lq, cid - (uint32_t)slot.j, l, rung, beta_next);
+        }
+      }
+    }
+    if constexpr (EXCH) {
+      __syncthreads();  // the counters are final
+      if (valid) {
+        const size_t row = (size_t)(chain - slot.j + rung);  // the outputs by rung; state and rung by chain
+        int8_t* dst = a.state + (size_t)chain * n;
+        for (int i = l; i < n; i += LPC) {
+          const float v = (float)st[i];
+          dst[i] = (int8_t)v;
+          if (a.samples_out) a.samples_out[row * n + i] = v;
+        }
+        e = gibbs_chain_sum<LPC>(e);
+        if (l == 0) {
+          a.rung[chain] = rung;
+          if (a.energy_out) a.energy_out[row] = e;
+          if (a.accept_out) a.accept_out[chain] = X.acc[slot.lq * a.n_replicas + slot.j];
+        }
+      }
+      return;
     }
     int8_t* dst = a.state + (size_t)chain * n;
     for (int i = l; i < n; i += LPC) {
@@ -534,10 +655,13 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
 // SCHED == GIBBS_WEIGH: the AIS draw -- one walk over the steps before the first sweep for the start energy (the fields of
 // the start state; no decision, no store), then one convert and one float64 add per update; the value a slot's spin has
 // is one bit per slot in a register, like `held`.
+// SCHED == GIBBS_EXCHANGE: the energy share of the AIS draw, two_beta from the rung the chain holds, and the workgroup's
+// barrier at every exchange.  No wave leaves before the last barrier: the lanes of an idle slot own no spin in any row (every
+// store of theirs goes to the sink), and a wave of idle slots alone passes over the sweep, not over the barrier.
 template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
-  constexpr bool AIS = SCHED == GIBBS_WEIGH;
+  constexpr bool AIS = SCHED == GIBBS_WEIGH, EXCH = SCHED == GIBBS_EXCHANGE, ENERGY = AIS || EXCH;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n, n_pad = (n + 15) & ~15;
   const int n_rows = a.n_rows;
@@ -570,10 +694,19 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   constexpr int CPW = 64 / LPC;
   const int wave = tid >> 6, lane = tid & 63;
   const int sub = lane / LPC, l = lane % LPC;
-  const int chain = (blockIdx.x * WAVES + wave) * CPW + sub;
-  const bool valid = chain < a.n_chains;
+  const GibbsSlot slot = gibbs_slot<EXCH, WAVES, CPW>(a, wave, sub);
+  const int chain = slot.chain;
+  const bool valid = slot.valid;
   _Float16* st = state + (size_t)(wave * CPW + sub) * n_pad;
   const uint32_t cid = a.chain_id0 + (uint32_t)chain;
+  [[maybe_unused]] GibbsExchangeLds X{};
+  if constexpr (EXCH) {
+    X = gibbs_exchange_carve(smem, gibbs_lane_lds_bytes(n_rows, MB, LPC, n, WAVES * CPW), WAVES * CPW);
+    gibbs_exchange_stage<WAVES * 64, WAVES * CPW>(a, X, tid);
+    // (an idle slot's row: the neighbour reads of its lanes find spins, not what LDS held before)
+    if (!valid)
+      for (int i = l; i < n; i += LPC) st[i] = (_Float16)1.0f;
+  }
 
   // (read before the chains start: a fresh chain's start configuration is keyed by the sweep index it starts at, so
   // non-persistent draws do not all restart from one configuration)
@@ -605,7 +738,11 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
     }
   }
   __syncthreads();  // the tables are staged
-  if (!valid) return;
+  if constexpr (!EXCH) {
+    if (!valid) return;
+  }
+  // the rows the wave walks (EXCH: a wave whose slots all idle has none -- it passes over the steps, not over the barriers)
+  const int rows_on = (EXCH && __builtin_amdgcn_ballot_w64(valid) == 0) ? 0 : n_rows;
 
   // the byte a lane stores its slot-k decision to: its spin's, or its own entry of the wave's sink when it has none
   // (an unconditional store keeps a class step one straight line of code)
@@ -626,20 +763,24 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   }
   [[maybe_unused]] const float* bt = nullptr;
   [[maybe_unused]] float beta_next = 0.0f;
-  if constexpr (SCHED) {
+  [[maybe_unused]] int rung = 0;  // EXCH: the rung the chain holds, and (beta_next) its beta
+  if constexpr (EXCH) {
+    if (valid) rung = a.init ? slot.j : min(max(a.rung[chain], 0), a.n_replicas - 1);
+    beta_next = X.ladder[rung];
+  } else if constexpr (SCHED) {
     bt = a.betas + (int64_t)chain * a.beta_stride;
     beta_next = bt[0];
   }
   [[maybe_unused]] double e = 0.0, lw = 0.0;
   [[maybe_unused]] float beta_prev = 0.0f;
   [[maybe_unused]] uint32_t up = 0u;  // AIS: bit k = the spin of slot k is +1
-  if constexpr (AIS) {
-    beta_prev = a.beta_from;
+  if constexpr (AIS) beta_prev = a.beta_from;
+  if constexpr (ENERGY) {
     // the sweep loop's walk over the steps, on the start state (it leaves `o` at step 0's offsets again)
 #pragma unroll
     for (int c = 0; c < MAXS / NR; ++c) {
       const int k0 = NR * c, k1 = k0 + NR - 1;
-      if (k0 >= n_rows) continue;
+      if (k0 >= rows_on) continue;
       const unsigned char* wlk = wl + (size_t)k0 * MB * LPC * 16;
       const unsigned char* ol_next = ol + (size_t)(k0 + NR < n_rows ? k0 + NR : 0) * MB * LPC * 8;
       float f[NR];
@@ -661,7 +802,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   }
   // AIS: slot K's decision S on the field F goes into the lane's energy share; lanes that update no spin there add 0
 #define DVG_GIBBS_WEIGH(K, S, F)                                                                            \
-  if constexpr (AIS) {                                                                                      \
+  if constexpr (ENERGY) {                                                                                    \
     const bool fr = DVG_GIBBS_FREE(K);                                                                      \
     const float sn = (float)(S), so = ((up >> (K)) & 1u) ? 1.0f : -1.0f;                                    \
     e += gibbs_energy_step(fr ? sn : so, so, F);                                                            \
@@ -670,7 +811,9 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
     const uint32_t tq = t >> 2, tw = t & 3u;
     float two_beta;
-    if constexpr (SCHED) {
+    if constexpr (EXCH) {
+      two_beta = __fmul_rn(2.0f, beta_next);
+    } else if constexpr (SCHED) {
       two_beta = __fmul_rn(2.0f, beta_next);
       if constexpr (AIS) {
         lw -= ((double)beta_next - (double)beta_prev) * e;
@@ -693,8 +836,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
 #pragma unroll
     for (int c = 0; c < MAXS / NR; ++c) {
       const int k0 = NR * c, k1 = k0 + NR - 1;
-      if (k0 >= n_rows) {  // (AIS: with the early exit the compiler left this loop rolled at 20 slots, the slot registers in scratch)
-        if constexpr (AIS) continue;
+      if (k0 >= rows_on) {  // (AIS: with the early exit the compiler left this loop rolled at 20 slots, the slot registers in scratch)
+        if constexpr (ENERGY) continue;
         else break;
       }
       const unsigned char* wlk = wl + (size_t)k0 * MB * LPC * 16;
@@ -723,10 +866,38 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
     }
+    if constexpr (EXCH) {
+      // (t, swap_every: kernel arguments -- the same in every wave of every workgroup)
+      if ((t + 1u) % (uint32_t)a.swap_every == 0u) {
+        const uint32_t x = (t + 1u) / (uint32_t)a.swap_every;
+        if (valid) gibbs_exchange_post<LPC, WAVES * CPW>(X, a.n_replicas, x, slot.lq, rung, l, e);
+        __syncthreads();
+        if (valid) gibbs_exchange_decide(a, X, WAVES * CPW, a.n_replicas, x, slot.lq, cid - (uint32_t)slot.j, l, rung, beta_next);
+      }
+    }
   }
 #undef DVG_GIBBS_WORD
 #undef DVG_GIBBS_WEIGH
 #undef DVG_GIBBS_FREE
+  if constexpr (EXCH) {
+    __syncthreads();  // the counters are final
+    if (valid) {
+      const size_t row = (size_t)(chain - slot.j + rung);  // the outputs by rung; state and rung by chain
+      int8_t* dst = a.state + (size_t)chain * n;
+      for (int i = l; i < n; i += LPC) {
+        const float v = (float)st[i];
+        dst[i] = (int8_t)v;
+        if (a.samples_out) a.samples_out[row * n + i] = v;
+      }
+      e = gibbs_chain_sum<LPC>(e);
+      if (l == 0) {
+        a.rung[chain] = rung;
+        if (a.energy_out) a.energy_out[row] = e;
+        if (a.accept_out) a.accept_out[chain] = X.acc[slot.lq * a.n_replicas + slot.j];
+      }
+    }
+    return;
+  }
   int8_t* dst = a.state + (size_t)chain * n;
   for (int i = l; i < n; i += LPC) {
     const float v = (float)st[i];
@@ -798,6 +969,16 @@ static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStrea
     if (p.form == GF_SLOTS) return gibbs_launch(gibbs_slot_kernel_of(p), p, a, s, a, p.slots);
   }
   return gibbs_launch(gibbs_kernel_of<HELD, SCHED>(p), p, a, s, a);
+}
+
+// the exchange draw: its own plan (the replica count is an input), the same tables
+static int gibbs_draw_exchange(const dvg_graph_t* g, GibbsExchangeArgs& a, hipStream_t s) {
+  GibbsDrawPlan p;
+  DVG_TRY(gibbs_exchange_plan(g->shape, a.n_chains / a.n_replicas, a.n_replicas, opt(OPT_GIBBS_GENERIC), &p, nullptr));
+  if (p.form == GF_LANE) {
+    a.lane_spin = g->lane_spin; a.lane_eid = g->lane_eid; a.lane_off = g->lane_off; a.n_rows = g->shape.lane_rows;
+  }
+  return gibbs_launch(gibbs_kernel_of<false, GIBBS_EXCHANGE>(p), p, a, s, a);
 }
 
 // What every draw checks, under its entry point's name `who`.  `missing`: the entry point's own null argument, if any
@@ -902,6 +1083,33 @@ extern "C" int dvg_gibbs_sample_ais(const dvg_graph_t* g, const float* linear, c
   a.betas = betas; a.beta_stride = beta_chain_stride;
   a.beta_from = beta_from; a.log_weight_out = log_weight_out; a.energy_out = energy_out;
   return gibbs_draw<false, GIBBS_WEIGH>(g, a, (hipStream_t)stream);
+}
+
+// The exchange draw ("DVG PT v1", include/dvg.h): ladders of n_replicas chains, each at the beta of the rung it holds; every
+// swap_every sweeps the chains of neighbouring rungs of a ladder exchange them on a Metropolis coin.
+extern "C" int dvg_gibbs_sample_tempered(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                         float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                         const float* ladder, int n_replicas, int swap_every,
+                                         int8_t* state, int32_t* rung, int n_chains, uint32_t chain_id0, uint64_t seed,
+                                         uint32_t sweep0, int n_sweeps, int init, float* samples_out,
+                                         double* energy_out, uint32_t* accept_out,
+                                         const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  DVG_TRY(gibbs_check("gibbs_tempered", g, linear && quadratic && state,
+                      !ladder ? "null ladder (a draw at one fixed beta is dvg_gibbs_sample)" : !rung ? "null rung" : nullptr,
+                      n_chains, n_sweeps, false, nullptr));
+  DVG_REQUIRE(n_sweeps >= 1, "gibbs_tempered: n_sweeps=%d (a draw of at least one sweep)", n_sweeps);
+  DVG_REQUIRE(n_replicas >= 2 && n_replicas <= GIBBS_MAX_REPLICAS, "gibbs_tempered: n_replicas=%d is not in 2..%d", n_replicas,
+              GIBBS_MAX_REPLICAS);
+  DVG_REQUIRE(n_chains % n_replicas == 0, "gibbs_tempered: n_chains=%d is not a multiple of n_replicas=%d (whole ladders)", n_chains,
+              n_replicas);
+  DVG_REQUIRE(swap_every >= 1, "gibbs_tempered: swap_every=%d must be at least 1", swap_every);
+  DVG_REQUIRE(!dyn, "gibbs_tempered: dyn must be NULL (the exchanges of a call are counted on the host, from its sweep0)");
+  GibbsExchangeArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, nullptr);
+  a.ladder = ladder; a.n_replicas = n_replicas; a.swap_every = swap_every;
+  a.rung = rung; a.energy_out = energy_out; a.accept_out = accept_out;
+  return gibbs_draw_exchange(g, a, (hipStream_t)stream);
 }
 
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,

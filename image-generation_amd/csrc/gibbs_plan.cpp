@@ -142,4 +142,34 @@ int gibbs_draw_plan(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, 
   return gibbs_plan_rolled(g, n_chains, kind == GK_HELD, g.max_class <= 16 ? 16 : g.max_class <= 32 ? 32 : 64, small ? 1 : 4, &p);
 }
 
+int gibbs_exchange_plan(const GibbsGraphShape& g, int n_ladders, int n_replicas, int64_t generic_option, GibbsDrawPlan* out,
+                        int* ladders_per_block) {
+  GibbsDrawPlan& p = *out;
+  const int R = n_replicas, n_chains = n_ladders * R;
+  DVG_TRY(gibbs_draw_plan(g, n_chains, GK_TABLE, generic_option, &p));
+  if (p.chains_per_block < R) {
+    // (every one-wave entry of both lists has its four-wave twin)
+    if (p.waves == 1 && 4 * p.chains_per_block >= R) {
+      p.waves = 4;
+      p.chains_per_block *= 4; p.threads = 4 * 64;
+      p.lds = p.form == GF_LANE ? gibbs_lane_lds_bytes(g.lane_rows, p.mb, p.lpc, g.n, p.chains_per_block)
+                                : gibbs_lds_bytes(g.n, g.n_batches, g.n_colours, p.chains_per_block);
+    } else {
+      p = GibbsDrawPlan{};
+      DVG_TRY(gibbs_plan_rolled(g, n_chains, false, 64, 16, &p));
+    }
+  }
+  const int per_block = p.chains_per_block / R;
+  size_t o[3];
+  p.lds = gibbs_exchange_lds_layout(p.lds, p.chains_per_block, o);
+  p.grid = (int)ceil_div(n_ladders, per_block);
+  if (ladders_per_block) *ladders_per_block = per_block;
+  if (p.lds > GIBBS_LDS_MAX) {
+    set_error("gibbs: graph (n=%d, %d neighbour batches) needs %zu B of LDS (the mailboxes of an exchange draw included) > 160 KiB",
+              g.n, g.n_batches, p.lds);
+    return DVG_E_UNSUPPORTED;
+  }
+  return DVG_OK;
+}
+
 }  // namespace dvg

@@ -49,6 +49,19 @@ __host__ __device__ __forceinline__ size_t gibbs_lane_lds_bytes(int slots, int m
   return (size_t)slots * mb * lpc * 24 + 2 * (size_t)chains * ((n + 15) & ~15) + 2 * 64 * (size_t)((chains * lpc + 63) / 64);
 }
 
+// The exchange draw (replica exchange, "DVG PT v1"): behind the form's own image of `form_bytes` bytes, for the `slots`
+// chain slots of a workgroup: two mailboxes of float64 chain energies [2][slots], indexed (ladder in workgroup, rung) |
+// accepted-exchange counters [slots], indexed (ladder in workgroup, lower rung) | the ladder's betas [16].  Returns the
+// bytes of the whole image.
+constexpr int GIBBS_MAX_REPLICAS = 16;
+__host__ __device__ __forceinline__ size_t gibbs_exchange_lds_layout(size_t form_bytes, int slots, size_t off[3]) {
+  size_t b = (form_bytes + 7) & ~(size_t)7;
+  off[0] = b; b += sizeof(double) * 2 * (size_t)slots;
+  off[1] = b; b += sizeof(uint32_t) * (size_t)slots;
+  off[2] = b; b += sizeof(float) * GIBBS_MAX_REPLICAS;
+  return b;
+}
+
 // ---------------------------------------------------------------- the instantiations, each family listed ONCE
 // The plan's "has a kernel" test and the tables of gibbs.hip that map a plan to a function pointer both expand from these.
 // Lane-major (gibbs_fast_kernel): (LPC, WAVES, MB, NR, MAXS).  A shape takes the FIRST entry with its lpc, mb and nr, its
@@ -82,8 +95,9 @@ struct GibbsGraphShape {
 GibbsGraphShape gibbs_graph_shape(int n, int n_colours, const int32_t* class_ptr, const int32_t* adj_ptr);
 
 // ---------------------------------------------------------------- the draw
-// plain: dvg_gibbs_sample; held: _clamped (kernels' HELD); table: _annealed (SCHED = GIBBS_TABLE); weigh: _ais (GIBBS_WEIGH)
-enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH };
+// plain: dvg_gibbs_sample; held: _clamped (kernels' HELD); table: _annealed (SCHED = GIBBS_TABLE); weigh: _ais (GIBBS_WEIGH);
+// exchange: _tempered (GIBBS_EXCHANGE) -- planned by gibbs_exchange_plan, which needs the replica count as well
+enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE };
 //   GF_ROLLED  gibbs_kernel<lpc, waves, HELD, SCHED>: any graph
 //   GF_LANE    gibbs_fast_kernel<lpc, waves, mb, nr, maxs, HELD, SCHED>: graphs with a lane-major image
 //   GF_SLOTS   gibbs_slot_kernel<maxs, ch, fix>: ch chains of a 16-wave workgroup side by side; the plain draw only
@@ -106,5 +120,13 @@ struct GibbsDrawPlan {
 // Pure: the same arguments give the same plan.  generic_option: option gibbs_generic as the call read it.
 // DVG_E_UNSUPPORTED (and the error message) when the form the graph must take needs more than 160 KiB of LDS.
 int gibbs_draw_plan(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, int64_t generic_option, GibbsDrawPlan* out);
+
+// The exchange draw's plan: n_ladders ladders of n_replicas (2..16) consecutive chains.  A ladder's chains hand rungs over
+// in LDS, so a workgroup must hold whole ladders.  Form: the table kind's plan for n_ladders * n_replicas chains if its
+// workgroup holds a ladder; else the same family at 4 waves if that does; else the rolled form (64, 16), which serves every
+// graph and holds 16 chains.  A workgroup holds chains_per_block / n_replicas ladders (*ladders_per_block; its other slots
+// idle), grid = ceil(n_ladders / that), lds = the form's own image plus gibbs_exchange_lds_layout.  Pure.
+int gibbs_exchange_plan(const GibbsGraphShape& g, int n_ladders, int n_replicas, int64_t generic_option, GibbsDrawPlan* out,
+                        int* ladders_per_block);
 
 }  // namespace dvg

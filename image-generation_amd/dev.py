@@ -25,6 +25,8 @@ _SIGS = {
     "dvg_dev_mmd_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "dvg_dev_gibbs_draw_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.POINTER(ctypes.c_int64)]),
+    "dvg_dev_gibbs_exchange_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.POINTER(ctypes.c_int64)]),
     "dvg_dev_conv_wino_stats_blocks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int]),
     "dvg_dev_wgrad_slab_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_conv_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 +
@@ -145,11 +147,28 @@ def gibbs_draw_plan(plan, n_chains, kind="plain"):
     o = (ctypes.c_int64 * 19)()
     _lib.check(lib().dvg_dev_gibbs_draw_plan(int(plan.n), int(plan.n_colours), class_ptr.ctypes.data, adj_ptr.ctypes.data,
                                              int(n_chains), GIBBS_KINDS.index(kind), o), "dvg_dev_gibbs_draw_plan")
+    return _gibbs_plan_dict(o)
+
+
+def _gibbs_plan_dict(o):
     form = GIBBS_FORMS[o[0]]
     params = {"rolled": dict(LPC=o[1], WAVES=o[2]), "lane": dict(LPC=o[1], WAVES=o[2], MB=o[3], NR=o[4], MAXS=o[5]),
               "slots": dict(MAXS=o[5], CH=o[6], FIX=bool(o[7]))}[form]
     return dict(form=form, params=params, slots=o[8], chains_per_workgroup=o[9], workgroups=o[10], threads=o[11],
                 lds_bytes=o[12], lane_image=dict(LPC=o[14], MB=o[15], NR=o[16], rows=o[17]) if o[13] else None, n_batches=o[18])
+
+
+def gibbs_exchange_plan(plan, n_ladders, n_replicas):
+    """The kernel form an exchange draw (``dvg_gibbs_sample_tempered``) of ``n_ladders`` ladders of ``n_replicas`` chains takes
+    on the graph of ``plan`` under the current option ``gibbs_generic`` (no device needed).  The entries of
+    :func:`gibbs_draw_plan` -- ``chains_per_workgroup`` counts chain slots, ``lds_bytes`` includes the exchange's mailboxes --
+    plus ``ladders_per_workgroup``: the whole ladders a workgroup holds (its other slots idle)."""
+    class_ptr = np.ascontiguousarray(plan.class_ptr, dtype=np.int32)
+    adj_ptr = np.ascontiguousarray(plan.adj_ptr, dtype=np.int32)
+    o = (ctypes.c_int64 * 20)()
+    _lib.check(lib().dvg_dev_gibbs_exchange_plan(int(plan.n), int(plan.n_colours), class_ptr.ctypes.data, adj_ptr.ctypes.data,
+                                                 int(n_ladders), int(n_replicas), o), "dvg_dev_gibbs_exchange_plan")
+    return dict(_gibbs_plan_dict(o), ladders_per_workgroup=o[19])
 
 
 def conv_wino(x_m, w, mode, M, Cin, Cout, L, bias=None, stats=False):

@@ -838,20 +838,31 @@ class ModelWrapper:
     # ------------------------------------------------------------------ generation (tensor-returning core)
     @torch.no_grad()
     def generate_images(self, sharpen: bool = False, lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD,
-                        betas=None) -> torch.Tensor:
+                        betas=None, tempered=None) -> torch.Tensor:
         """Sampler -> decoder -> clip, the compute of /root/reference/src/model_wrapper.py:355-385
         (plotting left to the caller).  Returns (NUM_READS, 1, 32, 32) on the device.  ``betas``: a (S,) or
         (NUM_READS, S) schedule -- generate from FRESH annealed chains (``GibbsSampler.sample_annealed``) instead of the
-        sampler's own draw."""
-        images, _samples = self._generate(sharpen, lower, upper, betas)
+        sampler's own draw.  ``tempered``: a mapping of :meth:`GibbsSampler.sample_tempered` keywords (``betas``: the
+        ladder; ``num_sweeps``, ``swap_every``, ...) -- generate from the target rung of NUM_READS fresh parallel-tempering
+        ladders instead.  One of the two at most."""
+        images, _samples = self._generate(sharpen, lower, upper, betas, tempered)
         return images
 
     @torch.no_grad()
-    def _generate(self, sharpen: bool, lower: float, upper: float, betas=None):
+    def _generate(self, sharpen: bool, lower: float, upper: float, betas=None, tempered=None):
+        if betas is not None and tempered is not None:
+            raise ValueError("give betas (annealed chains) or tempered (parallel-tempering ladders), not both")
+        if tempered is not None and ("betas" not in tempered or "num_ladders" in tempered):
+            raise ValueError("tempered: a mapping of sample_tempered keywords with the ladder as 'betas' (num_ladders is NUM_READS)")
         # (rank-local, like save(): data-parallel callers run sync_buffers() on every rank first)
         self._dvae.eval()
         self._grbm.eval()
-        if betas is None:
+        if tempered is not None:
+            kw = dict(tempered)
+            samples = self._grbm.sample_tempered(self.sampler, kw.pop("betas"), prefactor=self.PREFACTOR,
+                                                 linear_range=self.linear_range, quadratic_range=self.quadratic_range,
+                                                 num_ladders=int(self.sampler_kwargs.get("num_reads", 1)), **kw).target
+        elif betas is None:
             samples = self._grbm.sample(self.sampler, prefactor=self.PREFACTOR, device=self._device,
                                         linear_range=self.linear_range, quadratic_range=self.quadratic_range,
                                         sample_params=self.sampler_kwargs)

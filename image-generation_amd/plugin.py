@@ -190,6 +190,14 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         self._need_local_sampler(sampler, "log_partition")
         return sampler.log_partition(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, **kw)
 
+    def sample_tempered(self, sampler, betas, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """A parallel-tempering draw from the model under the prefactor-scaled, clamped ``(h, J)``: ladders of ``len(betas)``
+        chains that exchange rungs inside the kernel (:meth:`GibbsSampler.sample_tempered`; ``num_ladders``, ``num_sweeps``,
+        ``swap_every``, ``start``, ``rungs`` are passed on).  Returns its :class:`~.sampler.Tempered`; ``.target`` holds the
+        samples at ``betas[-1]``.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "sample_tempered")
+        return sampler.sample_tempered(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, betas, **kw)
+
     @torch.no_grad()
     def log_likelihood(self, x: torch.Tensor, sampler, *, prefactor: float, linear_range=None, quadratic_range=None,
                        log_z=None, **kw) -> torch.Tensor:

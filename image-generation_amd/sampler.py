@@ -176,6 +176,41 @@ class LogPartition:
         return f"LogPartition(log_z={float(self.log_z):.6f}, ess={float(self.ess):.1f}, std_err={float(self.std_err):.4f})"
 
 
+class Tempered:
+    """What :meth:`GibbsSampler.sample_tempered` returns, for Q ladders of R rungs; device tensors unless said otherwise.
+    ``samples`` (Q, R, n) float32 +-1 and ``energies`` (Q, R) float64, BY RUNG: ``[q, r]`` is the chain of ladder q that ended
+    the draw on rung r -- a sample at ``betas[r]``; ``target`` = ``samples[:, -1]``, the last rung's.  ``accepted`` (Q, R - 1)
+    int64: the accepted exchanges of each pair of neighbouring rungs; ``attempts`` (R - 1,) host int64: the exchanges of the
+    draw that had the pair (computed from the sweep range); ``acceptance_rate`` (R - 1,) float64: accepted over all ladders /
+    (Q attempts), NaN for a pair the draw never tried.  ``state`` (Q R, n) int8 and ``rungs`` (Q R,) int32, BY CHAIN: hand them
+    back as ``start`` / ``rungs`` to continue the draw."""
+
+    def __init__(self, samples, energies, accepted, attempts, state, rungs):
+        self.samples, self.energies, self.accepted, self.attempts, self.state, self.rungs = (samples, energies, accepted,
+                                                                                             attempts, state, rungs)
+
+    @classmethod
+    def from_draw(cls, n: int, R: int, out, energy, accept, sweep0: int, n_sweeps: int, swap_every: int, state, rungs) -> "Tempered":
+        Q = int(out.shape[0]) // R
+        x = np.arange(sweep0 + 1, sweep0 + n_sweeps + 1, dtype=np.int64)
+        x = x[x % swap_every == 0] // swap_every  # the numbers of the draw's exchanges; number x has the pairs r = x & 1, ...
+        attempts = np.array([int(((x & 1) == (r & 1)).sum()) for r in range(R - 1)], dtype=np.int64)
+        return cls(out.view(Q, R, n), energy.view(Q, R), accept.view(Q, R)[:, :R - 1].to(torch.int64), attempts, state, rungs)
+
+    @property
+    def target(self):
+        return self.samples[:, -1]
+
+    @property
+    def acceptance_rate(self):
+        tried = torch.from_numpy(self.attempts.astype(np.float64)).to(self.accepted.device) * int(self.accepted.shape[0])
+        return self.accepted.sum(0).to(torch.float64) / tried
+
+    def __repr__(self):
+        Q, R, n = self.samples.shape
+        return f"Tempered({Q} ladders x {R} rungs, n={n}, attempts={self.attempts.tolist()})"
+
+
 class GibbsSampler:
     """``sample_ising``-compatible local solver running on the MI355X.
 
@@ -216,6 +251,9 @@ class GibbsSampler:
         # ... and the weighed annealed draws (sample_ais, log_partition)
         self.ais_seed = self.seed ^ 0x61697331
         self.ais_sweep_count = 0
+        # ... and the exchange draws (sample_tempered)
+        self.pt_seed = self.seed ^ 0x70743031
+        self.pt_sweep_count = 0
         # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
         self._betas: Optional[torch.Tensor] = None
         self._fixed_sweeps = self.sweeps
@@ -233,6 +271,7 @@ class GibbsSampler:
         self.cond_sweep_count = 0
         self.anneal_sweep_count = 0
         self.ais_sweep_count = 0
+        self.pt_sweep_count = 0
 
     def set_beta_schedule(self, betas) -> None:
         """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
@@ -500,6 +539,86 @@ class GibbsSampler:
         samples, log_w, _energy = self.sample_ais(linear, quadratic, prefactor, linear_range, quadratic_range, betas,
                                                   num_reads=num_reads)
         return LogPartition.from_weights(self.plan.n, log_w, samples)
+
+    def sample_tempered(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                        betas, *, num_ladders: int, num_sweeps: Optional[int] = None, swap_every: int = 1,
+                        start: Optional[torch.Tensor] = None, rungs: Optional[torch.Tensor] = None) -> "Tempered":
+        """A parallel-tempering (replica-exchange) draw (``dvg_gibbs_sample_tempered``, "DVG PT v1" in include/dvg.h):
+        ``num_ladders`` ladders of R = ``len(betas)`` chains each.  A chain sweeps at the beta of the rung it holds; after
+        every ``swap_every`` sweeps the chains on neighbouring rungs of a ladder exchange their rungs on a Metropolis coin,
+        inside the kernel, so that the chain at the last rung -- the target -- is fed states that crossed between modes
+        where it is hot.
+
+        ``betas``: (R,), R in 2..16, rung 0 first (hot) and the target last; a host sequence, array or CPU tensor (checked:
+        finite, >= 0).  ``beta_schedule(b_hot, b_target, R)`` builds a geometric or linear ladder.  ``num_sweeps``: default
+        the sampler's ``sweeps``.  ``start=None``: fresh chains from the INIT stream, chain c on rung c % R; to continue a
+        draw give the ``state`` and ``rungs`` of its :class:`Tempered` as ``start`` ((Q R, n) int8 or float32 +-1) and
+        ``rungs`` ((Q R,) integer), both on the device, both or neither.  Returns a :class:`Tempered`; no host sync.
+
+        Its own key ``pt_seed`` and counter ``pt_sweep_count`` (which also numbers the exchanges): the training,
+        conditional, annealed and AIS streams are left alone.  Chain ids are ``chain_offset + arange(Q R)``."""
+        n = self.plan.n
+        # every argument check comes before the first library call (the ladder's upload included)
+        if torch.is_tensor(betas) and betas.is_cuda:
+            raise _lib.DvgError("betas: the ladder is a host sequence, array or CPU tensor (it is checked, then uploaded)")
+        ladder = _check_beta_table(betas, "betas")
+        if ladder.ndim != 1 or not 2 <= ladder.size <= 16:
+            raise _lib.DvgError(f"betas must be (replicas,) with 2 to 16 replicas, got {tuple(ladder.shape)}")
+        R = int(ladder.size)
+        for name, v in (("num_ladders", num_ladders), ("swap_every", swap_every),
+                        ("num_sweeps", self.sweeps if num_sweeps is None else num_sweeps)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        Q, S, swap_every = int(num_ladders), int(self.sweeps if num_sweeps is None else num_sweeps), int(swap_every)
+        if (start is None) != (rungs is None):
+            raise ValueError("start and rungs go together: give both (to continue a draw) or neither (fresh chains)")
+        if start is not None:
+            for name, t in (("start", start), ("rungs", rungs)):
+                if not torch.is_tensor(t):
+                    raise _lib.DvgError(f"{name} must be a tensor, got {type(t).__name__}")
+            if start.dtype not in (torch.float32, torch.int8):
+                raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
+            if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1 or start.shape[0] % R:
+                raise _lib.DvgError(f"start must be (ladders x {R}, {n}), got {tuple(start.shape)}")
+            if rungs.dtype not in (torch.int32, torch.int64) or tuple(rungs.shape) != (int(start.shape[0]),):
+                raise _lib.DvgError(f"rungs must be ({int(start.shape[0])},) int32 or int64, got {tuple(rungs.shape)} {rungs.dtype}")
+            if int(start.shape[0]) != Q * R:
+                raise _lib.DvgError(f"num_ladders={num_ladders!r} but start has {int(start.shape[0])} chains ({R} per ladder)")
+            for name, t in (("start", start), ("rungs", rungs)):
+                if not t.is_cuda:
+                    raise _lib.DvgError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
+        C = Q * R
+        lin = _lib.require_cuda(linear.detach(), "linear")
+        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
+        if lin.numel() != n or quad.numel() != self.plan.n_edges:
+            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
+        for name, t in (("start", start), ("rungs", rungs)):
+            if t is not None and t.device != lin.device:
+                raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
+        table = torch.from_numpy(ladder).to(lin.device)
+        if start is None:
+            state, rung, init = (torch.empty((C, n), dtype=torch.int8, device=lin.device),
+                                 torch.empty((C,), dtype=torch.int32, device=lin.device), 1)
+        else:  # the call's own chains
+            state, rung, init = start.detach().to(torch.int8, copy=True).contiguous(), rungs.detach().to(torch.int32, copy=True).contiguous(), 0
+        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
+        energy = torch.empty((C,), dtype=torch.float64, device=lin.device)
+        accept = torch.empty((C,), dtype=torch.int32, device=lin.device)  # (uint32 counts; a draw has fewer than 2^31 exchanges)
+        inf = float("inf")
+        hl, hh = linear_range if linear_range is not None else (-inf, inf)
+        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+        sweep0 = self.pt_sweep_count & 0xFFFFFFFF
+        with torch.cuda.device(lin.device):
+            _lib.check(
+                _lib.lib().dvg_gibbs_sample_tempered(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
+                                                     float(hh), float(jl), float(jh), table.data_ptr(), R, swap_every,
+                                                     state.data_ptr(), rung.data_ptr(), C, self.chain_offset & 0xFFFFFFFF,
+                                                     self.pt_seed, sweep0, S, init, out.data_ptr(), energy.data_ptr(),
+                                                     accept.data_ptr(), None, _lib.stream_ptr(lin.device)),
+                "dvg_gibbs_sample_tempered",
+            )
+        self.pt_sweep_count += S
+        return Tempered.from_draw(n, R, out, energy, accept, sweep0, S, swap_every, state, rung)
 
     # -- dimod-style entry point -----------------------------------------------------------
     def sample_ising(self, h: Dict, J: Dict, num_reads: int = 1, answer_mode: str = "raw", auto_scale: bool = False,

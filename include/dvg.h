@@ -178,6 +178,46 @@ int dvg_gibbs_sample_ais(const dvg_graph_t *g, const float *linear, const float 
                          uint32_t sweep0, int n_sweeps, int init, float *samples_out,
                          double *log_weight_out, double *energy_out,
                          const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The exchange draw ("DVG PT v1"): parallel tempering (replica exchange).  Chains of one model run side by side at the
+ * inverse temperatures of a LADDER and, every few sweeps, chains on neighbouring rungs exchange their rungs on a Metropolis
+ * coin, inside the kernel: the chain at the target beta keeps being fed states that crossed between modes where it is hot.
+ *   Ladders, chains, rungs.  n_chains = Q * R: Q ladders of R = n_replicas consecutive chains; chain c belongs to ladder
+ *     q = c / R and has id chain_id0 + c.  ladder: DEVICE pointer, float32 [R], beta of rung r (ascending is usual, not
+ *     required, not checked; finite and >= 0, not checked).  A chain keeps its state row and its id for the whole draw; what
+ *     moves between chains is the rung.  rung: DEVICE pointer, int32 [n_chains], in/out, values 0 .. R-1, a permutation
+ *     within each ladder (values outside are clamped into the range; anything but a permutation gives a draw without
+ *     meaning, never an access out of bounds).  init != 0: the start state comes from the INIT stream as in every draw, and
+ *     the kernel writes rung[c] = c % R, ignoring the input.
+ *   Sweeps and energies.  Sweep k of the call has global index t = sweep0 + k and is a v1 sweep of chain c at
+ *     beta = ladder[rung[c]] (two_beta = 2 * beta) -- what dvg_gibbs_sample_annealed does with that value in the chain's row,
+ *     same Philox counters (spin, chain id, t >> 2, STREAM_GIBBS).  Each chain carries the energy E_c of "DVG AIS v1" in
+ *     float64: the start walk sum_i 1/2 s_i (hs_i + f_i), then (s_new - s_old) f_i per update.
+ *   Exchanges.  After sweep t, if (t + 1) % swap_every == 0, exchange number x = (t + 1) / swap_every takes place: in every
+ *     ladder q, for r = x & 1, (x & 1) + 2, ... while r + 1 < R, with a the chain holding rung r and b the chain holding r + 1,
+ *       d    = ((double)ladder[r+1] - (double)ladder[r]) * (E_b - E_a)     float64: two subtractions, one product;
+ *       word = philox4x32_10(ctr = (r, chain_id0 + q R, x, STREAM_SWAP = 4), key = seed).x,  u = (word >> 8) 2^-24;
+ *       accept iff d >= 0 or u < exp(d) (float64 exp); on accept a takes rung r + 1 and b takes rung r.
+ *     The pairs of one exchange are disjoint: their order does not matter.  Only the order of the float64 additions of an
+ *     energy, and the last bit of exp, are the implementation's.
+ *   Outputs.  state and rung are stored BY CHAIN, so that a later call continues the draw; samples_out (n_chains, n) float32
+ *     and energy_out [n_chains] float64 BY RUNG: row / element q R + rung[c] is chain c's final state and its energy;
+ *     accept_out [n_chains] uint32: element q R + r = the accepted exchanges of the pair (r, r + 1) of ladder q in this call
+ *     (written, not added to; element q R + R - 1 is 0).  samples_out, energy_out and accept_out may each be NULL.
+ *   Continuation.  A call of S sweeps, and two calls of S1 + S2 = S sweeps that hand state and rung on with sweep0 advanced
+ *     by S1, are the same draw but for the second call's start energies, summed afresh: the same spins and rungs whenever no
+ *     acceptance is a near tie.
+ *   DVG_E_INVALID, before any launch: what dvg_gibbs_sample rejects, ladder == NULL, rung == NULL, n_replicas outside 2..16,
+ *     n_chains not a multiple of n_replicas, swap_every < 1, n_sweeps < 1, dyn != NULL (the draw is one-off, not part of a
+ *     captured step: the workgroup barriers of its exchanges are counted from the host's sweep0).  A workgroup holds whole
+ *     ladders; DVG_E_UNSUPPORTED if the graph's image with the exchange's mailboxes beside it exceeds the LDS.  No exchange
+ *     form of dvg_gibbs_sample_clamped. */
+int dvg_gibbs_sample_tempered(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                              float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                              const float *ladder, int n_replicas, int swap_every,
+                              int8_t *state, int32_t *rung, int n_chains, uint32_t chain_id0, uint64_t seed,
+                              uint32_t sweep0, int n_sweeps, int init, float *samples_out,
+                              double *energy_out, uint32_t *accept_out,
+                              const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and

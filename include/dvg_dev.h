@@ -53,6 +53,12 @@ int dvg_dev_mmd_plan(int64_t nx, int64_t ny, int dim, int64_t out[24]);
  * graph must take needs more than 160 KiB of LDS. */
 int dvg_dev_gibbs_draw_plan(int n, int n_colours, const int32_t *class_ptr, const int32_t *adj_ptr, int n_chains, int kind,
                             int64_t out[19]);
+/* The same for an exchange draw (dvg_gibbs_sample_tempered) of n_ladders ladders of n_replicas (2..16) chains
+ * (csrc/gibbs_plan.h, gibbs_exchange_plan: the table kind's form if its workgroup holds a ladder, else that family at four
+ * waves, else the rolled form (64, 16)).  out[0..18] as above -- out[9] chain SLOTS per workgroup, out[10] workgroups =
+ * ceil(n_ladders / out[19]), out[12] with the mailboxes, counters and ladder -- and out[19] the whole ladders a workgroup holds. */
+int dvg_dev_gibbs_exchange_plan(int n, int n_colours, const int32_t *class_ptr, const int32_t *adj_ptr, int n_ladders,
+                                int n_replicas, int64_t out[20]);
 /* The same layer in the Winograd F(4x4,3x3) form (csrc/conv_wino4.hip: 36 position GEMMs per 4x4 output tile, 2.25 multiplies
  * per output where F(2x2,3x3) issues 4.0): `u` = scratch of 36*Cin*Cout floats, `stats` rows = M / 1024 (tile blocks of 64
  * tiles), cus = CUs the persistent grid is sized for (0 = 256).  Shapes: whole 1024-pixel blocks of 4x4 / 8x8 / 16x16 images. */

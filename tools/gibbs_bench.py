@@ -10,6 +10,10 @@ table row per chain (a ladder: chain c ends at beta 20 (c + 1) / chains).
 `ais`: also the weighed annealed draw (dvg_gibbs_sample_ais: the annealed draw plus each chain's log importance weight and
 energy, accumulated in the kernel), timed as the annealed rows are -- the raw call on persistent chains, the same shared
 schedule and the same ladder; a second line gives the sums of the last draw's log weights and energies.
+`tempered`: also the exchange draw (dvg_gibbs_sample_tempered: ladders of `replicas=R` chains, default 4, `chains` / R of them, on a
+geometric ladder 10 -> 20), timed as the ais rows are -- the raw call on persistent chains and rungs: once with no exchange due
+(swap_every beyond every sweep: the weighed draw's work per update, nothing else) and once with an exchange after every sweep; a
+second line gives the last draw's accepted exchanges per pair of rungs.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -113,3 +117,29 @@ if "ais" in sys.argv:
         ts, out = timed(weighed)
         row(name, ts, C * n * sweeps, out)
         print(f"  {'':26s} sum of log weights {float(log_w.sum()):.6e}  sum of energies {float(energy.sum()):.6e}")
+if "tempered" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    R = max([int(a.split("=")[1]) for a in sys.argv if a.startswith("replicas=")] + [4])
+    Q = C // R
+    ladder = torch.from_numpy(smp.beta_schedule(10.0, 20.0, R)).cuda()
+    for name, every in (("tempered, no exchange due", 1 << 30), ("tempered, swap_every=1", 1)):
+        state = torch.empty((Q * R, n), dtype=torch.int8, device="cuda")
+        rung = torch.empty((Q * R,), dtype=torch.int32, device="cuda")
+        out = torch.empty((Q * R, n), dtype=torch.float32, device="cuda")
+        energy = torch.empty((Q * R,), dtype=torch.float64, device="cuda")
+        accept = torch.empty((Q * R,), dtype=torch.int32, device="cuda")
+        at = [0]
+
+        def exchange():
+            _lib.check(_lib.lib().dvg_gibbs_sample_tempered(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0,
+                                                            ladder.data_ptr(), R, every, state.data_ptr(), rung.data_ptr(), Q * R, 0,
+                                                            seed, at[0], sweeps, int(at[0] == 0), out.data_ptr(), energy.data_ptr(),
+                                                            accept.data_ptr(), None, _lib.stream_ptr()),
+                       "dvg_gibbs_sample_tempered")
+            at[0] += sweeps
+            return out
+
+        ts, out = timed(exchange)
+        row(name, ts, Q * R * n * sweeps, out)
+        print(f"  {'':26s} {Q} ladders x {R}: accepted per pair {accept.view(Q, R).sum(0)[:-1].tolist()} of {Q * (sweeps // every // 2)}"
+              f"  sum of energies {float(energy.sum()):.6e}")
