@@ -71,12 +71,22 @@ struct GibbsExchangeArgs : GibbsArgs {
   double* energy_out;    // [n_chains] by rung, or null
   uint32_t* accept_out;  // [n_chains]: element q R + r = accepted exchanges of the pair (r, r + 1) of ladder q; or null
 };
-constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3;
+// Traced draws (dvg_gibbs_sample_traced, "DVG trace v1" in include/dvg.h): the plain draw, with the chain's state written out
+// after chosen sweeps as one BIT per spin.  A fifth mode of SCHED, GIBBS_TRACE: the plain block plus the trace and which sweeps
+// it takes.  It runs at the fixed beta: the branches that read a beta table are `TABLE` (GIBBS_TABLE, GIBBS_WEIGH), not SCHED != 0.
+struct GibbsTraceArgs : GibbsArgs {
+  uint32_t* trace;       // [n_chains][n_records][(n + 31) / 32]: bit b of word w = spin 32 w + b is +1
+  int burn_in, thin;     // sweep k of the call is recorded iff k + 1 > burn_in and (k + 1 - burn_in) % thin == 0
+  int n_records;         // (n_sweeps - burn_in) / thin
+};
+constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3, GIBBS_TRACE = 4;
 template <bool HELD, int SCHED = 0>
 using GibbsArgsT = std::conditional_t<
-    SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
-    std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
-                       std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs, std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>;
+    SCHED == GIBBS_TRACE, GibbsTraceArgs,
+    std::conditional_t<SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
+                       std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
+                                          std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs,
+                                                             std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>>;
 
 // A chain's start state, its LPC lanes each taking spins l, l + LPC, ...: from the INIT stream (init) or from `state`.
 // HELD (a conditional draw): held spins from `state` always, free ones as above.
@@ -292,6 +302,45 @@ __device__ __forceinline__ void gibbs_exchange_decide(const GibbsExchangeArgs& a
   }
 }
 
+// ---------------------------------------------------------------- the record step (GIBBS_TRACE)
+// A chain's state row is n_pad = (n + 15) & ~15 float16 of +-1: the information is the sign bit.  Lane l of the chain's LPC
+// builds words l, l + LPC, ... < W = (n + 31) / 32 of the record: word w from halfwords 32 w .. 32 w + 31 of the row, four
+// 128-bit LDS reads of 8 halfwords each.  A read that would start at or behind n_pad reads the row's LAST 8 halfwords instead
+// (n_pad is a multiple of 8, so a read is inside the row or outside it as a whole; the address is clamped, not the read
+// predicated: the four reads of a word are issued back to back and waited for once): the last word of a graph with
+// n_pad % 32 == 16 ends in mid-word, with the next chain's row, the sinks or the held flags behind it, and nothing behind the
+// row is read.  Bits of spins >= n (the row's own pad, whatever it holds, and the clamped reads) are forced to 0.  The sign
+// bits of a read's four dwords (bits 15 and 31 of each) are gathered side by side, not one by one into one accumulator:
+// shallow dependency chains -- at one wave per SIMD nothing else hides them (the first form, 32 dependent shift-ors behind
+// predicated reads, cost 0.35 us per record; profiles/gibbs_trace.txt).  The stores: consecutive lanes, consecutive words.
+// Called behind the last class's fence of a sweep by the lanes that wrote the row -- one wave in every form: no workgroup
+// barrier.
+// A16: the rows are 16-byte aligned (the lane-major image; the padded-row image of the rolled form aligns them to 4 only, and
+// the compiler splits the read as the target needs).
+typedef uint32_t gu32x4 __attribute__((ext_vector_type(4)));
+typedef gu32x4 gu32x4_a4 __attribute__((aligned(4)));
+template <int LPC, bool A16>
+__device__ __forceinline__ void gibbs_record(const _Float16* st, int n, int n_pad, int l, uint32_t* rec) {
+  const int W = (n + 31) >> 5;
+  for (int w = l; w < W; w += LPC) {
+    uint32_t u[4];  // per read: the signs of halfwords 0, 2, 4, 6 at bits 0, 2, 4, 6 and of 1, 3, 5, 7 at bits 16, 18, 20, 22
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int h0 = min(32 * w + 8 * q, n_pad - 8);
+      gu32x4 v;
+      if constexpr (A16) v = *reinterpret_cast<const gu32x4*>(st + h0);
+      else v = *reinterpret_cast<const gu32x4_a4*>(st + h0);
+      u[q] = ((v[0] >> 15) & 0x00010001u) | (((v[1] >> 15) & 0x00010001u) << 2) | (((v[2] >> 15) & 0x00010001u) << 4) |
+             (((v[3] >> 15) & 0x00010001u) << 6);
+    }
+    const uint32_t a = u[0] | (u[1] << 8), b = u[2] | (u[3] << 8);  // 16 halfwords each: even ones at bits 0..14, odd at 16..30
+    // bit b: halfword 32 w + b has its sign bit set
+    const uint32_t minus = ((a | (a >> 15)) & 0xffffu) | (((b | (b >> 15)) & 0xffffu) << 16);
+    const int left = n - 32 * w;  // (>= 1)
+    rec[w] = ~minus & (left >= 32 ? 0xffffffffu : (1u << left) - 1u);
+  }
+}
+
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
 // HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
 // passed over in its class.  SCHED: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead.
@@ -300,10 +349,13 @@ __device__ __forceinline__ void gibbs_exchange_decide(const GibbsExchangeArgs& a
 // SCHED == GIBBS_EXCHANGE: the energy share as above, beta the entry of the rung the chain holds; at an exchange the
 // workgroup meets at a barrier (gibbs_exchange_post / _decide).  EVERY wave runs the sweep loop and reaches every barrier --
 // lanes of an idle slot with empty classes; the exchanges are counted from (sweep0, n_sweeps, swap_every) alone.
+// SCHED == GIBBS_TRACE: the plain draw at its fixed beta; behind a recorded sweep's last fence the chain's lanes pack its row
+// (gibbs_record).  Which sweeps: a countdown in scalar registers (`rec_at`, the next recorded k + 1), no division per sweep.
 template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
   constexpr bool AIS = SCHED == GIBBS_WEIGH, EXCH = SCHED == GIBBS_EXCHANGE, ENERGY = AIS || EXCH;
+  constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n;
   const GibbsLds L = gibbs_carve(smem, n, a.n_batches, a.n_colours);
@@ -356,13 +408,15 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
       const int R = a.n_replicas;
       if (valid) rung = a.init ? slot.j : min(max(a.rung[chain], 0), R - 1);
       beta_next = X.ladder[rung];
-    } else if constexpr (SCHED) {
+    } else if constexpr (TABLE) {
       bt = a.betas + (int64_t)chain * a.beta_stride;
       beta_next = bt[0];
     }
     [[maybe_unused]] double e = 0.0, lw = 0.0;
     [[maybe_unused]] float beta_prev = 0.0f;
     if constexpr (AIS) beta_prev = a.beta_from;
+    [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE: the next recorded sweep (as k + 1) and its record
+    if constexpr (TRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
     if constexpr (ENERGY) {
       for (int i = l; i < (valid ? n : 0); i += LPC) {
         const float hsi = L.hs[i];
@@ -374,7 +428,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
       float two_beta;
       if constexpr (EXCH) {
         two_beta = __fmul_rn(2.0f, beta_next);
-      } else if constexpr (SCHED) {
+      } else if constexpr (TABLE) {
         two_beta = __fmul_rn(2.0f, beta_next);
         if constexpr (AIS) {
           lw -= ((double)beta_next - (double)beta_prev) * e;
@@ -401,6 +455,13 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
         // the next class reads what this one wrote (same wave): order LDS traffic
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
+      }
+      if constexpr (TRACE) {
+        if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
+          gibbs_record<LPC, false>(st, n, n_pad, l, a.trace + ((size_t)chain * a.n_records + rec_m) * gibbs_held_words(n));
+          rec_at += (uint32_t)a.thin;
+          ++rec_m;
+        }
       }
       if constexpr (EXCH) {
         // (t, swap_every: kernel arguments -- the same in every wave of every workgroup)
@@ -658,10 +719,12 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
 // SCHED == GIBBS_EXCHANGE: the energy share of the AIS draw, two_beta from the rung the chain holds, and the workgroup's
 // barrier at every exchange.  No wave leaves before the last barrier: the lanes of an idle slot own no spin in any row (every
 // store of theirs goes to the sink), and a wave of idle slots alone passes over the sweep, not over the barrier.
+// SCHED == GIBBS_TRACE: the plain draw; gibbs_record behind a recorded sweep's last fence (the rows are 16-byte aligned here).
 template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
   constexpr bool AIS = SCHED == GIBBS_WEIGH, EXCH = SCHED == GIBBS_EXCHANGE, ENERGY = AIS || EXCH;
+  constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n, n_pad = (n + 15) & ~15;
   const int n_rows = a.n_rows;
@@ -767,7 +830,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   if constexpr (EXCH) {
     if (valid) rung = a.init ? slot.j : min(max(a.rung[chain], 0), a.n_replicas - 1);
     beta_next = X.ladder[rung];
-  } else if constexpr (SCHED) {
+  } else if constexpr (TABLE) {
     bt = a.betas + (int64_t)chain * a.beta_stride;
     beta_next = bt[0];
   }
@@ -775,6 +838,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   [[maybe_unused]] float beta_prev = 0.0f;
   [[maybe_unused]] uint32_t up = 0u;  // AIS: bit k = the spin of slot k is +1
   if constexpr (AIS) beta_prev = a.beta_from;
+  [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE: the next recorded sweep (as k + 1) and its record
+  if constexpr (TRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
   if constexpr (ENERGY) {
     // the sweep loop's walk over the steps, on the start state (it leaves `o` at step 0's offsets again)
 #pragma unroll
@@ -813,7 +878,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
     float two_beta;
     if constexpr (EXCH) {
       two_beta = __fmul_rn(2.0f, beta_next);
-    } else if constexpr (SCHED) {
+    } else if constexpr (TABLE) {
       two_beta = __fmul_rn(2.0f, beta_next);
       if constexpr (AIS) {
         lw -= ((double)beta_next - (double)beta_prev) * e;
@@ -865,6 +930,14 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
       // of each other, so a fence between them is harmless.)
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
+    }
+    if constexpr (TRACE) {
+      // (every lane still here is a valid chain's; the words of the held-flag helper: one bit per spin)
+      if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
+        gibbs_record<LPC, true>(st, n, n_pad, l, a.trace + ((size_t)chain * a.n_records + rec_m) * gibbs_held_words(n));
+        rec_at += (uint32_t)a.thin;
+        ++rec_m;
+      }
     }
     if constexpr (EXCH) {
       // (t, swap_every: kernel arguments -- the same in every wave of every workgroup)
@@ -959,7 +1032,11 @@ using namespace dvg;
 
 template <bool HELD, int SCHED = 0>
 static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStream_t s) {
-  constexpr GibbsDrawKind KIND = HELD ? GK_HELD : SCHED == GIBBS_WEIGH ? GK_WEIGH : SCHED == GIBBS_TABLE ? GK_TABLE : GK_PLAIN;
+  constexpr GibbsDrawKind KIND = HELD                   ? GK_HELD
+                                 : SCHED == GIBBS_WEIGH ? GK_WEIGH
+                                 : SCHED == GIBBS_TABLE ? GK_TABLE
+                                 : SCHED == GIBBS_TRACE ? GK_TRACE
+                                                        : GK_PLAIN;
   GibbsDrawPlan p;
   DVG_TRY(gibbs_draw_plan(g->shape, a.n_chains, KIND, opt(OPT_GIBBS_GENERIC), &p));
   if (p.form == GF_LANE) {
@@ -1110,6 +1187,31 @@ extern "C" int dvg_gibbs_sample_tempered(const dvg_graph_t* g, const float* line
   a.ladder = ladder; a.n_replicas = n_replicas; a.swap_every = swap_every;
   a.rung = rung; a.energy_out = energy_out; a.accept_out = accept_out;
   return gibbs_draw_exchange(g, a, (hipStream_t)stream);
+}
+
+// The traced draw ("DVG trace v1", include/dvg.h): dvg_gibbs_sample, with the chains' states after the recorded sweeps
+// written out one bit per spin.
+extern "C" int dvg_gibbs_sample_traced(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                       float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                       float beta, int8_t* state, int n_chains, uint32_t chain_id0,
+                                       uint64_t seed, uint32_t sweep0, int n_sweeps, int init,
+                                       float* samples_out, uint32_t* trace_out, int burn_in, int thin,
+                                       const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  DVG_TRY(gibbs_check("gibbs_traced", g, linear && quadratic && state,
+                      trace_out ? nullptr : "null trace_out (a draw that records nothing is dvg_gibbs_sample)", n_chains, n_sweeps,
+                      false, nullptr));
+  DVG_REQUIRE(burn_in >= 0, "gibbs_traced: burn_in=%d must be at least 0", burn_in);
+  DVG_REQUIRE(thin >= 1, "gibbs_traced: thin=%d must be at least 1", thin);
+  // (n_sweeps - burn_in >= thin, without the overflow of burn_in + thin)
+  DVG_REQUIRE(burn_in <= n_sweeps && n_sweeps - burn_in >= thin,
+              "gibbs_traced: n_sweeps=%d, burn_in=%d, thin=%d record nothing (a draw that records nothing is dvg_gibbs_sample)", n_sweeps,
+              burn_in, thin);
+  DVG_REQUIRE(!dyn, "gibbs_traced: dyn must be NULL (the draw is one-off: the recorded sweeps are counted from the host's sweep0)");
+  GibbsTraceArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, beta, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, nullptr);
+  a.trace = trace_out; a.burn_in = burn_in; a.thin = thin; a.n_records = (n_sweeps - burn_in) / thin;
+  return gibbs_draw<false, GIBBS_TRACE>(g, a, (hipStream_t)stream);
 }
 
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,

@@ -83,7 +83,7 @@ static int gibbs_plan_rolled(const GibbsGraphShape& g, int n_chains, bool held, 
 
 // The held draw takes the plain draw's choices, with two exceptions: it has no chains-side-by-side form, so the large
 // graphs' many-chain draws run the rolled kernel in 16-wave workgroups, and the A/B forms 3 and 4 count as 0.
-// The annealed draw, weighed or not: the same two exceptions.
+// The annealed draw, weighed or not, and the traced draw: the same two exceptions.
 int gibbs_draw_plan(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, int64_t generic_option, GibbsDrawPlan* out) {
   GibbsDrawPlan& p = *out;
   p = GibbsDrawPlan{};

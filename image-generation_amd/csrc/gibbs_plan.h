@@ -96,8 +96,10 @@ GibbsGraphShape gibbs_graph_shape(int n, int n_colours, const int32_t* class_ptr
 
 // ---------------------------------------------------------------- the draw
 // plain: dvg_gibbs_sample; held: _clamped (kernels' HELD); table: _annealed (SCHED = GIBBS_TABLE); weigh: _ais (GIBBS_WEIGH);
-// exchange: _tempered (GIBBS_EXCHANGE) -- planned by gibbs_exchange_plan, which needs the replica count as well
-enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE };
+// exchange: _tempered (GIBBS_EXCHANGE) -- planned by gibbs_exchange_plan, which needs the replica count as well;
+// trace: _traced (GIBBS_TRACE) -- the table kind's choices (no slots form), the table kind's LDS: a record is packed from the
+// state rows where they lie
+enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE, GK_TRACE };
 //   GF_ROLLED  gibbs_kernel<lpc, waves, HELD, SCHED>: any graph
 //   GF_LANE    gibbs_fast_kernel<lpc, waves, mb, nr, maxs, HELD, SCHED>: graphs with a lane-major image
 //   GF_SLOTS   gibbs_slot_kernel<maxs, ch, fix>: ch chains of a 16-wave workgroup side by side; the plain draw only

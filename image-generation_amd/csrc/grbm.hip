@@ -65,6 +65,59 @@ __global__ __launch_bounds__(256) void grbm_suffstats_reduce(const double* __res
   *dst = accumulate ? *dst + v : v;
 }
 
+// ---------------------------------------------------------------- moments of bit-packed rows (dvg_grbm_moments_packed)
+// rows (rows, W) uint32, one bit per spin (the traced draw's records).  A TILE is 64 rows -- one per lane of a wave.  A workgroup
+// takes `tiles_per_block` consecutive tiles and turns them into per-spin BIT COLUMNS in LDS, cols[tile][spin] = a 64-bit word
+// whose bit r is the spin's bit in row r of the tile: a wave takes (tile, word w) jobs, lane r reads word w of row r (rows
+// beyond the last read as 0), and 32 ballots give the columns of spins 32 w .. 32 w + 31, which lanes 0..31 keep one each
+// and store side by side.  Behind the barrier a thread walks spins and edges; over the T rows of a tile
+//   sum_r s_i = T - 2 popc(~col_i & tail),   sum_r s_i s_j = T - 2 popc((col_i ^ col_j) & tail),   tail = the T low bits,
+// summed over the workgroup's tiles in a register, then ONE integer atomic per spin / edge and workgroup: integer addition
+// commutes, so the result does not depend on the order the workgroups arrive in.  Columns of spins >= n are never stored.
+constexpr int MP_WAVES = 16, MP_LDS = 64 * 1024;
+
+__global__ __launch_bounds__(MP_WAVES * 64) void grbm_moments_packed_kernel(const uint32_t* __restrict__ bits, int64_t rows, int n,
+                                                                            int W, int n_edges, const int32_t* __restrict__ ei,
+                                                                            const int32_t* __restrict__ ej, int tiles_per_block,
+                                                                            unsigned long long* __restrict__ spin_sum,
+                                                                            unsigned long long* __restrict__ pair_sum) {
+  extern __shared__ __align__(16) unsigned char mp_smem[];
+  unsigned long long* cols = reinterpret_cast<unsigned long long*>(mp_smem);  // [tiles_per_block][n]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t n_tiles = (rows + 63) >> 6;
+  const int64_t tile0 = (int64_t)blockIdx.x * tiles_per_block;
+  if (tile0 >= n_tiles) return;  // (the whole workgroup: the grid is ceil(n_tiles / tiles_per_block))
+  const int kt = (int)(n_tiles - tile0 < tiles_per_block ? n_tiles - tile0 : tiles_per_block);
+  for (int job = wave; job < kt * W; job += MP_WAVES) {
+    const int k = job / W, w = job - k * W;
+    const int64_t r = (tile0 + k) * 64 + lane;
+    const uint32_t word = r < rows ? bits[r * W + w] : 0u;
+    unsigned long long col = 0ull;
+#pragma unroll
+    for (int b = 0; b < 32; ++b) {
+      const unsigned long long m = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
+      if (lane == b) col = m;
+    }
+    const int i = 32 * w + lane;
+    if (lane < 32 && i < n) cols[(size_t)k * n + i] = col;
+  }
+  __syncthreads();
+  const int64_t rows_here = (rows - tile0 * 64 < (int64_t)kt * 64) ? rows - tile0 * 64 : (int64_t)kt * 64;
+  const int last = (int)(rows_here - (int64_t)(kt - 1) * 64);  // rows of the workgroup's last tile: 1..64
+  const unsigned long long tail = last >= 64 ? ~0ull : (1ull << last) - 1ull;
+  for (int idx = tid; idx < n + n_edges; idx += MP_WAVES * 64) {
+    const int a = idx < n ? idx : ei[idx - n], b = idx < n ? -1 : ej[idx - n];
+    long long minus = 0;  // rows in which the spin, or the product of the pair, is -1
+    for (int k = 0; k < kt; ++k) {
+      const unsigned long long ca = cols[(size_t)k * n + a];
+      const unsigned long long x = b < 0 ? ~ca : ca ^ cols[(size_t)k * n + b];
+      minus += __popcll(k == kt - 1 ? x & tail : x);
+    }
+    const long long sum = (long long)rows_here - 2 * minus;
+    atomicAdd(idx < n ? spin_sum + idx : pair_sum + (idx - n), (unsigned long long)sum);  // (two's complement: the signed sum)
+  }
+}
+
 }  // namespace dvg
 
 using namespace dvg;
@@ -100,5 +153,35 @@ extern "C" int dvg_grbm_suffstats(const dvg_graph_t* g, const float* x, int64_t 
              g->n_edges, g->edge_i, g->edge_j, row_weight, (double*)ws);
   DVG_LAUNCH(K_GRBM_SUFFSTATS, grbm_suffstats_reduce, dim3(nb), dim3(256), 0, s, (const double*)ws, g->n,
              g->n_edges, scale, acc_linear, acc_quadratic, accumulate);
+  return DVG_OK;
+}
+
+// Exact integer moments of bit-packed rows (include/dvg.h): the traced draw's records, never unpacked.
+extern "C" int dvg_grbm_moments_packed(const dvg_graph_t* g, const uint32_t* bits, int64_t rows, int64_t* spin_sum,
+                                       int64_t* pair_sum, int accumulate, dvg_stream_t stream) {
+  DVG_REQUIRE(g && bits && spin_sum && pair_sum, "grbm_moments_packed: null argument");
+  DVG_REQUIRE(rows >= 1, "grbm_moments_packed: rows=%lld must be at least 1", (long long)rows);
+  const int n = g->n, W = (n + 31) / 32;
+  if ((size_t)n * 8 > (size_t)MP_LDS) {
+    set_error("grbm_moments_packed: n=%d > %d (a tile's bit columns are kept in %d KiB of LDS)", n, MP_LDS / 8, MP_LDS / 1024);
+    return DVG_E_UNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (!accumulate) {
+    DVG_CHECK_HIP(hipMemsetAsync(spin_sum, 0, sizeof(int64_t) * (size_t)n, s));
+    if (g->n_edges > 0) DVG_CHECK_HIP(hipMemsetAsync(pair_sum, 0, sizeof(int64_t) * (size_t)g->n_edges, s));
+  }
+  // tiles per workgroup: enough workgroups to fill the chip (about 128), as few atomics as that allows, within the LDS
+  const int64_t n_tiles = ceil_div(rows, 64);
+  const int64_t fit = MP_LDS / ((int64_t)n * 8);
+  int64_t per = ceil_div(n_tiles, 128);
+  per = per < 1 ? 1 : per > fit ? fit : per;
+  if (ceil_div(n_tiles, per) > 0x7fffffff) {
+    set_error("grbm_moments_packed: rows=%lld is more than one launch takes", (long long)rows);
+    return DVG_E_UNSUPPORTED;
+  }
+  DVG_LAUNCH(K_GRBM_SUFFSTATS, grbm_moments_packed_kernel, dim3((unsigned)ceil_div(n_tiles, per)), dim3(MP_WAVES * 64),
+             (size_t)per * n * 8, s, bits, rows, n, W, g->n_edges, g->edge_i, g->edge_j, (int)per,
+             reinterpret_cast<unsigned long long*>(spin_sum), reinterpret_cast<unsigned long long*>(pair_sum));
   return DVG_OK;
 }

@@ -133,12 +133,14 @@ def mmd_plan(nx, ny, d):
 
 GIBBS_FORMS = ("rolled", "lane", "slots")            # csrc/gibbs_plan.h: GibbsForm
 GIBBS_KINDS = ("plain", "held", "table", "weigh")    # GibbsDrawKind
+# ... by name: "trace" (dvg_gibbs_sample_traced) is GK_TRACE = 5, behind GK_EXCHANGE, which dvg_dev_gibbs_exchange_plan plans
+GIBBS_KIND_IDS = dict({k: i for i, k in enumerate(GIBBS_KINDS)}, trace=5)
 
 
 def gibbs_draw_plan(plan, n_chains, kind="plain"):
     """The kernel form a Gibbs draw of ``n_chains`` chains takes on the graph of ``plan`` (a ``graphs.GibbsPlan``) under
     the current option ``gibbs_generic`` (no device needed).  ``kind``: ``"plain"`` (``dvg_gibbs_sample``), ``"held"``
-    (``_clamped``), ``"table"`` (``_annealed``) or ``"weigh"`` (``_ais``).  ``form``: ``"rolled"`` (``gibbs_kernel``),
+    (``_clamped``), ``"table"`` (``_annealed``), ``"weigh"`` (``_ais``) or ``"trace"`` (``_traced``: the table kind's plan).  ``form``: ``"rolled"`` (``gibbs_kernel``),
     ``"lane"`` (``gibbs_fast_kernel``) or ``"slots"`` (``gibbs_slot_kernel``), ``params`` its template parameters;
     ``workgroups``, ``threads``, ``lds_bytes``: the launch, what ``dvg_gibbs_launch_info`` reports for the plain kind;
     ``lane_image``: the shape of the graph's lane-major image (csrc/graph.h), ``None`` for a graph that gets none."""
@@ -146,7 +148,7 @@ def gibbs_draw_plan(plan, n_chains, kind="plain"):
     adj_ptr = np.ascontiguousarray(plan.adj_ptr, dtype=np.int32)
     o = (ctypes.c_int64 * 19)()
     _lib.check(lib().dvg_dev_gibbs_draw_plan(int(plan.n), int(plan.n_colours), class_ptr.ctypes.data, adj_ptr.ctypes.data,
-                                             int(n_chains), GIBBS_KINDS.index(kind), o), "dvg_dev_gibbs_draw_plan")
+                                             int(n_chains), GIBBS_KIND_IDS[kind], o), "dvg_dev_gibbs_draw_plan")
     return _gibbs_plan_dict(o)
 
 

@@ -233,6 +233,31 @@ def grbm_energy(x, linear, quadratic, graph):
     return _Energy.apply(x, linear, quadratic, graph)
 
 
+def grbm_moments_packed(bits, graph, out=None):
+    """Exact integer moments of bit-packed +-1 rows (``dvg_grbm_moments_packed``): ``bits`` (rows, W) int32 on the device in
+    the layout of a traced draw (``sampler.Trace.bits``, ``sampler.pack_spins``; bits of spins >= n are ignored), ``graph``
+    a ``GraphHandle``.  Returns ``(spin_sum (n,), pair_sum (E,))`` int64: the sums over the rows of s_i and, per edge, of
+    s_i s_j.  ``out``: such a pair to add onto instead.  No host sync."""
+    n, E = int(graph.plan.n), int(graph.plan.n_edges)
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[1] != (n + 31) // 32 or bits.shape[0] < 1:
+        raise _lib.DvgError(f"bits must be (rows >= 1, {(n + 31) // 32}) int32, got "
+                            f"{tuple(bits.shape) if torch.is_tensor(bits) else type(bits).__name__}")
+    bd = require_cuda(bits.detach(), "bits")
+    if out is None:
+        spin_sum = torch.empty((n,), dtype=torch.int64, device=bd.device)
+        pair_sum = torch.empty((E,), dtype=torch.int64, device=bd.device)
+    else:
+        spin_sum, pair_sum = out
+        for name, t, k in (("spin_sum", spin_sum, n), ("pair_sum", pair_sum, E)):
+            if t.dtype != torch.int64 or tuple(t.shape) != (k,) or not t.is_contiguous() or t.device != bd.device:
+                raise _lib.DvgError(f"out: {name} must be a contiguous ({k},) int64 tensor on {bd.device}")
+    with torch.cuda.device(bd.device):
+        check(lib().dvg_grbm_moments_packed(graph.ptr, bd.data_ptr(), int(bd.shape[0]), spin_sum.data_ptr(),
+                                            pair_sum.data_ptr() if E else spin_sum.data_ptr(), int(out is not None),
+                                            stream_ptr(bd.device)), "dvg_grbm_moments_packed")
+    return spin_sum, pair_sum
+
+
 # ----------------------------------------------------------------------------- MSE
 
 

@@ -930,6 +930,19 @@ class ModelWrapper:
         return self._grbm.log_likelihood(spins, self.sampler, log_z=result.log_z, **ranges), result
 
     @torch.no_grad()
+    def prior_moments(self, **kw):
+        """The prior's moments ``<s_i>``, ``<s_i s_j>`` under the distribution the sampler draws from, over every record of
+        one traced draw (``GraphRestrictedBoltzmannMachine.model_moments``; ``num_reads``, ``num_sweeps``, ``burn_in``,
+        ``thin``, ``start`` are passed on, ``num_reads`` defaults to NUM_READS).  Returns ``(mean_spin, mean_pair)`` float64
+        on the device, shaped like the GRBM's ``linear`` / ``quadratic``.  Rank-local and eval-mode, like ``generate_images``."""
+        self._dvae.eval()
+        self._grbm.eval()
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        return self._grbm.model_moments(self.sampler, prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                        quadratic_range=self.quadratic_range, **kw)
+
+    @torch.no_grad()
     def reconstruct_images(self, batch: Optional[torch.Tensor] = None, sharpen: bool = False,
                            lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD) -> torch.Tensor:
         """Eval-mode encode -> discretise -> decode of one batch of training images, interleaved with the originals:

@@ -198,6 +198,25 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         self._need_local_sampler(sampler, "sample_tempered")
         return sampler.sample_tempered(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, betas, **kw)
 
+    def sample_trace(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """A traced draw from the model under the prefactor-scaled, clamped ``(h, J)``: the chains' states after every
+        ``thin``-th sweep behind ``burn_in``, bit-packed inside the kernel (:meth:`GibbsSampler.sample_trace`; ``num_reads``,
+        ``start``, ``num_sweeps``, ``burn_in``, ``thin`` are passed on).  Returns its :class:`~.sampler.Trace`.  The local
+        :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "sample_trace")
+        return sampler.sample_trace(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, **kw)
+
+    @torch.no_grad()
+    def model_moments(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """The model's moments ``<s_i>`` and ``<s_i s_j>`` estimated over every record of one traced draw
+        (:meth:`sample_trace`, ``**kw`` passed on; the sums are exact integers, ``dvg_grbm_moments_packed``).  Returns
+        ``(mean_spin, mean_pair)`` float64 on the device, shaped like ``linear`` / ``quadratic``.  The local
+        :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "model_moments")
+        trace = self.sample_trace(sampler, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range, **kw)
+        m = trace.moments(self.graph_handle(trace.bits.device))
+        return m.mean_spin.reshape(self._linear.shape), m.mean_pair.reshape(self._quadratic.shape)
+
     @torch.no_grad()
     def log_likelihood(self, x: torch.Tensor, sampler, *, prefactor: float, linear_range=None, quadratic_range=None,
                        log_z=None, **kw) -> torch.Tensor:

@@ -211,6 +211,89 @@ class Tempered:
         return f"Tempered({Q} ladders x {R} rungs, n={n}, attempts={self.attempts.tolist()})"
 
 
+def pack_spins(x: torch.Tensor) -> torch.Tensor:
+    """(..., n) spins (+1 where the entry is > 0) -> (..., W = ceil(n / 32)) int32 in the layout of "DVG trace v1"
+    (include/dvg.h): bit b of word w is 1 iff spin 32 w + b is +1, bits of spins >= n are 0.  Plain torch operations, on
+    the tensor's device (CPU tensors too)."""
+    n = int(x.shape[-1])
+    W = (n + 31) // 32
+    up = (x > 0).to(torch.int64)
+    up = torch.nn.functional.pad(up, (0, 32 * W - n)).reshape(*x.shape[:-1], W, 32)
+    words = (up << torch.arange(32, dtype=torch.int64, device=x.device)).sum(-1)  # 0 .. 2^32 - 1
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
+def unpack_spins(bits: torch.Tensor, n: int) -> torch.Tensor:
+    """The inverse of :func:`pack_spins`: (..., W) int32 -> (..., n) float32 +-1.  Bits of spins >= n are ignored."""
+    W = int(bits.shape[-1])
+    if W != (int(n) + 31) // 32:
+        raise ValueError(f"{W} words per row do not hold {n} spins")
+    b = (bits.to(torch.int64).unsqueeze(-1) >> torch.arange(32, dtype=torch.int64, device=bits.device)) & 1
+    return (2 * b.reshape(*bits.shape[:-1], 32 * W)[..., :int(n)] - 1).to(torch.float32)
+
+
+class Moments:
+    """Exact first and second moments of +-1 rows: ``spin_sum`` (n,) int64 = sum over rows of s_i, ``pair_sum`` (E,) int64 =
+    sum over rows of s_i s_j per edge of the graph, ``count`` the number of rows; ``mean_spin`` / ``mean_pair``: the sums
+    over ``count``, float64.  What :meth:`Trace.moments` returns (``dvg_grbm_moments_packed``)."""
+
+    def __init__(self, spin_sum, pair_sum, count):
+        self.spin_sum, self.pair_sum, self.count = spin_sum, pair_sum, int(count)
+
+    @classmethod
+    def from_sums(cls, spin_sum: torch.Tensor, pair_sum: torch.Tensor, count: int) -> "Moments":
+        if isinstance(count, bool) or int(count) != count or int(count) < 1:
+            raise ValueError(f"count must be an integer >= 1, got {count!r}")
+        for name, t in (("spin_sum", spin_sum), ("pair_sum", pair_sum)):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
+                raise ValueError(f"{name} must be a one-dimensional int64 tensor")
+        return cls(spin_sum, pair_sum, count)
+
+    @property
+    def mean_spin(self):
+        return self.spin_sum.to(torch.float64) / self.count
+
+    @property
+    def mean_pair(self):
+        return self.pair_sum.to(torch.float64) / self.count
+
+    def __repr__(self):
+        return f"Moments(n={int(self.spin_sum.shape[0])}, edges={int(self.pair_sum.shape[0])}, count={self.count})"
+
+
+def trace_sweeps(num_sweeps: int, burn_in: int, thin: int) -> np.ndarray:
+    """The recorded sweeps of a traced draw as the numbers k + 1 (k the 0-based sweep of the call), host int64: sweep k is
+    recorded iff ``k + 1 > burn_in`` and ``(k + 1 - burn_in) % thin == 0`` -- M = (num_sweeps - burn_in) // thin of them."""
+    return burn_in + thin * np.arange(1, max(0, (num_sweeps - burn_in) // thin) + 1, dtype=np.int64)
+
+
+class Trace:
+    """What :meth:`GibbsSampler.sample_trace` returns, for C chains and M records.  ``bits`` (C, M, W) int32 on the device:
+    the chains' states after the recorded sweeps, one bit per spin ("DVG trace v1": bit b of word w = spin 32 w + b is +1);
+    ``samples`` (C, n) float32 +-1: the final states; ``state`` (C, n) int8: the same, to hand back as ``start``;
+    ``sweeps`` (M,) host int64: the recorded sweeps, as k + 1 counted from the call's first sweep; ``n`` the spin count."""
+
+    def __init__(self, bits, samples, state, sweeps, n):
+        self.bits, self.samples, self.state, self.sweeps, self.n = bits, samples, state, sweeps, int(n)
+
+    def unpack(self) -> torch.Tensor:
+        """(C, M, n) float32 +-1, by plain torch bit operations on ``bits``' device (CPU tensors too)."""
+        return unpack_spins(self.bits, self.n)
+
+    def moments(self, graph) -> Moments:
+        """Exact moments over all C M records (``dvg_grbm_moments_packed``: the rows stay packed).  ``graph``: the
+        :class:`GraphHandle` whose edge list the pair sums follow."""
+        from . import functional as F  # (functional imports this module)
+
+        rows = self.bits.reshape(-1, self.bits.shape[-1])
+        spin_sum, pair_sum = F.grbm_moments_packed(rows, graph)
+        return Moments.from_sums(spin_sum, pair_sum, int(rows.shape[0]))
+
+    def __repr__(self):
+        C, M, _W = self.bits.shape
+        return f"Trace({C} chains x {M} records, n={self.n})"
+
+
 class GibbsSampler:
     """``sample_ising``-compatible local solver running on the MI355X.
 
@@ -254,6 +337,9 @@ class GibbsSampler:
         # ... and the exchange draws (sample_tempered)
         self.pt_seed = self.seed ^ 0x70743031
         self.pt_sweep_count = 0
+        # ... and the traced draws (sample_trace)
+        self.trace_seed = self.seed ^ 0x74726163
+        self.trace_sweep_count = 0
         # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
         self._betas: Optional[torch.Tensor] = None
         self._fixed_sweeps = self.sweeps
@@ -272,6 +358,7 @@ class GibbsSampler:
         self.anneal_sweep_count = 0
         self.ais_sweep_count = 0
         self.pt_sweep_count = 0
+        self.trace_sweep_count = 0
 
     def set_beta_schedule(self, betas) -> None:
         """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
@@ -619,6 +706,76 @@ class GibbsSampler:
             )
         self.pt_sweep_count += S
         return Tempered.from_draw(n, R, out, energy, accept, sweep0, S, swap_every, state, rung)
+
+    def sample_trace(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range, *,
+                     num_reads: Optional[int] = None, start: Optional[torch.Tensor] = None, num_sweeps: Optional[int] = None,
+                     burn_in: int = 0, thin: int = 1) -> "Trace":
+        """A traced draw (``dvg_gibbs_sample_traced``, "DVG trace v1" in include/dvg.h): ``num_sweeps`` (default: the
+        sampler's ``sweeps``) sweeps at the sampler's ``beta``, with the chains' states written out from inside the kernel
+        after every ``thin``-th sweep behind the first ``burn_in`` -- sweep k (0-based) iff ``k + 1 > burn_in`` and
+        ``(k + 1 - burn_in) % thin == 0``, M = ``(num_sweeps - burn_in) // thin`` records of n / 8 bytes per chain.
+
+        ``start=None``: ``num_reads`` fresh chains from the INIT stream; ``start`` (C, n) int8 or float32 +-1 on the device:
+        the chains begin at the call's own copy of it.  Returns a :class:`Trace`; no host sync.
+
+        Its own key ``trace_seed`` and counter ``trace_sweep_count``: the training, conditional, annealed, AIS and exchange
+        streams, the persistent chains, ``sweep_count`` and ``calls`` are left alone.  Chain ids are ``chain_offset +
+        arange(C)``."""
+        n = self.plan.n
+        # every argument check comes before the first library call
+        for name, v, low in (("num_sweeps", self.sweeps if num_sweeps is None else num_sweeps, 1), ("burn_in", burn_in, 0),
+                             ("thin", thin, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < low:
+                raise ValueError(f"{name} must be an integer >= {low}, got {v!r}")
+        S, burn_in, thin = int(self.sweeps if num_sweeps is None else num_sweeps), int(burn_in), int(thin)
+        M = (S - burn_in) // thin
+        if M < 1:
+            raise ValueError(f"num_sweeps={S}, burn_in={burn_in}, thin={thin} record nothing (a draw without a trace is sample_native)")
+        if start is not None:
+            if not torch.is_tensor(start):
+                raise _lib.DvgError(f"start must be a tensor, got {type(start).__name__}")
+            if start.dtype not in (torch.float32, torch.int8):
+                raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
+            if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1:
+                raise _lib.DvgError(f"start must be (chains, {n}), got {tuple(start.shape)}")
+            if num_reads is not None and num_reads != int(start.shape[0]):
+                raise _lib.DvgError(f"num_reads={num_reads!r} but start has {int(start.shape[0])} chains")
+            if not start.is_cuda:
+                raise _lib.DvgError(f"start must live on the GPU (got {start.device}); the HIP path has no CPU fallback")
+            C = int(start.shape[0])
+        elif num_reads is not None:
+            if isinstance(num_reads, bool) or not isinstance(num_reads, (int, float, np.integer, np.floating)) or \
+                    int(num_reads) != num_reads or int(num_reads) < 1:
+                raise ValueError(f"num_reads must be an integer >= 1, got {num_reads!r}")
+            C = int(num_reads)
+        else:
+            raise ValueError("a traced draw needs num_reads (fresh chains) or start to know how many chains to draw")
+        lin = _lib.require_cuda(linear.detach(), "linear")
+        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
+        if lin.numel() != n or quad.numel() != self.plan.n_edges:
+            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
+        if start is not None and start.device != lin.device:
+            raise _lib.DvgError(f"start is on {start.device}, the model parameters on {lin.device}")
+        if start is None:
+            state, init = torch.empty((C, n), dtype=torch.int8, device=lin.device), 1
+        else:
+            state, init = start.detach().to(torch.int8, copy=True).contiguous(), 0  # the call's own chains
+        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
+        bits = torch.empty((C, M, (n + 31) // 32), dtype=torch.int32, device=lin.device)
+        inf = float("inf")
+        hl, hh = linear_range if linear_range is not None else (-inf, inf)
+        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+        with torch.cuda.device(lin.device):
+            _lib.check(
+                _lib.lib().dvg_gibbs_sample_traced(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
+                                                   float(hh), float(jl), float(jh), self.beta, state.data_ptr(), C,
+                                                   self.chain_offset & 0xFFFFFFFF, self.trace_seed,
+                                                   self.trace_sweep_count & 0xFFFFFFFF, S, init, out.data_ptr(), bits.data_ptr(),
+                                                   burn_in, thin, None, _lib.stream_ptr(lin.device)),
+                "dvg_gibbs_sample_traced",
+            )
+        self.trace_sweep_count += S
+        return Trace(bits, out, state, trace_sweeps(S, burn_in, thin), n)
 
     # -- dimod-style entry point -----------------------------------------------------------
     def sample_ising(self, h: Dict, J: Dict, num_reads: int = 1, answer_mode: str = "raw", auto_scale: bool = False,

@@ -218,6 +218,29 @@ int dvg_gibbs_sample_tempered(const dvg_graph_t *g, const float *linear, const f
                               uint32_t sweep0, int n_sweeps, int init, float *samples_out,
                               double *energy_out, uint32_t *accept_out,
                               const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The traced draw ("DVG trace v1"): dvg_gibbs_sample with a history of the chains written from inside the kernel.  The
+ * spins, the random words, the INIT stream, state and samples_out are dvg_gibbs_sample's with the same arguments, bit for
+ * bit; the chains' states after chosen sweeps are written out as well, one BIT per spin.
+ *   Which sweeps are recorded.  Sweep k of the call is 0-based and has global index sweep0 + k.  It is recorded, after its
+ *     last colour class, iff  k + 1 > burn_in  and  (k + 1 - burn_in) % thin == 0.
+ *   Number of records.  M = (n_sweeps - burn_in) / thin, rounded down; record m (0 .. M-1) holds the state after sweep
+ *     k = burn_in + thin (m + 1) - 1.  The last sweep of the call is recorded iff (n_sweeps - burn_in) % thin == 0.
+ *   Layout.  W = (n + 31) / 32 words per record;  trace_out[(c M + m) W + w]  holds the packed spins of chain c at record m:
+ *     bit b of word w is 1 iff spin 32 w + b is +1; bits of spins >= n are 0.  trace_out: DEVICE pointer, uint32,
+ *     n_chains M W words; nothing is written beyond it.  dvg_grbm_moments_packed sums moments over such rows.
+ *   Continuation.  The record rule counts from the call's first sweep: two calls of S1 + S2 sweeps that hand `state` on with
+ *     sweep0 advanced by S1 record, at burn_in = 0 and thin = 1, what one call of S1 + S2 sweeps records.
+ *   DVG_E_INVALID, before any launch: what dvg_gibbs_sample rejects; trace_out == NULL; burn_in < 0; thin < 1; M < 1 (a draw
+ *     that records nothing is dvg_gibbs_sample); dyn != NULL (the draw is one-off, not part of a captured step: the recorded
+ *     sweeps are counted from the host's sweep0).  It takes the kernel forms of the annealed draw (csrc/gibbs_plan.h) and
+ *     their LDS: a record is packed from the state rows where they lie.  No traced form of dvg_gibbs_sample_clamped,
+ *     _annealed, _ais or _tempered. */
+int dvg_gibbs_sample_traced(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                            float prefactor, float h_lo, float h_hi, float j_lo, float j_hi, float beta,
+                            int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                            uint32_t sweep0, int n_sweeps, int init, float *samples_out,
+                            uint32_t *trace_out, int burn_in, int thin,
+                            const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and
@@ -242,6 +265,15 @@ size_t dvg_grbm_suffstats_workspace_bytes(const dvg_graph_t *g);
 int dvg_grbm_suffstats(const dvg_graph_t *g, const float *x, int64_t rows, const float *row_weight,
                        float scale, float *acc_linear, float *acc_quadratic, int accumulate,
                        void *ws, size_t ws_bytes, dvg_stream_t stream);
+/* Moments of bit-packed spin rows, exactly: bits (rows, W = (n + 31) / 32) uint32 in the layout of dvg_gibbs_sample_traced
+ * (bit b of word w of a row = spin 32 w + b is +1; bits of spins >= n are ignored and may hold anything).
+ *   spin_sum[i] (+)= sum_r s_ri ;   pair_sum[e] (+)= sum_r s_ri s_rj   over the graph's edge list (i, j) = (edge_i[e], edge_j[e]).
+ * Both outputs are DEVICE pointers, int64, [n] and [n_edges]; the sums are exact integers (popcounts of bit columns:
+ * sum_r s_i = T - 2 popc(~col_i), sum_r s_i s_j = T - 2 popc(col_i ^ col_j) over T rows), combined with integer atomics:
+ * deterministic.  accumulate == 0 overwrites.  The rows are never unpacked: n / 8 bytes of traffic per row.
+ * DVG_E_INVALID: a null pointer, rows < 1.  DVG_E_UNSUPPORTED: n > 8192 (a tile's bit columns are kept in 64 KiB of LDS). */
+int dvg_grbm_moments_packed(const dvg_graph_t *g, const uint32_t *bits, int64_t rows,
+                            int64_t *spin_sum, int64_t *pair_sum, int accumulate, dvg_stream_t stream);
 
 /* ------------------------------------------------------------------ input pipeline
  * The reference's per-image transform Resize((S,S)) -> ToTensor() -> round

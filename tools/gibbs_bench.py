@@ -14,6 +14,10 @@ schedule and the same ladder; a second line gives the sums of the last draw's lo
 geometric ladder 10 -> 20), timed as the ais rows are -- the raw call on persistent chains and rungs: once with no exchange due
 (swap_every beyond every sweep: the weighed draw's work per update, nothing else) and once with an exchange after every sweep; a
 second line gives the last draw's accepted exchanges per pair of rungs.
+`trace`: also the traced draw (dvg_gibbs_sample_traced: the plain draw plus the chains' states after every `thin`-th sweep, one bit
+per spin), timed as the ais rows are -- the raw call on persistent chains -- at thin=10 and thin=1 (burn_in 0); then
+dvg_grbm_moments_packed over the thin=1 records (chains x sweeps rows of n / 8 bytes) and, next to it, dvg_grbm_suffstats over the
+same rows unpacked to float32 (the unpacking is not timed); a last line says whether the two give the same moments.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -143,3 +147,51 @@ if "tempered" in sys.argv:
         row(name, ts, Q * R * n * sweeps, out)
         print(f"  {'':26s} {Q} ladders x {R}: accepted per pair {accept.view(Q, R).sum(0)[:-1].tolist()} of {Q * (sweeps // every // 2)}"
               f"  sum of energies {float(energy.sum()):.6e}")
+if "trace" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    W = (n + 31) // 32
+    for thin in (10, 1):
+        M = sweeps // thin
+        state = torch.empty((C, n), dtype=torch.int8, device="cuda")
+        out = torch.empty((C, n), dtype=torch.float32, device="cuda")
+        bits = torch.empty((C, M, W), dtype=torch.int32, device="cuda")
+        at = [0]
+
+        def traced():
+            _lib.check(_lib.lib().dvg_gibbs_sample_traced(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0, 20.0,
+                                                          state.data_ptr(), C, 0, seed, at[0], sweeps, int(at[0] == 0), out.data_ptr(),
+                                                          bits.data_ptr(), 0, thin, None, _lib.stream_ptr()),
+                       "dvg_gibbs_sample_traced")
+            at[0] += sweeps
+            return out
+
+        ts, out = timed(traced)
+        row(f"traced, thin={thin} ({M} records)", ts, C * n * sweeps, out)
+    # the moments of the last draw's C x sweeps records: packed, and through the float32 kernel over the same rows unpacked
+    rows = C * sweeps
+    spin_sum = torch.empty((n,), dtype=torch.int64, device="cuda")
+    pair_sum = torch.empty((plan.n_edges,), dtype=torch.int64, device="cuda")
+
+    def packed():
+        _lib.check(_lib.lib().dvg_grbm_moments_packed(s.graph.ptr, bits.data_ptr(), rows, spin_sum.data_ptr(), pair_sum.data_ptr(), 0,
+                                                      _lib.stream_ptr()), "dvg_grbm_moments_packed")
+        return spin_sum
+
+    ts, _ = timed(packed)
+    t = float(np.median(ts))
+    print(f"  {'moments, packed rows':26s} {t:9.1f} us per call  {rows} rows x {4 * W} B  (min {min(ts):.1f} max {max(ts):.1f})")
+    x = smp.unpack_spins(bits.view(rows, W), n).contiguous()
+    acc_l = torch.empty((n,), dtype=torch.float32, device="cuda")
+    acc_q = torch.empty((plan.n_edges,), dtype=torch.float32, device="cuda")
+    ws = torch.empty(_lib.lib().dvg_grbm_suffstats_workspace_bytes(s.graph.ptr), dtype=torch.uint8, device="cuda")
+
+    def unpacked():
+        _lib.check(_lib.lib().dvg_grbm_suffstats(s.graph.ptr, x.data_ptr(), rows, None, 1.0, acc_l.data_ptr(), acc_q.data_ptr(), 0,
+                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "dvg_grbm_suffstats")
+        return acc_l
+
+    ts, _ = timed(unpacked)
+    t = float(np.median(ts))
+    print(f"  {'suffstats, float32 rows':26s} {t:9.1f} us per call  {rows} rows x {4 * n} B  (min {min(ts):.1f} max {max(ts):.1f})")
+    same = bool((acc_l.double() == spin_sum.double()).all()) and bool((acc_q.double() == pair_sum.double()).all())
+    print(f"  {'':26s} the two give the same sums: {same}  (sum of spin sums {int(spin_sum.sum())}, of pair sums {int(pair_sum.sum())})")
