@@ -5,6 +5,7 @@ the memory and the stream.  No CPU fallback: CPU tensors raise.
 from __future__ import annotations
 
 import ctypes
+import numbers
 from typing import Optional
 
 import torch
@@ -256,6 +257,44 @@ def grbm_moments_packed(bits, graph, out=None):
                                             pair_sum.data_ptr() if E else spin_sum.data_ptr(), int(out is not None),
                                             stream_ptr(bd.device)), "dvg_grbm_moments_packed")
     return spin_sum, pair_sum
+
+
+def trace_autocorr(bits, n, max_lag, *, chain_sums=True, out=None):
+    """Exact autocorrelation sums of a bit-packed trace (``dvg_trace_autocorr``, "DVG acf v1"): ``bits`` (C, M, W) int32 on
+    the device in the layout of a traced draw (``sampler.Trace.bits``; bits of spins >= n are ignored), ``n`` the spin count,
+    ``max_lag`` = L in 0 .. M - 1.  Returns ``(lag_sum (L + 1, n) int64, spin_sum (n,) int64, chain_sum (C, n) int32)``: per
+    spin the sums over chains of s(m) s(m + t) over the M - t pairs of lag t, of s(m), and per chain of s(m);
+    ``chain_sums=False`` leaves the last out (None).  ``out``: a pair ``(lag_sum, spin_sum)`` to add onto instead (pooling
+    traces; ``chain_sum`` is always this trace's own).  ``sampler.Autocorrelation.from_sums`` turns them into estimates.  No
+    host sync."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError(f"n must be an integer >= 1, got {n!r}")
+    n = int(n)
+    W = (n + 31) // 32
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() != 3 or bits.shape[2] != W or bits.shape[0] < 1 or \
+            bits.shape[1] < 1:
+        raise _lib.DvgError(f"bits must be (chains >= 1, records >= 1, {W}) int32, got "
+                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
+    C, M = int(bits.shape[0]), int(bits.shape[1])
+    if isinstance(max_lag, bool) or not isinstance(max_lag, numbers.Integral) or not 0 <= max_lag < M:
+        raise ValueError(f"max_lag must be an integer in 0 .. {M - 1} (records - 1), got {max_lag!r}")
+    max_lag = int(max_lag)
+    bd = require_cuda(bits.detach(), "bits")
+    if out is None:
+        lag_sum = torch.empty((max_lag + 1, n), dtype=torch.int64, device=bd.device)
+        spin_sum = torch.empty((n,), dtype=torch.int64, device=bd.device)
+    else:
+        lag_sum, spin_sum = out
+        for name, t, shape in (("lag_sum", lag_sum, (max_lag + 1, n)), ("spin_sum", spin_sum, (n,))):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                    t.device != bd.device:
+                raise _lib.DvgError(f"out: {name} must be a contiguous {shape} int64 tensor on {bd.device}")
+    chain_sum = torch.empty((C, n), dtype=torch.int32, device=bd.device) if chain_sums else None
+    with torch.cuda.device(bd.device):
+        check(_lib.lib().dvg_trace_autocorr(bd.data_ptr(), C, M, n, max_lag, lag_sum.data_ptr(), spin_sum.data_ptr(),
+                                            chain_sum.data_ptr() if chain_sums else None, int(out is not None),
+                                            stream_ptr(bd.device)), "dvg_trace_autocorr")
+    return lag_sum, spin_sum, chain_sum
 
 
 # ----------------------------------------------------------------------------- MSE

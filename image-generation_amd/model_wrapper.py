@@ -943,6 +943,19 @@ class ModelWrapper:
                                         quadratic_range=self.quadratic_range, **kw)
 
     @torch.no_grad()
+    def prior_mixing(self, max_lag=None, **kw):
+        """How the sampler's chains mix on the prior: the :class:`~.sampler.Autocorrelation` of one traced draw
+        (``GraphRestrictedBoltzmannMachine.mixing``; ``num_reads``, ``num_sweeps``, ``burn_in``, ``thin``, ``start`` are
+        passed on, ``num_reads`` defaults to NUM_READS) over lags 0 .. ``max_lag`` records -- ``tau_int_sweeps`` is the
+        number of sweeps between two independent samples.  Rank-local and eval-mode, like ``prior_moments``."""
+        self._dvae.eval()
+        self._grbm.eval()
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        return self._grbm.mixing(self.sampler, prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                 quadratic_range=self.quadratic_range, max_lag=max_lag, **kw)
+
+    @torch.no_grad()
     def reconstruct_images(self, batch: Optional[torch.Tensor] = None, sharpen: bool = False,
                            lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD) -> torch.Tensor:
         """Eval-mode encode -> discretise -> decode of one batch of training images, interleaved with the originals:

@@ -218,6 +218,15 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         return m.mean_spin.reshape(self._linear.shape), m.mean_pair.reshape(self._quadratic.shape)
 
     @torch.no_grad()
+    def mixing(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, max_lag=None, **kw):
+        """How the sampler's chains mix on this model: one traced draw (:meth:`sample_trace`, ``**kw`` passed on) and its
+        :class:`~.sampler.Autocorrelation` over lags 0 .. ``max_lag`` records (:meth:`Trace.autocorrelation`): ``rho``,
+        ``tau_int``, ``ess``, ``r_hat``.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "mixing")
+        trace = self.sample_trace(sampler, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range, **kw)
+        return trace.autocorrelation(max_lag)
+
+    @torch.no_grad()
     def log_likelihood(self, x: torch.Tensor, sampler, *, prefactor: float, linear_range=None, quadratic_range=None,
                        log_z=None, **kw) -> torch.Tensor:
         """``log p(x) = -beta E_s(x) - log Z`` per row of ``x`` ((B, n) +-1 on the device) under the distribution

@@ -261,6 +261,105 @@ class Moments:
         return f"Moments(n={int(self.spin_sum.shape[0])}, edges={int(self.pair_sum.shape[0])}, count={self.count})"
 
 
+class Autocorrelation:
+    """Autocorrelation estimates from the exact sums of a trace of C chains x M records (``dvg_trace_autocorr``, "DVG acf v1"):
+    ``lag_sum`` (L + 1, n) int64 = sum over chains and over the M - t pairs of lag t of s_i(m) s_i(m + t), ``spin_sum`` (n,)
+    int64 = sum over chains and records of s_i, ``chain_sum`` (C, n) int32 = the same per chain, or None; ``thin`` the sweeps
+    between two records.  Every property is float64 torch on the sums' device (CPU tensors too), no host sync:
+
+    ``counts`` (L + 1,) host int64: C (M - t) pairs;  ``mean_spin`` (n,): the pooled mean mu;
+    ``rho`` (L + 1, n): (lag_sum / counts - mu^2) / (1 - mu^2) -- around the POOLED mean, so chains stuck in different modes
+    show as slow; NaN for a spin with mu^2 = 1;
+    ``tau_int`` (n,), in records: 1 + 2 sum_{t = 1}^{T} rho[t], T the number of leading lags 1, 2, .. with rho > 0 (the initial
+    positive sequence), at most L; ``truncated`` (n,) bool: rho > 0 at every lag 1 .. L (L >= 1) -- the window hit max_lag
+    and tau_int is a lower bound; ``tau_int_sweeps`` = tau_int * thin; ``ess`` = C M / tau_int;
+    ``overlap`` (L + 1,): lag_sum.sum(1) / (n counts), the spin-overlap autocorrelation q(t);
+    ``r_hat`` (n,): Gelman-Rubin over the chains' means (needs ``chain_sum``, C >= 2, M >= 2)."""
+
+    def __init__(self, lag_sum, spin_sum, chain_sum, chains, records, thin=1):
+        self.lag_sum, self.spin_sum, self.chain_sum = lag_sum, spin_sum, chain_sum
+        self.chains, self.records, self.thin = int(chains), int(records), int(thin)
+
+    @classmethod
+    def from_sums(cls, lag_sum: torch.Tensor, spin_sum: torch.Tensor, chain_sum: Optional[torch.Tensor], chains: int,
+                  records: int, thin: int = 1) -> "Autocorrelation":
+        for name, v in (("chains", chains), ("records", records), ("thin", thin)):
+            if isinstance(v, bool) or int(v) != v or int(v) < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        if not torch.is_tensor(lag_sum) or lag_sum.dtype != torch.int64 or lag_sum.dim() != 2 or lag_sum.shape[0] < 1:
+            raise ValueError("lag_sum must be a (max_lag + 1, n) int64 tensor")
+        n = int(lag_sum.shape[1])
+        if int(lag_sum.shape[0]) > int(records):
+            raise ValueError(f"lag_sum holds lags 0 .. {int(lag_sum.shape[0]) - 1}, but {int(records)} records have lags below {int(records)}")
+        if not torch.is_tensor(spin_sum) or spin_sum.dtype != torch.int64 or tuple(spin_sum.shape) != (n,):
+            raise ValueError(f"spin_sum must be a ({n},) int64 tensor")
+        if chain_sum is not None and (not torch.is_tensor(chain_sum) or chain_sum.dtype != torch.int32 or
+                                      tuple(chain_sum.shape) != (int(chains), n)):
+            raise ValueError(f"chain_sum must be a ({int(chains)}, {n}) int32 tensor or None")
+        return cls(lag_sum, spin_sum, chain_sum, chains, records, thin)
+
+    @property
+    def max_lag(self) -> int:
+        return int(self.lag_sum.shape[0]) - 1
+
+    @property
+    def counts(self) -> np.ndarray:
+        return self.chains * (self.records - np.arange(self.max_lag + 1, dtype=np.int64))
+
+    def _counts(self):
+        return torch.from_numpy(self.counts).to(device=self.lag_sum.device, dtype=torch.float64)
+
+    @property
+    def mean_spin(self):
+        return self.spin_sum.to(torch.float64) / (self.chains * self.records)
+
+    @property
+    def rho(self):
+        mu2 = self.mean_spin ** 2
+        return (self.lag_sum.to(torch.float64) / self._counts()[:, None] - mu2) / (1.0 - mu2)
+
+    @property
+    def tau_int(self):
+        rho = self.rho
+        window = torch.cumprod((rho[1:] > 0).to(torch.float64), dim=0)  # 1 over the initial positive sequence, 0 behind it
+        tau = 1.0 + 2.0 * torch.where(window > 0, rho[1:], torch.zeros_like(rho[1:])).sum(0)
+        return torch.where(torch.isnan(rho[0]), rho[0], tau)  # (a frozen spin: rho is NaN at every lag, lag 0 included)
+
+    @property
+    def truncated(self):
+        rho = self.rho[1:]
+        if rho.shape[0] == 0:
+            return torch.zeros(rho.shape[1], dtype=torch.bool, device=rho.device)
+        return (rho > 0).all(0)
+
+    @property
+    def tau_int_sweeps(self):
+        return self.tau_int * self.thin
+
+    @property
+    def ess(self):
+        return (self.chains * self.records) / self.tau_int
+
+    @property
+    def overlap(self):
+        return self.lag_sum.sum(1).to(torch.float64) / (self.lag_sum.shape[1] * self._counts())
+
+    @property
+    def r_hat(self):
+        C, M = self.chains, self.records
+        if self.chain_sum is None or C < 2 or M < 2:
+            raise ValueError(f"r_hat needs the chains' sums, at least 2 chains and at least 2 records (chain_sum "
+                             f"{'missing' if self.chain_sum is None else 'given'}, {C} chains, {M} records)")
+        m_c = self.chain_sum.to(torch.float64) / M
+        Wv = (1.0 - m_c ** 2).mean(0) * (M / (M - 1.0))
+        Bm = m_c.var(0, unbiased=True)
+        return torch.sqrt(((M - 1.0) / M * Wv + Bm) / Wv)
+
+    def __repr__(self):
+        return (f"Autocorrelation({self.chains} chains x {self.records} records, n={int(self.lag_sum.shape[1])}, "
+                f"max_lag={self.max_lag}, thin={self.thin})")
+
+
 def trace_sweeps(num_sweeps: int, burn_in: int, thin: int) -> np.ndarray:
     """The recorded sweeps of a traced draw as the numbers k + 1 (k the 0-based sweep of the call), host int64: sweep k is
     recorded iff ``k + 1 > burn_in`` and ``(k + 1 - burn_in) % thin == 0`` -- M = (num_sweeps - burn_in) // thin of them."""
@@ -288,6 +387,25 @@ class Trace:
         rows = self.bits.reshape(-1, self.bits.shape[-1])
         spin_sum, pair_sum = F.grbm_moments_packed(rows, graph)
         return Moments.from_sums(spin_sum, pair_sum, int(rows.shape[0]))
+
+    @property
+    def thin(self) -> int:
+        """The sweeps between two records (1 for a single record)."""
+        return int(self.sweeps[1] - self.sweeps[0]) if len(self.sweeps) > 1 else 1
+
+    def autocorrelation(self, max_lag: Optional[int] = None, chain_sums: bool = True) -> Autocorrelation:
+        """Exact autocorrelation sums of every spin over lags 0 .. ``max_lag`` records (``dvg_trace_autocorr``: the records
+        stay packed), as an :class:`Autocorrelation` carrying the trace's ``thin``.  ``max_lag``: an integer in 0 .. M - 1,
+        default min(M - 1, 512); ``chain_sums=False`` leaves the per-chain sums (``r_hat``) out."""
+        from . import functional as F  # (functional imports this module)
+
+        C, M, _W = self.bits.shape
+        if max_lag is None:
+            max_lag = min(int(M) - 1, 512)
+        if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag < M:
+            raise ValueError(f"max_lag must be an integer in 0 .. {int(M) - 1} (records - 1), got {max_lag!r}")
+        lag_sum, spin_sum, chain_sum = F.trace_autocorr(self.bits, self.n, int(max_lag), chain_sums=bool(chain_sums))
+        return Autocorrelation.from_sums(lag_sum, spin_sum, chain_sum, int(C), int(M), self.thin)
 
     def __repr__(self):
         C, M, _W = self.bits.shape

@@ -274,6 +274,22 @@ int dvg_grbm_suffstats(const dvg_graph_t *g, const float *x, int64_t rows, const
  * DVG_E_INVALID: a null pointer, rows < 1.  DVG_E_UNSUPPORTED: n > 8192 (a tile's bit columns are kept in 64 KiB of LDS). */
 int dvg_grbm_moments_packed(const dvg_graph_t *g, const uint32_t *bits, int64_t rows,
                             int64_t *spin_sum, int64_t *pair_sum, int accumulate, dvg_stream_t stream);
+/* Autocorrelation sums of a bit-packed trace, exactly ("DVG acf v1"): bits (n_chains C, n_records M, W = (n + 31) / 32)
+ * uint32 in the layout of "DVG trace v1" (bit b of word w = spin 32 w + b is +1; bits of spins >= n are ignored and may hold
+ * anything).  With s_i(c, m) = +-1 the spin of chain c at record m, and L = max_lag:
+ *   lag_sum[t n + i]   (+)= sum_c sum_{m = 0}^{M - 1 - t} s_i(c, m) s_i(c, m + t)   for t = 0 .. L, i < n;  lag_sum[0][i] = C M
+ *   spin_sum[i]        (+)= sum_c sum_m s_i(c, m)
+ *   chain_sum[c n + i]   = sum_m s_i(c, m)      int32; optional (NULL: not written); always overwritten, never accumulated
+ * All three are DEVICE pointers; lag_sum and spin_sum are int64.  accumulate == 0 overwrites them, 1 adds onto them (pooling
+ * several traces).  Every value is an exact integer: a chain's records are transposed into one M-bit time column per spin
+ * and  sum_m s(m) s(m + t) = (M - t) - 2 popc((x ^ (x >> t)) & low(M - t));  workgroups combine through integer atomics only,
+ * so the result is deterministic.  Nothing is written beyond (L + 1) n, n and C n elements.  The entry needs n only, no graph.
+ * DVG_E_INVALID, before any HIP call: bits, lag_sum or spin_sum null; n_chains, n_records or n < 1; max_lag < 0 or
+ * max_lag >= n_records.  DVG_E_UNSUPPORTED: n_records > 16384 (the time columns of 32 spins are kept in 64 KiB of LDS);
+ * C M W beyond what one launch indexes. */
+int dvg_trace_autocorr(const uint32_t *bits, int n_chains, int n_records, int n, int max_lag,
+                       int64_t *lag_sum, int64_t *spin_sum, int32_t *chain_sum,
+                       int accumulate, dvg_stream_t stream);
 
 /* ------------------------------------------------------------------ input pipeline
  * The reference's per-image transform Resize((S,S)) -> ToTensor() -> round

@@ -18,6 +18,10 @@ second line gives the last draw's accepted exchanges per pair of rungs.
 per spin), timed as the ais rows are -- the raw call on persistent chains -- at thin=10 and thin=1 (burn_in 0); then
 dvg_grbm_moments_packed over the thin=1 records (chains x sweeps rows of n / 8 bytes) and, next to it, dvg_grbm_suffstats over the
 same rows unpacked to float32 (the unpacking is not timed); a last line says whether the two give the same moments.
+`autocorr`: also dvg_trace_autocorr (the exact sums over chains and records of s_i(m) s_i(m + t), t = 0 .. 64, of bit-packed records)
+over the thin=1 trace of that draw (chains x sweeps records), timed as the moments row is; next to it the same sums by torch over the
+same records unpacked to float32, one product and one reduction per lag (the unpacking is not timed); a last line says whether the
+two agree.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -195,3 +199,35 @@ if "trace" in sys.argv:
     print(f"  {'suffstats, float32 rows':26s} {t:9.1f} us per call  {rows} rows x {4 * n} B  (min {min(ts):.1f} max {max(ts):.1f})")
     same = bool((acc_l.double() == spin_sum.double()).all()) and bool((acc_q.double() == pair_sum.double()).all())
     print(f"  {'':26s} the two give the same sums: {same}  (sum of spin sums {int(spin_sum.sum())}, of pair sums {int(pair_sum.sum())})")
+if "autocorr" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    trace = s.sample_trace(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)  # burn_in 0, thin 1: chains x sweeps records
+    L, M = min(64, sweeps - 1), sweeps
+    lag_sum = torch.empty((L + 1, n), dtype=torch.int64, device="cuda")
+    spin_sum = torch.empty((n,), dtype=torch.int64, device="cuda")
+    chain_sum = torch.empty((C, n), dtype=torch.int32, device="cuda")
+
+    def packed():
+        _lib.check(_lib.lib().dvg_trace_autocorr(trace.bits.data_ptr(), C, M, n, L, lag_sum.data_ptr(), spin_sum.data_ptr(),
+                                                 chain_sum.data_ptr(), 0, _lib.stream_ptr()), "dvg_trace_autocorr")
+        return lag_sum
+
+    ts, _ = timed(packed)
+    t_packed = float(np.median(ts))
+    print(f"  {'autocorr, packed records':26s} {t_packed:9.1f} us per call  {C} x {M} records x {4 * ((n + 31) // 32)} B, lags 0..{L}"
+          f"  (min {min(ts):.1f} max {max(ts):.1f})")
+    x = trace.unpack().contiguous()  # (C, M, n) float32
+    by_torch = torch.empty((L + 1, n), dtype=torch.float32, device="cuda")
+
+    def unpacked():
+        for t in range(L + 1):
+            by_torch[t] = (x[:, :M - t] * x[:, t:]).sum((0, 1))
+        return by_torch
+
+    ts, _ = timed(unpacked)
+    t_torch = float(np.median(ts))
+    print(f"  {'the same by torch, float32':26s} {t_torch:9.1f} us per call  {C} x {M} records x {4 * n} B, {L + 1} lags one at a time"
+          f"  (min {min(ts):.1f} max {max(ts):.1f})   {t_torch / t_packed:.1f} x the packed call")
+    same = bool((by_torch.double() == lag_sum.double()).all()) and bool((x.sum((0, 1)).double() == spin_sum.double()).all()) and \
+        bool((x.sum(1).double() == chain_sum.double()).all())
+    print(f"  {'':26s} the two give the same sums: {same}  (sum of lag sums {int(lag_sum.sum())}, of spin sums {int(spin_sum.sum())})")
