@@ -125,6 +125,10 @@ SIGNATURES = {
     "dvg_gibbs_launch_info": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "dvg_grbm_moments_packed": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "dvg_trace_autocorr": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dvg_packed_overlap": (
+        c_int,
+        [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
+    ),
     "dvg_grbm_energy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dvg_grbm_suffstats_workspace_bytes": (c_size_t, [c_void_p]),
     "dvg_grbm_suffstats": (

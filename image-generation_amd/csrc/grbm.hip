@@ -222,6 +222,159 @@ __global__ __launch_bounds__(AC_WAVES * 64) void trace_autocorr_kernel(const uin
   }
 }
 
+// ---------------------------------------------------------------- overlaps of bit-packed rows (dvg_packed_overlap)
+// All pairs (row of A, row of B) of a group: d = popc(x ^ y) over the spins < n, GEMM-shaped on bits.  A TILE is 64 rows.  A
+// UNIT is (group, A tile ta, a span of B tiles); a workgroup of 256 threads walks the units `blockIdx.x + i gridDim.x`.  For
+// each B tile of the span it stages, OV_KC = 16 words of the rows at a time, both tiles in LDS word-major -- T[k][row], 64
+// rows of one word side by side, the last word masked to n, rows beyond the last read as 0 -- and thread (ty, tx) = (tid >> 4,
+// tid & 15) keeps the 4 x 4 block of pairs (rows 4 ty .. 4 ty + 3 of A) x (rows 4 tx .. 4 tx + 3 of B): per word one 128-bit
+// read of each tile serves 16 XOR + popcount-accumulate steps.  With W <= 16 (n <= 512) the A tile is staged once per unit.
+// Self mode (B = A): units take the tiles tb >= ta only and count r < r'; with `nearest` they take every tb (a row's nearest
+// partner may lie on either side of it), count r < r' as before and take the minimum over r != r'.
+// Histogram: LDS counters h[d][copy], copy = lane & (copies - 1), `copies` = the largest power of two <= 8 for which
+// (n + 1) copies words fit OV_HIST_LDS (8 up to n = 1055, 1 at 8192).  The distances of unrelated rows crowd into about sqrt(n)
+// bins; copies spread the lanes that meet on one distance over several addresses.  Measured at n = 512 on rows of fair coins
+// the update costs nothing one can see at 1, 8 or 32 copies (the popcounts bound the kernel), so the copies are kept few: a
+// small LDS footprint lets four workgroups share a CU, which is what the time does depend on.  The counters live across the
+// workgroup's units and are flushed once, nonzero bins only, with 64-bit integer atomics (and every OV_FLUSH_TILES tiles =
+// 2^28 pairs, so that a 32-bit counter cannot wrap).  Integer addition commutes: the order of the workgroups does not matter.
+// nearest: a thread keeps min over its B rows of (d << 32 | row of B) per A row across the unit's span; 16 lanes combine by
+// shuffles; one store per A row and unit where the unit spans all of B, else one unsigned 64-bit atomic minimum onto the
+// output, which the host filled with 0xFF bytes (-1 = no partner = the unsigned maximum).  The minimum of the keys is the
+// smallest distance and, among equals, the smallest row.
+// LDS banks (bank = dword mod 64 for ds_read_b128 in its four 16-lane groups, mod 32 for ds_write_b32 and ds_add_u32 in
+// 32-lane halves): row r of word k sits at T[k][r ^ 4 k].  Reads: 16 lanes of a group hold 16 different tx or one ty (two
+// over lanes l and l + 16): B gives the 16 slots of one 256-byte row, each bank once; A is one or two addresses, broadcast.
+// Staging: lane (ty, tx) writes word k = tx of row ty + 16 p -- a 32-lane half holds rows r, r + 1 and k = 0 .. 15, bank
+// (r ^ 4 k) mod 32: two addresses per bank at the most, which costs a ds_write_b32 nothing.  The XOR is there for that: plain
+// T[k][r] would put the 16 words of a row on one bank.  Histogram adds: bank = (8 d + lane mod 8) mod 32 -- lanes of a half
+// that share a distance and a copy add to one address and serialise, lanes whose distances differ by a multiple of 4 share a
+// bank: data-dependent, up to 32-way in the worst case (all pairs at one distance with one copy), and not seen in the time.
+constexpr int OV_THREADS = 256, OV_TILE = 64, OV_KC = 16, OV_MAX_N = 8192, OV_HIST_LDS = 33 * 1024, OV_MAX_COPIES = 8;
+constexpr int OV_TILE_LDS = 2 * OV_KC * OV_TILE * 4, OV_FLUSH_TILES = 1 << 16, OV_UNITS = 2048, OV_GRID = 1024;
+
+__device__ __forceinline__ void ov_flush(unsigned int* h, int n, int copies, int tid, unsigned long long* __restrict__ hist) {
+  for (int d = tid; d <= n; d += OV_THREADS) {
+    unsigned long long s = 0ull;
+    for (int c = 0; c < copies; ++c) {
+      const int at = d * copies + ((c + tid) & (copies - 1));  // (rotated by the lane: each bank once)
+      s += h[at];
+      h[at] = 0u;
+    }
+    if (s) atomicAdd(hist + d, s);
+  }
+}
+
+template <bool NEAREST>
+__global__ __launch_bounds__(OV_THREADS) void packed_overlap_kernel(
+    const uint32_t* __restrict__ a, int64_t rows_a, int64_t a_rs, int64_t a_gs, const uint32_t* __restrict__ b, int64_t rows_b,
+    int64_t b_rs, int64_t b_gs, int self, int n, int W, int copies, int64_t nta, int64_t ntb, int64_t span, int64_t ns,
+    int64_t units, unsigned long long* __restrict__ hist, unsigned long long* __restrict__ nearest) {
+  extern __shared__ __align__(16) unsigned char ov_smem[];
+  uint32_t* As = reinterpret_cast<uint32_t*>(ov_smem);  // [OV_KC][64], row r of word k at [k][r ^ 4 k]
+  uint32_t* Bs = As + OV_KC * OV_TILE;
+  unsigned int* h = Bs + OV_KC * OV_TILE;  // [n + 1][copies]
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, cp = tid & (copies - 1);
+  for (int i = tid; i < (n + 1) * copies; i += OV_THREADS) h[i] = 0u;
+  const uint32_t last_mask = (n & 31) ? (1u << (n & 31)) - 1u : ~0u;
+  const bool resident = W <= OV_KC;  // the A tile is whole in LDS: staged once per unit
+  int since = 0;                     // tiles since the last flush
+  for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
+    const int64_t s = u % ns, rest = u / ns, ta = rest % nta, g = rest / nta;
+    int64_t tb0 = s * span;
+    const int64_t tb1 = tb0 + span < ntb ? tb0 + span : ntb;
+    if (self && !NEAREST && tb0 < ta) tb0 = ta;
+    const uint32_t* ag = a + g * a_gs;
+    const uint32_t* bg = b + g * b_gs;
+    const int64_t a0 = ta * OV_TILE;
+    unsigned long long best[4] = {~0ull, ~0ull, ~0ull, ~0ull};
+    for (int64_t tb = tb0; tb < tb1; ++tb) {
+      const int64_t b0 = tb * OV_TILE;
+      unsigned int acc[4][4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0u;
+      for (int k0 = 0; k0 < W; k0 += OV_KC) {
+        const int kc = W - k0 < OV_KC ? W - k0 : OV_KC, kc4 = (kc + 3) & ~3;
+        __syncthreads();  // (the words of the last chunk have been read)
+        if (tx < kc4) {
+          const int k = k0 + tx;
+          const uint32_t m = k == W - 1 ? last_mask : ~0u;
+          if (!resident || tb == tb0) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+              const int row = ty + 16 * p;
+              const int64_t r = a0 + row;
+              As[tx * OV_TILE + (row ^ (4 * tx))] = (tx < kc && r < rows_a) ? ag[r * a_rs + k] & m : 0u;
+            }
+          }
+#pragma unroll
+          for (int p = 0; p < 4; ++p) {
+            const int row = ty + 16 * p;
+            const int64_t r = b0 + row;
+            Bs[tx * OV_TILE + (row ^ (4 * tx))] = (tx < kc && r < rows_b) ? bg[r * b_rs + k] & m : 0u;
+          }
+        }
+        __syncthreads();
+        for (int kk = 0; kk < kc4; kk += 4) {
+#pragma unroll
+          for (int k = kk; k < kk + 4; ++k) {
+            const uint4 av = *reinterpret_cast<const uint4*>(As + k * OV_TILE + 4 * (ty ^ (k & 15)));
+            const uint4 bv = *reinterpret_cast<const uint4*>(Bs + k * OV_TILE + 4 * (tx ^ (k & 15)));
+            const uint32_t ar[4] = {av.x, av.y, av.z, av.w}, br[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+              for (int j = 0; j < 4; ++j) acc[i][j] += __popc(ar[i] ^ br[j]);
+          }
+        }
+      }
+      // the tile's 16 pairs of this thread, by their rows inside the tiles: li < na, lj < nb exist; on the diagonal tile of
+      // self mode li < lj is counted and li != lj has a partner; tiles below the diagonal (self mode with nearest) count nothing
+      const int na = rows_a - a0 < OV_TILE ? (int)(rows_a - a0) : OV_TILE, nb = rows_b - b0 < OV_TILE ? (int)(rows_b - b0) : OV_TILE;
+      const bool diag = self && ta == tb, below = self && tb < ta;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int li = 4 * ty + i;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int lj = 4 * tx + j;
+          const bool valid = li < na && lj < nb;
+          if (valid && !below && (!diag || li < lj)) atomicAdd(h + acc[i][j] * copies + cp, 1u);
+          if (NEAREST && valid && (!diag || li != lj)) {
+            const unsigned long long key = ((unsigned long long)acc[i][j] << 32) | (unsigned long long)(b0 + lj);
+            best[i] = key < best[i] ? key : best[i];
+          }
+        }
+      }
+      if (++since == OV_FLUSH_TILES) {  // (uniform over the workgroup)
+        __syncthreads();
+        ov_flush(h, n, copies, tid, hist);
+        since = 0;
+      }
+    }
+    if (NEAREST) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        unsigned long long v = best[i];
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {
+          const unsigned long long o = __shfl_xor(v, off, 64);
+          v = o < v ? o : v;
+        }
+        const int64_t r = a0 + 4 * ty + i;
+        if (tx == 0 && r < rows_a) {
+          if (ns == 1) nearest[g * rows_a + r] = v;  // (this unit saw every row of B)
+          else if (v != ~0ull) atomicMin(nearest + g * rows_a + r, v);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  ov_flush(h, n, copies, tid, hist);
+}
+
 }  // namespace dvg
 
 using namespace dvg;
@@ -335,5 +488,71 @@ extern "C" int dvg_trace_autocorr(const uint32_t* bits, int n_chains, int n_reco
   DVG_LAUNCH(K_GRBM_SUFFSTATS, trace_autocorr_kernel, dim3((unsigned)W, (unsigned)slabs, (unsigned)chunks), dim3(AC_WAVES * 64),
              lds, s, bits, n_chains, n_records, n, (int)W, max_lag, (int)per, (int)batch, reinterpret_cast<unsigned long long*>(lag_sum),
              reinterpret_cast<unsigned long long*>(spin_sum), chain_sum);
+  return DVG_OK;
+}
+
+// Exact Hamming-distance histogram and nearest rows of bit-packed rows ("DVG overlap v1", include/dvg.h): never unpacked.
+extern "C" int dvg_packed_overlap(const uint32_t* a, int64_t rows_a, int64_t a_row_stride, int64_t a_group_stride,
+                                  const uint32_t* b, int64_t rows_b, int64_t b_row_stride, int64_t b_group_stride, int groups,
+                                  int n, int64_t* hist, int64_t* nearest, int accumulate, dvg_stream_t stream) {
+  DVG_REQUIRE(a, "packed_overlap: a is null");
+  DVG_REQUIRE(hist, "packed_overlap: hist is null");
+  DVG_REQUIRE(rows_a >= 1, "packed_overlap: rows_a=%lld must be at least 1", (long long)rows_a);
+  DVG_REQUIRE(groups >= 1, "packed_overlap: groups=%d must be at least 1", groups);
+  DVG_REQUIRE(n >= 1, "packed_overlap: n=%d must be at least 1", n);
+  const int64_t W = ((int64_t)n + 31) / 32;
+  DVG_REQUIRE(a_row_stride >= W, "packed_overlap: a_row_stride=%lld is less than the %lld words of a row", (long long)a_row_stride,
+              (long long)W);
+  DVG_REQUIRE(a_group_stride >= 0, "packed_overlap: a_group_stride=%lld is negative", (long long)a_group_stride);
+  const int self = b == nullptr;
+  if (self) {
+    b = a, rows_b = rows_a, b_row_stride = a_row_stride, b_group_stride = a_group_stride;
+  } else {
+    DVG_REQUIRE(rows_b >= 1, "packed_overlap: rows_b=%lld must be at least 1", (long long)rows_b);
+    DVG_REQUIRE(b_row_stride >= W, "packed_overlap: b_row_stride=%lld is less than the %lld words of a row",
+                (long long)b_row_stride, (long long)W);
+    DVG_REQUIRE(b_group_stride >= 0, "packed_overlap: b_group_stride=%lld is negative", (long long)b_group_stride);
+  }
+  if (n > OV_MAX_N) {
+    set_error("packed_overlap: n=%d > %d (a workgroup keeps the n + 1 bins of the histogram as 32-bit counters in %d KiB of LDS)",
+              n, OV_MAX_N, OV_HIST_LDS / 1024);
+    return DVG_E_UNSUPPORTED;
+  }
+  if (rows_a >= (1ll << 31)) {
+    set_error("packed_overlap: rows_a=%lld must be below 2^31 (a row index is the low half of a nearest element)", (long long)rows_a);
+    return DVG_E_UNSUPPORTED;
+  }
+  if (rows_b >= (1ll << 31)) {
+    set_error("packed_overlap: rows_b=%lld must be below 2^31 (a row index is the low half of a nearest element)", (long long)rows_b);
+    return DVG_E_UNSUPPORTED;
+  }
+  if ((__int128)rows_a * rows_b * groups >= ((__int128)1 << 62)) {
+    set_error("packed_overlap: groups=%d x rows_a=%lld x rows_b=%lld pairs are 2^62 or more", groups, (long long)rows_a,
+              (long long)rows_b);
+    return DVG_E_UNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  int copies = OV_MAX_COPIES;
+  while (copies > 1 && (size_t)(n + 1) * copies * 4 > (size_t)OV_HIST_LDS) copies >>= 1;
+  const size_t lds = (size_t)OV_TILE_LDS + (size_t)(n + 1) * copies * 4;
+  // units: (group, A tile, span of B tiles); B is split only as far as it takes to fill the chip
+  const int64_t nta = ceil_div(rows_a, OV_TILE), ntb = ceil_div(rows_b, OV_TILE), base = (int64_t)groups * nta;
+  int64_t ns = base >= OV_UNITS ? 1 : ceil_div(OV_UNITS, base);
+  ns = ns > ntb ? ntb : ns;
+  const int64_t span = ceil_div(ntb, ns);
+  ns = ceil_div(ntb, span);
+  const int64_t units = base * ns;
+  if (!accumulate) DVG_CHECK_HIP(hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)(n + 1), s));
+  if (nearest && ns > 1) DVG_CHECK_HIP(hipMemsetAsync(nearest, 0xFF, sizeof(int64_t) * (size_t)groups * (size_t)rows_a, s));
+  const dim3 grid((unsigned)(units < OV_GRID ? units : OV_GRID));
+  if (nearest) {
+    DVG_LAUNCH(K_GRBM_SUFFSTATS, packed_overlap_kernel<true>, grid, dim3(OV_THREADS), lds, s, a, rows_a, a_row_stride,
+               a_group_stride, b, rows_b, b_row_stride, b_group_stride, self, n, (int)W, copies, nta, ntb, span, ns, units,
+               reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(nearest));
+  } else {
+    DVG_LAUNCH(K_GRBM_SUFFSTATS, packed_overlap_kernel<false>, grid, dim3(OV_THREADS), lds, s, a, rows_a, a_row_stride,
+               a_group_stride, b, rows_b, b_row_stride, b_group_stride, self, n, (int)W, copies, nta, ntb, span, ns, units,
+               reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(nearest));
+  }
   return DVG_OK;
 }

@@ -297,6 +297,72 @@ def trace_autocorr(bits, n, max_lag, *, chain_sums=True, out=None):
     return lag_sum, spin_sum, chain_sum
 
 
+def _packed_rows(t, name, W):
+    """``(rows, row_stride, groups, group_stride)`` of a 2-D (rows, W) or 3-D (C, M, W) int32 tensor of packed rows, in words."""
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() not in (2, 3) or t.shape[-1] != W or min(t.shape) < 1:
+        raise _lib.DvgError(f"{name} must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
+                            f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
+    if W > 1 and t.stride(-1) != 1:
+        raise _lib.DvgError(f"{name}: the last dimension must have stride 1, got strides {tuple(t.stride())}")
+    rows = int(t.shape[0])
+    rs = int(t.stride(0)) if rows > 1 else W
+    groups = int(t.shape[1]) if t.dim() == 3 else 1
+    gs = int(t.stride(1)) if groups > 1 else 0
+    if rs < W or gs < 0:
+        raise _lib.DvgError(f"{name}: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(t.stride())})")
+    return rows, rs, groups, gs
+
+
+def packed_overlap(a, b=None, *, n, nearest=False, out=None):
+    """Exact Hamming-distance histogram and nearest rows of bit-packed +-1 rows (``dvg_packed_overlap``, "DVG overlap v1").
+    ``a``: (rows, W) or (C, M, W) int32 on the device (``sampler.pack_spins``, ``sampler.Trace.bits``; bits of spins >= n are
+    ignored); the 3-D form is M groups of C rows -- a trace's chains at equal times.  ``b``: None -- self mode, the unordered
+    pairs r < r' of ``a`` within each group -- or 2-D (with a 3-D ``a``: shared by every group) or 3-D with the same M: all
+    pairs (row of a, row of b).  The last dimension must have stride 1; row and group strides are taken from the tensors, so
+    slices need no copy.  Returns ``(hist (n + 1,) int64, nearest)``: ``hist[d]`` pairs at distance d over all groups (the
+    overlap is q = 1 - 2 d / n: ``sampler.Overlap.from_hist``); ``nearest`` None, or with ``nearest=True`` a pair ``(dist,
+    row)`` of int32 tensors shaped (rows,) or (M, C): every row's smallest distance to a row of ``b`` (self mode: to another
+    row of ``a``) and the smallest row index that attains it, -1 where there is no partner.  ``out``: a histogram to add
+    onto.  No host sync."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError(f"n must be an integer >= 1, got {n!r}")
+    n = int(n)
+    W = (n + 31) // 32
+    rows_a, a_rs, groups, a_gs = _packed_rows(a, "a", W)
+    rows_b, b_rs, b_gs = 0, 0, 0
+    if b is not None:
+        rows_b, b_rs, groups_b, b_gs = _packed_rows(b, "b", W)
+        if b.dim() == 3 and (a.dim() != 3 or groups_b != groups):
+            raise _lib.DvgError(f"b: a 3-D b needs a 3-D a with the same number of records, got a {tuple(a.shape)} and b {tuple(b.shape)}")
+        if b.dim() == 2:
+            b_gs = 0
+        if b.device != a.device:
+            raise _lib.DvgError(f"b must be on the device of a ({a.device}), got {b.device}")
+    if not a.is_cuda:
+        raise _lib.DvgError(f"a must live on the GPU (got {a.device}); the HIP path has no CPU fallback")
+    ad, bd = a.detach(), b.detach() if b is not None else None
+    if out is None:
+        hist = torch.empty((n + 1,), dtype=torch.int64, device=ad.device)
+    else:
+        hist = out
+        if not torch.is_tensor(hist) or hist.dtype != torch.int64 or tuple(hist.shape) != (n + 1,) or not hist.is_contiguous() or \
+                hist.device != ad.device:
+            raise _lib.DvgError(f"out: hist must be a contiguous ({n + 1},) int64 tensor on {ad.device}")
+    near = torch.empty((groups * rows_a,), dtype=torch.int64, device=ad.device) if nearest else None
+    with torch.cuda.device(ad.device):
+        check(lib().dvg_packed_overlap(ad.data_ptr(), rows_a, a_rs, a_gs, bd.data_ptr() if bd is not None else None, rows_b, b_rs,
+                                       b_gs, groups, n, hist.data_ptr(), near.data_ptr() if nearest else None,
+                                       int(out is not None), stream_ptr(ad.device)), "dvg_packed_overlap")
+    if not nearest:
+        return hist, None
+    none = near < 0
+    dist = torch.where(none, near, near >> 32).to(torch.int32)
+    row = torch.where(none, near, near & 0x7FFFFFFF).to(torch.int32)
+    if a.dim() == 3:
+        dist, row = dist.view(groups, rows_a), row.view(groups, rows_a)
+    return hist, (dist, row)
+
+
 # ----------------------------------------------------------------------------- MSE
 
 

@@ -956,6 +956,48 @@ class ModelWrapper:
                                  quadratic_range=self.quadratic_range, max_lag=max_lag, **kw)
 
     @torch.no_grad()
+    def prior_overlap(self, **kw):
+        """Which modes the sampler's chains populate on the prior: the :class:`~.sampler.Overlap` between distinct chains at
+        equal times of one traced draw (``GraphRestrictedBoltzmannMachine.replica_overlap``; ``num_reads``, ``num_sweeps``,
+        ``burn_in``, ``thin``, ``start`` are passed on, ``num_reads`` defaults to NUM_READS) -- ``q2``, ``binder`` and
+        ``mass`` tell one mode from two mirror modes from many.  Rank-local and eval-mode, like ``prior_mixing``."""
+        self._dvae.eval()
+        self._grbm.eval()
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        return self._grbm.replica_overlap(self.sampler, prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                          quadratic_range=self.quadratic_range, **kw)
+
+    @torch.no_grad()
+    def latent_novelty(self, images: torch.Tensor, samples: Optional[torch.Tensor] = None) -> dict:
+        """How far generated latents lie from the data's: encode ``images`` -> hard spins (heaviside, H(0) = 0, as
+        ``generate_variations`` does) -> packed rows (``sampler.pack_spins``); ``samples`` (rows, n) +-1 spins, or None for
+        one draw of the sampler as ``generate_images`` takes it.  Returns a dict: ``nearest_dist`` / ``nearest_row`` (rows,)
+        int32, each generated latent's Hamming distance to its nearest data latent and that latent's index in ``images``;
+        ``overlap``, the :class:`~.sampler.Overlap` of all (generated, data) pairs; ``data_nearest_dist`` (B,) int32, every
+        data latent's distance to its nearest OTHER data latent (-1 for a single image) -- the baseline to read the first
+        against: generated codes far closer than that are copies, far further are codes the encoder never emits.
+        Rank-local and eval-mode, like ``generate_images``."""
+        from .sampler import Overlap, pack_spins
+
+        self._dvae.eval()
+        self._grbm.eval()
+        images = images.to(self._device)
+        spins = F.heaviside_latent_to_discrete(self._dvae.encoder(images)).squeeze(1)  # (B, n) +-1
+        n = int(spins.shape[1])
+        if samples is None:
+            samples = self._grbm.sample(self.sampler, prefactor=self.PREFACTOR, device=self._device,
+                                        linear_range=self.linear_range, quadratic_range=self.quadratic_range,
+                                        sample_params=self.sampler_kwargs)
+        samples = samples.to(self._device)
+        if samples.dim() != 2 or int(samples.shape[1]) != n:
+            raise ValueError(f"samples must be (rows, {n}) spins, got {tuple(samples.shape)}")
+        data, drawn = pack_spins(spins), pack_spins(samples)
+        hist, (dist, row) = F.packed_overlap(drawn, data, n=n, nearest=True)
+        _hist, (data_dist, _row) = F.packed_overlap(data, n=n, nearest=True)
+        return dict(nearest_dist=dist, nearest_row=row, overlap=Overlap.from_hist(hist, n), data_nearest_dist=data_dist)
+
+    @torch.no_grad()
     def reconstruct_images(self, batch: Optional[torch.Tensor] = None, sharpen: bool = False,
                            lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD) -> torch.Tensor:
         """Eval-mode encode -> discretise -> decode of one batch of training images, interleaved with the originals:

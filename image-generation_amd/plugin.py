@@ -227,6 +227,15 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         return trace.autocorrelation(max_lag)
 
     @torch.no_grad()
+    def replica_overlap(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """Which modes the sampler's chains populate on this model: one traced draw (:meth:`sample_trace`, ``**kw`` passed
+        on) and the :class:`~.sampler.Overlap` between its distinct chains at equal times (:meth:`Trace.overlap`): ``q2``,
+        ``binder``, ``mass``.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "replica_overlap")
+        trace = self.sample_trace(sampler, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range, **kw)
+        return trace.overlap()
+
+    @torch.no_grad()
     def log_likelihood(self, x: torch.Tensor, sampler, *, prefactor: float, linear_range=None, quadratic_range=None,
                        log_z=None, **kw) -> torch.Tensor:
         """``log p(x) = -beta E_s(x) - log Z`` per row of ``x`` ((B, n) +-1 on the device) under the distribution

@@ -360,6 +360,77 @@ class Autocorrelation:
                 f"max_lag={self.max_lag}, thin={self.thin})")
 
 
+class Overlap:
+    """The distribution of the spin overlap q = (1 / n) sum_i s_i^a s_i^b = 1 - 2 d / n over pairs of +-1 rows, from the exact
+    histogram of their Hamming distances d (``dvg_packed_overlap``, "DVG overlap v1"): ``hist`` (n + 1,) int64, ``hist[d]``
+    pairs at distance d.  Every property is float64 torch on the histogram's device (CPU tensors too), no host sync:
+
+    ``pairs`` (): the number of pairs;  ``q`` (n + 1,): the grid 1 - 2 d / n;  ``density`` (n + 1,): hist / pairs, P(q);
+    ``mean_q``, ``mean_abs_q``, ``q2``, ``q4``: the means of q, |q|, q^2, q^4;  ``binder`` = (3 - q4 / q2^2) / 2: 1 for a
+    distribution on +-q0 (one mode and its mirror), 0 for a Gaussian round 0;  ``hamming_mean``: the mean of d;
+    ``mass(lo, hi)``: the share of pairs with lo <= |q| <= hi.  No pairs at all give NaN, as IEEE division does."""
+
+    def __init__(self, hist, n):
+        self.hist, self.n = hist, int(n)
+
+    @classmethod
+    def from_hist(cls, hist: torch.Tensor, n: int) -> "Overlap":
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n must be an integer >= 1, got {n!r}")
+        if not torch.is_tensor(hist) or hist.dtype != torch.int64 or tuple(hist.shape) != (int(n) + 1,):
+            raise ValueError(f"hist must be a ({int(n) + 1},) int64 tensor")
+        return cls(hist, n)
+
+    def _h(self):
+        return self.hist.to(torch.float64)
+
+    def _mean(self, f):
+        return (self._h() * f).sum() / self.pairs
+
+    @property
+    def pairs(self):
+        return self._h().sum()
+
+    @property
+    def q(self):
+        return 1.0 - 2.0 * torch.arange(self.n + 1, dtype=torch.float64, device=self.hist.device) / self.n
+
+    @property
+    def density(self):
+        return self._h() / self.pairs
+
+    @property
+    def mean_q(self):
+        return self._mean(self.q)
+
+    @property
+    def mean_abs_q(self):
+        return self._mean(self.q.abs())
+
+    @property
+    def q2(self):
+        return self._mean(self.q ** 2)
+
+    @property
+    def q4(self):
+        return self._mean(self.q ** 4)
+
+    @property
+    def binder(self):
+        return (3.0 - self.q4 / self.q2 ** 2) / 2.0
+
+    @property
+    def hamming_mean(self):
+        return self._mean(torch.arange(self.n + 1, dtype=torch.float64, device=self.hist.device))
+
+    def mass(self, lo: float, hi: float):
+        aq = self.q.abs()
+        return self._mean(((aq >= lo) & (aq <= hi)).to(torch.float64))
+
+    def __repr__(self):
+        return f"Overlap(n={self.n})"
+
+
 def trace_sweeps(num_sweeps: int, burn_in: int, thin: int) -> np.ndarray:
     """The recorded sweeps of a traced draw as the numbers k + 1 (k the 0-based sweep of the call), host int64: sweep k is
     recorded iff ``k + 1 > burn_in`` and ``(k + 1 - burn_in) % thin == 0`` -- M = (num_sweeps - burn_in) // thin of them."""
@@ -406,6 +477,18 @@ class Trace:
             raise ValueError(f"max_lag must be an integer in 0 .. {int(M) - 1} (records - 1), got {max_lag!r}")
         lag_sum, spin_sum, chain_sum = F.trace_autocorr(self.bits, self.n, int(max_lag), chain_sums=bool(chain_sums))
         return Autocorrelation.from_sums(lag_sum, spin_sum, chain_sum, int(C), int(M), self.thin)
+
+    def overlap(self, other=None, nearest: bool = False):
+        """The equal-time replica overlap (``dvg_packed_overlap``: the records stay packed) as an :class:`Overlap`: over every
+        record the pairs of distinct chains of this trace, or with ``other`` -- a :class:`Trace` with as many records, its
+        ``bits``, or a flat (rows, W) set shared by every record -- the pairs (chain, row of ``other``).  ``nearest=True``
+        returns ``(Overlap, (dist, row))`` with the (M, C) int32 nearest partners of ``functional.packed_overlap``."""
+        from . import functional as F  # (functional imports this module)
+
+        b = other.bits if isinstance(other, Trace) else other
+        hist, near = F.packed_overlap(self.bits, b, n=self.n, nearest=bool(nearest))
+        o = Overlap.from_hist(hist, self.n)
+        return (o, near) if nearest else o
 
     def __repr__(self):
         C, M, _W = self.bits.shape

@@ -290,6 +290,31 @@ int dvg_grbm_moments_packed(const dvg_graph_t *g, const uint32_t *bits, int64_t 
 int dvg_trace_autocorr(const uint32_t *bits, int n_chains, int n_records, int n, int max_lag,
                        int64_t *lag_sum, int64_t *spin_sum, int32_t *chain_sum,
                        int accumulate, dvg_stream_t stream);
+/* Hamming distances between bit-packed spin rows, exactly ("DVG overlap v1"): their histogram -- the overlap distribution
+ * P(q), q = 1 - 2 d / n -- and every row's nearest partner.  Rows are packed as in "DVG trace v1": W = (n + 31) / 32 words,
+ * bit b of word w = spin 32 w + b is +1; bits of spins >= n are ignored and may hold anything.  Strides count words: row r
+ * of group g of A starts at a + g a_group_stride + r a_row_stride, B likewise.  A flat set is groups = 1, row_stride = W; a
+ * trace (C, M, W) at equal times is rows = C, row_stride = M W, groups = M, group_stride = W; b_group_stride = 0 compares
+ * every group of A with one shared B.  d(x, y) = popc((x ^ y) over the spins < n).
+ *   cross mode (b != NULL): in every group all rows_a rows_b pairs (row of A, row of B);
+ *   self mode  (b == NULL): in every group the rows_a (rows_a - 1) / 2 unordered pairs r < r' of A, never the diagonal;
+ *                           rows_b and the strides of B are ignored.
+ *   hist[d] (+)= the number of pairs at distance d, d = 0 .. n, summed over the groups; int64 [n + 1]; accumulate == 0
+ *              overwrites, 1 adds onto it (pooling calls)
+ *   nearest[g rows_a + r] = d_min 2^32 + r_min: the smallest distance from row r of A to a row of B of group g (self mode: to
+ *              another row r' != r of A) and the SMALLEST row that attains it; -1 where there is no partner (self mode,
+ *              rows_a == 1).  int64 [groups rows_a]; optional (NULL: not written); always overwritten, never accumulated
+ * Both are DEVICE pointers.  Every value is an exact integer; workgroups combine through integer atomics only (64-bit adds
+ * onto hist, unsigned 64-bit minima onto nearest, which is first filled with 0xFF bytes where B is split over workgroups), so
+ * the result is deterministic.  Nothing is written beyond n + 1 and groups rows_a elements.  The entry needs n only, no graph.
+ * DVG_E_INVALID, before any HIP call: a or hist null; rows_a, groups or n < 1; b != NULL with rows_b < 1; a row stride < W
+ * (of B only when b != NULL); a group stride < 0.  DVG_E_UNSUPPORTED: n > 8192 (a workgroup keeps the n + 1 bins of the
+ * histogram in LDS as 32-bit counters, in up to 8 copies as 33 KiB hold them: 8 up to n = 1055, 1 at 8192); rows_a or rows_b >=
+ * 2^31 (a row index is the low half of a nearest element); groups rows_a rows_b >= 2^62. */
+int dvg_packed_overlap(const uint32_t *a, int64_t rows_a, int64_t a_row_stride, int64_t a_group_stride,
+                       const uint32_t *b, int64_t rows_b, int64_t b_row_stride, int64_t b_group_stride,
+                       int groups, int n,
+                       int64_t *hist, int64_t *nearest, int accumulate, dvg_stream_t stream);
 
 /* ------------------------------------------------------------------ input pipeline
  * The reference's per-image transform Resize((S,S)) -> ToTensor() -> round

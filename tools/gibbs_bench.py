@@ -22,6 +22,11 @@ same rows unpacked to float32 (the unpacking is not timed); a last line says whe
 over the thin=1 trace of that draw (chains x sweeps records), timed as the moments row is; next to it the same sums by torch over the
 same records unpacked to float32, one product and one reduction per lag (the unpacking is not timed); a last line says whether the
 two agree.
+`overlap`: also dvg_packed_overlap (the exact histogram of Hamming distances between bit-packed rows, and every row's nearest
+partner) twice: over the thin=1 trace of that draw in self mode at equal times (`sweeps` groups of `chains` rows), and as a novelty
+call, `novelty=AxB` (default 1024x60000) random rows of n spins in cross mode with `nearest`; next to each the same by torch on
+the rows unpacked to float32 -- a (batched) matmul, (n - G) / 2, torch.bincount, and min for the nearest row (the unpacking is not
+timed); a last line each says whether the two agree element by element.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -231,3 +236,61 @@ if "autocorr" in sys.argv:
     same = bool((by_torch.double() == lag_sum.double()).all()) and bool((x.sum((0, 1)).double() == spin_sum.double()).all()) and \
         bool((x.sum(1).double() == chain_sum.double()).all())
     print(f"  {'':26s} the two give the same sums: {same}  (sum of lag sums {int(lag_sum.sum())}, of spin sums {int(spin_sum.sum())})")
+if "overlap" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    trace = s.sample_trace(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)  # burn_in 0, thin 1: chains x sweeps records
+    W, M = (n + 31) // 32, sweeps
+    hist = torch.empty((n + 1,), dtype=torch.int64, device="cuda")
+
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:26s} {t:9.1f} us per call  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    def packed_self():
+        _lib.check(_lib.lib().dvg_packed_overlap(trace.bits.data_ptr(), C, M * W, W, None, 0, 0, 0, M, n, hist.data_ptr(), None, 0,
+                                                 _lib.stream_ptr()), "dvg_packed_overlap")
+        return hist
+
+    ts, _ = timed(packed_self)
+    t_packed = report("overlap, packed trace", ts, f"{M} groups x {C} rows x {4 * W} B, {M * C * (C - 1) // 2} pairs")
+    x = trace.unpack().transpose(0, 1).contiguous()  # (M, C, n) float32
+    iu = torch.triu_indices(C, C, 1, device="cuda")
+
+    def torch_self():
+        d = (n - torch.bmm(x, x.transpose(1, 2))) / 2
+        return torch.bincount(d[:, iu[0], iu[1]].reshape(-1).long(), minlength=n + 1)
+
+    ts, by_torch = timed(torch_self)
+    t_torch = report("the same by torch, float32", ts, f"{M} x {C} rows x {4 * n} B   {float(np.median(ts)) / t_packed:.1f} x the packed call")
+    print(f"  {'':26s} the two give the same histogram: {bool(torch.equal(by_torch, hist))}  (pairs {int(hist.sum())}, "
+          f"sum of d {int((hist * torch.arange(n + 1, device='cuda')).sum())})")
+    RA, RB = ([tuple(int(v) for v in a.split("=")[1].split("x")) for a in sys.argv if a.startswith("novelty=")] + [(1024, 60000)])[0]
+    g = torch.Generator(device="cuda").manual_seed(seed % 2 ** 31)
+    # rows round two centres, as codes of one data set are: the distances spread and the nearest row is not at n / 2
+    flip = lambda rows, p: torch.where(torch.rand((rows, n), device="cuda", generator=g) < p, -1.0, 1.0)  # noqa: E731
+    centre = flip(2, 0.5)
+    xa = centre[torch.arange(RA, device="cuda") % 2] * flip(RA, 0.2)
+    xb = centre[torch.arange(RB, device="cuda") % 2] * flip(RB, 0.2)
+    a, b = smp.pack_spins(xa), smp.pack_spins(xb)
+    near = torch.empty((RA,), dtype=torch.int64, device="cuda")
+
+    def packed_cross():
+        _lib.check(_lib.lib().dvg_packed_overlap(a.data_ptr(), RA, W, 0, b.data_ptr(), RB, W, 0, 1, n, hist.data_ptr(), near.data_ptr(), 0,
+                                                 _lib.stream_ptr()), "dvg_packed_overlap")
+        return hist
+
+    ts, _ = timed(packed_cross)
+    t_packed = report("novelty, packed rows", ts, f"{RA} x {RB} rows x {4 * W} B, with nearest")
+
+    def torch_cross():
+        d = (n - xa @ xb.T) / 2
+        return torch.bincount(d.reshape(-1).long(), minlength=n + 1), d.min(1)
+
+    ts, (by_torch, (dmin, _at)) = timed(torch_cross)
+    report("the same by torch, float32", ts, f"{RA} x {RB} rows x {4 * n} B   {float(np.median(ts)) / t_packed:.1f} x the packed call")
+    d = (n - xa @ xb.T) / 2
+    first = torch.where(d == dmin[:, None], torch.arange(RB, device="cuda")[None, :], RB).min(1).values  # the smallest row at d_min
+    same = bool(torch.equal(by_torch, hist)) and bool(torch.equal(near >> 32, dmin.long())) and bool(torch.equal(near & 0xFFFFFFFF, first))
+    print(f"  {'':26s} the two give the same histogram and nearest rows: {same}  (pairs {int(hist.sum())}, "
+          f"sum of nearest d {int((near >> 32).sum())})")
