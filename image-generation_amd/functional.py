@@ -4,6 +4,7 @@ the memory and the stream.  No CPU fallback: CPU tensors raise.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import numbers
 from typing import Optional
@@ -361,6 +362,67 @@ def packed_overlap(a, b=None, *, n, nearest=False, out=None):
     if a.dim() == 3:
         dist, row = dist.view(groups, rows_a), row.view(groups, rows_a)
     return hist, (dist, row)
+
+
+Resampled = collections.namedtuple("Resampled", "parents state family weights")
+
+
+def _population_arguments(log_weight, populations, chain_id0, seed, step, state, family):
+    """The argument checks of :func:`population_resample`, none of which touches the library.  Returns (C, n)."""
+    if not torch.is_tensor(log_weight) or log_weight.dtype != torch.float64 or log_weight.dim() != 1 or log_weight.numel() < 1:
+        raise _lib.DvgError(f"log_weight must be a (chains >= 1,) float64 tensor, got "
+                            f"{(tuple(log_weight.shape), log_weight.dtype) if torch.is_tensor(log_weight) else type(log_weight).__name__}")
+    C = int(log_weight.shape[0])
+    for name, v, top in (("populations", populations, 2 ** 31), ("chain_id0", chain_id0, 2 ** 32), ("seed", seed, 2 ** 64),
+                         ("step", step, 2 ** 32)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not (name == "populations") <= v < top:
+            raise ValueError(f"{name} must be an integer in {int(name == 'populations')} .. {top - 1}, got {v!r}")
+    if C % int(populations):
+        raise ValueError(f"populations={populations!r} does not divide the {C} chains of log_weight")
+    if C // int(populations) > 2 ** 20:
+        raise ValueError(f"populations={populations!r}: {C // int(populations)} chains per population are more than 2^20")
+    n = 0
+    if state is not None:
+        if not torch.is_tensor(state) or state.dtype != torch.int8 or state.dim() != 2 or int(state.shape[0]) != C or state.shape[1] < 1:
+            raise _lib.DvgError(f"state must be a ({C}, n >= 1) int8 tensor, got "
+                                f"{(tuple(state.shape), state.dtype) if torch.is_tensor(state) else type(state).__name__}")
+        n = int(state.shape[1])
+    if family is not None and (not torch.is_tensor(family) or family.dtype != torch.int32 or tuple(family.shape) != (C,)):
+        raise _lib.DvgError(f"family must be a ({C},) int32 tensor, got "
+                            f"{(tuple(family.shape), family.dtype) if torch.is_tensor(family) else type(family).__name__}")
+    if not log_weight.is_cuda:
+        raise _lib.DvgError(f"log_weight must live on the GPU (got {log_weight.device}); the HIP path has no CPU fallback")
+    for name, t in (("state", state), ("family", family)):
+        if t is not None and t.device != log_weight.device:
+            raise _lib.DvgError(f"{name} must be on the device of log_weight ({log_weight.device}), got {t.device}")
+    return C, n
+
+
+def population_resample(log_weight, *, populations=1, chain_id0=0, seed, step, state=None, family=None, weights=False):
+    """Population annealing's resampling step (``dvg_population_resample``, "DVG PA v1" in include/dvg.h): systematic
+    resampling of weighed chains in exact integer arithmetic.  ``log_weight``: (C,) float64 on the device, ``populations``
+    independent populations of C / populations consecutive chains (at most 2^20 each); ``chain_id0``, ``seed``, ``step``: the
+    Philox counter and key of the populations' offsets.  ``state`` (C, n) int8: the chains' rows, gathered out of place;
+    ``family`` (C,) int32: the founders' indices to hand down (None: a child gets its parent's index).  Returns the namedtuple
+    ``(parents, state, family, weights)`` of device tensors: ``parents`` (C,) int32, child j's parent; ``state`` the
+    gathered rows or None; ``family`` (C,) int32; ``weights`` None, or with ``weights=True`` the (C,) int64 integer weights
+    k_c in 0 .. 2^32.  It owns its workspace; no host sync."""
+    C, n = _population_arguments(log_weight, populations, chain_id0, seed, step, state, family)
+    lw = log_weight.detach().contiguous()
+    dev = lw.device
+    st = state.detach().contiguous() if state is not None else None
+    fam = family.detach().contiguous() if family is not None else None
+    parents = torch.empty((C,), dtype=torch.int32, device=dev)
+    state_out = torch.empty_like(st) if st is not None else None
+    family_out = torch.empty((C,), dtype=torch.int32, device=dev)
+    k = torch.empty((C,), dtype=torch.int64, device=dev) if weights else None
+    with torch.cuda.device(dev):
+        ws = torch.empty((int(lib().dvg_population_resample_workspace_bytes(C)),), dtype=torch.uint8, device=dev)
+        check(lib().dvg_population_resample(lw.data_ptr(), C, int(populations), int(chain_id0), int(seed), int(step),
+                                            _lib.ptr(st), _lib.ptr(state_out), n, _lib.ptr(fam), family_out.data_ptr(),
+                                            parents.data_ptr(), _lib.ptr(k), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
+              "dvg_population_resample")
+    return Resampled(parents, state_out, family_out, k)
 
 
 # ----------------------------------------------------------------------------- MSE

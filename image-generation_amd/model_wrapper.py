@@ -915,18 +915,22 @@ class ModelWrapper:
         return (out, samples, held) if return_latents else out
 
     @torch.no_grad()
-    def prior_log_likelihood(self, images: torch.Tensor, *, num_sweeps: int = 1000, num_reads: int = 1024):
+    def prior_log_likelihood(self, images: torch.Tensor, *, num_sweeps: int = 1000, num_reads: int = 1024, method: str = "ais",
+                             num_populations: int = 8):
         """How well the prior fits given images' latent codes: encode -> hard spins (heaviside, H(0) = 0, as
         ``generate_variations`` does) -> ``log p(spins)`` under the distribution the sampler draws from
         (``GraphRestrictedBoltzmannMachine.log_likelihood``), with ``log Z`` from one AIS run of ``num_reads`` chains
         over ``num_sweeps`` sweeps.  Returns the (B,) float64 log-likelihoods on the device and the ``LogPartition``
-        result (its ``std_err`` is the estimate's).  Rank-local and eval-mode, like ``generate_images``."""
+        result (its ``std_err`` is the estimate's).  ``method="population"``: ``log Z`` from a population-annealing draw of
+        ``num_reads`` chains in ``num_populations`` populations over the same sweeps instead, the result a
+        ``sampler.Population``.  Rank-local and eval-mode, like ``generate_images``."""
         self._dvae.eval()
         self._grbm.eval()
         images = images.to(self._device)
         spins = F.heaviside_latent_to_discrete(self._dvae.encoder(images)).squeeze(1)  # (B, n) +-1
         ranges = dict(prefactor=self.PREFACTOR, linear_range=self.linear_range, quadratic_range=self.quadratic_range)
-        result = self._grbm.log_partition(self.sampler, num_sweeps=num_sweeps, num_reads=num_reads, **ranges)
+        extra = dict(method=method, num_populations=num_populations) if method != "ais" else {}
+        result = self._grbm.log_partition(self.sampler, num_sweeps=num_sweeps, num_reads=num_reads, **extra, **ranges)
         return self._grbm.log_likelihood(spins, self.sampler, log_z=result.log_z, **ranges), result
 
     @torch.no_grad()

@@ -182,13 +182,39 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         if not (isinstance(sampler, GibbsSampler) and list(sampler.nodes) == self._nodes):
             raise TypeError(f"{what} needs the local GibbsSampler built on this model's nodes, got {type(sampler).__name__}")
 
-    def log_partition(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+    def log_partition(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, method: str = "ais", **kw):
         """The AIS estimate of ``log Z`` of the distribution ``sampler`` draws from -- ``exp(-beta E_s)`` with ``E_s`` the
         energy under the prefactor-scaled, clamped ``(h, J)`` and ``beta = sampler.beta`` unless ``beta=`` says otherwise
         (:meth:`GibbsSampler.log_partition`; ``num_sweeps``, ``num_reads``, ``schedule`` are passed on).  The local
-        :class:`GibbsSampler` only."""
+        :class:`GibbsSampler` only.
+
+        ``method="population"``: population annealing instead (:meth:`sample_population`): ``betas = linspace(0, beta,
+        num_sweeps + 1)[1:]`` at one sweep per beta, ``num_reads`` (default 1024) chains in ``num_populations`` (default 8)
+        populations.  Returns the :class:`~.sampler.Population`, which has ``.log_z`` and ``.std_err`` like the
+        :class:`~.sampler.LogPartition` of the default method."""
         self._need_local_sampler(sampler, "log_partition")
-        return sampler.log_partition(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, **kw)
+        if method not in ("ais", "population"):
+            raise ValueError(f"method must be 'ais' or 'population', got {method!r}")
+        if method == "ais":
+            return sampler.log_partition(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, **kw)
+        beta, num_sweeps = kw.pop("beta", None), kw.pop("num_sweeps", 1000)
+        if isinstance(num_sweeps, bool) or int(num_sweeps) != num_sweeps or int(num_sweeps) < 1:
+            raise ValueError(f"num_sweeps must be an integer >= 1, got {num_sweeps!r}")
+        b = float(sampler.beta if beta is None else beta)
+        if not np.isfinite(b) or b <= 0.0:
+            raise ValueError(f"beta={beta!r} must be finite and > 0")
+        betas = np.linspace(0.0, b, int(num_sweeps) + 1)[1:].astype(np.float32)
+        return self.sample_population(sampler, betas, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range,
+                                      num_reads=kw.pop("num_reads", 1024), num_populations=kw.pop("num_populations", 8), **kw)
+
+    def sample_population(self, sampler, betas, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """A population-annealing draw from the model under the prefactor-scaled, clamped ``(h, J)``: chains annealed through
+        ``betas`` and resampled in proportion to their weights after every step, on the device
+        (:meth:`GibbsSampler.sample_population`; ``num_reads``, ``num_populations``, ``sweeps_per_beta``, ``history`` are
+        passed on).  Returns its :class:`~.sampler.Population`: equally weighted samples at ``betas[-1]``, ``log_z``,
+        ``std_err`` and the surviving families.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "sample_population")
+        return sampler.sample_population(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, betas, **kw)
 
     def sample_tempered(self, sampler, betas, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
         """A parallel-tempering draw from the model under the prefactor-scaled, clamped ``(h, J)``: ladders of ``len(betas)``

@@ -211,6 +211,64 @@ class Tempered:
         return f"Tempered({Q} ladders x {R} rungs, n={n}, attempts={self.attempts.tolist()})"
 
 
+class Population:
+    """What :meth:`GibbsSampler.sample_population` returns, for P populations of R chains annealed over T temperature steps;
+    tensors live where the draw's do.  ``samples`` (C, n) float32 +-1 and ``state`` (C, n) int8: the final population,
+    equally weighted samples at the last beta.  ``log_z_populations`` (P,) float64: each population's estimate, ``n log 2 +
+    sum_t (logsumexp_c log_weights[t] - log R)``; ``log_z``: ``logsumexp_p - log P``, the estimate of the mean of the
+    ``Z_p``; ``std_err``: the relative standard error of that mean, ``std(Z_p, ddof=1) / mean(Z_p) / sqrt(P)``, NaN for P = 1.
+    ``families`` (C,) int32: the index of the founder -- the chain at the start -- each final chain descends from;
+    ``survivors`` (P,) int64: the distinct families of each population; ``rho_t`` (P,) float64: ``R sum_f (n_f / R)^2`` over
+    its families' sizes n_f -- ``R / rho_t`` independent samples remain.  ``ess`` (T, P) float64: the effective sample size
+    ``(sum w)^2 / sum w^2`` of each step's weights, which says where the schedule is too coarse.  ``log_weights`` (T, C)
+    float64 and ``parents`` (T, C) int32: each step's weights and resampling, kept with ``history=True``, else None."""
+
+    def __init__(self, samples, state, log_z_populations, log_z, std_err, families, survivors, rho_t, ess, log_weights=None,
+                 parents=None):
+        self.samples, self.state, self.log_z_populations, self.log_z, self.std_err = samples, state, log_z_populations, log_z, std_err
+        self.families, self.survivors, self.rho_t, self.ess, self.log_weights, self.parents = (families, survivors, rho_t, ess,
+                                                                                              log_weights, parents)
+
+    @staticmethod
+    def step_estimates(log_weights: torch.Tensor, P: int):
+        """(log mean weight, ess) per step and population, both (T, P), from (T, C) float64 log weights: plain torch ops."""
+        lw = log_weights.view(log_weights.shape[0], P, -1)
+        lse = torch.logsumexp(lw, 2)
+        return lse - float(np.log(lw.shape[2])), torch.exp(2.0 * lse - torch.logsumexp(2.0 * lw, 2))
+
+    @classmethod
+    def from_estimates(cls, log_z_populations, families, ess, samples=None, state=None, log_weights=None, parents=None) -> "Population":
+        P = int(log_z_populations.shape[0])
+        R = int(families.shape[0]) // P
+        log_z = torch.logsumexp(log_z_populations, 0) - float(np.log(P))
+        z = torch.exp(log_z_populations - log_z_populations.max())
+        std_err = z.std(unbiased=True) / z.mean() / float(np.sqrt(P)) if P > 1 else torch.full_like(log_z, float("nan"))
+        # a family's founder lies in its own population, p R .. p R + R - 1: its index there is the remainder
+        local = torch.remainder(families.view(P, R).to(torch.int64), R)
+        sizes = torch.zeros((P, R), dtype=torch.int64, device=families.device).scatter_add_(1, local, torch.ones_like(local))
+        survivors = (sizes > 0).sum(1)
+        rho_t = (sizes * sizes).sum(1).to(torch.float64) / float(R)
+        return cls(samples, state, log_z_populations, log_z, std_err, families, survivors, rho_t, ess, log_weights, parents)
+
+    @classmethod
+    def from_history(cls, n: int, log_weights: torch.Tensor, families: torch.Tensor, populations: int = 1, samples=None,
+                     state=None, parents=None) -> "Population":
+        """The estimates from plain tensors (CPU ones too): ``log_weights`` (T, C) float64, every step's; ``families`` (C,)
+        integer founder indices of the final chains; ``populations`` P dividing C."""
+        if log_weights.dim() != 2 or log_weights.dtype != torch.float64 or min(log_weights.shape) < 1:
+            raise ValueError(f"log_weights must be (steps >= 1, chains >= 1) float64, got {tuple(log_weights.shape)} {log_weights.dtype}")
+        T, C = (int(v) for v in log_weights.shape)
+        P = int(populations)
+        if P < 1 or C % P or tuple(families.shape) != (C,):
+            raise ValueError(f"populations={populations!r} must divide the {C} chains, and families be ({C},), got {tuple(families.shape)}")
+        inc, ess = cls.step_estimates(log_weights, P)
+        return cls.from_estimates(n * float(np.log(2.0)) + inc.sum(0), families, ess, samples, state, log_weights, parents)
+
+    def __repr__(self):
+        return (f"Population({int(self.log_z_populations.shape[0])} x {int(self.families.shape[0]) // int(self.log_z_populations.shape[0])} "
+                f"chains, {int(self.ess.shape[0])} steps, log_z={float(self.log_z):.6f}, std_err={float(self.std_err):.4f})")
+
+
 def pack_spins(x: torch.Tensor) -> torch.Tensor:
     """(..., n) spins (+1 where the entry is > 0) -> (..., W = ceil(n / 32)) int32 in the layout of "DVG trace v1"
     (include/dvg.h): bit b of word w is 1 iff spin 32 w + b is +1, bits of spins >= n are 0.  Plain torch operations, on
@@ -509,6 +567,8 @@ class GibbsSampler:
         chain_offset: global id of this sampler's first chain (rank sharding).
     """
 
+    PA_BLOCK_BYTES = 1 << 26  # sample_population without `history`: the log weights of this many bytes of steps are kept at a time
+
     def __init__(self, plan: GibbsPlan, nodes: Sequence, *, beta: float, sweeps: int, seed: int,
                  persistent: bool = True, device="cuda", chain_offset: int = 0,
                  h_range: Tuple[float, float] = (-4.0, 4.0), j_range: Tuple[float, float] = (-1.0, 1.0)):
@@ -541,6 +601,9 @@ class GibbsSampler:
         # ... and the traced draws (sample_trace)
         self.trace_seed = self.seed ^ 0x74726163
         self.trace_sweep_count = 0
+        # ... and the population-annealing draws (sample_population), whose counter also numbers the resamplings
+        self.pa_seed = self.seed ^ 0x70613031
+        self.pa_sweep_count = 0
         # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
         self._betas: Optional[torch.Tensor] = None
         self._fixed_sweeps = self.sweeps
@@ -560,6 +623,7 @@ class GibbsSampler:
         self.ais_sweep_count = 0
         self.pt_sweep_count = 0
         self.trace_sweep_count = 0
+        self.pa_sweep_count = 0
 
     def set_beta_schedule(self, betas) -> None:
         """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
@@ -827,6 +891,88 @@ class GibbsSampler:
         samples, log_w, _energy = self.sample_ais(linear, quadratic, prefactor, linear_range, quadratic_range, betas,
                                                   num_reads=num_reads)
         return LogPartition.from_weights(self.plan.n, log_w, samples)
+
+    def sample_population(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                          betas, *, num_reads: int, num_populations: int = 1, sweeps_per_beta: int = 1,
+                          history: bool = False) -> "Population":
+        """A population-annealing draw (sequential Monte Carlo; "DVG PA v1" in include/dvg.h): ``num_reads`` fresh chains in
+        ``num_populations`` independent populations of consecutive chains are annealed through ``betas`` (T,) -- a host
+        sequence, array or CPU tensor, finite and >= 0, with ``betas[-1] = 0`` before it -- and after every temperature step
+        each population is resampled in proportion to its chains' weights: heavy chains are copied, light ones dropped, so
+        every chain keeps working and the samples are equally weighted at every temperature.  Step t: (1)
+        ``dvg_gibbs_sample_ais`` on the chains in place, ``sweeps_per_beta`` sweeps at ``betas[t]`` weighed from
+        ``betas[t - 1]``; (2) each population's ``logsumexp(log_weights) - log R`` is added to its log Z (plain torch ops, a
+        block of steps at a time); (3) ``dvg_population_resample`` with ``step`` the global index of the sweep after the step's last.  The last step is
+        resampled too.  (The weight depends on the state before the sweeps only and the sweeps leave the new distribution
+        invariant: move-then-resample is properly weighted.)  Returns a :class:`Population`; ``history=True`` keeps every
+        step's ``log_weights`` and ``parents``.  The table is uploaded once; no host sync.
+
+        Its own key ``pa_seed`` and counter ``pa_sweep_count``: every other stream and counter is left alone.  Chain ids are
+        ``chain_offset + arange(num_reads)``."""
+        n = self.plan.n
+        # every argument check comes before the first library call (the table's upload included)
+        if torch.is_tensor(betas) and betas.is_cuda:
+            raise _lib.DvgError("betas: the schedule is a host sequence, array or CPU tensor (it is checked, then uploaded)")
+        sched = _check_beta_table(betas, "betas")
+        if sched.ndim != 1:
+            raise _lib.DvgError(f"betas must be (steps,), got {tuple(sched.shape)}")
+        for name, v in (("num_reads", num_reads), ("num_populations", num_populations), ("sweeps_per_beta", sweeps_per_beta)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        C, P, theta, T = int(num_reads), int(num_populations), int(sweeps_per_beta), int(sched.size)
+        if C % P:
+            raise ValueError(f"num_populations={num_populations!r} does not divide num_reads={num_reads!r}")
+        if C // P > 2 ** 20:
+            raise ValueError(f"num_reads={num_reads!r} / num_populations={num_populations!r}: more than 2^20 chains per population")
+        lin = _lib.require_cuda(linear.detach(), "linear")
+        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
+        if lin.numel() != n or quad.numel() != self.plan.n_edges:
+            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
+        dev = lin.device
+        L = _lib.lib()
+        table = torch.from_numpy(np.repeat(sched, theta)).to(dev)  # (T theta,) float32: each call points into it
+        state, other = (torch.empty((C, n), dtype=torch.int8, device=dev) for _ in range(2))
+        families, other_families = None, torch.empty((C,), dtype=torch.int32, device=dev)
+        # the steps' log weights are kept in rows (all T with `history`, else a ring of at most PA_BLOCK_BYTES) and the
+        # estimates are taken a block of rows at a time: a handful of torch launches per block instead of per step
+        rows = T if history else min(T, max(1, self.PA_BLOCK_BYTES // (8 * C)))
+        log_w = torch.empty((rows, C), dtype=torch.float64, device=dev)
+        parents = torch.empty((T if history else 1, C), dtype=torch.int32, device=dev)
+        log_z = torch.full((P,), n * float(np.log(2.0)), dtype=torch.float64, device=dev)
+        ess = torch.empty((T, P), dtype=torch.float64, device=dev)
+        inf = float("inf")
+        hl, hh = linear_range if linear_range is not None else (-inf, inf)
+        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+        with torch.cuda.device(dev):
+            ws = torch.empty((int(L.dvg_population_resample_workspace_bytes(C)),), dtype=torch.uint8, device=dev)
+            stream = _lib.stream_ptr(dev)
+            for t in range(T):
+                lw = log_w.data_ptr() + 8 * C * (t % rows)
+                par = parents.data_ptr() + (4 * C * t if history else 0)
+                sweep0 = self.pa_sweep_count + t * theta
+                _lib.check(
+                    L.dvg_gibbs_sample_ais(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl), float(hh),
+                                           float(jl), float(jh), table.data_ptr() + 4 * t * theta, 0,
+                                           float(sched[t - 1]) if t else 0.0, state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF,
+                                           self.pa_seed, sweep0 & 0xFFFFFFFF, theta, int(t == 0), None, lw, None, None, stream),
+                    "dvg_gibbs_sample_ais",
+                )
+                _lib.check(
+                    L.dvg_population_resample(lw, C, P, self.chain_offset & 0xFFFFFFFF, self.pa_seed,
+                                              (sweep0 + theta) & 0xFFFFFFFF, state.data_ptr(), other.data_ptr(), n,
+                                              _lib.ptr(families), other_families.data_ptr(), par, None, ws.data_ptr(), ws.numel(),
+                                              stream),
+                    "dvg_population_resample",
+                )
+                state, other = other, state
+                families, other_families = other_families, (families if families is not None else torch.empty_like(other_families))
+                if (t + 1) % rows == 0 or t == T - 1:  # the block of steps whose weights the rows hold
+                    first = t - t % rows
+                    inc, ess[first:t + 1] = Population.step_estimates(log_w[:t + 1 - first], P)
+                    log_z = log_z + inc.sum(0)
+        self.pa_sweep_count += T * theta
+        return Population.from_estimates(log_z, families, ess, state.to(torch.float32), state, log_w if history else None,
+                                         parents if history else None)
 
     def sample_tempered(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
                         betas, *, num_ladders: int, num_sweeps: Optional[int] = None, swap_every: int = 1,

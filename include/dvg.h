@@ -315,6 +315,46 @@ int dvg_packed_overlap(const uint32_t *a, int64_t rows_a, int64_t a_row_stride, 
                        const uint32_t *b, int64_t rows_b, int64_t b_row_stride, int64_t b_group_stride,
                        int groups, int n,
                        int64_t *hist, int64_t *nearest, int accumulate, dvg_stream_t stream);
+/* Population annealing's resampling step ("DVG PA v1"): weighed chains -- dvg_gibbs_sample_ais returns each chain's log weight
+ * -- are resampled in proportion to their weights: heavy chains are copied, light ones dropped, and the children are equally
+ * weighted.  n_chains = P R: P = n_populations independent populations of R consecutive chains each; population p holds the
+ * chains p R .. p R + R - 1.  Per population, with lw its R log weights (float64):
+ *   1. m = max lw (exact in any order).
+ *   2. d_c = lw_c - m, one float64 subtraction;  z_c = clamp((float)d_c, -87, 0), the conversion rounding to the nearest
+ *      float32;  w_c = spec_exp(z_c), the bit-specified float32 exp of csrc/philox.h and oracle/gibbs.py;
+ *      k_c = (uint64)((double)w_c 2^32): the scaling is exact, the conversion truncates, 0 <= k_c <= 2^32.  The heaviest chain
+ *      has k = 2^32; a chain whose w_c is below 2^-32 (more than 32 log 2 ~= 22.2 below the maximum; -inf too) has k = 0 and
+ *      never a child.  NaN and +inf are not allowed and not checked.
+ *   3. S_c = k_0 + ... + k_c in uint64,  K = S_{R-1}:  2^32 <= K <= 2^52 as R <= 2^20.
+ *   4. o = philox4x32_10(ctr = (0, chain_id0 + p R, step, STREAM_RESAMPLE = 5), key = seed) (the key split lo / hi as in every
+ *      stream);  r64 = (o.x << 32) | o.y;  V = mulhi64(r64, K), in [0, K) and uniform to within K / 2^64 <= 2^-12 per value.
+ *   5. Systematic resampling: q = K / R, rem = K % R (integers); child j = 0 .. R-1 points at
+ *      t_j = j q + (j rem + V) / R  (integer division, every term below 2^53)  = floor((j K + V) / R) < K,
+ *      and its parent is the smallest c with S_c > t_j.
+ *   6. parent_out[p R + j] = p R + c;  state_out[p R + j] = state_in[p R + c], a row of n int8;  family_out[p R + j] =
+ *      family_in[p R + c], or p R + c, the parent's global index, where family_in == NULL;  weight_out[p R + c] = k_c.
+ * Everything is integer or bit-specified float arithmetic: the result is a function of (lw, seed, chain_id0, step) alone, no
+ * last bit is the implementation's.  A chain gets floor(R k_c / K) or ceil(R k_c / K) children; the parents of a population
+ * are non-decreasing; equal weights give the identity; and as the counter holds the population's own first chain id, a call
+ * on the populations a .. b alone with chain_id0 advanced by a R gives that slice of the whole call (rank-sharded chains).
+ * The float32 weights bias the resampling by <= 2^-24 relative per chain; an estimate of log Z uses the float64 log weights,
+ * not k.
+ *   All pointers are DEVICE pointers.  log_weight float64 [n_chains]; parent_out int32 [n_chains], required; state_in /
+ *   state_out int8 (n_chains, n), both or neither; family_out int32 [n_chains] and weight_out uint64 [n_chains] optional
+ *   (NULL: not written); family_in is read only with family_out.  Out of place.  Nothing is written beyond n_chains elements
+ *   or rows of any output.  The entry needs no graph, enqueues on `stream` and allocates nothing; ws: a workspace of at least
+ *   dvg_population_resample_workspace_bytes(n_chains) bytes.  Populations of up to 1024 chains take one workgroup each; larger
+ *   ones separate stream-ordered launches (block sums, a scan of the sums, apply): no workgroup waits for another.
+ * DVG_E_INVALID, before any HIP call: log_weight, parent_out or ws null; n_chains < 1, n_populations < 1, n_chains not a
+ * multiple of n_populations; exactly one of state_in, state_out null; n < 1 with a state; state_in == state_out; family_in ==
+ * family_out != NULL.  DVG_E_WORKSPACE: ws_bytes below the query.  DVG_E_UNSUPPORTED: R > 2^20 (K must stay below 2^53). */
+size_t dvg_population_resample_workspace_bytes(int n_chains);
+int dvg_population_resample(const double *log_weight, int n_chains, int n_populations,
+                            uint32_t chain_id0, uint64_t seed, uint32_t step,
+                            const int8_t *state_in, int8_t *state_out, int n,
+                            const int32_t *family_in, int32_t *family_out,
+                            int32_t *parent_out, uint64_t *weight_out,
+                            void *ws, size_t ws_bytes, dvg_stream_t stream);
 
 /* ------------------------------------------------------------------ input pipeline
  * The reference's per-image transform Resize((S,S)) -> ToTensor() -> round

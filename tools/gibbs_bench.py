@@ -27,6 +27,14 @@ partner) twice: over the thin=1 trace of that draw in self mode at equal times (
 call, `novelty=AxB` (default 1024x60000) random rows of n spins in cross mode with `nearest`; next to each the same by torch on
 the rows unpacked to float32 -- a (batched) matmul, (n - G) / 2, torch.bincount, and min for the nearest row (the unpacking is not
 timed); a last line each says whether the two agree element by element.
+`population`: also population annealing ("DVG PA v1").  (a) dvg_population_resample alone, `resample=PxR,...` (default 8x128,1x65536)
+populations x chains of n spins with normal(0, 3) log weights, states gathered, against the same operation by torch: exp of the
+shifted weights, cumsum, searchsorted, index_select (float64: its parents may differ at near ties; the line says how many do).
+(b) GibbsSampler.sample_population of `chains` chains in 8 populations over `sweeps` betas 0 -> 20 at one sweep each, against ONE
+dvg_gibbs_sample_ais call of the same sweeps, against the draw's AIS calls alone (one call per step: launches plus the
+start-energy walk each call repeats) and its resample calls alone: the per-step overhead and the resample's share of it.  (c)
+std_err of log Z at equal sweeps, `seeds=K` (default 4) seeds each: population annealing (between its 8 populations), AIS by its
+effective sample size, and AIS between 8 groups of its chains -- the populations' formula on the same footing.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -294,3 +302,99 @@ if "overlap" in sys.argv:
     same = bool(torch.equal(by_torch, hist)) and bool(torch.equal(near >> 32, dmin.long())) and bool(torch.equal(near & 0xFFFFFFFF, first))
     print(f"  {'':26s} the two give the same histogram and nearest rows: {same}  (pairs {int(hist.sum())}, "
           f"sum of nearest d {int((near >> 32).sum())})")
+if "population" in sys.argv:
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:30s} {t:9.1f} us  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    shapes = ([a.split("=")[1] for a in sys.argv if a.startswith("resample=")] + ["8x128,1x65536"])[0]
+    for P, R in (tuple(int(v) for v in item.split("x")) for item in shapes.split(",")):
+        Cr = P * R
+        lw = torch.from_numpy(np.random.default_rng(Cr).normal(0.0, 3.0, Cr)).cuda()
+        state = torch.where(torch.rand((Cr, n), device="cuda") < 0.5, -1, 1).to(torch.int8)
+        other, parents = torch.empty_like(state), torch.empty((Cr,), dtype=torch.int32, device="cuda")
+        ws = torch.empty((int(_lib.lib().dvg_population_resample_workspace_bytes(Cr)),), dtype=torch.uint8, device="cuda")
+
+        def by_hip():
+            _lib.check(_lib.lib().dvg_population_resample(lw.data_ptr(), Cr, P, 0, seed, 7, state.data_ptr(), other.data_ptr(), n, None,
+                                                          None, parents.data_ptr(), None, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                       "dvg_population_resample")
+            return parents
+
+        offset = torch.rand((P, 1), dtype=torch.float64, device="cuda")
+        j = torch.arange(R, dtype=torch.float64, device="cuda")[None, :]
+        first = (torch.arange(P, device="cuda") * R)[:, None]
+
+        def by_torch():
+            w = torch.exp(lw.view(P, R) - lw.view(P, R).max(1, keepdim=True).values)
+            S = torch.cumsum(w, 1)
+            at = (j + offset) * (S[:, -1:] / R)
+            par = (torch.searchsorted(S, at, right=True).clamp_(max=R - 1) + first).view(-1)
+            return par, torch.index_select(state, 0, par)
+
+        ts, _ = timed(by_hip)
+        t_hip = report(f"resample {P} x {R}, HIP", ts, f"{Cr} chains x {n} B")
+        ts, (par, _rows) = timed(by_torch)
+        report(f"resample {P} x {R}, torch", ts, f"{float(np.median(ts)) / t_hip:.1f} x the HIP call")
+        # the same offset through both: V / K of the HIP call is not exported, so only the shape of the result is compared
+        kids_hip = torch.bincount(parents.long(), minlength=Cr)
+        kids_torch = torch.bincount(par.long(), minlength=Cr)
+        print(f"  {'':30s} children per chain differ by at most {int((kids_hip - kids_torch).abs().max())} (other offsets); "
+              f"gathered rows equal their parents': {bool(torch.equal(other, state[parents.long()]))}")
+
+    betas = np.linspace(0.0, 20.0, sweeps + 1)[1:].astype(np.float32)
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    ts, pop = timed(lambda: s.sample_population(lin, quad, 0.05, (-4, 4), (-1, 1), betas, num_reads=C, num_populations=8).samples)
+    t_pop = report("population draw", ts, f"{C} chains, 8 populations, {sweeps} steps of one sweep")
+    table = torch.from_numpy(betas).cuda()
+    state = torch.empty((C, n), dtype=torch.int8, device="cuda")
+    other, parents = torch.empty_like(state), torch.empty((C,), dtype=torch.int32, device="cuda")
+    log_w = torch.empty((C,), dtype=torch.float64, device="cuda")
+    ws = torch.empty((int(_lib.lib().dvg_population_resample_workspace_bytes(C)),), dtype=torch.uint8, device="cuda")
+
+    def ais(first, count, init):
+        _lib.check(_lib.lib().dvg_gibbs_sample_ais(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0,
+                                                   table.data_ptr() + 4 * first, 0, float(betas[first - 1]) if first else 0.0,
+                                                   state.data_ptr(), C, 0, seed, first, count, init, None, log_w.data_ptr(), None, None,
+                                                   _lib.stream_ptr()), "dvg_gibbs_sample_ais")
+
+    def one_call():
+        ais(0, sweeps, 1)
+        return log_w
+
+    def per_step():
+        for t in range(sweeps):
+            ais(t, 1, int(t == 0))
+        return log_w
+
+    def resamples():
+        for t in range(sweeps):
+            _lib.check(_lib.lib().dvg_population_resample(log_w.data_ptr(), C, 8, 0, seed, t + 1, state.data_ptr(), other.data_ptr(), n,
+                                                          None, None, parents.data_ptr(), None, ws.data_ptr(), ws.numel(),
+                                                          _lib.stream_ptr()), "dvg_population_resample")
+        return parents
+
+    ts, _ = timed(one_call)
+    t_one = report("one AIS call", ts, f"{C} chains, {sweeps} sweeps")
+    ts, _ = timed(per_step)
+    t_steps = report("an AIS call per step", ts, f"{(float(np.median(ts)) - t_one) / sweeps:.2f} us per step beyond the one call")
+    ts, _ = timed(resamples)
+    t_res = report("the resample calls alone", ts, f"{float(np.median(ts)) / sweeps:.2f} us per step")
+    over = (t_pop - t_one) / sweeps
+    print(f"  {'':30s} per-step overhead of the population draw {over:.2f} us: AIS call per step {(t_steps - t_one) / sweeps:.2f}, "
+          f"resample {t_res / sweeps:.2f} ({100 * t_res / sweeps / over:.0f} %), log Z and ess by torch "
+          f"{over - (t_steps - t_one + t_res) / sweeps:.2f}")
+
+    K = max([int(a.split("=")[1]) for a in sys.argv if a.startswith("seeds=")] + [4])
+    print(f"  std_err of log Z at beta 20, {C} chains, {sweeps} sweeps, {K} seeds:")
+    for k in range(K):
+        sk = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed + k, persistent=True)
+        pa = sk.sample_population(lin, quad, 0.05, (-4, 4), (-1, 1), betas, num_reads=C, num_populations=8)
+        lp = sk.log_partition(lin, quad, 0.05, (-4, 4), (-1, 1), num_sweeps=sweeps, num_reads=C)
+        groups = torch.logsumexp(lp.log_weights.view(8, -1), 1)
+        z = torch.exp(groups - groups.max())
+        print(f"    seed + {k}: population log_z {float(pa.log_z):.4f} std_err {float(pa.std_err):.4f} (survivors "
+              f"{int(pa.survivors.min())} .. {int(pa.survivors.max())} of {C // 8}, worst step ess {float(pa.ess.min()):.1f});  AIS log_z "
+              f"{float(lp.log_z):.4f} std_err by ess {float(lp.std_err):.4f} (ess {float(lp.ess):.1f}), between 8 groups "
+              f"{float(z.std(unbiased=True) / z.mean() / 8 ** 0.5):.4f}")
