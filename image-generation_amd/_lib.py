@@ -129,6 +129,11 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     ),
+    "dvg_grbm_energy_packed": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64, c_int64,
+         c_void_p, c_void_p],
+    ),
     "dvg_population_resample_workspace_bytes": (c_size_t, [c_int]),
     "dvg_population_resample": (
         c_int,

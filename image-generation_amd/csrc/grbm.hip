@@ -375,6 +375,114 @@ __global__ __launch_bounds__(OV_THREADS) void packed_overlap_kernel(
   ov_flush(h, n, copies, tid, hist);
 }
 
+// ---------------------------------------------------------------- energies of bit-packed rows (dvg_grbm_energy_packed)
+// E(row) = sum_i hs_i s_i + sum_e Js_e s_i s_j in float64, hs / Js the scaled, clamped float32 fields the sampler draws from.
+// A TILE is 64 consecutive rows of the flattened (group, row) index -- one per lane; a workgroup of EN_WAVES waves takes the
+// tiles `blockIdx.x + k gridDim.x` (one tile each up to EN_GRID tiles).  It turns its tile into per-spin BIT COLUMNS in LDS with
+// the ballots of the moments kernel: a wave takes the words w = wave, wave + EN_WAVES, .., lane r reads word w of its row (rows
+// beyond the last read as 0), 32 ballots give the 64-bit columns of spins 32 w .. 32 w + 31 (bit r = the spin's bit in row r),
+// kept by lanes 0..31; columns of spins >= n are never stored.  A column is stored as its two halves, lo[spin] (rows 0..31) and
+// hi[spin] (rows 32..63): lane r only ever needs the half that holds its own bit.
+// Behind the barrier wave v takes the terms v per .. v per + per - 1 of the n + n_edges terms (spins first, then edges in the
+// order of the edge list), per = ceil((n + n_edges) / EN_WAVES), 64 terms at a time: lane t loads the block's t-th h_i or J_e
+// and scales and clamps it -- clamp(rn(prefactor h_i), h_lo, h_hi), once per term and tile, never per row -- then the wave
+// walks the block.  A term is WAVE-UNIFORM: its number (a scalar loop counter), i and j (scalar loads), its field (v_readlane
+// from the lane that holds it) and the mask x = ~col_i (the rows in which s_i = -1) or col_i ^ col_j (the rows in which s_i s_j
+// = -1), read from LDS at one address per 32-lane half.  Lane r moves its own bit of x into bit 31 with a shift by 31 - (r mod
+// 32) -- a per-lane constant, not a per-term amount -- and XORs it onto the float32 field's sign; the conversion to float64 is
+// exact, and one float64 accumulator per lane takes the terms in order.  The waves' partial sums meet in LDS, part[wave][lane];
+// behind a second barrier wave 0 adds them in wave order and its lanes store 64 consecutive doubles (rows beyond the last are
+// not stored).  The order of the additions is fixed by (n, n_edges) alone: no atomics, the same bits on every call.  A
+// workgroup's next tile needs no third barrier: the columns are rewritten behind barrier 2, which every wave passes with its
+// terms done, and part[] behind the next tile's barrier 1, which wave 0 reaches with its sums read.
+// LDS: 8 n bytes of columns + EN_WAVES 512 bytes of partial sums (72 KiB at n = 8192).  Banks (bank = dword mod 32 for
+// ds_read_b32 and ds_write_b32 in 32-lane halves, dword mod 64 for ds_read_b64 in 32-lane halves, mod 32 for ds_write_b64 in
+// groups of 16 lanes): the term loop's ds_read_b32 is one address per half -- a broadcast; the transpose writes lo[32 w + l] and
+// hi[32 w + l], l < 32: 32 consecutive dwords, each bank once; part[wave][lane] is written and read with consecutive lanes on
+// consecutive doubles, each bank once per group.  No conflict by the rule.
+constexpr int EN_WAVES = 16, EN_UNROLL = 4, EN_MAX_N = 8192, EN_PART_LDS = EN_WAVES * 64 * 8, EN_LDS_MAX = EN_MAX_N * 8 + EN_PART_LDS;
+constexpr int64_t EN_GRID = 1 << 20;
+
+// field of the block's term k (held by lane k) with this lane's bit of the mask `minus` as its sign, exactly in float64
+__device__ __forceinline__ double en_term(uint32_t fields, int k, uint32_t minus, int to_sign) {
+  const uint32_t field = (uint32_t)__builtin_amdgcn_readlane((int)fields, k);
+  return (double)__uint_as_float(field ^ ((minus << to_sign) & 0x80000000u));
+}
+
+__global__ __launch_bounds__(EN_WAVES * 64) void grbm_energy_packed_kernel(
+    const uint32_t* __restrict__ bits, int64_t rows, int64_t row_stride, int64_t groups, int64_t group_stride, int n, int W,
+    int n_edges, const int32_t* __restrict__ ei, const int32_t* __restrict__ ej, const float* __restrict__ h,
+    const float* __restrict__ J, float prefactor, float h_lo, float h_hi, float j_lo, float j_hi, double* __restrict__ out) {
+  extern __shared__ __align__(16) unsigned char en_smem[];
+  uint32_t* lo = reinterpret_cast<uint32_t*>(en_smem);  // [n] rows 0..31 of the tile, then [n] rows 32..63
+  double* part = reinterpret_cast<double*>(lo + 2 * n);  // [EN_WAVES][64]
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t* mine = lane < 32 ? lo : lo + n;  // the halves that hold this lane's bit
+  const int to_sign = 31 - (lane & 31);
+  const int terms = n + n_edges, per = (terms + EN_WAVES - 1) / EN_WAVES;
+  const int t0 = wave * per < terms ? wave * per : terms, t1 = t0 + per < terms ? t0 + per : terms;  // this wave's terms
+  const int i1 = t1 < n ? t1 : n, e0 = (t0 > n ? t0 : n) - n, e1 = t1 - n;  // spins t0 .. i1 - 1 and edges e0 .. e1 - 1 of them
+  const int64_t total = groups * rows, n_tiles = (total + 63) >> 6;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t idx = tile * 64 + lane;
+    const uint32_t* row = nullptr;  // (null: a row beyond the last)
+    if (idx < total) {
+      const int64_t g = groups == 1 ? 0 : idx / rows;
+      row = bits + g * group_stride + (idx - g * rows) * row_stride;
+    }
+    for (int w = wave; w < W; w += EN_WAVES) {
+      const uint32_t word = row ? row[w] : 0u;
+      unsigned long long col = 0ull;
+#pragma unroll
+      for (int b = 0; b < 32; ++b) {
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
+        if (lane == b) col = m;
+      }
+      const int i = 32 * w + lane;
+      if (lane < 32 && i < n) {
+        lo[i] = (uint32_t)col;
+        lo[n + i] = (uint32_t)(col >> 32);
+      }
+    }
+    __syncthreads();
+    double acc = 0.0;
+    for (int b0 = t0; b0 < i1; b0 += 64) {
+      const int cnt = i1 - b0 < 64 ? i1 - b0 : 64;
+      const uint32_t hs = lane < cnt ? __float_as_uint(fminf(fmaxf(__fmul_rn(prefactor, h[b0 + lane]), h_lo), h_hi)) : 0u;
+      int k = 0;
+      for (; k + EN_UNROLL <= cnt; k += EN_UNROLL) {  // (unrolled by hand: the reads of EN_UNROLL terms in flight together)
+        uint32_t x[EN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EN_UNROLL; ++u) x[u] = ~mine[b0 + k + u];
+#pragma unroll
+        for (int u = 0; u < EN_UNROLL; ++u) acc += en_term(hs, k + u, x[u], to_sign);
+      }
+      for (; k < cnt; ++k) acc += en_term(hs, k, ~mine[b0 + k], to_sign);
+    }
+    for (int b0 = e0; b0 < e1; b0 += 64) {
+      const int cnt = e1 - b0 < 64 ? e1 - b0 : 64;
+      const uint32_t Js = lane < cnt ? __float_as_uint(fminf(fmaxf(__fmul_rn(prefactor, J[b0 + lane]), j_lo), j_hi)) : 0u;
+      int k = 0;
+      for (; k + EN_UNROLL <= cnt; k += EN_UNROLL) {
+        uint32_t x[EN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < EN_UNROLL; ++u) x[u] = mine[ei[b0 + k + u]] ^ mine[ej[b0 + k + u]];
+#pragma unroll
+        for (int u = 0; u < EN_UNROLL; ++u) acc += en_term(Js, k + u, x[u], to_sign);
+      }
+      for (; k < cnt; ++k) acc += en_term(Js, k, mine[ei[b0 + k]] ^ mine[ej[b0 + k]], to_sign);
+    }
+    part[wave * 64 + lane] = acc;
+    __syncthreads();
+    if (wave == 0 && idx < total) {
+      double s = part[lane];
+#pragma unroll
+      for (int v = 1; v < EN_WAVES; ++v) s += part[v * 64 + lane];
+      out[idx] = s;
+    }
+  }
+}
+
 }  // namespace dvg
 
 using namespace dvg;
@@ -440,6 +548,44 @@ extern "C" int dvg_grbm_moments_packed(const dvg_graph_t* g, const uint32_t* bit
   DVG_LAUNCH(K_GRBM_SUFFSTATS, grbm_moments_packed_kernel, dim3((unsigned)ceil_div(n_tiles, per)), dim3(MP_WAVES * 64),
              (size_t)per * n * 8, s, bits, rows, n, W, g->n_edges, g->edge_i, g->edge_j, (int)per,
              reinterpret_cast<unsigned long long*>(spin_sum), reinterpret_cast<unsigned long long*>(pair_sum));
+  return DVG_OK;
+}
+
+// Float64 energies of bit-packed rows under the sampler's scaled, clamped fields ("DVG energy v1", include/dvg.h): the rows
+// are never unpacked.
+extern "C" int dvg_grbm_energy_packed(const dvg_graph_t* g, const float* linear, const float* quadratic, float prefactor,
+                                      float h_lo, float h_hi, float j_lo, float j_hi, const uint32_t* bits, int64_t rows,
+                                      int64_t row_stride, int64_t groups, int64_t group_stride, double* energy_out,
+                                      dvg_stream_t stream) {
+  DVG_REQUIRE(g, "grbm_energy_packed: g is null");
+  DVG_REQUIRE(linear, "grbm_energy_packed: linear is null");
+  DVG_REQUIRE(quadratic, "grbm_energy_packed: quadratic is null");
+  DVG_REQUIRE(bits, "grbm_energy_packed: bits is null");
+  DVG_REQUIRE(energy_out, "grbm_energy_packed: energy_out is null");
+  DVG_REQUIRE(rows >= 1, "grbm_energy_packed: rows=%lld must be at least 1", (long long)rows);
+  DVG_REQUIRE(groups >= 1, "grbm_energy_packed: groups=%lld must be at least 1", (long long)groups);
+  const int n = g->n;
+  const int64_t W = ((int64_t)n + 31) / 32;
+  DVG_REQUIRE(row_stride >= W, "grbm_energy_packed: row_stride=%lld is less than the %lld words of a row", (long long)row_stride,
+              (long long)W);
+  DVG_REQUIRE(group_stride >= 0, "grbm_energy_packed: group_stride=%lld is negative", (long long)group_stride);
+  DVG_REQUIRE(std::isfinite(prefactor), "grbm_energy_packed: prefactor=%g is not finite", (double)prefactor);
+  if ((__int128)groups * rows >= ((__int128)1 << 62)) {
+    set_error("grbm_energy_packed: groups=%lld x rows=%lld energies are 2^62 or more", (long long)groups, (long long)rows);
+    return DVG_E_UNSUPPORTED;
+  }
+  if (n > EN_MAX_N) {
+    set_error("grbm_energy_packed: n=%d > %d (a tile's bit columns are kept in %d KiB of LDS)", n, EN_MAX_N, EN_MAX_N * 8 / 1024);
+    return DVG_E_UNSUPPORTED;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n_tiles = ceil_div(groups * rows, 64);
+  const size_t lds = (size_t)n * 8 + (size_t)EN_PART_LDS;
+  static std::atomic<uint64_t> attr_done{0};
+  if (lds > 64 * 1024) DVG_TRY(raise_dynamic_lds(attr_done, (const void*)grbm_energy_packed_kernel, EN_LDS_MAX));
+  DVG_LAUNCH(K_GRBM_SUFFSTATS, grbm_energy_packed_kernel, dim3((unsigned)(n_tiles < EN_GRID ? n_tiles : EN_GRID)),
+             dim3(EN_WAVES * 64), lds, s, bits, rows, row_stride, groups, group_stride, n, (int)W, g->n_edges, g->edge_i, g->edge_j,
+             linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, energy_out);
   return DVG_OK;
 }
 

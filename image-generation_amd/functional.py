@@ -364,6 +364,63 @@ def packed_overlap(a, b=None, *, n, nearest=False, out=None):
     return hist, (dist, row)
 
 
+def _clamp_range(r, name):
+    """``(lo, hi)`` floats of a solver range, None meaning no clamp."""
+    if r is None:
+        return -float("inf"), float("inf")
+    try:
+        lo, hi = r
+        ok = all(isinstance(v, numbers.Real) and not isinstance(v, bool) and v == v for v in (lo, hi))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{name} must be None or a pair (lo, hi) of numbers, got {r!r}")
+    return float(lo), float(hi)
+
+
+def grbm_energy_packed(bits, graph, linear, quadratic, *, prefactor=1.0, linear_range=None, quadratic_range=None):
+    """Float64 energies of bit-packed +-1 rows (``dvg_grbm_energy_packed``, "DVG energy v1") under the fields every draw uses,
+    ``hs = clamp(prefactor linear, *linear_range)`` and ``Js`` likewise in float32 (a range of None does not clamp; the
+    defaults give the raw GRBM energy).  ``bits``: (rows, W) or (C, M, W) int32 on the device (``sampler.pack_spins``,
+    ``sampler.Trace.bits``; bits of spins >= n are ignored); the last dimension must have stride 1, the other strides are
+    taken from the tensor, so slices need no copy.  ``graph`` a ``GraphHandle``; ``linear`` (n) and ``quadratic`` (E) float32
+    on the same device.  Returns ``sum_i hs_i s_i + sum_e Js_e s_i s_j`` per row, float64 (rows,) or (C, M): every addend
+    exact, the order of the additions fixed -- the same bits on every call.  No host sync."""
+    n, E = int(graph.plan.n), int(graph.plan.n_edges)
+    W = (n + 31) // 32
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
+        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
+                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
+    if W > 1 and bits.stride(-1) != 1:
+        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
+    rows = int(bits.shape[-2])
+    rs = int(bits.stride(-2)) if rows > 1 else W
+    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
+    gs = int(bits.stride(0)) if groups > 1 else 0
+    if rs < W:
+        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
+    for name, t, k in (("linear", linear, n), ("quadratic", quadratic, E)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != k:
+            raise _lib.DvgError(f"{name} must be a float32 tensor of the graph's {k} values, got "
+                                f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
+    if isinstance(prefactor, bool) or not isinstance(prefactor, numbers.Real) or not float("-inf") < prefactor < float("inf"):
+        raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
+    hl, hh = _clamp_range(linear_range, "linear_range")
+    jl, jh = _clamp_range(quadratic_range, "quadratic_range")
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    for name, t in (("linear", linear), ("quadratic", quadratic)):
+        if t.device != bits.device:
+            raise _lib.DvgError(f"{name} must be on the device of bits ({bits.device}), got {t.device}")
+    bd, lin, quad = bits.detach(), linear.detach().contiguous(), quadratic.detach().contiguous()
+    out = torch.empty((groups * rows,), dtype=torch.float64, device=bd.device)
+    with torch.cuda.device(bd.device):
+        check(lib().dvg_grbm_energy_packed(graph.ptr, lin.data_ptr(), quad.data_ptr() if E else lin.data_ptr(), float(prefactor), hl,
+                                           hh, jl, jh, bd.data_ptr(), rows, rs, groups, gs, out.data_ptr(),
+                                           stream_ptr(bd.device)), "dvg_grbm_energy_packed")
+    return out.view(groups, rows) if bits.dim() == 3 else out
+
+
 Resampled = collections.namedtuple("Resampled", "parents state family weights")
 
 

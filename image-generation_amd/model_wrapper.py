@@ -960,6 +960,20 @@ class ModelWrapper:
                                  quadratic_range=self.quadratic_range, max_lag=max_lag, **kw)
 
     @torch.no_grad()
+    def prior_energy_mixing(self, max_lag=None, **kw):
+        """How the sampler's chains mix in energy on the prior: the :class:`~.sampler.EnergySeries` of one traced draw
+        (``GraphRestrictedBoltzmannMachine.energy_mixing``; ``num_reads``, ``num_sweeps``, ``burn_in``, ``thin``, ``start`` are
+        passed on, ``num_reads`` defaults to NUM_READS) over lags 0 .. ``max_lag`` records -- the energy's ``tau_int_sweeps``
+        bounds how slowly the chains mix, its ``r_hat`` says whether they found the same basin.  Rank-local and eval-mode,
+        like ``prior_mixing``; of the sampler's counters only ``trace_sweep_count`` moves."""
+        self._dvae.eval()
+        self._grbm.eval()
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        return self._grbm.energy_mixing(self.sampler, prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                        quadratic_range=self.quadratic_range, max_lag=max_lag, **kw)
+
+    @torch.no_grad()
     def prior_overlap(self, **kw):
         """Which modes the sampler's chains populate on the prior: the :class:`~.sampler.Overlap` between distinct chains at
         equal times of one traced draw (``GraphRestrictedBoltzmannMachine.replica_overlap``; ``num_reads``, ``num_sweeps``,

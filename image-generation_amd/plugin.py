@@ -14,7 +14,7 @@ from typing import Callable, Iterable, Optional
 import numpy as np
 import torch
 
-from . import functional as F
+from . import _lib, functional as F
 from .graphs import GibbsPlan, build_plan
 from .sampler import GibbsSampler, GraphHandle, SampleSet
 
@@ -251,6 +251,30 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         self._need_local_sampler(sampler, "mixing")
         trace = self.sample_trace(sampler, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range, **kw)
         return trace.autocorrelation(max_lag)
+
+    @torch.no_grad()
+    def energy_packed(self, bits: torch.Tensor, *, prefactor: float, linear_range=None, quadratic_range=None) -> torch.Tensor:
+        """The float64 energies of bit-packed rows ((rows, W) or (C, M, W) int32 on the device: ``sampler.pack_spins``,
+        ``Trace.bits``) under the prefactor-scaled, clamped ``(h, J)`` the samplers draw from (``dvg_grbm_energy_packed``:
+        the rows stay packed); ``prefactor=1`` without ranges is ``grbm(x)`` of the unpacked rows, in float64."""
+        if not torch.is_tensor(bits) or not bits.is_cuda:
+            raise _lib.DvgError(f"bits must be a tensor on the GPU (got {bits.device if torch.is_tensor(bits) else type(bits).__name__}); "
+                                "the HIP path has no CPU fallback")
+        return F.grbm_energy_packed(bits, self.graph_handle(bits.device), self._linear, self._quadratic, prefactor=prefactor,
+                                    linear_range=linear_range, quadratic_range=quadratic_range)
+
+    @torch.no_grad()
+    def energy_mixing(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, max_lag=None, **kw):
+        """How the sampler's chains mix in ENERGY on this model: one traced draw (:meth:`sample_trace`, ``**kw`` passed on)
+        and the :class:`~.sampler.EnergySeries` of its records' energies under the same scaled, clamped ``(h, J)``
+        (:meth:`Trace.energy_series`) over lags 0 .. ``max_lag`` records: ``tau_int``, ``ess``, ``r_hat``,
+        ``heat_capacity``.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "energy_mixing")
+        if max_lag is not None and (isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or max_lag < 0):
+            raise ValueError(f"max_lag must be None or an integer >= 0, got {max_lag!r}")
+        trace = self.sample_trace(sampler, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range, **kw)
+        return trace.energy_series(self.graph_handle(trace.bits.device), self._linear, self._quadratic, prefactor, linear_range,
+                                   quadratic_range, max_lag=max_lag)
 
     @torch.no_grad()
     def replica_overlap(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):

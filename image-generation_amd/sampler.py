@@ -418,6 +418,105 @@ class Autocorrelation:
                 f"max_lag={self.max_lag}, thin={self.thin})")
 
 
+class EnergySeries:
+    """Mixing statistics of the energies of C chains x M records (``dvg_grbm_energy_packed``, "DVG energy v1"; :meth:`Trace.energy`):
+    ``energies`` (C, M) float64, ``thin`` the sweeps between two records, ``max_lag`` = L.  Every property is float64 torch on
+    the energies' device (CPU tensors too), no host sync; d(c, m) = E(c, m) - mean:
+
+    ``mean``: the pooled mean;  ``var``: the pooled variance, dividing by C M;  ``chain_mean`` (C,);
+    ``rho`` (L + 1,): rho[t] = [sum_c sum_{m < M - t} d(c, m) d(c, m + t) / (C (M - t))] / var -- around the POOLED mean, so chains
+    stuck in different basins show as slow; NaN when var = 0;
+    ``tau_int``, in records: 1 + 2 sum_{t = 1}^{T} rho[t], T the number of leading lags 1, 2, .. with rho > 0 (the initial
+    positive sequence), at most L; ``truncated``: rho > 0 at every lag 1 .. L (L >= 1) -- the window hit max_lag and tau_int
+    is a lower bound; ``tau_int_sweeps`` = tau_int * thin; ``ess`` = C M / tau_int;
+    ``r_hat``: Gelman-Rubin, sqrt(((M - 1) / M W + B) / W) with W the mean within-chain variance (ddof = 1) and B the variance
+    of the chain means (ddof = 1) -- :attr:`Autocorrelation.r_hat`'s formula; needs C >= 2 and M >= 2;
+    ``heat_capacity(beta)`` = beta^2 var;  ``std_err``: the between-chain standard deviation of ``chain_mean`` over sqrt(C), the
+    standard error of ``mean`` whatever the autocorrelation within a chain; NaN at C = 1."""
+
+    def __init__(self, energies, thin, max_lag):
+        self.energies, self.thin, self.max_lag = energies, int(thin), int(max_lag)
+        self.chains, self.records = int(energies.shape[0]), int(energies.shape[1])
+
+    @classmethod
+    def from_energies(cls, energies: torch.Tensor, thin: int = 1, max_lag: Optional[int] = None) -> "EnergySeries":
+        if not torch.is_tensor(energies) or energies.dtype != torch.float64 or energies.dim() != 2 or min(energies.shape) < 1:
+            raise ValueError(f"energies must be a (chains >= 1, records >= 1) float64 tensor, got "
+                             f"{(tuple(energies.shape), energies.dtype) if torch.is_tensor(energies) else type(energies).__name__}")
+        if isinstance(thin, bool) or not isinstance(thin, (int, np.integer)) or thin < 1:
+            raise ValueError(f"thin must be an integer >= 1, got {thin!r}")
+        M = int(energies.shape[1])
+        if max_lag is None:
+            max_lag = min(M - 1, 512)
+        if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag < M:
+            raise ValueError(f"max_lag must be an integer in 0 .. {M - 1} (records - 1), got {max_lag!r}")
+        return cls(energies, thin, max_lag)
+
+    @property
+    def mean(self):
+        return self.energies.mean()
+
+    def _d(self):
+        return self.energies - self.mean
+
+    @property
+    def var(self):
+        return (self._d() ** 2).mean()
+
+    @property
+    def chain_mean(self):
+        return self.energies.mean(1)
+
+    @property
+    def rho(self):
+        d, C, M = self._d(), self.chains, self.records
+        cov = torch.stack([(d[:, :M - t] * d[:, t:]).sum() / (C * (M - t)) for t in range(self.max_lag + 1)])
+        return cov / self.var  # (var = 0: 0 / 0 = NaN at every lag)
+
+    @property
+    def tau_int(self):
+        rho = self.rho
+        window = torch.cumprod((rho[1:] > 0).to(torch.float64), dim=0)  # 1 over the initial positive sequence, 0 behind it
+        tau = 1.0 + 2.0 * torch.where(window > 0, rho[1:], torch.zeros_like(rho[1:])).sum()
+        return torch.where(torch.isnan(rho[0]), rho[0], tau)
+
+    @property
+    def truncated(self):
+        rho = self.rho[1:]
+        if rho.shape[0] == 0:
+            return torch.zeros((), dtype=torch.bool, device=rho.device)
+        return (rho > 0).all()
+
+    @property
+    def tau_int_sweeps(self):
+        return self.tau_int * self.thin
+
+    @property
+    def ess(self):
+        return (self.chains * self.records) / self.tau_int
+
+    @property
+    def r_hat(self):
+        C, M = self.chains, self.records
+        if C < 2 or M < 2:
+            raise ValueError(f"r_hat needs at least 2 chains and at least 2 records ({C} chains, {M} records)")
+        Wv = self.energies.var(1, unbiased=True).mean()
+        Bm = self.chain_mean.var(0, unbiased=True)
+        return torch.sqrt(((M - 1.0) / M * Wv + Bm) / Wv)
+
+    def heat_capacity(self, beta: float):
+        return float(beta) ** 2 * self.var
+
+    @property
+    def std_err(self):
+        if self.chains < 2:
+            return torch.full_like(self.mean, float("nan"))
+        return self.chain_mean.std(0, unbiased=True) / float(np.sqrt(self.chains))
+
+    def __repr__(self):
+        return f"EnergySeries({self.chains} chains x {self.records} records, max_lag={self.max_lag}, thin={self.thin})"
+
+
 class Overlap:
     """The distribution of the spin overlap q = (1 / n) sum_i s_i^a s_i^b = 1 - 2 d / n over pairs of +-1 rows, from the exact
     histogram of their Hamming distances d (``dvg_packed_overlap``, "DVG overlap v1"): ``hist`` (n + 1,) int64, ``hist[d]``
@@ -535,6 +634,25 @@ class Trace:
             raise ValueError(f"max_lag must be an integer in 0 .. {int(M) - 1} (records - 1), got {max_lag!r}")
         lag_sum, spin_sum, chain_sum = F.trace_autocorr(self.bits, self.n, int(max_lag), chain_sums=bool(chain_sums))
         return Autocorrelation.from_sums(lag_sum, spin_sum, chain_sum, int(C), int(M), self.thin)
+
+    def energy(self, graph, linear, quadratic, prefactor: float = 1.0, linear_range=None, quadratic_range=None) -> torch.Tensor:
+        """The (C, M) float64 energies of the records under the prefactor-scaled, clamped ``(linear, quadratic)`` -- hand in
+        what the draw was given and these are the energies its chains moved in (``dvg_grbm_energy_packed``: the records stay
+        packed).  ``graph``: the :class:`GraphHandle` whose edge list ``quadratic`` follows."""
+        from . import functional as F  # (functional imports this module)
+
+        return F.grbm_energy_packed(self.bits, graph, linear, quadratic, prefactor=prefactor, linear_range=linear_range,
+                                    quadratic_range=quadratic_range)
+
+    def energy_series(self, graph, linear, quadratic, prefactor: float = 1.0, linear_range=None, quadratic_range=None,
+                      max_lag: Optional[int] = None) -> EnergySeries:
+        """:meth:`energy` as an :class:`EnergySeries` carrying the trace's ``thin``, over lags 0 .. ``max_lag`` records
+        (default min(M - 1, 512))."""
+        M = int(self.bits.shape[1]) if torch.is_tensor(self.bits) and self.bits.dim() == 3 else 0
+        if max_lag is not None and (isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 0 <= max_lag < M):
+            raise ValueError(f"max_lag must be an integer in 0 .. {M - 1} (records - 1), got {max_lag!r}")
+        e = self.energy(graph, linear, quadratic, prefactor, linear_range, quadratic_range)
+        return EnergySeries.from_energies(e, self.thin, max_lag)
 
     def overlap(self, other=None, nearest: bool = False):
         """The equal-time replica overlap (``dvg_packed_overlap``: the records stay packed) as an :class:`Overlap`: over every

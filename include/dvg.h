@@ -274,6 +274,28 @@ int dvg_grbm_suffstats(const dvg_graph_t *g, const float *x, int64_t rows, const
  * DVG_E_INVALID: a null pointer, rows < 1.  DVG_E_UNSUPPORTED: n > 8192 (a tile's bit columns are kept in 64 KiB of LDS). */
 int dvg_grbm_moments_packed(const dvg_graph_t *g, const uint32_t *bits, int64_t rows,
                             int64_t *spin_sum, int64_t *pair_sum, int accumulate, dvg_stream_t stream);
+/* Energies of bit-packed spin rows in float64 ("DVG energy v1"), under the fields every draw uses.  Rows are packed as in
+ * "DVG trace v1": W = (n + 31) / 32 words, bit b of word w = spin 32 w + b is +1; bits of spins >= n are ignored and may hold
+ * anything.  Strides count words, as in dvg_packed_overlap: row r of group g starts at bits + g group_stride + r row_stride.  A
+ * flat set is groups = 1, row_stride = W; a trace (C, M, W) is groups = C, group_stride = M W, rows = M, row_stride = W; slices
+ * of either need no copy.
+ *   Fields.  hs_i = clamp(rn(prefactor linear_i), h_lo, h_hi),  Js_e = clamp(rn(prefactor quadratic_e), j_lo, j_hi)  in float32,
+ *     one rounding each: what dvg_gibbs_sample and its kin draw from (oracle/gibbs.py::scaled_fields).  prefactor = 1 with
+ *     infinite clamps gives the raw GRBM energy of dvg_grbm_energy.
+ *   Value.  energy_out[g rows + r] = sum_i (double)hs_i s_i + sum_e (double)Js_e s_i s_j  over the graph's edge list (i, j) =
+ *     (edge_i[e], edge_j[e]), s = +-1 the row's spins.  Every addend is exact in float64; only the order of the float64
+ *     additions is the implementation's, and it is fixed by (n, n_edges) alone: no floating-point atomics, two calls on the
+ *     same input return the same bits.  energy_out: DEVICE pointer, float64, groups rows elements; nothing is written beyond.
+ * linear [n], quadratic [n_edges] and bits are DEVICE pointers.  The call enqueues on `stream`, allocates nothing and needs no
+ * workspace.  The rows are never unpacked: n / 8 bytes of traffic per row.
+ * DVG_E_INVALID, before any HIP call: g, linear, quadratic, bits or energy_out null; rows < 1; groups < 1; row_stride < W;
+ * group_stride < 0; a non-finite prefactor.  DVG_E_UNSUPPORTED: groups rows >= 2^62; n > 8192 (a tile's bit columns are kept
+ * in 64 KiB of LDS, beside 8 KiB of partial sums). */
+int dvg_grbm_energy_packed(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                           float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                           const uint32_t *bits, int64_t rows, int64_t row_stride,
+                           int64_t groups, int64_t group_stride,
+                           double *energy_out, dvg_stream_t stream);
 /* Autocorrelation sums of a bit-packed trace, exactly ("DVG acf v1"): bits (n_chains C, n_records M, W = (n + 31) / 32)
  * uint32 in the layout of "DVG trace v1" (bit b of word w = spin 32 w + b is +1; bits of spins >= n are ignored and may hold
  * anything).  With s_i(c, m) = +-1 the spin of chain c at record m, and L = max_lag:

@@ -1,0 +1,407 @@
+"""GPU checks of ``dvg_grbm_energy_packed`` ("DVG energy v1") -- the float64 energies of bit-packed rows under the scaled,
+clamped float32 fields every draw uses -- against the numpy definition (``tests/energy_oracle.py``).  Every addend is exact
+in float64, so with generic float32 ``(h, J)`` the device and numpy differ as two orderings of the same N = n + n_edges
+addends do, |E_dev - E_ref| <= 4 N 2^-53 A with A = sum |hs| + sum |Js|, and with fields on a dyadic grid (every partial sum
+exact) not at all: equality bit for bit.  Rows: traced draws' records (``dvg_gibbs_sample_traced``) and rows of random words
+whose bits of spins >= n are set at random and must be ignored.  Row counts 1, 35, 63, 64, 65, 287 = 41 x 7 (a tile is 64 rows:
+below one, one short, exact, one over, several with a tail) on ``pegasus64`` (two whole words a row), ``random77`` (a partial
+last word, spin 3 isolated) and ``zephyr1024`` (32 words).  Layouts (traces, slices, padded rows), extremes, determinism,
+rejected calls, agreement with ``dvg_grbm_energy`` and ``dvg_gibbs_sample_ais``, and the Python surface built on it."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ais_oracle  # noqa: E402
+import energy_oracle as eo  # noqa: E402
+from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
+from oracle import gibbs  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+SEED = 775321899904
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GUARD = -1234.56789
+ROWS = [1, 35, 63, 64, 65, 287]
+GRAPHS = ["pegasus64", "random77", "zephyr1024"]
+H_RANGE, J_RANGE = (-4.0, 4.0), (-1.0, 1.0)
+DYADIC = dict(prefactor=0.5, h_range=(-1.0, 1.0), j_range=(-0.5, 0.5))
+
+
+@functools.lru_cache(maxsize=None)
+def _solver_plan(fam, n):
+    g = graphs.pegasus_graph(16) if fam == "pegasus" else graphs.zephyr_graph(12)
+    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, g))
+    nodes, ei, ej = graphs.edges_of(mg)
+    return graphs.build_plan(n, ei, ej), nodes
+
+
+@functools.lru_cache(maxsize=None)
+def _random_plan(n=77, p_edge=0.35):
+    rng = np.random.default_rng(n)
+    iu, ju = np.triu_indices(n, 1)
+    keep = rng.uniform(size=iu.size) < p_edge
+    keep &= (iu != 3) & (ju != 3)
+    plan = graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
+    assert np.diff(plan.adj_ptr)[3] == 0
+    return plan
+
+
+class _Case:
+    """The graph, its handle, 287 rows of each kind on the device -- a traced draw of 41 chains x 7 records, and random words
+    -- and two sets of fields: ``generic`` float32 values whose clamps are active at prefactor 0.3 and idle at 0.05, and
+    ``dyadic`` integer multiples of 2^-10 in [-2, 2].  Built once per graph; references are computed once per field set over
+    all 287 rows (``want``), the tests take the first ``rows`` of them."""
+
+    def __init__(self, name):
+        self.plan = plan = {"pegasus64": lambda: _solver_plan("pegasus", 64)[0], "random77": _random_plan,
+                            "zephyr1024": lambda: _solver_plan("zephyr", 1024)[0]}[name]()
+        p = dict(h_scale=0.5, j_scale=2.0, prefactor=0.3, beta=1.5) if name == "random77" else dict(h_scale=0.05, j_scale=5.0,
+                                                                                                   prefactor=0.05, beta=20.0)
+        rng = np.random.default_rng(plan.n)
+        h = (p["h_scale"] * rng.uniform(-1, 1, plan.n)).astype(np.float32)
+        J = (p["j_scale"] * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)
+        self.gh = gh = smp.GraphHandle(plan, "cuda")
+        C, S, self.W = 41, 7, (plan.n + 31) // 32
+        state = torch.empty((C, plan.n), dtype=torch.int8, device="cuda")
+        traced = torch.empty((C * S, self.W), dtype=torch.int32, device="cuda")
+        lin, quad = torch.from_numpy(h).cuda(), torch.from_numpy(J).cuda()
+        _lib.check(_lib.lib().dvg_gibbs_sample_traced(gh.ptr, lin.data_ptr(), quad.data_ptr(), p["prefactor"], -4.0, 4.0, -1.0, 1.0,
+                                                      p["beta"], state.data_ptr(), C, 1000, SEED, 6, S, 1, None, traced.data_ptr(), 0, 1,
+                                                      None, _lib.stream_ptr()), "dvg_gibbs_sample_traced")
+        torch.cuda.synchronize()
+        noise = rng.integers(0, 2 ** 32, size=(C * S, self.W), dtype=np.uint64).astype(np.uint32)
+        if plan.n % 32:
+            assert (noise[:, -1] >> np.uint32(plan.n % 32)).any()  # bits of spins >= n are set
+        self.rows = {"trace": traced, "noise": torch.from_numpy(noise.view(np.int32)).cuda()}
+        self.host = {k: v.cpu().numpy().view(np.uint32) for k, v in self.rows.items()}
+        self.pad_noise = rng.integers(0, 2 ** 32, size=(C * S, 3), dtype=np.uint64).astype(np.uint32)
+        self.generic = ((20.0 * rng.uniform(-1, 1, plan.n)).astype(np.float32), (5.0 * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32))
+        self.dyadic = ((rng.integers(-2048, 2049, plan.n) / 1024.0).astype(np.float32),
+                       (rng.integers(-2048, 2049, plan.n_edges) / 1024.0).astype(np.float32))
+        self._dev = {}
+
+    def fields(self, which):
+        """The raw ``(h, J)`` of a field set on the device."""
+        if which not in self._dev:
+            h, J = getattr(self, which)
+            self._dev[which] = torch.from_numpy(h).cuda(), torch.from_numpy(J).cuda()
+        return self._dev[which]
+
+    @functools.lru_cache(maxsize=None)
+    def scaled(self, which, prefactor, h_range, j_range):
+        return gibbs.scaled_fields(*getattr(self, which), prefactor, h_range, j_range)
+
+    @functools.lru_cache(maxsize=None)
+    def want(self, kind, which, prefactor, h_range, j_range):
+        """``(E (287,), A)`` of all rows of a kind by the helper."""
+        hs, Js = self.scaled(which, prefactor, h_range, j_range)
+        return eo.energies(self.host[kind], self.plan.n, hs, Js, self.plan.edge_i, self.plan.edge_j)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    return _Case(name)
+
+
+def _raw(case, which, prefactor, h_range, j_range, bits, rows, row_stride, groups, group_stride, out, *, null=None):
+    """The C entry on device pointers; ``null``: the name of one pointer to pass as NULL."""
+    lin, quad = case.fields(which)
+    ptr = dict(g=case.gh.ptr, linear=lin.data_ptr(), quadratic=quad.data_ptr(), bits=bits.data_ptr(), energy_out=out.data_ptr())
+    if null is not None:
+        ptr[null] = None
+    rc = _lib.lib().dvg_grbm_energy_packed(ptr["g"], ptr["linear"], ptr["quadratic"], prefactor, h_range[0], h_range[1], j_range[0],
+                                           j_range[1], ptr["bits"], rows, row_stride, groups, group_stride, ptr["energy_out"],
+                                           _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return rc
+
+
+def _guarded(count):
+    return torch.full((count + 1,), GUARD, dtype=torch.float64, device="cuda")
+
+
+def _flat(case, kind, rows, which, prefactor, h_range, j_range):
+    """The energies of the first ``rows`` rows of a kind as a flat set, the guard checked."""
+    bits = case.rows[kind][:rows].contiguous()
+    out = _guarded(rows)
+    assert _raw(case, which, prefactor, h_range, j_range, bits, rows, case.W, 1, 0, out) == 0, _lib.lib().dvg_last_error()
+    got = out.cpu().numpy()
+    assert got[rows] == GUARD, "written past the output"
+    return got[:rows]
+
+
+# ------------------------------------------------------------------------------------------------ 1. the bound, 2. exactness
+@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("name", GRAPHS)
+def test_energies_lie_within_the_bound_of_two_orderings(name, rows):
+    case = _case(name)
+    N = case.plan.n + case.plan.n_edges
+    for prefactor in (0.05, 0.3):
+        hs, Js = case.scaled("generic", prefactor, H_RANGE, J_RANGE)
+        active = bool((np.abs(hs) == 4.0).any() and (np.abs(Js) == 1.0).any())
+        assert active == (prefactor == 0.3)  # the clamps bite at 0.3 and are idle at 0.05
+        for kind in ("trace", "noise"):
+            want, A = case.want(kind, "generic", prefactor, H_RANGE, J_RANGE)
+            got = _flat(case, kind, rows, "generic", prefactor, H_RANGE, J_RANGE)
+            err, bound = np.abs(got - want[:rows]), eo.bound(case.plan.n, case.plan.n_edges, A)
+            print(f"{name} {kind} x {rows}, prefactor {prefactor}: |E| up to {np.abs(want[:rows]).max():.4g}, worst error {err.max():.3e}, "
+                  f"bound 4 x {N} x 2^-53 x {A:.4g} = {bound:.3e}")
+            assert np.isfinite(got).all() and (err <= bound).all()
+            assert np.abs(want[:rows]).max() > 1e3 * bound  # (teeth: the energies are not lost in the bound)
+
+
+@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("name", GRAPHS)
+def test_energies_on_dyadic_fields_are_exact(name, rows):
+    """h, J integer multiples of 2^-10 in [-2, 2], prefactor 0.5, clamps +-1 and +-0.5 (the second active): every addend a
+    multiple of 2^-11 of magnitude <= 1, every partial sum exact whatever the order -- the output equals the helper bit for bit."""
+    case = _case(name)
+    hs, Js = case.scaled("dyadic", **DYADIC)
+    assert (np.abs(Js) == 0.5).sum() > (np.abs(case.dyadic[1]) == 1.0).sum() and np.abs(hs).max() <= 1.0  # the J clamp bites
+    assert np.array_equal(hs * 2048, np.round(hs * 2048)) and np.array_equal(Js * 2048, np.round(Js * 2048))
+    for kind in ("trace", "noise"):
+        want, _A = case.want(kind, "dyadic", **DYADIC)
+        got = _flat(case, kind, rows, "dyadic", **DYADIC)
+        assert np.array_equal(got, want[:rows]), (kind, np.flatnonzero(got != want[:rows])[:8])
+        assert len(np.unique(want[:rows])) > min(rows, 2) // 2  # (teeth: the rows' energies differ)
+
+
+# ------------------------------------------------------------------------------------------------ 3. layouts
+@pytest.mark.parametrize("C,M", [(1, 5), (2, 1), (41, 7), (65, 3), (130, 2)])
+@pytest.mark.parametrize("name", GRAPHS)
+def test_trace_layout_is_exact(name, C, M):
+    """groups = C, group_stride = M W, rows = M, row_stride = W: element c M + m is record m of chain c."""
+    case = _case(name)
+    for kind in ("trace", "noise"):
+        bits = case.rows[kind][:C * M].contiguous()
+        out = _guarded(C * M)
+        assert _raw(case, "dyadic", *DYADIC.values(), bits, M, case.W, C, M * case.W, out) == 0, _lib.lib().dvg_last_error()
+        got = out.cpu().numpy()
+        assert got[C * M] == GUARD and np.array_equal(got[:C * M], case.want(kind, "dyadic", **DYADIC)[0][:C * M])
+        via = F.grbm_energy_packed(bits.view(C, M, case.W), case.gh, *case.fields("dyadic"), prefactor=0.5, linear_range=(-1, 1),
+                                   quadratic_range=(-0.5, 0.5))
+        assert via.shape == (C, M) and via.dtype == torch.float64 and via.is_cuda and np.array_equal(via.cpu().numpy().ravel(), got[:C * M])
+
+
+@pytest.mark.parametrize("name", GRAPHS)
+def test_views_and_padded_rows_need_no_copy(name):
+    case = _case(name)
+    W = case.W
+    call = lambda b: F.grbm_energy_packed(b, case.gh, *case.fields("dyadic"), prefactor=0.5, linear_range=(-1, 1),  # noqa: E731
+                                          quadratic_range=(-0.5, 0.5)).cpu().numpy()
+    for kind in ("trace", "noise"):
+        want = case.want(kind, "dyadic", **DYADIC)[0]
+        flat, trace = case.rows[kind], case.rows[kind].view(41, 7, W)
+        w3 = want.reshape(41, 7)
+        for view, ref in ((trace[:, 1:], w3[:, 1:]), (trace[::2], w3[::2]), (trace[:, ::3], w3[:, ::3]), (flat[5::7], want[5::7]),
+                          (trace[3], w3[3]), (trace[:, 2], w3[:, 2]), (trace[:1].expand(3, 7, W), np.repeat(w3[:1], 3, axis=0))):
+            got = call(view)
+            assert got.shape == ref.shape and np.array_equal(got, ref), (kind, tuple(view.shape), tuple(view.stride()))
+        # rows padded to W + 3 words, noise in the padding
+        padded = torch.cat([flat, torch.from_numpy(case.pad_noise.view(np.int32)).cuda()], dim=1)
+        assert padded.shape == (287, W + 3)
+        assert np.array_equal(call(padded[:, :W]), want) and np.array_equal(call(padded.view(41, 7, W + 3)[:, :, :W]), w3)
+        out = _guarded(287)
+        assert _raw(case, "dyadic", *DYADIC.values(), padded, 287, W + 3, 1, 0, out) == 0
+        assert np.array_equal(out.cpu().numpy()[:287], want) and float(out[287]) == GUARD
+
+
+# ------------------------------------------------------------------------------------------------ 4. extremes
+@pytest.mark.parametrize("name", GRAPHS)
+def test_all_up_all_down_and_one_flipped_spin(name):
+    case = _case(name)
+    plan, W = case.plan, case.W
+    ends = torch.tensor([[-1] * W, [0] * W], dtype=torch.int32, device="cuda")  # all +1 (noise above n included), all -1
+    hs, Js = (v.astype(np.float64) for v in case.scaled("dyadic", **DYADIC))
+    out = _guarded(2)
+    assert _raw(case, "dyadic", *DYADIC.values(), ends, 2, W, 1, 0, out) == 0
+    assert out.cpu().numpy().tolist() == [hs.sum() + Js.sum(), -hs.sum() + Js.sum(), GUARD]
+    hs, Js = (v.astype(np.float64) for v in case.scaled("generic", 0.3, H_RANGE, J_RANGE))
+    assert _raw(case, "generic", 0.3, H_RANGE, J_RANGE, ends, 2, W, 1, 0, out) == 0
+    bound = eo.bound(plan.n, plan.n_edges, np.abs(hs).sum() + np.abs(Js).sum())
+    assert np.abs(out.cpu().numpy()[:2] - np.array([hs.sum() + Js.sum(), -hs.sum() + Js.sum()])).max() <= bound
+    if name == "random77":  # spin 3 has no edge: flipping it moves the energy by 2 hs_3 exactly
+        hs3 = float(case.scaled("dyadic", **DYADIC)[0][3])
+        assert hs3 != 0.0
+        rows = case.rows["noise"].clone()
+        before = F.grbm_energy_packed(rows, case.gh, *case.fields("dyadic"), prefactor=0.5, linear_range=(-1, 1), quadratic_range=(-0.5, 0.5))
+        was_up = ((rows[:, 0] >> 3) & 1).to(torch.float64)
+        rows[:, 0] ^= 8
+        after = F.grbm_energy_packed(rows, case.gh, *case.fields("dyadic"), prefactor=0.5, linear_range=(-1, 1), quadratic_range=(-0.5, 0.5))
+        assert torch.equal(after - before, -2.0 * hs3 * (2.0 * was_up - 1.0)) and 0 < int(was_up.sum()) < 287
+
+
+# ------------------------------------------------------------------------------------------------ 5. determinism, 6. rejected calls
+@pytest.mark.parametrize("name", GRAPHS)
+def test_two_calls_return_the_same_bits(name):
+    case = _case(name)
+    for kind in ("trace", "noise"):
+        a = _flat(case, kind, 287, "generic", 0.3, H_RANGE, J_RANGE)
+        b = _flat(case, kind, 287, "generic", 0.3, H_RANGE, J_RANGE)
+        assert np.array_equal(a.view(np.int64), b.view(np.int64))
+
+
+def test_rejected_calls_leave_the_output_intact():
+    case = _case("pegasus64")
+    bits = case.rows["trace"]
+    out = _guarded(287)
+    good = dict(rows=287, row_stride=case.W, groups=1, group_stride=0)
+    for null in ("g", "linear", "quadratic", "bits", "energy_out"):
+        assert _raw(case, "generic", 0.3, H_RANGE, J_RANGE, bits, *good.values(), out, null=null) == -1, null
+    for bad in (dict(rows=0), dict(rows=-3), dict(groups=0), dict(groups=-1), dict(row_stride=case.W - 1), dict(row_stride=0),
+                dict(groups=2, group_stride=-1)):
+        assert _raw(case, "generic", 0.3, H_RANGE, J_RANGE, bits, *dict(good, **bad).values(), out) == -1, bad
+    for bad in (float("nan"), float("inf")):
+        assert _raw(case, "generic", bad, H_RANGE, J_RANGE, bits, *good.values(), out) == -1, bad
+    assert _raw(case, "generic", 0.3, H_RANGE, J_RANGE, bits, 2 ** 31, case.W, 2 ** 31, 0, out) == -4
+    assert (out == GUARD).all()
+
+
+# ------------------------------------------------------------------------------------------------ 7. the existing entries
+@pytest.mark.parametrize("name", GRAPHS)
+def test_agrees_with_the_float32_energy_of_unpacked_rows(name):
+    """``dvg_grbm_energy`` on ``unpack_spins`` of the same rows, handed the already scaled ``(hs, Js)`` as its raw parameters:
+    the same exact addends summed in float64, then rounded to float32 -- 2^-24 relative, doubled for the margin of a tie."""
+    case = _case(name)
+    plan = case.plan
+    hs, Js = case.scaled("generic", 0.3, H_RANGE, J_RANGE)
+    for kind in ("trace", "noise"):
+        got = _flat(case, kind, 287, "generic", 0.3, H_RANGE, J_RANGE)
+        x = smp.unpack_spins(case.rows[kind], plan.n).contiguous()
+        e32 = F.grbm_energy(x, torch.from_numpy(hs).cuda(), torch.from_numpy(Js).cuda(), case.gh)
+        assert e32.dtype == torch.float32 and e32.shape == (287,)
+        A = float(np.abs(hs.astype(np.float64)).sum() + np.abs(Js.astype(np.float64)).sum())
+        err = np.abs(e32.cpu().numpy().astype(np.float64) - got)
+        tol = 2.0 ** -23 * np.abs(got) + eo.bound(plan.n, plan.n_edges, A)
+        print(f"{name} {kind}: float32 energies off by up to {err.max():.3e} (tolerance {tol[err.argmax()]:.3e})")
+        assert (err <= tol).all()
+
+
+@pytest.mark.parametrize("name,C", [("pegasus64", 5), ("random77", 19)])
+def test_agrees_with_the_energy_an_ais_draw_returns(name, C):
+    """``dvg_gibbs_sample_ais`` returns the running energy of its definition -- the start energy from float32 fields, then
+    (s_new - s_old) f per update -- which ``tests/test_gibbs_ais_host.py`` holds to the float64 energy of the same state within
+    B = 1/2 sum_i g_i + 2 (sum of g_i over the chain's flips), g_i = gamma_d (|hs_i| + sum_j |Js_ij|), gamma_d = d u / (1 - d u),
+    u = 2^-24, plus the float64 slack 4 N 2^-53 A of its own additions.  The energy of ``pack_spins(samples)`` is that float64
+    energy to within this entry's own 4 (n + n_edges) 2^-53 A."""
+    case = _case(name)
+    plan = case.plan
+    h, J = case.generic
+    prefactor, S, sweep0, id0 = 0.05, 7, 6, 1000
+    hs, Js = case.scaled("generic", prefactor, H_RANGE, J_RANGE)
+    betas = np.linspace(0.0, 2.0, S + 1)[1:].astype(np.float32)
+    ids = np.arange(C, dtype=np.uint32) + id0
+    r = ais_oracle.ais(plan, hs, Js, betas, ids, SEED, sweep0, trace=True)
+    lin, quad = case.fields("generic")
+    state = torch.empty((C, plan.n), dtype=torch.int8, device="cuda")
+    samples = torch.empty((C, plan.n), dtype=torch.float32, device="cuda")
+    log_w, energy = torch.empty(C, dtype=torch.float64, device="cuda"), torch.empty(C, dtype=torch.float64, device="cuda")
+    table = torch.from_numpy(betas).cuda()
+    _lib.check(_lib.lib().dvg_gibbs_sample_ais(case.gh.ptr, lin.data_ptr(), quad.data_ptr(), prefactor, -4.0, 4.0, -1.0, 1.0,
+                                               table.data_ptr(), 0, 0.0, state.data_ptr(), C, id0, SEED, sweep0, S, 1, samples.data_ptr(),
+                                               log_w.data_ptr(), energy.data_ptr(), None, _lib.stream_ptr()), "dvg_gibbs_sample_ais")
+    torch.cuda.synchronize()
+    assert np.array_equal(samples.cpu().numpy(), r.spins.astype(np.float32))  # (the flips of the bound are the helper's)
+    got = F.grbm_energy_packed(smp.pack_spins(samples), case.gh, lin, quad, prefactor=prefactor, linear_range=H_RANGE,
+                               quadratic_range=J_RANGE).cpu().numpy()
+    adj_ptr = np.asarray(plan.adj_ptr)
+    deg = np.diff(adj_ptr).astype(np.float64)
+    u = 2.0 ** -24
+    gamma = deg * u / (1.0 - deg * u)
+    absrow = np.zeros(plan.n)
+    np.add.at(absrow, np.repeat(np.arange(plan.n), np.diff(adj_ptr)), np.abs(Js.astype(np.float64))[np.asarray(plan.adj_eid)])
+    g = gamma * (np.abs(hs.astype(np.float64)) + absrow)
+    flipped = sum(((r.states[k + 1] != r.states[k]) * g[None, :]).sum(axis=1) for k in range(S))
+    A = float(np.abs(hs.astype(np.float64)).sum() + np.abs(Js.astype(np.float64)).sum())
+    tol = 0.5 * g.sum() + 2.0 * flipped + 4.0 * r.N * 2.0 ** -53 * r.A + eo.bound(plan.n, plan.n_edges, A)
+    err = np.abs(energy.cpu().numpy() - got)
+    print(f"{name}: the AIS draw's energies off by up to {err.max():.3e} (tolerance {tol[err.argmax()]:.3e}), |E| up to {np.abs(got).max():.4g}")
+    assert (err <= tol).all() and np.abs(got).max() > 1e2 * tol.max()
+
+
+# ------------------------------------------------------------------------------------------------ 8. the Python layers
+def _equals_helper(e, bits, plan, h, J, prefactor, h_range=H_RANGE, j_range=J_RANGE):
+    hs, Js = gibbs.scaled_fields(h, J, prefactor, h_range, j_range)
+    want, A = eo.energies(bits.cpu().numpy().view(np.uint32), plan.n, hs, Js, plan.edge_i, plan.edge_j)
+    got = e.cpu().numpy()
+    assert e.dtype == torch.float64 and e.is_cuda and got.shape == want.shape
+    assert (np.abs(got - want) <= eo.bound(plan.n, plan.n_edges, A)).all()
+
+
+def test_grbm_energy_mixing_is_the_series_of_the_same_trace():
+    from image_generation_amd.plugin import GraphRestrictedBoltzmannMachine
+
+    plan, nodes = _solver_plan("zephyr", 128)
+    rng = np.random.default_rng(2)
+    h = (0.05 * rng.uniform(-1, 1, plan.n)).astype(np.float32)
+    J = (5.0 * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)
+    mk = lambda: smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=4, seed=SEED, persistent=True, chain_offset=5,  # noqa: E731
+                                  h_range=(-4, 4), j_range=(-1, 1))
+    grbm = GraphRestrictedBoltzmannMachine(nodes, list(zip(np.asarray(nodes)[plan.edge_i].tolist(),
+                                                           np.asarray(nodes)[plan.edge_j].tolist()))).cuda()
+    with torch.no_grad():
+        grbm._linear.copy_(torch.from_numpy(h).cuda())
+        grbm._quadratic.copy_(torch.from_numpy(J).cuda())
+    ranges = dict(prefactor=0.05, linear_range=H_RANGE, quadratic_range=J_RANGE)
+    kw = dict(ranges, num_reads=9, num_sweeps=12, burn_in=2, thin=3)
+    s1, s2 = mk(), mk()
+    trace = grbm.sample_trace(s1, **kw)
+    gh = grbm.graph_handle("cuda")
+    lin, quad = grbm._linear.detach(), grbm._quadratic.detach()
+    e = F.grbm_energy_packed(trace.bits, gh, lin, quad, **ranges)
+    assert e.shape == (9, 3)
+    _equals_helper(e, trace.bits, plan, h, J, 0.05)
+    assert torch.equal(trace.energy(gh, lin, quad, **ranges), e) and torch.equal(grbm.energy_packed(trace.bits, **ranges), e)
+    assert torch.equal(grbm.energy_packed(trace.bits.view(27, -1), **ranges), e.view(27))
+    # the defaults are the raw GRBM energy: grbm(x) of the unpacked rows, in float64
+    raw = trace.energy(gh, lin, quad)
+    _equals_helper(raw, trace.bits, plan, h, J, 1.0, None, None)
+    e32 = grbm(trace.unpack().reshape(27, -1)).detach().double().view(9, 3)
+    A = float(np.abs(h.astype(np.float64)).sum() + np.abs(J.astype(np.float64)).sum())
+    assert (torch.abs(e32 - raw) <= 2.0 ** -23 * raw.abs() + eo.bound(plan.n, plan.n_edges, A)).all()
+    series = trace.energy_series(gh, lin, quad, max_lag=2, **ranges)
+    assert isinstance(series, smp.EnergySeries) and torch.equal(series.energies, e) and (series.thin, series.max_lag, series.chains) == (3, 2, 9)
+    want = eo.estimates(e.cpu().numpy(), thin=3, max_lag=2)
+    for name in ("mean", "var", "rho", "tau_int", "tau_int_sweeps", "ess", "r_hat", "std_err", "chain_mean"):
+        got = getattr(series, name)
+        assert got.is_cuda and got.dtype == torch.float64 and np.allclose(got.cpu().numpy(), want[name], rtol=1e-12, atol=0.0, equal_nan=True), name
+    assert bool(series.truncated) == want["truncated"]
+    mixing = grbm.energy_mixing(s2, max_lag=2, **kw)  # the same draw on a second sampler
+    assert torch.equal(mixing.energies, e) and (mixing.thin, mixing.max_lag) == (3, 2) and s2.trace_sweep_count == 12
+    assert (s2.sweep_count, s2.calls) == (0, 0) and s2._state is None
+    assert grbm.energy_mixing(s2, **kw).max_lag == 2  # (the default: min(M - 1, 512))
+    with pytest.raises(TypeError):
+        grbm.energy_mixing(object(), prefactor=0.05, num_reads=2)
+    with pytest.raises(ValueError, match="max_lag"):
+        grbm.energy_mixing(s2, max_lag=3, **kw)
+    with pytest.raises(_lib.DvgError, match="device of bits"):
+        F.grbm_energy_packed(trace.bits, gh, lin.cpu(), quad, **ranges)
+
+
+def test_model_wrapper_prior_energy_mixing():
+    from image_generation_amd.model_wrapper import ModelWrapper
+
+    torch.manual_seed(0)
+    m = ModelWrapper("Advantage_system4", n_latents=64, training_parameter_file=os.path.join(ROOT, "tests", "golden", "step_params.yaml"))
+    m.setup()
+    m.overlap_sampler = False  # (as in the AIS file: this test takes no stream from the process's pool)
+    series = m.prior_energy_mixing(num_reads=33, num_sweeps=20, burn_in=6, thin=2, max_lag=4)
+    s = m.sampler
+    assert (s.trace_sweep_count, s.sweep_count, s.calls, s.ais_sweep_count) == (20, 0, 0, 0) and s._state is None
+    assert isinstance(series, smp.EnergySeries) and series.energies.shape == (33, 7) and (series.thin, series.max_lag) == (2, 4)
+    assert series.energies.dtype == torch.float64 and series.energies.is_cuda and float(series.tau_int) >= 1.0 and float(series.r_hat) > 0.0
+    s.reset()  # the same draw again, by hand
+    trace = m._grbm.sample_trace(s, prefactor=m.PREFACTOR, linear_range=m.linear_range, quadratic_range=m.quadratic_range,
+                                 num_reads=33, num_sweeps=20, burn_in=6, thin=2)
+    e = trace.energy(m._grbm.graph_handle(trace.bits.device), m._grbm._linear.detach(), m._grbm._quadratic.detach(), m.PREFACTOR,
+                     m.linear_range, m.quadratic_range)
+    assert torch.equal(series.energies, e)
+    h, J = m._grbm._linear.detach().cpu().numpy().reshape(-1), m._grbm._quadratic.detach().cpu().numpy().reshape(-1)
+    hs, Js = gibbs.scaled_fields(h, J, m.PREFACTOR, m.linear_range, m.quadratic_range)
+    plan = m._grbm.plan
+    want, A = eo.energies(trace.bits.cpu().numpy().view(np.uint32), plan.n, hs, Js, plan.edge_i, plan.edge_j)
+    assert (np.abs(e.cpu().numpy() - want) <= eo.bound(plan.n, plan.n_edges, A)).all()

@@ -27,6 +27,10 @@ partner) twice: over the thin=1 trace of that draw in self mode at equal times (
 call, `novelty=AxB` (default 1024x60000) random rows of n spins in cross mode with `nearest`; next to each the same by torch on
 the rows unpacked to float32 -- a (batched) matmul, (n - G) / 2, torch.bincount, and min for the nearest row (the unpacking is not
 timed); a last line each says whether the two agree element by element.
+`energy`: also dvg_grbm_energy_packed (the float64 energies of bit-packed rows under the scaled, clamped fields, "DVG energy v1")
+over the thin=1 trace of that draw (chains x sweeps rows), timed as the moments row is; next to it the stock path -- sampler.unpack_spins
+to float32 followed by dvg_grbm_energy on the scaled, clamped fields -- timed with the unpacking and without it; a last line gives the
+largest deviation of the float32 energies from the float64 ones against the float32 rounding of that call's output.
 `population`: also population annealing ("DVG PA v1").  (a) dvg_population_resample alone, `resample=PxR,...` (default 8x128,1x65536)
 populations x chains of n spins with normal(0, 3) log weights, states gathered, against the same operation by torch: exp of the
 shifted weights, cumsum, searchsorted, index_select (float64: its parents may differ at near ties; the line says how many do).
@@ -302,6 +306,42 @@ if "overlap" in sys.argv:
     same = bool(torch.equal(by_torch, hist)) and bool(torch.equal(near >> 32, dmin.long())) and bool(torch.equal(near & 0xFFFFFFFF, first))
     print(f"  {'':26s} the two give the same histogram and nearest rows: {same}  (pairs {int(hist.sum())}, "
           f"sum of nearest d {int((near >> 32).sum())})")
+if "energy" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    trace = s.sample_trace(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)  # burn_in 0, thin 1: chains x sweeps records
+    W, M = (n + 31) // 32, sweeps
+    rows = C * M
+    energy = torch.empty((rows,), dtype=torch.float64, device="cuda")
+
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:26s} {t:9.1f} us per call  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    def packed():
+        _lib.check(_lib.lib().dvg_grbm_energy_packed(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0,
+                                                     trace.bits.data_ptr(), M, W, C, M * W, energy.data_ptr(), _lib.stream_ptr()),
+                   "dvg_grbm_energy_packed")
+        return energy
+
+    ts, _ = timed(packed)
+    t_packed = report("energy, packed rows", ts, f"{C} x {M} rows x {4 * W} B, {n} + {plan.n_edges} terms a row")
+    hs, Js = (0.05 * lin).clamp(-4.0, 4.0), (0.05 * quad).clamp(-1.0, 1.0)  # (float32: one rounding each, as the kernel's)
+    e32 = torch.empty((rows,), dtype=torch.float32, device="cuda")
+
+    def stock(x):
+        _lib.check(_lib.lib().dvg_grbm_energy(s.graph.ptr, x.data_ptr(), rows, hs.data_ptr(), Js.data_ptr(), e32.data_ptr(),
+                                              _lib.stream_ptr()), "dvg_grbm_energy")
+        return e32
+
+    ts, _ = timed(lambda: stock(smp.unpack_spins(trace.bits.view(rows, W), n).contiguous()))
+    t_stock = report("unpack + float32 energy", ts, f"{rows} rows x {4 * n} B   {float(np.median(ts)) / t_packed:.1f} x the packed call")
+    x = smp.unpack_spins(trace.bits.view(rows, W), n).contiguous()
+    ts, _ = timed(lambda: stock(x))
+    report("float32 energy alone", ts, f"the unpacking not timed   {float(np.median(ts)) / t_packed:.1f} x the packed call")
+    dev = (e32.double() - energy).abs()
+    print(f"  {'':26s} float32 energies off by up to {float(dev.max()):.3e}, 2^-23 |E| up to {float(energy.abs().max()) * 2.0 ** -23:.3e}  "
+          f"(sum of energies {float(energy.sum()):.6e})")
 if "population" in sys.argv:
     def report(name, ts, what):
         t = float(np.median(ts))
