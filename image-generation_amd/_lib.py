@@ -122,6 +122,12 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int, c_uint32, c_uint64,
          c_uint32, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
     ),
+    "dvg_gibbs_sample_tempered_traced": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p,
+         c_int, c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+         c_int, c_void_p, c_void_p],
+    ),
     "dvg_gibbs_launch_info": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "dvg_grbm_moments_packed": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "dvg_trace_autocorr": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -79,14 +79,28 @@ struct GibbsTraceArgs : GibbsArgs {
   int burn_in, thin;     // sweep k of the call is recorded iff k + 1 > burn_in and (k + 1 - burn_in) % thin == 0
   int n_records;         // (n_sweeps - burn_in) / thin
 };
-constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3, GIBBS_TRACE = 4;
+// Traced exchange draws (dvg_gibbs_sample_tempered_traced, "DVG PT trace v1" in include/dvg.h): the exchange draw, with a
+// history BY RUNG written out behind the exchange block of chosen sweeps -- the packed row of the chain that now holds rung r,
+// its carried energy, and by chain the rung it holds.  A sixth mode of SCHED, GIBBS_EXCHANGE_TRACE: the exchange block plus
+// the three outputs and which sweeps they take.  The kernels treat it as GIBBS_EXCHANGE everywhere (`EXCH`); `XTRACE` adds
+// the record step alone.
+struct GibbsExchangeTraceArgs : GibbsExchangeArgs {
+  uint32_t* trace;         // [n_chains][n_records][(n + 31) / 32] by rung: row q R + r = the chain of ladder q holding rung r
+  double* energy_trace;    // [n_chains][n_records] by rung, or null
+  uint8_t* rung_trace;     // [n_chains][n_records] by chain, or null
+  int burn_in, thin;       // the rule of GibbsTraceArgs
+  int n_records;           // (n_sweeps - burn_in) / thin
+};
+constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3, GIBBS_TRACE = 4, GIBBS_EXCHANGE_TRACE = 5;
 template <bool HELD, int SCHED = 0>
 using GibbsArgsT = std::conditional_t<
-    SCHED == GIBBS_TRACE, GibbsTraceArgs,
-    std::conditional_t<SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
-                       std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
-                                          std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs,
-                                                             std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>>;
+    SCHED == GIBBS_EXCHANGE_TRACE, GibbsExchangeTraceArgs,
+    std::conditional_t<
+        SCHED == GIBBS_TRACE, GibbsTraceArgs,
+        std::conditional_t<SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
+                           std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
+                                              std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs,
+                                                                 std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>>>;
 
 // A chain's start state, its LPC lanes each taking spins l, l + LPC, ...: from the INIT stream (init) or from `state`.
 // HELD (a conditional draw): held spins from `state` always, free ones as above.
@@ -341,6 +355,22 @@ __device__ __forceinline__ void gibbs_record(const _Float16* st, int n, int n_pa
   }
 }
 
+// The record step of GIBBS_EXCHANGE_TRACE, behind the exchange block of a recorded sweep: the lanes of a VALID chain, together.
+// `row` = q R + (the rung the chain holds now), `m` the record.  The chain's own LDS row and registers only: no workgroup
+// barrier, no LDS of its own.  The energy is the sum of a COPY of the lanes' shares: `e` itself goes on as it was, so the draw's
+// later sums (the next exchange's, energy_out's) add the same shares in the same order as the draw without records.
+template <int LPC, bool A16>
+__device__ __forceinline__ void gibbs_exchange_record(const GibbsExchangeTraceArgs& a, const _Float16* st, int n, int n_pad, int l,
+                                                      int chain, size_t row, uint32_t m, int rung, double e) {
+  const size_t M = (size_t)a.n_records;
+  gibbs_record<LPC, A16>(st, n, n_pad, l, a.trace + (row * M + m) * gibbs_held_words(n));
+  if (a.energy_trace) {  // (a kernel argument: uniform)
+    const double E = gibbs_chain_sum<LPC>(e);
+    if (l == 0) a.energy_trace[row * M + m] = E;
+  }
+  if (a.rung_trace && l == 0) a.rung_trace[(size_t)chain * M + m] = (uint8_t)rung;
+}
+
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
 // HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
 // passed over in its class.  SCHED: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead.
@@ -351,10 +381,14 @@ __device__ __forceinline__ void gibbs_record(const _Float16* st, int n, int n_pa
 // lanes of an idle slot with empty classes; the exchanges are counted from (sweep0, n_sweeps, swap_every) alone.
 // SCHED == GIBBS_TRACE: the plain draw at its fixed beta; behind a recorded sweep's last fence the chain's lanes pack its row
 // (gibbs_record).  Which sweeps: a countdown in scalar registers (`rec_at`, the next recorded k + 1), no division per sweep.
+// SCHED == GIBBS_EXCHANGE_TRACE: the exchange draw (EXCH); behind the exchange block of a recorded sweep the lanes of a valid
+// chain write its record to the row of the rung it NOW holds (gibbs_exchange_record), on the same countdown.  Idle slots count
+// down too and record nothing; they still reach every barrier.
 template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
-  constexpr bool AIS = SCHED == GIBBS_WEIGH, EXCH = SCHED == GIBBS_EXCHANGE, ENERGY = AIS || EXCH;
+  constexpr bool AIS = SCHED == GIBBS_WEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE, EXCH = SCHED == GIBBS_EXCHANGE || XTRACE;
+  constexpr bool ENERGY = AIS || EXCH;
   constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n;
@@ -415,8 +449,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
     [[maybe_unused]] double e = 0.0, lw = 0.0;
     [[maybe_unused]] float beta_prev = 0.0f;
     if constexpr (AIS) beta_prev = a.beta_from;
-    [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE: the next recorded sweep (as k + 1) and its record
-    if constexpr (TRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
+    [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE, XTRACE: the next recorded sweep (as k + 1) and its record
+    if constexpr (TRACE || XTRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
     if constexpr (ENERGY) {
       for (int i = l; i < (valid ? n : 0); i += LPC) {
         const float hsi = L.hs[i];
@@ -471,6 +505,13 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
           __syncthreads();
           if (valid)
             gibbs_exchange_decide(a, X, WAVES * CPW, a.n_replicas, x, slot.lq, cid - (uint32_t)slot.j, l, rung, beta_next);
+        }
+      }
+      if constexpr (XTRACE) {
+        if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
+          if (valid) gibbs_exchange_record<LPC, false>(a, st, n, n_pad, l, chain, (size_t)(chain - slot.j + rung), rec_m, rung, e);
+          rec_at += (uint32_t)a.thin;
+          ++rec_m;
         }
       }
     }
@@ -720,10 +761,12 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
 // barrier at every exchange.  No wave leaves before the last barrier: the lanes of an idle slot own no spin in any row (every
 // store of theirs goes to the sink), and a wave of idle slots alone passes over the sweep, not over the barrier.
 // SCHED == GIBBS_TRACE: the plain draw; gibbs_record behind a recorded sweep's last fence (the rows are 16-byte aligned here).
+// SCHED == GIBBS_EXCHANGE_TRACE: the exchange draw; gibbs_exchange_record behind a recorded sweep's exchange block.
 template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
-  constexpr bool AIS = SCHED == GIBBS_WEIGH, EXCH = SCHED == GIBBS_EXCHANGE, ENERGY = AIS || EXCH;
+  constexpr bool AIS = SCHED == GIBBS_WEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE, EXCH = SCHED == GIBBS_EXCHANGE || XTRACE;
+  constexpr bool ENERGY = AIS || EXCH;
   constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n, n_pad = (n + 15) & ~15;
@@ -838,8 +881,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   [[maybe_unused]] float beta_prev = 0.0f;
   [[maybe_unused]] uint32_t up = 0u;  // AIS: bit k = the spin of slot k is +1
   if constexpr (AIS) beta_prev = a.beta_from;
-  [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE: the next recorded sweep (as k + 1) and its record
-  if constexpr (TRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
+  [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE, XTRACE: the next recorded sweep (as k + 1) and its record
+  if constexpr (TRACE || XTRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
   if constexpr (ENERGY) {
     // the sweep loop's walk over the steps, on the start state (it leaves `o` at step 0's offsets again)
 #pragma unroll
@@ -948,6 +991,14 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
         if (valid) gibbs_exchange_decide(a, X, WAVES * CPW, a.n_replicas, x, slot.lq, cid - (uint32_t)slot.j, l, rung, beta_next);
       }
     }
+    if constexpr (XTRACE) {
+      // (the rows are 16-byte aligned here, as the plain trace's; the lanes of an idle slot only count)
+      if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
+        if (valid) gibbs_exchange_record<LPC, true>(a, st, n, n_pad, l, chain, (size_t)(chain - slot.j + rung), rec_m, rung, e);
+        rec_at += (uint32_t)a.thin;
+        ++rec_m;
+      }
+    }
   }
 #undef DVG_GIBBS_WORD
 #undef DVG_GIBBS_WEIGH
@@ -1048,14 +1099,16 @@ static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStrea
   return gibbs_launch(gibbs_kernel_of<HELD, SCHED>(p), p, a, s, a);
 }
 
-// the exchange draw: its own plan (the replica count is an input), the same tables
-static int gibbs_draw_exchange(const dvg_graph_t* g, GibbsExchangeArgs& a, hipStream_t s) {
+// the exchange draw: its own plan (the replica count is an input), the same tables.  SCHED: GIBBS_EXCHANGE or, with the
+// records, GIBBS_EXCHANGE_TRACE -- the same plan, the same forms, the same LDS.
+template <int SCHED>
+static int gibbs_draw_exchange(const dvg_graph_t* g, GibbsArgsT<false, SCHED>& a, hipStream_t s) {
   GibbsDrawPlan p;
   DVG_TRY(gibbs_exchange_plan(g->shape, a.n_chains / a.n_replicas, a.n_replicas, opt(OPT_GIBBS_GENERIC), &p, nullptr));
   if (p.form == GF_LANE) {
     a.lane_spin = g->lane_spin; a.lane_eid = g->lane_eid; a.lane_off = g->lane_off; a.n_rows = g->shape.lane_rows;
   }
-  return gibbs_launch(gibbs_kernel_of<false, GIBBS_EXCHANGE>(p), p, a, s, a);
+  return gibbs_launch(gibbs_kernel_of<false, SCHED>(p), p, a, s, a);
 }
 
 // What every draw checks, under its entry point's name `who`.  `missing`: the entry point's own null argument, if any
@@ -1164,6 +1217,23 @@ extern "C" int dvg_gibbs_sample_ais(const dvg_graph_t* g, const float* linear, c
 
 // The exchange draw ("DVG PT v1", include/dvg.h): ladders of n_replicas chains, each at the beta of the rung it holds; every
 // swap_every sweeps the chains of neighbouring rungs of a ladder exchange them on a Metropolis coin.
+// what both exchange draws check, under the entry point's name `who`; `missing`: the entry point's own null argument, if any
+static int gibbs_exchange_check(const char* who, const dvg_graph_t* g, const float* linear, const float* quadratic, const float* ladder,
+                                int n_replicas, int swap_every, const int8_t* state, const int32_t* rung, int n_chains, int n_sweeps,
+                                const char* missing, const dvg_step_state_t* dyn) {
+  DVG_TRY(gibbs_check(who, g, linear && quadratic && state,
+                      !ladder ? "null ladder (a draw at one fixed beta is dvg_gibbs_sample)" : !rung ? "null rung" : missing,
+                      n_chains, n_sweeps, false, nullptr));
+  DVG_REQUIRE(n_sweeps >= 1, "%s: n_sweeps=%d (a draw of at least one sweep)", who, n_sweeps);
+  DVG_REQUIRE(n_replicas >= 2 && n_replicas <= GIBBS_MAX_REPLICAS, "%s: n_replicas=%d is not in 2..%d", who, n_replicas,
+              GIBBS_MAX_REPLICAS);
+  DVG_REQUIRE(n_chains % n_replicas == 0, "%s: n_chains=%d is not a multiple of n_replicas=%d (whole ladders)", who, n_chains,
+              n_replicas);
+  DVG_REQUIRE(swap_every >= 1, "%s: swap_every=%d must be at least 1", who, swap_every);
+  DVG_REQUIRE(!dyn, "%s: dyn must be NULL (the exchanges of a call are counted on the host, from its sweep0)", who);
+  return DVG_OK;
+}
+
 extern "C" int dvg_gibbs_sample_tempered(const dvg_graph_t* g, const float* linear, const float* quadratic,
                                          float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
                                          const float* ladder, int n_replicas, int swap_every,
@@ -1171,22 +1241,43 @@ extern "C" int dvg_gibbs_sample_tempered(const dvg_graph_t* g, const float* line
                                          uint32_t sweep0, int n_sweeps, int init, float* samples_out,
                                          double* energy_out, uint32_t* accept_out,
                                          const dvg_step_state_t* dyn, dvg_stream_t stream) {
-  DVG_TRY(gibbs_check("gibbs_tempered", g, linear && quadratic && state,
-                      !ladder ? "null ladder (a draw at one fixed beta is dvg_gibbs_sample)" : !rung ? "null rung" : nullptr,
-                      n_chains, n_sweeps, false, nullptr));
-  DVG_REQUIRE(n_sweeps >= 1, "gibbs_tempered: n_sweeps=%d (a draw of at least one sweep)", n_sweeps);
-  DVG_REQUIRE(n_replicas >= 2 && n_replicas <= GIBBS_MAX_REPLICAS, "gibbs_tempered: n_replicas=%d is not in 2..%d", n_replicas,
-              GIBBS_MAX_REPLICAS);
-  DVG_REQUIRE(n_chains % n_replicas == 0, "gibbs_tempered: n_chains=%d is not a multiple of n_replicas=%d (whole ladders)", n_chains,
-              n_replicas);
-  DVG_REQUIRE(swap_every >= 1, "gibbs_tempered: swap_every=%d must be at least 1", swap_every);
-  DVG_REQUIRE(!dyn, "gibbs_tempered: dyn must be NULL (the exchanges of a call are counted on the host, from its sweep0)");
+  DVG_TRY(gibbs_exchange_check("gibbs_tempered", g, linear, quadratic, ladder, n_replicas, swap_every, state, rung, n_chains, n_sweeps,
+                               nullptr, dyn));
   GibbsExchangeArgs a;
   gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
                   n_sweeps, init, samples_out, nullptr);
   a.ladder = ladder; a.n_replicas = n_replicas; a.swap_every = swap_every;
   a.rung = rung; a.energy_out = energy_out; a.accept_out = accept_out;
-  return gibbs_draw_exchange(g, a, (hipStream_t)stream);
+  return gibbs_draw_exchange<GIBBS_EXCHANGE>(g, a, (hipStream_t)stream);
+}
+
+// The traced exchange draw ("DVG PT trace v1", include/dvg.h): dvg_gibbs_sample_tempered, with a history by rung -- packed
+// state, carried energy -- and the rung walk by chain written out behind the exchange block of the recorded sweeps.
+extern "C" int dvg_gibbs_sample_tempered_traced(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                                float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                                const float* ladder, int n_replicas, int swap_every,
+                                                int8_t* state, int32_t* rung, int n_chains, uint32_t chain_id0, uint64_t seed,
+                                                uint32_t sweep0, int n_sweeps, int init, float* samples_out,
+                                                double* energy_out, uint32_t* accept_out,
+                                                uint32_t* trace_out, double* energy_trace_out, uint8_t* rung_trace_out,
+                                                int burn_in, int thin, const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  DVG_TRY(gibbs_exchange_check("gibbs_tempered_traced", g, linear, quadratic, ladder, n_replicas, swap_every, state, rung, n_chains,
+                               n_sweeps, trace_out ? nullptr : "null trace_out (a draw that records nothing is dvg_gibbs_sample_tempered)",
+                               dyn));
+  DVG_REQUIRE(burn_in >= 0, "gibbs_tempered_traced: burn_in=%d must be at least 0", burn_in);
+  DVG_REQUIRE(thin >= 1, "gibbs_tempered_traced: thin=%d must be at least 1", thin);
+  // (n_sweeps - burn_in >= thin, without the overflow of burn_in + thin)
+  DVG_REQUIRE(burn_in <= n_sweeps && n_sweeps - burn_in >= thin,
+              "gibbs_tempered_traced: n_sweeps=%d, burn_in=%d, thin=%d record nothing (a draw that records nothing is "
+              "dvg_gibbs_sample_tempered)", n_sweeps, burn_in, thin);
+  GibbsExchangeTraceArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, nullptr);
+  a.ladder = ladder; a.n_replicas = n_replicas; a.swap_every = swap_every;
+  a.rung = rung; a.energy_out = energy_out; a.accept_out = accept_out;
+  a.trace = trace_out; a.energy_trace = energy_trace_out; a.rung_trace = rung_trace_out;
+  a.burn_in = burn_in; a.thin = thin; a.n_records = (n_sweeps - burn_in) / thin;
+  return gibbs_draw_exchange<GIBBS_EXCHANGE_TRACE>(g, a, (hipStream_t)stream);
 }
 
 // The traced draw ("DVG trace v1", include/dvg.h): dvg_gibbs_sample, with the chains' states after the recorded sweeps

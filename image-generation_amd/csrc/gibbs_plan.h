@@ -96,7 +96,8 @@ GibbsGraphShape gibbs_graph_shape(int n, int n_colours, const int32_t* class_ptr
 
 // ---------------------------------------------------------------- the draw
 // plain: dvg_gibbs_sample; held: _clamped (kernels' HELD); table: _annealed (SCHED = GIBBS_TABLE); weigh: _ais (GIBBS_WEIGH);
-// exchange: _tempered (GIBBS_EXCHANGE) -- planned by gibbs_exchange_plan, which needs the replica count as well;
+// exchange: _tempered (GIBBS_EXCHANGE) and _tempered_traced (GIBBS_EXCHANGE_TRACE: the same plan, a record is packed from the
+// chain's own row and registers) -- planned by gibbs_exchange_plan, which needs the replica count as well;
 // trace: _traced (GIBBS_TRACE) -- the table kind's choices (no slots form), the table kind's LDS: a record is packed from the
 // state rows where they lie
 enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE, GK_TRACE };

@@ -974,6 +974,22 @@ class ModelWrapper:
                                         quadratic_range=self.quadratic_range, max_lag=max_lag, **kw)
 
     @torch.no_grad()
+    def prior_tempered_mixing(self, betas, max_lag=None, **kw):
+        """Does tempering help under the trained prior?  One traced exchange draw over the ladder ``betas`` and one plain traced
+        draw of the same sweeps, chains, ``burn_in`` and ``thin`` at ``betas[-1]``
+        (``GraphRestrictedBoltzmannMachine.tempered_mixing``; ``num_ladders``, ``num_sweeps``, ``swap_every``, ``burn_in``,
+        ``thin`` are passed on, ``num_ladders`` defaults to NUM_READS), over lags 0 .. ``max_lag`` records.  Returns a dict:
+        ``tempered_autocorrelation`` / ``tempered_energy`` of the target rung, ``plain_autocorrelation`` / ``plain_energy`` of
+        the plain draw, and the ladder's ``acceptance_rate``, ``round_trips`` and ``flow``.  Rank-local and eval-mode, like
+        ``prior_energy_mixing``; of the sampler's counters only ``pt_sweep_count`` and ``trace_sweep_count`` move."""
+        self._dvae.eval()
+        self._grbm.eval()
+        if "num_ladders" not in kw:
+            kw["num_ladders"] = int(self.sampler_kwargs.get("num_reads", 1))
+        return self._grbm.tempered_mixing(self.sampler, betas, prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                          quadratic_range=self.quadratic_range, max_lag=max_lag, **kw)
+
+    @torch.no_grad()
     def prior_overlap(self, **kw):
         """Which modes the sampler's chains populate on the prior: the :class:`~.sampler.Overlap` between distinct chains at
         equal times of one traced draw (``GraphRestrictedBoltzmannMachine.replica_overlap``; ``num_reads``, ``num_sweeps``,

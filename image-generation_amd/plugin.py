@@ -276,6 +276,49 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         return trace.energy_series(self.graph_handle(trace.bits.device), self._linear, self._quadratic, prefactor, linear_range,
                                    quadratic_range, max_lag=max_lag)
 
+    def sample_tempered_trace(self, sampler, betas, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """A traced parallel-tempering draw from the model under the prefactor-scaled, clamped ``(h, J)``: :meth:`sample_tempered`
+        with the ladders' history -- per rung the packed states and energies, per chain the rung walk -- written inside the
+        kernel (:meth:`GibbsSampler.sample_tempered_trace`; ``num_ladders``, ``num_sweeps``, ``swap_every``, ``burn_in``,
+        ``thin``, ``start``, ``rungs``, ``energies``, ``rung_walk`` are passed on).  Returns its
+        :class:`~.sampler.TemperedTrace`.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "sample_tempered_trace")
+        return sampler.sample_tempered_trace(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, betas, **kw)
+
+    @torch.no_grad()
+    def tempered_mixing(self, sampler, betas, *, prefactor: float, linear_range=None, quadratic_range=None, max_lag=None, **kw):
+        """Does tempering help on this model?  One traced exchange draw over the ladder ``betas`` (:meth:`sample_tempered_trace`;
+        ``num_ladders``, ``num_sweeps``, ``swap_every``, ``burn_in``, ``thin`` are passed on) and one plain traced draw
+        (:meth:`sample_trace`) of the same sweeps, ``burn_in``, ``thin`` and as many chains (``num_ladders``) at ``betas[-1]``
+        -- the sampler's ``beta`` is set to it for that draw and put back.  Returns a dict: ``tempered_autocorrelation`` /
+        ``tempered_energy`` (the target rung's :class:`~.sampler.Autocorrelation` and :class:`~.sampler.EnergySeries`, from the
+        carried energies), ``plain_autocorrelation`` / ``plain_energy`` (the plain draw's, its energies exact:
+        :meth:`Trace.energy_series`), ``acceptance_rate`` (R - 1,), ``round_trips`` (Q, R) and ``flow`` (R,) of the ladder.
+        Compare the two ``tau_int_sweeps``: an exchange draw spends R chains per target sample.  The local
+        :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "tempered_mixing")
+        if max_lag is not None and (isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or max_lag < 0):
+            raise ValueError(f"max_lag must be None or an integer >= 0, got {max_lag!r}")
+        for name in ("start", "rungs", "energies", "rung_walk"):
+            if name in kw:
+                raise ValueError(f"tempered_mixing draws fresh ladders with every record: {name} is not an argument of it")
+        ranges = dict(prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range)
+        tt = self.sample_tempered_trace(sampler, betas, **ranges, **kw)
+        plain_kw = {k: kw[k] for k in ("num_sweeps", "burn_in", "thin") if k in kw}
+        beta = sampler.beta
+        try:
+            sampler.beta = float(tt.betas[-1])
+            plain = self.sample_trace(sampler, num_reads=int(tt.bits.shape[0]), **ranges, **plain_kw)
+        finally:
+            sampler.beta = beta
+        target = tt.target
+        return dict(
+            tempered_autocorrelation=target.autocorrelation(max_lag), tempered_energy=tt.energy_series(-1, max_lag),
+            plain_autocorrelation=plain.autocorrelation(max_lag),
+            plain_energy=plain.energy_series(self.graph_handle(plain.bits.device), self._linear, self._quadratic, prefactor,
+                                             linear_range, quadratic_range, max_lag=max_lag),
+            acceptance_rate=tt.final.acceptance_rate, round_trips=tt.round_trips(), flow=tt.flow())
+
     @torch.no_grad()
     def replica_overlap(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
         """Which modes the sampler's chains populate on this model: one traced draw (:meth:`sample_trace`, ``**kw`` passed

@@ -671,6 +671,100 @@ class Trace:
         return f"Trace({C} chains x {M} records, n={self.n})"
 
 
+class TemperedTrace:
+    """What :meth:`GibbsSampler.sample_tempered_trace` returns, for Q ladders of R rungs and M records ("DVG PT trace v1");
+    device tensors unless said otherwise.  BY RUNG: ``bits`` (Q, R, M, W) int32, ``[q, r, m]`` the packed state ("DVG trace
+    v1") at record m of the chain of ladder q that holds rung r then -- a sample at ``betas[r]``; ``energies`` (Q, R, M)
+    float64, that chain's carried energy, or None.  BY CHAIN: ``walk`` (Q, R, M) uint8, ``[q, j, m]`` the rung chain j of
+    ladder q holds at record m, or None.  A record is taken behind the exchange that follows its sweep.  ``sweeps`` (M,) host
+    int64: the recorded sweeps as k + 1 (``trace_sweeps``); ``final``: the :class:`Tempered` of the draw (hand its ``state`` /
+    ``rungs`` back to continue); ``betas`` (R,) host float32; ``n`` the spin count.
+
+    The ladder diagnostics ``occupancy``, ``round_trips`` and ``flow`` are exact integer counts over ``walk``, in vectorised
+    torch on its device (CPU tensors too), no host sync.  Their LABEL RULE: at a record a chain is "up" if the last extreme
+    rung it held (0 or R - 1, this record included) was rung 0, "down" if it was rung R - 1, and unlabelled before it first
+    holds either."""
+
+    def __init__(self, bits, energies, walk, sweeps, final, betas, n):
+        self.bits, self.energies, self.walk, self.sweeps, self.final = bits, energies, walk, sweeps, final
+        self.betas, self.n = np.asarray(betas, dtype=np.float32), int(n)
+
+    @property
+    def thin(self) -> int:
+        """The sweeps between two records (1 for a single record)."""
+        return int(self.sweeps[1] - self.sweeps[0]) if len(self.sweeps) > 1 else 1
+
+    def rung(self, r: int) -> Trace:
+        """The Q chains-at-rung-r as a :class:`Trace` of contiguous (Q, M, W) ``bits``: ``autocorrelation``, ``energy``,
+        ``overlap`` and ``moments`` work on it unchanged.  Its ``samples`` are the final states at rung r; it has no ``state``
+        (a draw is continued from ``final``).  ``r``: -R .. R - 1."""
+        R = int(self.bits.shape[1])
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not -R <= r < R:
+            raise ValueError(f"r must be an integer in {-R} .. {R - 1}, got {r!r}")
+        samples = self.final.samples[:, r] if self.final is not None and self.final.samples is not None else None
+        return Trace(self.bits[:, r].contiguous(), samples, None, self.sweeps, self.n)
+
+    @property
+    def target(self) -> Trace:
+        """``rung(R - 1)``: the history at ``betas[-1]``."""
+        return self.rung(int(self.bits.shape[1]) - 1)
+
+    def energy_series(self, r: int = -1, max_lag: Optional[int] = None) -> EnergySeries:
+        """The carried energies of the chains at rung ``r`` (default: the target) as an :class:`EnergySeries` of Q chains x M
+        records with the trace's ``thin``, over lags 0 .. ``max_lag`` records (default min(M - 1, 512))."""
+        if self.energies is None:
+            raise ValueError("this trace was drawn with energies=False")
+        R = int(self.energies.shape[1])
+        if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not -R <= r < R:
+            raise ValueError(f"r must be an integer in {-R} .. {R - 1}, got {r!r}")
+        return EnergySeries.from_energies(self.energies[:, r].contiguous(), self.thin, max_lag)
+
+    def _walk(self, what: str) -> torch.Tensor:
+        if self.walk is None:
+            raise ValueError(f"{what} needs the rung walk: this trace was drawn with rung_walk=False")
+        return self.walk.to(torch.int64)
+
+    def _labels(self, what: str):
+        """(walk int64, label int64): +1 up, -1 down, 0 unlabelled -- running maxima of "last record at rung 0" and "last
+        record at rung R - 1" (records counted from 1; 0: never)."""
+        w = self._walk(what)
+        R, M = int(w.shape[1]), int(w.shape[2])
+        idx = torch.arange(1, M + 1, dtype=torch.int64, device=w.device)
+        zero = torch.zeros((), dtype=torch.int64, device=w.device)
+        last_bottom = torch.cummax(torch.where(w == 0, idx, zero), dim=2).values
+        last_top = torch.cummax(torch.where(w == R - 1, idx, zero), dim=2).values
+        return w, (last_bottom > last_top).to(torch.int64) - (last_top > last_bottom).to(torch.int64)
+
+    def occupancy(self) -> torch.Tensor:
+        """(Q, R, R) int64: ``[q, j, r]`` = the records chain j of ladder q spent on rung r (each row sums to M)."""
+        w = self._walk("occupancy")
+        Q, R, _M = w.shape
+        return torch.zeros((Q, R, R), dtype=torch.int64, device=w.device).scatter_add_(2, w, torch.ones_like(w))
+
+    def round_trips(self) -> torch.Tensor:
+        """(Q, R) int64 per chain: floor(label changes / 2) under the class's label rule -- a change is a record whose label
+        differs from the record before it, both labelled.  A chain that went rung 0 -> R - 1 -> 0 (or R - 1 -> 0 -> R - 1)
+        made one round trip."""
+        _w, lab = self._labels("round_trips")
+        changes = ((lab[:, :, 1:] != lab[:, :, :-1]) & (lab[:, :, :-1] != 0)).sum(2)
+        return torch.div(changes, 2, rounding_mode="floor")
+
+    def flow(self) -> torch.Tensor:
+        """(R,) float64: f(r) = up(r) / (up(r) + down(r)), up(r) / down(r) the records over all ladders and chains at which a
+        chain labelled up / down (the class's label rule) held rung r; unlabelled records are not counted, and a rung no
+        labelled chain has visited gives NaN.  f(0) = 1 and f(R - 1) = 0 wherever defined; a ladder with evenly spent effort
+        falls linearly in between."""
+        w, lab = self._labels("flow")
+        R = int(w.shape[1])
+        up = torch.zeros(R, dtype=torch.int64, device=w.device).scatter_add_(0, w.reshape(-1), (lab == 1).to(torch.int64).reshape(-1))
+        down = torch.zeros(R, dtype=torch.int64, device=w.device).scatter_add_(0, w.reshape(-1), (lab == -1).to(torch.int64).reshape(-1))
+        return up.to(torch.float64) / (up + down).to(torch.float64)
+
+    def __repr__(self):
+        Q, R, M, _W = self.bits.shape
+        return f"TemperedTrace({Q} ladders x {R} rungs x {M} records, n={self.n})"
+
+
 class GibbsSampler:
     """``sample_ising``-compatible local solver running on the MI355X.
 
@@ -1109,8 +1203,15 @@ class GibbsSampler:
 
         Its own key ``pt_seed`` and counter ``pt_sweep_count`` (which also numbers the exchanges): the training,
         conditional, annealed and AIS streams are left alone.  Chain ids are ``chain_offset + arange(Q R)``."""
+        ladder, R, Q, S, swap_every, _M, lin, quad = self._tempered_arguments(linear, quadratic, betas, num_ladders, num_sweeps,
+                                                                              swap_every, start, rungs)
+        return self._tempered_draw(lin, quad, prefactor, linear_range, quadratic_range, ladder, R, Q, S, swap_every, start, rungs)
+
+    def _tempered_arguments(self, linear, quadratic, betas, num_ladders, num_sweeps, swap_every, start, rungs, record=None):
+        """The argument checks of the exchange draws, every one before the first library call (the ladder's upload included).
+        ``record``: the traced draw's ``(burn_in, thin)``, checked as :meth:`sample_trace` does.  Returns the ladder (host
+        float32), R, Q, the sweeps, ``swap_every``, the records M (None without ``record``) and the parameters."""
         n = self.plan.n
-        # every argument check comes before the first library call (the ladder's upload included)
         if torch.is_tensor(betas) and betas.is_cuda:
             raise _lib.DvgError("betas: the ladder is a host sequence, array or CPU tensor (it is checked, then uploaded)")
         ladder = _check_beta_table(betas, "betas")
@@ -1122,6 +1223,15 @@ class GibbsSampler:
             if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
         Q, S, swap_every = int(num_ladders), int(self.sweeps if num_sweeps is None else num_sweeps), int(swap_every)
+        M = None
+        if record is not None:
+            for name, v, low in (("burn_in", record[0], 0), ("thin", record[1], 1)):
+                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < low:
+                    raise ValueError(f"{name} must be an integer >= {low}, got {v!r}")
+            M = (S - int(record[0])) // int(record[1])
+            if M < 1:
+                raise ValueError(f"num_sweeps={S}, burn_in={int(record[0])}, thin={int(record[1])} record nothing (a draw without "
+                                 "a trace is sample_tempered)")
         if (start is None) != (rungs is None):
             raise ValueError("start and rungs go together: give both (to continue a draw) or neither (fresh chains)")
         if start is not None:
@@ -1139,7 +1249,6 @@ class GibbsSampler:
             for name, t in (("start", start), ("rungs", rungs)):
                 if not t.is_cuda:
                     raise _lib.DvgError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
-        C = Q * R
         lin = _lib.require_cuda(linear.detach(), "linear")
         quad = _lib.require_cuda(quadratic.detach(), "quadratic")
         if lin.numel() != n or quad.numel() != self.plan.n_edges:
@@ -1147,6 +1256,13 @@ class GibbsSampler:
         for name, t in (("start", start), ("rungs", rungs)):
             if t is not None and t.device != lin.device:
                 raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
+        return ladder, R, Q, S, swap_every, M, lin, quad
+
+    def _tempered_draw(self, lin, quad, prefactor, linear_range, quadratic_range, ladder, R, Q, S, swap_every, start, rungs,
+                       record=None):
+        """The exchange draw on checked arguments.  ``record``: None, or the traced draw's ``(burn_in, thin, M, energies,
+        rung_walk)`` -- then ``(Tempered, bits, energies or None, walk or None)`` is returned."""
+        n, C = self.plan.n, Q * R
         table = torch.from_numpy(ladder).to(lin.device)
         if start is None:
             state, rung, init = (torch.empty((C, n), dtype=torch.int8, device=lin.device),
@@ -1160,6 +1276,23 @@ class GibbsSampler:
         hl, hh = linear_range if linear_range is not None else (-inf, inf)
         jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
         sweep0 = self.pt_sweep_count & 0xFFFFFFFF
+        if record is not None:
+            burn_in, thin, M, with_energies, with_walk = record
+            bits = torch.empty((Q, R, M, (n + 31) // 32), dtype=torch.int32, device=lin.device)
+            e_trace = torch.empty((Q, R, M), dtype=torch.float64, device=lin.device) if with_energies else None
+            walk = torch.empty((Q, R, M), dtype=torch.uint8, device=lin.device) if with_walk else None
+            with torch.cuda.device(lin.device):
+                _lib.check(
+                    _lib.lib().dvg_gibbs_sample_tempered_traced(
+                        self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl), float(hh), float(jl), float(jh),
+                        table.data_ptr(), R, swap_every, state.data_ptr(), rung.data_ptr(), C, self.chain_offset & 0xFFFFFFFF,
+                        self.pt_seed, sweep0, S, init, out.data_ptr(), energy.data_ptr(), accept.data_ptr(), bits.data_ptr(),
+                        None if e_trace is None else e_trace.data_ptr(), None if walk is None else walk.data_ptr(), burn_in, thin,
+                        None, _lib.stream_ptr(lin.device)),
+                    "dvg_gibbs_sample_tempered_traced",
+                )
+            self.pt_sweep_count += S
+            return Tempered.from_draw(n, R, out, energy, accept, sweep0, S, swap_every, state, rung), bits, e_trace, walk
         with torch.cuda.device(lin.device):
             _lib.check(
                 _lib.lib().dvg_gibbs_sample_tempered(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
@@ -1171,6 +1304,30 @@ class GibbsSampler:
             )
         self.pt_sweep_count += S
         return Tempered.from_draw(n, R, out, energy, accept, sweep0, S, swap_every, state, rung)
+
+    def sample_tempered_trace(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
+                              quadratic_range, betas, *, num_ladders: int, num_sweeps: Optional[int] = None, swap_every: int = 1,
+                              burn_in: int = 0, thin: int = 1, start: Optional[torch.Tensor] = None,
+                              rungs: Optional[torch.Tensor] = None, energies: bool = True, rung_walk: bool = True) -> "TemperedTrace":
+        """A traced parallel-tempering draw (``dvg_gibbs_sample_tempered_traced``, "DVG PT trace v1" in include/dvg.h):
+        :meth:`sample_tempered` -- the same draw, bit for bit -- with a history of the ladders written from inside the
+        kernel: after every ``thin``-th sweep behind the first ``burn_in`` (sweep k iff ``k + 1 > burn_in`` and
+        ``(k + 1 - burn_in) % thin == 0``, M = ``(num_sweeps - burn_in) // thin`` records), and after the exchange that
+        follows such a sweep, per rung the packed state and (``energies``) the carried energy of the chain that holds it,
+        and (``rung_walk``) per chain the rung it holds.
+
+        The arguments and their checks are :meth:`sample_tempered`'s and :meth:`sample_trace`'s, all before the first
+        library call.  Returns a :class:`TemperedTrace`; no host sync.
+
+        The stream is :meth:`sample_tempered`'s: the key ``pt_seed``, and ``pt_sweep_count`` advances by ``num_sweeps``;
+        every other stream and counter is left alone."""
+        ladder, R, Q, S, swap_every, M, lin, quad = self._tempered_arguments(linear, quadratic, betas, num_ladders, num_sweeps,
+                                                                             swap_every, start, rungs, record=(burn_in, thin))
+        burn_in, thin = int(burn_in), int(thin)
+        final, bits, e_trace, walk = self._tempered_draw(lin, quad, prefactor, linear_range, quadratic_range, ladder, R, Q, S,
+                                                         swap_every, start, rungs,
+                                                         record=(burn_in, thin, M, bool(energies), bool(rung_walk)))
+        return TemperedTrace(bits, e_trace, walk, trace_sweeps(S, burn_in, thin), final, ladder, self.plan.n)
 
     def sample_trace(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range, *,
                      num_reads: Optional[int] = None, start: Optional[torch.Tensor] = None, num_sweeps: Optional[int] = None,

@@ -233,14 +233,50 @@ int dvg_gibbs_sample_tempered(const dvg_graph_t *g, const float *linear, const f
  *   DVG_E_INVALID, before any launch: what dvg_gibbs_sample rejects; trace_out == NULL; burn_in < 0; thin < 1; M < 1 (a draw
  *     that records nothing is dvg_gibbs_sample); dyn != NULL (the draw is one-off, not part of a captured step: the recorded
  *     sweeps are counted from the host's sweep0).  It takes the kernel forms of the annealed draw (csrc/gibbs_plan.h) and
- *     their LDS: a record is packed from the state rows where they lie.  No traced form of dvg_gibbs_sample_clamped,
- *     _annealed, _ais or _tempered. */
+ *     their LDS: a record is packed from the state rows where they lie.  The traced form of dvg_gibbs_sample_tempered is
+ *     dvg_gibbs_sample_tempered_traced; no traced form of dvg_gibbs_sample_clamped, _annealed or _ais. */
 int dvg_gibbs_sample_traced(const dvg_graph_t *g, const float *linear, const float *quadratic,
                             float prefactor, float h_lo, float h_hi, float j_lo, float j_hi, float beta,
                             int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
                             uint32_t sweep0, int n_sweeps, int init, float *samples_out,
                             uint32_t *trace_out, int burn_in, int thin,
                             const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The traced exchange draw ("DVG PT trace v1"): dvg_gibbs_sample_tempered with a history of the LADDER written from inside
+ * the kernel -- per rung the state and the energy of the chain holding it, per chain the rung it holds.  With the same
+ * arguments the spins, the random words, the exchanges, state, rung, samples_out, energy_out and accept_out are "DVG PT v1"'s,
+ * bit for bit: the records add nothing to any decision.
+ *   Which sweeps are recorded.  The rule of "DVG trace v1": sweep k of the call (0-based, global index sweep0 + k) iff
+ *     k + 1 > burn_in  and  (k + 1 - burn_in) % thin == 0;  M = (n_sweeps - burn_in) / thin records, rounded down; record m
+ *     belongs to sweep k = burn_in + thin (m + 1) - 1.
+ *   When the record is taken.  After the sweep's last colour class AND after the exchange that follows that sweep, if one is
+ *     due ((sweep0 + k + 1) % swap_every == 0): a record shows who holds each rung as the next sweep will find it.  When the
+ *     call's last sweep is recorded ((n_sweeps - burn_in) % thin == 0), the last record is samples_out packed, its energies
+ *     are energy_out and its rungs are rung on exit.
+ *   Layout.  W = (n + 31) / 32; ladder q = c / R, j = c % R, R = n_replicas.  All three are DEVICE pointers; nothing is
+ *     written beyond the sizes given.
+ *       trace_out[((q R + r) M + m) W + w]   uint32, n_chains M W words, BY RUNG: the packed state, at record m, of the chain
+ *         of ladder q that holds rung r then -- bit b of word w is 1 iff spin 32 w + b is +1, bits of spins >= n are 0.  As
+ *         (Q, R, M, W), [:, R-1] is the history of the target: at every record a sample at ladder[R-1].
+ *       energy_trace_out[(q R + r) M + m]    float64, n_chains M, BY RUNG: that chain's carried energy E_c ("DVG PT v1": the
+ *         start walk plus (s_new - s_old) f_i per update) at record m.  May be NULL.
+ *       rung_trace_out[c M + m]              uint8, n_chains M, BY CHAIN: the rung chain c holds at record m.  May be NULL.
+ *     Only the order of the float64 additions of a recorded energy is the implementation's (it sums a copy of the chain's
+ *     partial sums: the carried energy itself goes on unchanged).
+ *   Continuation.  As "DVG PT v1"; the record rule counts from the call's first sweep: two calls of S1 + S2 sweeps that hand
+ *     state and rung on with sweep0 advanced by S1 record, at burn_in = 0 and thin = 1, what one call of S1 + S2 sweeps
+ *     records -- but for the second call's start energies, summed afresh.
+ *   DVG_E_INVALID, before any launch: what dvg_gibbs_sample_tempered rejects (dyn != NULL included); trace_out == NULL (a
+ *     draw that records nothing is dvg_gibbs_sample_tempered); burn_in < 0; thin < 1; M < 1.  DVG_E_UNSUPPORTED as the exchange
+ *     draw: it takes that draw's plan, kernel forms and LDS unchanged -- a record is packed from the chain's own state row and
+ *     registers, behind the exchange's barrier, and adds no barrier.  A rejected call writes nothing. */
+int dvg_gibbs_sample_tempered_traced(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                                     float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                     const float *ladder, int n_replicas, int swap_every,
+                                     int8_t *state, int32_t *rung, int n_chains, uint32_t chain_id0, uint64_t seed,
+                                     uint32_t sweep0, int n_sweeps, int init, float *samples_out,
+                                     double *energy_out, uint32_t *accept_out,
+                                     uint32_t *trace_out, double *energy_trace_out, uint8_t *rung_trace_out, int burn_in, int thin,
+                                     const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and

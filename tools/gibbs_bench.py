@@ -14,6 +14,11 @@ schedule and the same ladder; a second line gives the sums of the last draw's lo
 geometric ladder 10 -> 20), timed as the ais rows are -- the raw call on persistent chains and rungs: once with no exchange due
 (swap_every beyond every sweep: the weighed draw's work per update, nothing else) and once with an exchange after every sweep; a
 second line gives the last draw's accepted exchanges per pair of rungs.
+`tempered_trace`: also the traced exchange draw (dvg_gibbs_sample_tempered_traced: the exchange draw plus, per rung and recorded
+sweep, the packed state and energy of the chain holding it, and per chain the rung), `replicas=R` as above, `thin=T` (default 1),
+swap_every=1: the raw exchange call, the traced call with all three records and with the states alone, the cost per record; then
+the two routes to a history of the ladder through the sampler -- a sample_tempered call per record that hands state and rungs on
+plus a pack_spins of its samples, against one sample_tempered_trace -- and whether the two record the same states.
 `trace`: also the traced draw (dvg_gibbs_sample_traced: the plain draw plus the chains' states after every `thin`-th sweep, one bit
 per spin), timed as the ais rows are -- the raw call on persistent chains -- at thin=10 and thin=1 (burn_in 0); then
 dvg_grbm_moments_packed over the thin=1 records (chains x sweeps rows of n / 8 bytes) and, next to it, dvg_grbm_suffstats over the
@@ -168,6 +173,81 @@ if "tempered" in sys.argv:
         row(name, ts, Q * R * n * sweeps, out)
         print(f"  {'':26s} {Q} ladders x {R}: accepted per pair {accept.view(Q, R).sum(0)[:-1].tolist()} of {Q * (sweeps // every // 2)}"
               f"  sum of energies {float(energy.sum()):.6e}")
+if "tempered_trace" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    R = max([int(a.split("=")[1]) for a in sys.argv if a.startswith("replicas=")] + [4])
+    thin = max([int(a.split("=")[1]) for a in sys.argv if a.startswith("thin=")] + [1])
+    Q, W, M = C // R, (n + 31) // 32, sweeps // thin
+    ladder_host = smp.beta_schedule(10.0, 20.0, R)
+    ladder = torch.from_numpy(ladder_host).cuda()
+    state = torch.empty((Q * R, n), dtype=torch.int8, device="cuda")
+    rung = torch.empty((Q * R,), dtype=torch.int32, device="cuda")
+    out = torch.empty((Q * R, n), dtype=torch.float32, device="cuda")
+    energy = torch.empty((Q * R,), dtype=torch.float64, device="cuda")
+    accept = torch.empty((Q * R,), dtype=torch.int32, device="cuda")
+    bits = torch.empty((Q, R, M, W), dtype=torch.int32, device="cuda")
+    e_trace = torch.empty((Q, R, M), dtype=torch.float64, device="cuda")
+    walk = torch.empty((Q, R, M), dtype=torch.uint8, device="cuda")
+    at = [0]
+
+    def exchange():
+        _lib.check(_lib.lib().dvg_gibbs_sample_tempered(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0,
+                                                        ladder.data_ptr(), R, 1, state.data_ptr(), rung.data_ptr(), Q * R, 0, seed,
+                                                        at[0], sweeps, int(at[0] == 0), out.data_ptr(), energy.data_ptr(),
+                                                        accept.data_ptr(), None, _lib.stream_ptr()), "dvg_gibbs_sample_tempered")
+        at[0] += sweeps
+        return out
+
+    def recorded(with_energies, with_walk):
+        def draw():
+            _lib.check(_lib.lib().dvg_gibbs_sample_tempered_traced(
+                s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0, ladder.data_ptr(), R, 1, state.data_ptr(),
+                rung.data_ptr(), Q * R, 0, seed, at[0], sweeps, int(at[0] == 0), out.data_ptr(), energy.data_ptr(), accept.data_ptr(),
+                bits.data_ptr(), e_trace.data_ptr() if with_energies else None, walk.data_ptr() if with_walk else None, 0, thin, None,
+                _lib.stream_ptr()), "dvg_gibbs_sample_tempered_traced")
+            at[0] += sweeps
+            return out
+        return draw
+
+    ts, o = timed(exchange)
+    t_plain = float(np.median(ts))
+    row(f"tempered, {Q} x {R}, swap_every=1", ts, Q * R * n * sweeps, o)
+    at[0] = 0
+    ts, o = timed(recorded(True, True))
+    t_all = float(np.median(ts))
+    row(f"... traced, thin={thin}, all three", ts, Q * R * n * sweeps, o)
+    at[0] = 0
+    ts, o = timed(recorded(False, False))
+    t_bits = float(np.median(ts))
+    row(f"... traced, thin={thin}, states only", ts, Q * R * n * sweeps, o)
+    print(f"  {'':26s} {M} records: {(t_all - t_plain) / M:.3f} us per record with energies and walk, {(t_bits - t_plain) / M:.3f} us the "
+          f"states alone ({Q * R * (4 * W + 9)} B a record)")
+
+    # the route without the entry: a call per record that hands state and rungs on, and a pack_spins per call
+    def by_calls():
+        res, rows = None, []
+        for m in range(M):
+            res = s.sample_tempered(lin, quad, 0.05, (-4, 4), (-1, 1), ladder_host, num_ladders=Q, num_sweeps=thin, swap_every=1,
+                                    start=None if res is None else res.state, rungs=None if res is None else res.rungs)
+            rows.append(smp.pack_spins(res.samples))
+        return torch.stack(rows, 2)
+
+    def by_entry():
+        return s.sample_tempered_trace(lin, quad, 0.05, (-4, 4), (-1, 1), ladder_host, num_ladders=Q, num_sweeps=sweeps,
+                                       swap_every=1, thin=thin).bits
+
+    ts, a = timed(by_calls)
+    t_calls = float(np.median(ts))
+    print(f"  {'a call per record + pack':26s} {t_calls:9.1f} us per draw  ({t_calls / M:.2f} us per record; min {min(ts):.1f} max {max(ts):.1f})")
+    ts, b = timed(by_entry)
+    t_entry = float(np.median(ts))
+    print(f"  {'sample_tempered_trace':26s} {t_entry:9.1f} us per draw  ({t_calls / t_entry:.2f} x faster; min {min(ts):.1f} max {max(ts):.1f})")
+    s.reset()  # (the streams advanced while timing: compared from the same start)
+    a = by_calls()
+    s.reset()
+    b = by_entry()
+    print(f"  {'':26s} from the same start the two routes record the same states: {bool(torch.equal(a, b))} (but for near ties: the route by "
+          f"calls sums its start energies afresh every call)")
 if "trace" in sys.argv:
     s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
     W = (n + 31) // 32
