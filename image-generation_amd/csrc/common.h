@@ -82,6 +82,8 @@ enum KernelId : int {
   K_WGRAD_WINO,     // conv_wino_wgrad8_kernel (profiler name "conv_wino_wgrad_kernel"): Winograd form of the encoder's 3x3 weight gradients (work = executed FLOPs)
   K_IGEMM_WINO4,    // conv_wino4_kernel: Winograd F(4x4,3x3) form of the encoder's 3x3 layers (work = executed FLOPs: 1/4 of the direct form's)
   K_WGRAD_WINO4,    // conv_wino4_wgrad_kernel: F(4x4,3x3) form of the encoder's 3x3 weight gradients (work = executed FLOPs)
+  K_CORR_TRANSPOSE, // packed_correlation_transpose_kernel (correlation.hip): packed rows -> bit columns
+  K_CORR_PRODUCT,   // packed_correlation_kernel: the spins x spins product on bit columns (work = n n T spin products)
   K_COUNT
 };
 

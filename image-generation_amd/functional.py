@@ -421,6 +421,60 @@ def grbm_energy_packed(bits, graph, linear, quadratic, *, prefactor=1.0, linear_
     return out.view(groups, rows) if bits.dim() == 3 else out
 
 
+# rows of one slab of dvg_packed_correlation's product kernel (CR_SLAB_ROWS, csrc/correlation.hip): the most a 32-bit count sees
+PACKED_CORRELATION_SLAB_ROWS = 1 << 18
+
+
+def packed_correlation(bits, *, n, spin_sums=True, out=None):
+    """Exact full pair-correlation sums of bit-packed +-1 rows (``dvg_packed_correlation``, "DVG corr v1"): every pair of spins,
+    not the graph's edges only.  ``bits``: (rows, W) or (C, M, W) int32 on the device (``sampler.pack_spins``,
+    ``sampler.Trace.bits``; bits of spins >= n are ignored); all rows are pooled.  The last dimension must have stride 1, the
+    other strides are taken from the tensor, so slices need no copy.  Returns ``(spin_sum (n,) | None, pair_sum (n, n))``
+    int64: the sums over the rows of s_i (``spin_sums=False``: None) and of s_i s_j -- symmetric, the diagonal the number of
+    rows.  ``out``: such a pair to add onto (pooling calls).  ``sampler.Correlations.from_sums`` turns them into estimates.
+    It allocates its workspace, the size of the input; no host sync."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError(f"n must be an integer >= 1, got {n!r}")
+    n = int(n)
+    W = (n + 31) // 32
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
+        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
+                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
+    if W > 1 and bits.stride(-1) != 1:
+        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
+    rows = int(bits.shape[-2])
+    rs = int(bits.stride(-2)) if rows > 1 else W
+    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
+    gs = int(bits.stride(0)) if groups > 1 else 0
+    if rs < W or gs < 0:
+        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
+    spin_sum = pair_sum = None
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise _lib.DvgError("out must be a pair (spin_sum | None, pair_sum)")
+        spin_sum, pair_sum = out
+        if (spin_sum is not None) != bool(spin_sums):
+            raise _lib.DvgError(f"out: spin_sum must be {'a tensor' if spin_sums else 'None'} with spin_sums={bool(spin_sums)}")
+        for name, t, shape in (("spin_sum", spin_sum, (n,)), ("pair_sum", pair_sum, (n, n))):
+            if name == "spin_sum" and t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                    t.device != bits.device:
+                raise _lib.DvgError(f"out: {name} must be a contiguous {shape} int64 tensor on {bits.device}")
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    bd = bits.detach()
+    if out is None:
+        spin_sum = torch.empty((n,), dtype=torch.int64, device=bd.device) if spin_sums else None
+        pair_sum = torch.empty((n, n), dtype=torch.int64, device=bd.device)
+    with torch.cuda.device(bd.device):
+        ws = _ws(lib().dvg_packed_correlation_workspace_bytes(rows, groups, n), bd.device)
+        check(lib().dvg_packed_correlation(bd.data_ptr(), rows, rs, groups, gs, n, _lib.ptr(spin_sum), pair_sum.data_ptr(),
+                                           int(out is not None), ws.data_ptr(), ws.numel(), stream_ptr(bd.device)),
+              "dvg_packed_correlation")
+    return spin_sum, pair_sum
+
+
 Resampled = collections.namedtuple("Resampled", "parents state family weights")
 
 

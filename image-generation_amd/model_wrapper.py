@@ -947,6 +947,46 @@ class ModelWrapper:
                                         quadratic_range=self.quadratic_range, **kw)
 
     @torch.no_grad()
+    def prior_correlations(self, **kw):
+        """The prior's correlations between EVERY pair of latent spins under the distribution the sampler draws from: the
+        :class:`~.sampler.Correlations` over every record of one traced draw
+        (``GraphRestrictedBoltzmannMachine.model_correlations``; ``num_reads``, ``num_sweeps``, ``burn_in``, ``thin``, ``start``
+        are passed on, ``num_reads`` defaults to NUM_READS) -- ``chi_sg``, and through ``off_edge_share(graph)`` how much of
+        the prior's correlation sits on pairs the graph has no coupling for.  Rank-local and eval-mode, like ``prior_overlap``;
+        of the sampler's counters only ``trace_sweep_count`` moves."""
+        self._dvae.eval()
+        self._grbm.eval()
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        return self._grbm.model_correlations(self.sampler, prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                             quadratic_range=self.quadratic_range, **kw)
+
+    @torch.no_grad()
+    def latent_correlation_gap(self, images: torch.Tensor, k: int = 16, **kw) -> dict:
+        """Is the graph rich enough for the encoder's latent code?  Encode ``images`` -> hard spins (heaviside, H(0) = 0, as
+        ``latent_novelty`` does) -> packed rows (``sampler.pack_spins``) -> their full :class:`~.sampler.Correlations`
+        (``dvg_packed_correlation``), set against the prior's from one traced draw (:meth:`prior_correlations`, ``**kw``
+        passed on).  Returns a dict: ``data`` / ``prior``, the two :class:`~.sampler.Correlations`; ``spin_rms``,
+        ``pair_rms``, ``edge_rms``, ``off_edge_rms`` of ``data.gap(prior, graph)`` -- the quasi-NLL gradient matches the
+        edges only, so ``off_edge_rms`` beside ``edge_rms`` is what training cannot close; ``off_edge_share_data``, the share
+        of the data's squared connected correlation on pairs that are not edges; ``top_pairs``, ``(i, j, value)`` of the
+        ``k`` non-edges of largest |C_ij| in the data: the couplings the graph lacks most.  Rank-local and eval-mode, like
+        ``prior_overlap``."""
+        from .sampler import Correlations, pack_spins
+
+        self._dvae.eval()
+        self._grbm.eval()
+        images = images.to(self._device)
+        spins = F.heaviside_latent_to_discrete(self._dvae.encoder(images)).squeeze(1)  # (B, n) +-1
+        n = int(spins.shape[1])
+        spin_sum, pair_sum = F.packed_correlation(pack_spins(spins), n=n)
+        data = Correlations.from_sums(spin_sum, pair_sum, int(spins.shape[0]))
+        prior = self.prior_correlations(**kw)
+        plan = self._grbm.plan
+        return dict(data=data, prior=prior, **data.gap(prior, plan), off_edge_share_data=data.off_edge_share(plan),
+                    top_pairs=data.top_pairs(k, plan))
+
+    @torch.no_grad()
     def prior_mixing(self, max_lag=None, **kw):
         """How the sampler's chains mix on the prior: the :class:`~.sampler.Autocorrelation` of one traced draw
         (``GraphRestrictedBoltzmannMachine.mixing``; ``num_reads``, ``num_sweeps``, ``burn_in``, ``thin``, ``start`` are

@@ -244,6 +244,17 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         return m.mean_spin.reshape(self._linear.shape), m.mean_pair.reshape(self._quadratic.shape)
 
     @torch.no_grad()
+    def model_correlations(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """The model's correlations between EVERY pair of spins, estimated over every record of one traced draw
+        (:meth:`sample_trace`, ``**kw`` passed on; the sums are exact integers, ``dvg_packed_correlation``).  Returns the
+        :class:`~.sampler.Correlations` (:meth:`Trace.correlations`): ``connected``, ``pearson``, ``chi_sg``,
+        ``off_edge_share(graph)`` -- what :meth:`model_moments` cannot show, the pairs that are not edges.  The local
+        :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "model_correlations")
+        trace = self.sample_trace(sampler, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range, **kw)
+        return trace.correlations()
+
+    @torch.no_grad()
     def mixing(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, max_lag=None, **kw):
         """How the sampler's chains mix on this model: one traced draw (:meth:`sample_trace`, ``**kw`` passed on) and its
         :class:`~.sampler.Autocorrelation` over lags 0 .. ``max_lag`` records (:meth:`Trace.autocorrelation`): ``rho``,

@@ -588,6 +588,128 @@ class Overlap:
         return f"Overlap(n={self.n})"
 
 
+class Correlations:
+    """Full pair correlations of +-1 rows from their exact sums (``dvg_packed_correlation``, "DVG corr v1"): ``spin_sum`` (n,)
+    int64 = sum over rows of s_i, ``pair_sum`` (n, n) int64 = sum over rows of s_i s_j for EVERY pair of spins, ``count`` = T
+    the number of rows.  Every member is float64 torch on the sums' device (CPU tensors too), no host sync.  With m =
+    spin_sum / T and P = pair_sum / T:
+
+    ``mean_spin`` (n,): m;  ``mean_pair`` (n, n): P;  ``connected`` (n, n): C = P - m m^T;
+    ``pearson`` (n, n): C_ij / sqrt(C_ii C_jj), NaN where a spin is frozen (C_ii = 0);
+    ``chi_sg`` (): (1 / n) sum_ij C_ij^2, the diagonal included -- the spin-glass susceptibility;
+    ``on_edges(graph)`` (E,): C at the plan's (edge_i, edge_j), shaped like ``quadratic``;
+    ``off_edge_share(graph)`` (): sum of C_ij^2 over the pairs i < j that are NOT edges / the same over all i < j -- the share
+    of the correlation the graph has no coupling for; NaN if the denominator is 0;
+    ``top_pairs(k, graph=None)``: ``(i, j, value)``, the k pairs i < j of largest |C_ij| (fewer if there are fewer), edges
+    excluded when a graph is given, ``value`` = C_ij; ties go to the smaller flat index i n + j;
+    ``gap(other, graph=None)``: a dict against another :class:`Correlations` -- ``spin_rms`` the root mean square of m - m',
+    ``pair_rms`` that of P - P' over i < j, and with a graph ``edge_rms`` / ``off_edge_rms`` the same over the edges / over
+    the pairs i < j that are not edges (NaN over no pairs).
+    ``graph``: a :class:`GraphHandle`, or its plan."""
+
+    def __init__(self, spin_sum, pair_sum, count):
+        self.spin_sum, self.pair_sum, self.count = spin_sum, pair_sum, int(count)
+
+    @classmethod
+    def from_sums(cls, spin_sum: torch.Tensor, pair_sum: torch.Tensor, count: int) -> "Correlations":
+        if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or int(count) < 1:
+            raise ValueError(f"count must be an integer >= 1, got {count!r}")
+        if not torch.is_tensor(spin_sum) or spin_sum.dtype != torch.int64 or spin_sum.dim() != 1 or spin_sum.shape[0] < 1:
+            raise ValueError("spin_sum must be a one-dimensional int64 tensor")
+        n = int(spin_sum.shape[0])
+        if not torch.is_tensor(pair_sum) or pair_sum.dtype != torch.int64 or tuple(pair_sum.shape) != (n, n):
+            raise ValueError(f"pair_sum must be a ({n}, {n}) int64 tensor")
+        if pair_sum.device != spin_sum.device:
+            raise ValueError(f"pair_sum must be on the device of spin_sum ({spin_sum.device}), got {pair_sum.device}")
+        return cls(spin_sum, pair_sum, count)
+
+    @property
+    def n(self) -> int:
+        return int(self.spin_sum.shape[0])
+
+    @property
+    def mean_spin(self):
+        return self.spin_sum.to(torch.float64) / self.count
+
+    @property
+    def mean_pair(self):
+        return self.pair_sum.to(torch.float64) / self.count
+
+    @property
+    def connected(self):
+        m = self.mean_spin
+        return self.mean_pair - m[:, None] * m[None, :]
+
+    @property
+    def pearson(self):
+        c = self.connected
+        d = torch.diagonal(c)
+        return c / torch.sqrt(d[:, None] * d[None, :])
+
+    @property
+    def chi_sg(self):
+        return (self.connected ** 2).sum() / self.n
+
+    def _edges(self, graph):
+        """The plan's edge list as device index tensors, the (n, n) bool mask of the pairs i < j that are edges, and (host
+        integers) the number of distinct edges and of pairs i < j."""
+        plan = getattr(graph, "plan", graph)
+        n = self.n
+        if int(plan.n) != n:
+            raise ValueError(f"the graph has {int(plan.n)} spins, the sums {n}")
+        ei, ej = np.asarray(plan.edge_i, dtype=np.int64), np.asarray(plan.edge_j, dtype=np.int64)
+        lo, hi = np.minimum(ei, ej), np.maximum(ei, ej)
+        mask = np.zeros((n, n), dtype=bool)
+        mask[lo, hi] = True
+        dev = self.pair_sum.device
+        return (torch.from_numpy(ei).to(dev), torch.from_numpy(ej).to(dev), torch.from_numpy(mask).to(dev), int(mask.sum()),
+                n * (n - 1) // 2)
+
+    def _upper(self):
+        return torch.triu(torch.ones((self.n, self.n), dtype=torch.bool, device=self.pair_sum.device), diagonal=1)
+
+    def on_edges(self, graph):
+        ei, ej, _mask, _e, _p = self._edges(graph)
+        return self.connected[ei, ej]
+
+    def off_edge_share(self, graph):
+        _ei, _ej, mask, _e, _p = self._edges(graph)
+        c2 = self.connected ** 2
+        upper = self._upper()
+        return (c2 * (upper & ~mask)).sum() / (c2 * upper).sum()
+
+    def top_pairs(self, k: int, graph=None):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0:
+            raise ValueError(f"k must be an integer >= 0, got {k!r}")
+        n, c = self.n, self.connected
+        iu = torch.triu_indices(n, n, 1, device=c.device)  # the pairs i < j in the order of their flat index i n + j
+        key, pairs = c[iu[0], iu[1]].abs(), n * (n - 1) // 2
+        if graph is not None:
+            _ei, _ej, mask, edges, _p = self._edges(graph)
+            key = torch.where(mask[iu[0], iu[1]], torch.full_like(key, -1.0), key)  # (behind every pair that is not an edge)
+            pairs -= edges
+        order = torch.sort(key, descending=True, stable=True).indices[:min(int(k), pairs)]
+        i, j = iu[0][order], iu[1][order]
+        return i, j, c[i, j]
+
+    def gap(self, other: "Correlations", graph=None) -> dict:
+        if not isinstance(other, Correlations) or other.n != self.n:
+            raise ValueError(f"other must be Correlations of the same {self.n} spins")
+        dm = self.mean_spin - other.mean_spin.to(self.spin_sum.device)
+        d2 = (self.mean_pair - other.mean_pair.to(self.pair_sum.device)) ** 2
+        upper = self._upper()
+        rms = lambda s, cnt: torch.sqrt(s / cnt) if cnt else torch.full_like(s, float("nan"))  # noqa: E731
+        res = dict(spin_rms=torch.sqrt((dm ** 2).mean()), pair_rms=rms((d2 * upper).sum(), self.n * (self.n - 1) // 2))
+        if graph is not None:
+            ei, ej, mask, edges, pairs = self._edges(graph)
+            res["edge_rms"] = rms(d2[ei, ej].sum(), int(ei.numel()))
+            res["off_edge_rms"] = rms((d2 * (upper & ~mask)).sum(), pairs - edges)
+        return res
+
+    def __repr__(self):
+        return f"Correlations(n={self.n}, count={self.count})"
+
+
 def trace_sweeps(num_sweeps: int, burn_in: int, thin: int) -> np.ndarray:
     """The recorded sweeps of a traced draw as the numbers k + 1 (k the 0-based sweep of the call), host int64: sweep k is
     recorded iff ``k + 1 > burn_in`` and ``(k + 1 - burn_in) % thin == 0`` -- M = (num_sweeps - burn_in) // thin of them."""
@@ -665,6 +787,15 @@ class Trace:
         hist, near = F.packed_overlap(self.bits, b, n=self.n, nearest=bool(nearest))
         o = Overlap.from_hist(hist, self.n)
         return (o, near) if nearest else o
+
+    def correlations(self) -> Correlations:
+        """The full pair correlations over all C M records, pooled (``dvg_packed_correlation``: the records stay packed), as
+        a :class:`Correlations` -- every pair of spins, where :meth:`moments` has the graph's edges only."""
+        from . import functional as F  # (functional imports this module)
+
+        C, M, _W = self.bits.shape
+        spin_sum, pair_sum = F.packed_correlation(self.bits, n=self.n)
+        return Correlations.from_sums(spin_sum, pair_sum, int(C) * int(M))
 
     def __repr__(self):
         C, M, _W = self.bits.shape

@@ -373,6 +373,31 @@ int dvg_packed_overlap(const uint32_t *a, int64_t rows_a, int64_t a_row_stride, 
                        const uint32_t *b, int64_t rows_b, int64_t b_row_stride, int64_t b_group_stride,
                        int groups, int n,
                        int64_t *hist, int64_t *nearest, int accumulate, dvg_stream_t stream);
+/* The full pair-correlation sums of bit-packed spin rows, exactly ("DVG corr v1"): s_i s_j summed over the rows for EVERY pair
+ * of spins, not the graph's edges only (dvg_grbm_moments_packed) -- the spins x spins product of the +-1 rows, taken on their
+ * bits.  Rows are packed as in "DVG trace v1": W = (n + 31) / 32 words, bit b of word w = spin 32 w + b is +1; bits of spins
+ * >= n are ignored and may hold anything.  Strides count words, as in dvg_grbm_energy_packed: row r of group g starts at bits +
+ * g group_stride + r row_stride; a flat set is groups = 1, row_stride = W; slices of a trace need no copy.  All T = groups rows
+ * rows are pooled.
+ *   pair_sum[i n + j] (+)= sum over the T rows of s_i s_j, every i, j < n: int64 [n][n], both triangles written and equal, the
+ *              diagonal gets T
+ *   spin_sum[i] (+)= sum over the T rows of s_i: int64 [n]; optional (NULL: not written)
+ *   accumulate == 0 overwrites both, 1 adds onto their contents (pooling calls)
+ * Both are DEVICE pointers.  Every value is an exact integer, T - 2 popc(col_i ^ col_j) over the spins' bit columns; workgroups
+ * combine through 64-bit integer atomics only, so the result does not depend on arrival order and two calls return the same
+ * bits.  Nothing is written beyond n n and n elements.  The entry needs n only, no graph.  It enqueues two kernels on `stream`
+ * (rows -> bit columns in the workspace, then the column product) and allocates nothing.
+ *   ws: DEVICE memory, aligned to 16 bytes, of dvg_packed_correlation_workspace_bytes(rows, groups, n) bytes: the size of the
+ *       input rounded up to 1024 rows (n columns of ceil(T / 1024) 128 bytes); the query is > 0, monotone in rows, and 0 for
+ *       arguments the entry rejects.
+ * DVG_E_INVALID, before any HIP call: bits, pair_sum or ws null (or ws not aligned to 16 bytes); rows, groups or n < 1;
+ * row_stride < W; group_stride < 0.  DVG_E_UNSUPPORTED: n > 8192 (as the other packed-row entries); groups rows >= 2^62, or
+ * more than one launch takes (2^49 rows).  DVG_E_WORKSPACE: ws_bytes below the query.  A rejected call writes nothing. */
+size_t dvg_packed_correlation_workspace_bytes(int64_t rows, int64_t groups, int n);
+int dvg_packed_correlation(const uint32_t *bits, int64_t rows, int64_t row_stride,
+                           int64_t groups, int64_t group_stride, int n,
+                           int64_t *spin_sum, int64_t *pair_sum, int accumulate,
+                           void *ws, size_t ws_bytes, dvg_stream_t stream);
 /* Population annealing's resampling step ("DVG PA v1"): weighed chains -- dvg_gibbs_sample_ais returns each chain's log weight
  * -- are resampled in proportion to their weights: heavy chains are copied, light ones dropped, and the children are equally
  * weighted.  n_chains = P R: P = n_populations independent populations of R consecutive chains each; population p holds the

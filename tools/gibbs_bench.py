@@ -36,6 +36,13 @@ timed); a last line each says whether the two agree element by element.
 over the thin=1 trace of that draw (chains x sweeps rows), timed as the moments row is; next to it the stock path -- sampler.unpack_spins
 to float32 followed by dvg_grbm_energy on the scaled, clamped fields -- timed with the unpacking and without it; a last line gives the
 largest deviation of the float32 energies from the float64 ones against the float32 rounding of that call's output.
+`correlation`: also dvg_packed_correlation (the exact sums of s_i s_j over bit-packed rows for EVERY pair of spins, "DVG corr v1")
+against the stock path -- sampler.unpack_spins -> .float() -> x.T @ x, exact below 2^24 rows -- in this one process, at three sizes
+of its own (the n, chains and sweeps of the command line do not enter): the thin=1 traces of 256 chains x 200 sweeps on the Zephyr
+sub-graphs of 512 and of 1024 spins (51 200 rows each) and of 32 chains x 32 sweeps on the latter (1024 rows).  The two paths
+alternate, five timings of five calls each, medians; the raw entry with its workspace allocated once, functional.packed_correlation
+(which allocates workspace and outputs per call) beside it, and the stock product alone (the unpacking not timed); a last line each
+says whether the integers of the two paths are equal.
 `population`: also population annealing ("DVG PA v1").  (a) dvg_population_resample alone, `resample=PxR,...` (default 8x128,1x65536)
 populations x chains of n spins with normal(0, 3) log weights, states gathered, against the same operation by torch: exp of the
 shifted weights, cumsum, searchsorted, index_select (float64: its parents may differ at near ties; the line says how many do).
@@ -422,6 +429,62 @@ if "energy" in sys.argv:
     dev = (e32.double() - energy).abs()
     print(f"  {'':26s} float32 energies off by up to {float(dev.max()):.3e}, 2^-23 |E| up to {float(energy.abs().max()) * 2.0 ** -23:.3e}  "
           f"(sum of energies {float(energy.sum()):.6e})")
+if "correlation" in sys.argv:
+    from image_generation_amd import functional as F
+
+    def time_of(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            call()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / 5 * 1e3
+
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:34s} {t:9.1f} us per call  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    for nc, Cc, Mc in ((512, 256, 200), (1024, 256, 200), (1024, 32, 32)):
+        mgc, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(nc, seed, graphs.zephyr_graph(12)))
+        nodes_c, eic, ejc = graphs.edges_of(mgc)
+        plan_c = graphs.build_plan(nc, eic, ejc)
+        rc = np.random.default_rng(1)
+        lin_c = torch.from_numpy((0.05 * rc.uniform(-1, 1, nc)).astype(np.float32)).cuda()
+        quad_c = torch.from_numpy((5.0 * rc.uniform(-1, 1, plan_c.n_edges)).astype(np.float32)).cuda()
+        sc = smp.GibbsSampler(plan_c, nodes_c, beta=20.0, sweeps=Mc, seed=seed, persistent=True)
+        bits = sc.sample_trace(lin_c, quad_c, 0.05, (-4, 4), (-1, 1), num_reads=Cc).bits  # burn_in 0, thin 1: (chains, sweeps, W)
+        Wc, rows = (nc + 31) // 32, Cc * Mc
+        spin_sum = torch.empty((nc,), dtype=torch.int64, device="cuda")
+        pair_sum = torch.empty((nc, nc), dtype=torch.int64, device="cuda")
+        ws = torch.empty((int(_lib.lib().dvg_packed_correlation_workspace_bytes(Mc, Cc, nc)),), dtype=torch.uint8, device="cuda")
+
+        def packed():
+            _lib.check(_lib.lib().dvg_packed_correlation(bits.data_ptr(), Mc, Wc, Cc, Mc * Wc, nc, spin_sum.data_ptr(), pair_sum.data_ptr(), 0,
+                                                         ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "dvg_packed_correlation")
+
+        def stock():
+            x = smp.unpack_spins(bits.view(rows, Wc), nc).float()
+            return x.T @ x
+
+        x_kept = smp.unpack_spins(bits.view(rows, Wc), nc).float()
+        calls = (packed, lambda: F.packed_correlation(bits, n=nc), stock, lambda: x_kept.T @ x_kept)
+        for call in calls:
+            call()
+        torch.cuda.synchronize()
+        ts = [[] for _ in calls]
+        for _ in range(5):  # the paths alternate
+            for k, call in enumerate(calls):
+                ts[k].append(time_of(call))
+        print(f" correlation: {rows} rows ({Cc} chains x {Mc} records) of {nc} spins, {4 * Wc} B a row packed, {4 * nc} B unpacked")
+        t_packed = report("dvg_packed_correlation", ts[0], f"{nc} x {nc} sums, workspace {ws.numel()} B")
+        report("functional.packed_correlation", ts[1], f"allocating per call   {float(np.median(ts[1])) / t_packed:.2f} x the raw entry")
+        t_stock = report("unpack_spins + float32 x.T @ x", ts[2], f"{float(np.median(ts[2])) / t_packed:.2f} x the raw entry")
+        report("float32 x.T @ x alone", ts[3], f"the unpacking not timed   {float(np.median(ts[3])) / t_packed:.2f} x the raw entry")
+        by_torch = stock()
+        same = bool(torch.equal(by_torch.long(), pair_sum)) and bool(torch.equal(x_kept.sum(0).long(), spin_sum))
+        print(f"  {'':34s} the two paths give the same integers: {same}  (sum of pair sums {int(pair_sum.sum())}, of spin sums "
+              f"{int(spin_sum.sum())}); not slower than the stock path with its unpack: {t_packed <= t_stock}")
 if "population" in sys.argv:
     def report(name, ts, what):
         t = float(np.median(ts))
