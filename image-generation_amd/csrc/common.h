@@ -84,6 +84,8 @@ enum KernelId : int {
   K_WGRAD_WINO4,    // conv_wino4_wgrad_kernel: F(4x4,3x3) form of the encoder's 3x3 weight gradients (work = executed FLOPs)
   K_CORR_TRANSPOSE, // packed_correlation_transpose_kernel (correlation.hip): packed rows -> bit columns
   K_CORR_PRODUCT,   // packed_correlation_kernel: the spins x spins product on bit columns (work = n n T spin products)
+  K_FIELDS_ROWS,    // grbm_fields_packed_kernel (fields.hip): local fields of packed rows, per-row outputs, per-slab pooled sums (work = n T spins)
+  K_FIELDS_REDUCE,  // grbm_fields_reduce_kernel: the slabs' pooled sums in slab order
   K_COUNT
 };
 

@@ -475,6 +475,87 @@ def packed_correlation(bits, *, n, spin_sums=True, out=None):
     return spin_sum, pair_sum
 
 
+Fields = collections.namedtuple("Fields", "log_pl unstable cond_sum cond_pair fields")
+
+
+def grbm_fields_packed(bits, graph, linear, quadratic, *, beta, prefactor=1.0, linear_range=None, quadratic_range=None,
+                       log_pl=True, unstable=True, conditional=True, fields=False, out=None):
+    """Per-spin statistics of bit-packed +-1 rows through the model's local fields (``dvg_grbm_fields_packed``, "DVG fields
+    v1"): with ``hs`` / ``Js`` the scaled, clamped float32 fields every draw uses (:func:`grbm_energy_packed`), ``f_i`` the
+    sampler's float32 local field and ``z = clamp(2 beta f, -87, 87)`` its logit, per row and in float64
+    ``log_pl = sum_i log P(s_i | rest)``, the count of ``unstable`` spins (``s_i f_i > 0``: the flip lowers the energy), and
+    pooled over the rows ``cond_sum[i] = sum_r E[s_i | rest of row r]``, ``cond_pair[e] = sum_r (m_ri s_rj + m_rj s_ri)`` -- the
+    Rao-Blackwellised moment sums.  ``bits``: (rows, W) or (C, M, W) int32 on the device, the strides taken from the tensor as
+    in :func:`grbm_energy_packed`; ``graph`` a ``GraphHandle``; ``linear`` (n) and ``quadratic`` (E) float32 on the same
+    device; ``beta`` a finite number >= 0.  ``log_pl`` / ``unstable`` / ``conditional`` / ``fields`` choose the outputs (at
+    least one).  Returns ``Fields(log_pl, unstable, cond_sum, cond_pair, fields)``: float64 and int32 (rows,) or (C, M),
+    float64 (n,) and (E,), float32 (rows, n) or (C, M, n); None for what was not asked for.  ``out``: a pair ``(cond_sum,
+    cond_pair)`` to add this call's pooled sums onto (needs ``conditional``).  The order of every addition is fixed by the
+    shapes alone: the same bits on every call.  It allocates its workspace; no host sync."""
+    n, E = int(graph.plan.n), int(graph.plan.n_edges)
+    W = (n + 31) // 32
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
+        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
+                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
+    if W > 1 and bits.stride(-1) != 1:
+        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
+    rows = int(bits.shape[-2])
+    rs = int(bits.stride(-2)) if rows > 1 else W
+    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
+    gs = int(bits.stride(0)) if groups > 1 else 0
+    if rs < W:
+        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
+    for name, t, k in (("linear", linear, n), ("quadratic", quadratic, E)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != k:
+            raise _lib.DvgError(f"{name} must be a float32 tensor of the graph's {k} values, got "
+                                f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
+    if isinstance(prefactor, bool) or not isinstance(prefactor, numbers.Real) or not float("-inf") < prefactor < float("inf"):
+        raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
+    if isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not 0 <= beta < float("inf"):
+        raise ValueError(f"beta must be a finite number >= 0, got {beta!r}")
+    hl, hh = _clamp_range(linear_range, "linear_range")
+    jl, jh = _clamp_range(quadratic_range, "quadratic_range")
+    for name, v in (("log_pl", log_pl), ("unstable", unstable), ("conditional", conditional), ("fields", fields)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{name} must be True or False, got {v!r}")
+    if not (log_pl or unstable or conditional or fields):
+        raise ValueError("no output requested: at least one of log_pl, unstable, conditional, fields must be True")
+    cond_sum = cond_pair = None
+    if out is not None:
+        if not conditional:
+            raise _lib.DvgError("out: pooled sums to add onto need conditional=True")
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise _lib.DvgError("out must be a pair (cond_sum, cond_pair)")
+        cond_sum, cond_pair = out
+        for name, t, k in (("cond_sum", cond_sum, n), ("cond_pair", cond_pair, E)):
+            if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != (k,) or not t.is_contiguous() or \
+                    t.device != bits.device:
+                raise _lib.DvgError(f"out: {name} must be a contiguous ({k},) float64 tensor on {bits.device}")
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    for name, t in (("linear", linear), ("quadratic", quadratic)):
+        if t.device != bits.device:
+            raise _lib.DvgError(f"{name} must be on the device of bits ({bits.device}), got {t.device}")
+    bd, lin, quad = bits.detach(), linear.detach().contiguous(), quadratic.detach().contiguous()
+    T, dev = groups * rows, bd.device
+    shape = (groups, rows) if bits.dim() == 3 else (rows,)
+    lp = torch.empty((T,), dtype=torch.float64, device=dev) if log_pl else None
+    un = torch.empty((T,), dtype=torch.int32, device=dev) if unstable else None
+    fo = torch.empty((T, n), dtype=torch.float32, device=dev) if fields else None
+    if conditional and out is None:
+        cond_sum = torch.empty((n,), dtype=torch.float64, device=dev)
+        cond_pair = torch.empty((E,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        ws = _ws(lib().dvg_grbm_fields_packed_workspace_bytes(graph.ptr, rows, groups), dev) if conditional else None
+        check(lib().dvg_grbm_fields_packed(graph.ptr, lin.data_ptr(), quad.data_ptr() if E else lin.data_ptr(), float(prefactor), hl,
+                                           hh, jl, jh, float(beta), bd.data_ptr(), rows, rs, groups, gs, _lib.ptr(lp), _lib.ptr(un),
+                                           _lib.ptr(cond_sum), (cond_pair.data_ptr() if E else cond_sum.data_ptr()) if conditional else None,
+                                           _lib.ptr(fo), int(out is not None), _lib.ptr(ws), ws.numel() if conditional else 0,
+                                           stream_ptr(dev)), "dvg_grbm_fields_packed")
+    return Fields(lp.view(shape) if log_pl else None, un.view(shape) if unstable else None, cond_sum, cond_pair,
+                  fo.view(*shape, n) if fields else None)
+
+
 Resampled = collections.namedtuple("Resampled", "parents state family weights")
 
 

@@ -934,6 +934,29 @@ class ModelWrapper:
         return self._grbm.log_likelihood(spins, self.sampler, log_z=result.log_z, **ranges), result
 
     @torch.no_grad()
+    def prior_pseudo_likelihood(self, images: torch.Tensor, **kw) -> dict:
+        """How well the prior fits given images' latent codes WITHOUT an estimate of ``log Z``: encode ``images`` -> hard spins
+        (heaviside, H(0) = 0, as ``prior_log_likelihood`` does) -> their :class:`~.sampler.PseudoLikelihood` under the prior
+        at the sampler's beta (``GraphRestrictedBoltzmannMachine.pseudo_likelihood``), beside that of the records of one
+        traced draw from the prior itself (``num_reads``, ``num_sweeps``, ``burn_in``, ``thin``, ``start`` are passed on,
+        ``num_reads`` defaults to NUM_READS).  Returns a dict: ``data`` / ``prior``, the two; ``gap`` = ``data.per_spin -
+        prior.per_spin`` -- at or above 0 the codes look like the prior's own draws spin by spin, far below they do not;
+        ``local_minimum_share_prior``: the share of the draw's records that sit in a local minimum of the energy.  Rank-local
+        and eval-mode, like ``prior_overlap``; of the sampler's counters only ``trace_sweep_count`` moves."""
+        self._dvae.eval()
+        self._grbm.eval()
+        images = images.to(self._device)
+        spins = F.heaviside_latent_to_discrete(self._dvae.encoder(images)).squeeze(1)  # (B, n) +-1
+        ranges = dict(prefactor=self.PREFACTOR, linear_range=self.linear_range, quadratic_range=self.quadratic_range)
+        beta = float(self.sampler.beta)
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        data = self._grbm.pseudo_likelihood(spins, beta=beta, **ranges)
+        trace = self._grbm.sample_trace(self.sampler, **ranges, **kw)
+        prior = self._grbm.pseudo_likelihood(trace.bits, beta=beta, **ranges)
+        return dict(data=data, prior=prior, gap=data.per_spin - prior.per_spin, local_minimum_share_prior=prior.local_minimum_share)
+
+    @torch.no_grad()
     def prior_moments(self, **kw):
         """The prior's moments ``<s_i>``, ``<s_i s_j>`` under the distribution the sampler draws from, over every record of
         one traced draw (``GraphRestrictedBoltzmannMachine.model_moments``; ``num_reads``, ``num_sweeps``, ``burn_in``,

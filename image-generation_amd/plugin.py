@@ -331,6 +331,37 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
             acceptance_rate=tt.final.acceptance_rate, round_trips=tt.round_trips(), flow=tt.flow())
 
     @torch.no_grad()
+    def pseudo_likelihood(self, x_or_bits: torch.Tensor, *, beta: float, prefactor: float, linear_range=None, quadratic_range=None):
+        """The :class:`~.sampler.PseudoLikelihood` of spin rows under the prefactor-scaled, clamped ``(h, J)`` at ``beta``:
+        ``sum_i log P(s_i | rest)`` per row -- the likelihood-type score that needs no ``log Z`` -- the rows' unstable spins,
+        and the Rao-Blackwellised moments (``dvg_grbm_fields_packed``).  ``x_or_bits``: bit-packed rows ((rows, W) or (C, M, W)
+        int32: ``Trace.bits``) or +-1 rows ((..., n), any other dtype; packed with ``sampler.pack_spins``), on the GPU."""
+        from .sampler import pack_spins, pseudo_likelihood
+
+        if not torch.is_tensor(x_or_bits) or not x_or_bits.is_cuda:
+            raise _lib.DvgError("x_or_bits must be a tensor on the GPU (got "
+                                f"{x_or_bits.device if torch.is_tensor(x_or_bits) else type(x_or_bits).__name__}); the HIP path has "
+                                "no CPU fallback")
+        bits = x_or_bits
+        if bits.dtype != torch.int32:
+            if bits.dim() < 2 or bits.shape[-1] != len(self._nodes):
+                raise _lib.DvgError(f"x_or_bits: +-1 rows must be (..., {len(self._nodes)}), got {tuple(bits.shape)}")
+            bits = pack_spins(bits.detach().reshape(-1, bits.shape[-1]) if bits.dim() > 3 else bits.detach())
+        return pseudo_likelihood(bits, self.graph_handle(bits.device), self._linear, self._quadratic, beta=beta, prefactor=prefactor,
+                                 linear_range=linear_range, quadratic_range=quadratic_range)
+
+    @torch.no_grad()
+    def pseudo_likelihood_grad(self, x_or_bits: torch.Tensor, *, beta: float, prefactor: float, linear_range=None,
+                               quadratic_range=None):
+        """``(mean log PL, grad_linear, grad_quadratic)``: the mean pseudo-log-likelihood of the rows
+        (:meth:`pseudo_likelihood`) and its gradient with respect to this model's ``linear`` and ``quadratic``, float64 on the
+        device and shaped like them -- ascend it and ``(h, J)`` are trained with no negative-phase sampler at all."""
+        pl = self.pseudo_likelihood(x_or_bits, beta=beta, prefactor=prefactor, linear_range=linear_range,
+                                    quadratic_range=quadratic_range)
+        gl, gq = pl.grad(prefactor, self._linear, self._quadratic, linear_range, quadratic_range)
+        return pl.mean, gl, gq
+
+    @torch.no_grad()
     def replica_overlap(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
         """Which modes the sampler's chains populate on this model: one traced draw (:meth:`sample_trace`, ``**kw`` passed
         on) and the :class:`~.sampler.Overlap` between its distinct chains at equal times (:meth:`Trace.overlap`): ``q2``,

@@ -710,6 +710,125 @@ class Correlations:
         return f"Correlations(n={self.n}, count={self.count})"
 
 
+class PseudoLikelihood:
+    """The pseudo-likelihood of T +-1 rows under a model and what comes with it (``dvg_grbm_fields_packed``, "DVG fields v1";
+    :meth:`Trace.pseudo_likelihood`): ``log_pl`` (T,) or (C, M) float64, ``sum_i log P(s_i | rest)`` of every row at ``beta``;
+    ``unstable`` int32 of the same shape, the row's spins whose flip would lower the energy; ``cond_sum`` (n,) and ``cond_pair``
+    (E,) float64, the pooled sums of ``m_ri = E[s_i | rest of row r]`` and of ``m_ri s_rj + m_rj s_ri`` per edge; ``spin_sum``
+    (n,) and ``pair_sum`` (E,) int64, the exact sums of ``s_i`` and ``s_i s_j`` over the same rows (``dvg_grbm_moments_packed``).
+    Every member is float64 torch on the data's device (CPU tensors too), no host sync:
+
+    ``count``: T (a host integer);  ``mean``: the mean of ``log_pl``;  ``per_spin``: mean / n;
+    ``std_err``: the standard error of ``mean`` -- for (C, M) the between-chain standard deviation of the chain means over
+    sqrt(C), whatever the autocorrelation within a chain; for flat rows their standard deviation (ddof = 1) over sqrt(T); NaN
+    with fewer than 2 chains or rows;
+    ``local_minimum_share``: the share of rows without an unstable spin;
+    ``mean_spin`` = cond_sum / T and ``mean_pair`` = cond_pair / (2 T): the Rao-Blackwellised ``<s_i>`` and ``<s_i s_j>``;
+    ``residual_linear`` = spin_sum - cond_sum and ``residual_quadratic`` = 2 pair_sum - cond_pair: the pseudo-likelihood's
+    residual sums, of zero mean under the model;
+    ``grad(prefactor, linear, quadratic, linear_range, quadratic_range)``: the gradient of ``mean`` with respect to the raw
+    ``linear`` and ``quadratic`` the rows were scored under, shaped like them: ``-beta residual / T`` per scaled field, times
+    ``prefactor``, times 1 where ``lo <= rn(prefactor h) <= hi`` in float32 and 0 where the clamp is active."""
+
+    def __init__(self, log_pl, unstable, cond_sum, cond_pair, spin_sum, pair_sum, beta):
+        self.log_pl, self.unstable, self.cond_sum, self.cond_pair = log_pl, unstable, cond_sum, cond_pair
+        self.spin_sum, self.pair_sum, self.beta = spin_sum, pair_sum, float(beta)
+
+    @classmethod
+    def from_outputs(cls, log_pl, unstable, cond_sum, cond_pair, spin_sum, pair_sum, beta) -> "PseudoLikelihood":
+        if not torch.is_tensor(log_pl) or log_pl.dtype != torch.float64 or log_pl.dim() not in (1, 2) or log_pl.numel() < 1:
+            raise ValueError("log_pl must be a float64 tensor of shape (rows >= 1,) or (chains >= 1, records >= 1)")
+        if not torch.is_tensor(unstable) or unstable.dtype != torch.int32 or unstable.shape != log_pl.shape:
+            raise ValueError(f"unstable must be an int32 tensor of log_pl's shape {tuple(log_pl.shape)}")
+        for name, t, dt in (("cond_sum", cond_sum, torch.float64), ("cond_pair", cond_pair, torch.float64),
+                            ("spin_sum", spin_sum, torch.int64), ("pair_sum", pair_sum, torch.int64)):
+            if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1:
+                raise ValueError(f"{name} must be a one-dimensional {str(dt).replace('torch.', '')} tensor")
+        if cond_sum.shape[0] < 1 or spin_sum.shape != cond_sum.shape or pair_sum.shape != cond_pair.shape:
+            raise ValueError(f"spin_sum {tuple(spin_sum.shape)} / pair_sum {tuple(pair_sum.shape)} must have the shapes of cond_sum "
+                             f"{tuple(cond_sum.shape)} / cond_pair {tuple(cond_pair.shape)}, at least one spin")
+        if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not 0 <= beta < float("inf"):
+            raise ValueError(f"beta must be a finite number >= 0, got {beta!r}")
+        return cls(log_pl, unstable, cond_sum, cond_pair, spin_sum, pair_sum, beta)
+
+    @property
+    def n(self) -> int:
+        return int(self.cond_sum.shape[0])
+
+    @property
+    def count(self) -> int:
+        return int(self.log_pl.numel())
+
+    @property
+    def mean(self):
+        return self.log_pl.mean()
+
+    @property
+    def per_spin(self):
+        return self.mean / self.n
+
+    @property
+    def std_err(self):
+        x = self.log_pl.mean(1) if self.log_pl.dim() == 2 else self.log_pl
+        k = int(x.shape[0])
+        if k < 2:
+            return torch.full_like(self.mean, float("nan"))
+        return x.std(0, unbiased=True) / float(np.sqrt(k))
+
+    @property
+    def local_minimum_share(self):
+        return (self.unstable == 0).to(torch.float64).mean()
+
+    @property
+    def mean_spin(self):
+        return self.cond_sum / self.count
+
+    @property
+    def mean_pair(self):
+        return self.cond_pair / (2.0 * self.count)
+
+    @property
+    def residual_linear(self):
+        return self.spin_sum.to(torch.float64) - self.cond_sum
+
+    @property
+    def residual_quadratic(self):
+        return 2.0 * self.pair_sum.to(torch.float64) - self.cond_pair
+
+    def grad(self, prefactor, linear, quadratic, linear_range=None, quadratic_range=None):
+        if isinstance(prefactor, bool) or not isinstance(prefactor, (int, float, np.integer, np.floating)) or \
+                not float("-inf") < prefactor < float("inf"):
+            raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
+        out = []
+        for name, raw, res, rng in (("linear", linear, self.residual_linear, linear_range),
+                                    ("quadratic", quadratic, self.residual_quadratic, quadratic_range)):
+            if not torch.is_tensor(raw) or raw.dtype != torch.float32 or raw.numel() != res.numel():
+                raise ValueError(f"{name} must be a float32 tensor of {res.numel()} values")
+            g = (-self.beta * float(prefactor) / self.count) * res
+            if rng is not None:
+                lo, hi = rng
+                scaled = raw.detach().reshape(-1).to(res.device) * torch.tensor(float(prefactor), dtype=torch.float32, device=res.device)
+                g = g * ((scaled >= float(lo)) & (scaled <= float(hi))).to(torch.float64)
+            out.append(g.reshape(raw.shape))
+        return out[0], out[1]
+
+    def __repr__(self):
+        return f"PseudoLikelihood(n={self.n}, count={self.count}, beta={self.beta:g})"
+
+
+def pseudo_likelihood(bits, graph, linear, quadratic, *, beta, prefactor=1.0, linear_range=None, quadratic_range=None) -> PseudoLikelihood:
+    """The :class:`PseudoLikelihood` of bit-packed rows ((rows, W) or (C, M, W) int32 on the device, views welcome) under the
+    prefactor-scaled, clamped ``(linear, quadratic)`` at ``beta``: one pass of ``dvg_grbm_fields_packed`` over the rows and
+    the exact sums of ``dvg_grbm_moments_packed``; the rows stay packed.  ``graph``: the :class:`GraphHandle` whose edge list
+    ``quadratic`` follows."""
+    from . import functional as F  # (functional imports this module)
+
+    f = F.grbm_fields_packed(bits, graph, linear, quadratic, beta=beta, prefactor=prefactor, linear_range=linear_range,
+                             quadratic_range=quadratic_range, log_pl=True, unstable=True, conditional=True, fields=False)
+    spin_sum, pair_sum = F.grbm_moments_packed(bits.detach().reshape(-1, bits.shape[-1]).contiguous(), graph)
+    return PseudoLikelihood.from_outputs(f.log_pl, f.unstable, f.cond_sum, f.cond_pair, spin_sum, pair_sum, beta)
+
+
 def trace_sweeps(num_sweeps: int, burn_in: int, thin: int) -> np.ndarray:
     """The recorded sweeps of a traced draw as the numbers k + 1 (k the 0-based sweep of the call), host int64: sweep k is
     recorded iff ``k + 1 > burn_in`` and ``(k + 1 - burn_in) % thin == 0`` -- M = (num_sweeps - burn_in) // thin of them."""
@@ -787,6 +906,15 @@ class Trace:
         hist, near = F.packed_overlap(self.bits, b, n=self.n, nearest=bool(nearest))
         o = Overlap.from_hist(hist, self.n)
         return (o, near) if nearest else o
+
+    def pseudo_likelihood(self, graph, linear, quadratic, *, beta, prefactor: float = 1.0, linear_range=None,
+                          quadratic_range=None) -> PseudoLikelihood:
+        """The :class:`PseudoLikelihood` of the C x M records under the prefactor-scaled, clamped ``(linear, quadratic)`` at
+        ``beta`` -- hand in what the draw was given and its ``local_minimum_share`` says how many records sit in a local
+        minimum, its ``mean_spin`` / ``mean_pair`` are the Rao-Blackwellised moments of :meth:`moments`' rows
+        (``dvg_grbm_fields_packed``: the records stay packed)."""
+        return pseudo_likelihood(self.bits, graph, linear, quadratic, beta=beta, prefactor=prefactor, linear_range=linear_range,
+                                 quadratic_range=quadratic_range)
 
     def correlations(self) -> Correlations:
         """The full pair correlations over all C M records, pooled (``dvg_packed_correlation``: the records stay packed), as

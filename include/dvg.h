@@ -332,6 +332,46 @@ int dvg_grbm_energy_packed(const dvg_graph_t *g, const float *linear, const floa
                            const uint32_t *bits, int64_t rows, int64_t row_stride,
                            int64_t groups, int64_t group_stride,
                            double *energy_out, dvg_stream_t stream);
+/* Local fields of bit-packed spin rows and the per-spin statistics built on them ("DVG fields v1"): the pseudo-log-likelihood
+ * of a row, its number of unstable spins, the Rao-Blackwellised moment sums and the fields themselves.  Rows are packed as in
+ * "DVG trace v1" and addressed by (rows, row_stride, groups, group_stride) in words exactly as in dvg_grbm_energy_packed; T =
+ * groups rows, row r of group g has the flat index t = g rows + r.
+ *   Fields.  hs, Js: the scaled, clamped float32 fields of "DVG energy v1" (oracle/gibbs.py::scaled_fields).
+ *   Local field.  The sampler's, bit for bit ("DVG block-Gibbs v1"): in float32 f = hs_i, then for each entry of spin i's CSR
+ *     row in row order f = rn(f + (s_j > 0 ? Js : -Js)); an isolated spin has f = hs_i.
+ *   Logit.  z = clamp(rn(two_beta f), -87, 87), two_beta = rn(2 beta) in float32: what the Gibbs update feeds to spec_exp.
+ *   Per spin, in float64 from (double)z and s = s_i:  a = s z;  nlp = max(a, 0) + log1p(exp(-|a|)) = -log P(s_i | rest);
+ *     e = exp(-|z|);  m = -sign(z) (1 - e) / (1 + e) = E[s_i | rest], m = 0 at z = 0.  A spin is UNSTABLE iff s_i f > 0 in
+ *     float32 (the flip lowers the energy by 2 s_i f); f = 0 is stable.
+ *   Outputs, all DEVICE pointers, each of the four optional (NULL), at least one given:
+ *     log_pl[T]      float64: -sum_i nlp of the row
+ *     unstable[T]    int32: the row's number of unstable spins; 0 = a local minimum of the energy
+ *     cond_sum[n], cond_pair[n_edges]   float64, given together or not at all: cond_sum[i] (+)= sum_r m_ri, cond_pair[e] (+)=
+ *                    sum_r (m_ri s_rj + m_rj s_ri) for (i, j) = (edge_i[e], edge_j[e]); accumulate == 0 overwrites both, 1
+ *                    adds the call's sums onto their contents (one addition per element)
+ *     field_out[T n] float32: the local fields, row-major
+ *   The pseudo-likelihood's residual sums follow from these and the exact integers of dvg_grbm_moments_packed: sum_r (s_i - m_i)
+ *   = spin_sum_i - cond_sum_i, and 2 pair_sum_e - cond_pair_e for an edge; they are not returned separately.
+ *   Determinism.  No floating-point atomics; the order of every float64 addition is fixed by (n, n_edges, rows, groups) alone
+ *   -- a row's nlp in a fixed order of its spins, the pooled sums row by row inside a slab of rows and then slab by slab, the
+ *   split into at most 512 slabs a function of T alone -- never by the device's CU count or arrival order: two calls return
+ *   the same bits.  Nothing is written beyond the sizes above.
+ *   ws: DEVICE memory aligned to 16 bytes, dvg_grbm_fields_packed_workspace_bytes(g, rows, groups) bytes, needed for the pooled
+ *       sums only (otherwise ignored, may be NULL): min(ceil(T / 64), 512) slabs of n + 2 n_edges float64 partial sums, reduced
+ *       in slab order by a second kernel.  The query is monotone in rows and groups and 0 for arguments the entry rejects.
+ * linear [n], quadratic [n_edges] and bits are DEVICE pointers; the call enqueues on `stream` and allocates nothing.
+ * DVG_E_INVALID, before any HIP call: g, linear, quadratic or bits null; no output requested; cond_sum without cond_pair or the
+ * reverse; ws null or not aligned to 16 bytes when the pooled sums are asked for; rows < 1; groups < 1; row_stride < W;
+ * group_stride < 0; a non-finite prefactor; beta not finite or < 0.  DVG_E_UNSUPPORTED: groups rows >= 2^62; n > 8192 (a tile's
+ * bit columns are kept in 64 KiB of LDS).  DVG_E_WORKSPACE: ws_bytes below the query.  A rejected call writes nothing. */
+size_t dvg_grbm_fields_packed_workspace_bytes(const dvg_graph_t *g, int64_t rows, int64_t groups);
+int dvg_grbm_fields_packed(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                           float prefactor, float h_lo, float h_hi, float j_lo, float j_hi, float beta,
+                           const uint32_t *bits, int64_t rows, int64_t row_stride,
+                           int64_t groups, int64_t group_stride,
+                           double *log_pl, int32_t *unstable, double *cond_sum, double *cond_pair,
+                           float *field_out, int accumulate,
+                           void *ws, size_t ws_bytes, dvg_stream_t stream);
 /* Autocorrelation sums of a bit-packed trace, exactly ("DVG acf v1"): bits (n_chains C, n_records M, W = (n + 31) / 32)
  * uint32 in the layout of "DVG trace v1" (bit b of word w = spin 32 w + b is +1; bits of spins >= n are ignored and may hold
  * anything).  With s_i(c, m) = +-1 the spin of chain c at record m, and L = max_lag:

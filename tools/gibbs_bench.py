@@ -43,6 +43,11 @@ sub-graphs of 512 and of 1024 spins (51 200 rows each) and of 32 chains x 32 swe
 alternate, five timings of five calls each, medians; the raw entry with its workspace allocated once, functional.packed_correlation
 (which allocates workspace and outputs per call) beside it, and the stock product alone (the unpacking not timed); a last line each
 says whether the integers of the two paths are equal.
+`fields`: also dvg_grbm_fields_packed (pseudo-log-likelihoods, unstable-spin counts and Rao-Blackwellised moment sums of bit-packed
+rows through the sampler's local fields, "DVG fields v1") over the thin=1 trace of that draw (chains x sweeps rows) at beta 1, the
+raw entry with outputs and workspace allocated once; next to it the stock path in torch -- sampler.unpack_spins to float32, x @
+J_dense + h, float64 softplus and tanh, the pooled products over the edge list -- timed with the unpacking and without it; a last line
+gives the largest deviations of the stock path's values (its float32 fields come from a matmul, in another order) from the entry's.
 `population`: also population annealing ("DVG PA v1").  (a) dvg_population_resample alone, `resample=PxR,...` (default 8x128,1x65536)
 populations x chains of n spins with normal(0, 3) log weights, states gathered, against the same operation by torch: exp of the
 shifted weights, cumsum, searchsorted, index_select (float64: its parents may differ at near ties; the line says how many do).
@@ -485,6 +490,58 @@ if "correlation" in sys.argv:
         same = bool(torch.equal(by_torch.long(), pair_sum)) and bool(torch.equal(x_kept.sum(0).long(), spin_sum))
         print(f"  {'':34s} the two paths give the same integers: {same}  (sum of pair sums {int(pair_sum.sum())}, of spin sums "
               f"{int(spin_sum.sum())}); not slower than the stock path with its unpack: {t_packed <= t_stock}")
+if "fields" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    trace = s.sample_trace(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)  # burn_in 0, thin 1: chains x sweeps records
+    W, M, E, beta = (n + 31) // 32, sweeps, plan.n_edges, 1.0
+    rows = C * M
+    log_pl = torch.empty((rows,), dtype=torch.float64, device="cuda")
+    unstable = torch.empty((rows,), dtype=torch.int32, device="cuda")
+    cond_sum, cond_pair = torch.empty((n,), dtype=torch.float64, device="cuda"), torch.empty((E,), dtype=torch.float64, device="cuda")
+    ws = torch.empty((_lib.lib().dvg_grbm_fields_packed_workspace_bytes(s.graph.ptr, M, C),), dtype=torch.uint8, device="cuda")
+
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:26s} {t:9.1f} us per call  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    def packed(want_cond=True):
+        _lib.check(_lib.lib().dvg_grbm_fields_packed(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0, beta,
+                                                     trace.bits.data_ptr(), M, W, C, M * W, log_pl.data_ptr(), unstable.data_ptr(),
+                                                     cond_sum.data_ptr() if want_cond else None, cond_pair.data_ptr() if want_cond else None,
+                                                     None, 0, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "dvg_grbm_fields_packed")
+        return log_pl
+
+    ts, _ = timed(packed)
+    t_packed = report("fields, packed rows", ts, f"{C} x {M} rows x {4 * W} B, {n} spins + {2 * E} CSR entries a row")
+    ts, _ = timed(lambda: packed(False))
+    report("  without the pooled sums", ts, "log_pl and unstable only")
+    hs, Js = (0.05 * lin).clamp(-4.0, 4.0), (0.05 * quad).clamp(-1.0, 1.0)  # (float32: one rounding each, as the kernel's)
+    ei_t, ej_t = torch.from_numpy(np.asarray(plan.edge_i, np.int64)).cuda(), torch.from_numpy(np.asarray(plan.edge_j, np.int64)).cuda()
+    Jd = torch.zeros((n, n), dtype=torch.float32, device="cuda")
+    Jd[ei_t, ej_t] = Js
+    Jd = Jd + Jd.T
+
+    def stock(x):
+        f = x @ Jd + hs
+        z = (2.0 * beta * f).clamp(-87.0, 87.0).double()
+        xd = x.double()
+        lp = -torch.nn.functional.softplus(xd * z).sum(1)
+        m = -torch.tanh(0.5 * z)
+        un = ((x * f) > 0).sum(1, dtype=torch.int32)
+        return lp, un, m.sum(0), (m[:, ei_t] * xd[:, ej_t] + m[:, ej_t] * xd[:, ei_t]).sum(0)
+
+    ts, _ = timed(lambda: stock(smp.unpack_spins(trace.bits.view(rows, W), n).contiguous())[0])
+    report("unpack + torch", ts, f"{rows} rows x {4 * n} B   {float(np.median(ts)) / t_packed:.1f} x the packed call")
+    x = smp.unpack_spins(trace.bits.view(rows, W), n).contiguous()
+    ts, _ = timed(lambda: stock(x)[0])
+    report("torch alone", ts, f"the unpacking not timed   {float(np.median(ts)) / t_packed:.1f} x the packed call")
+    packed()
+    lp, un, cs, cp = stock(x)
+    print(f"  {'':26s} stock path off by up to {float((lp - log_pl).abs().max()):.3e} in log_pl (|log_pl| up to {float(log_pl.abs().max()):.4g}), "
+          f"{int((un != unstable).sum())} of {rows} unstable counts, {float((cs - cond_sum).abs().max()):.3e} in cond_sum, "
+          f"{float((cp - cond_pair).abs().max()) if E else 0.0:.3e} in cond_pair  (mean log_pl {float(log_pl.mean()):.6f}, "
+          f"local minima {float((unstable == 0).double().mean()):.4f})")
 if "population" in sys.argv:
     def report(name, ts, what):
         t = float(np.median(ts))
