@@ -146,6 +146,11 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64,
          c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
     ),
+    "dvg_grbm_descend_packed": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64, c_int64,
+         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
     "dvg_packed_correlation_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "dvg_packed_correlation": (
         c_int,

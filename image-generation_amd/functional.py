@@ -556,6 +556,75 @@ def grbm_fields_packed(bits, graph, linear, quadratic, *, beta, prefactor=1.0, l
                   fo.view(*shape, n) if fields else None)
 
 
+Descent = collections.namedtuple("Descent", "bits sweeps flips unstable")
+DESCEND_MAX_SWEEPS = 65536  # (DS_MAX_SWEEPS, csrc/descent.hip: with n <= 8192 a row's flip count then fits an int32)
+
+
+def grbm_descend_packed(bits, graph, linear, quadratic, *, prefactor=1.0, linear_range=None, quadratic_range=None,
+                        max_sweeps=1000, out=None):
+    """Zero-temperature descent of bit-packed +-1 rows to local minima of the energy (``dvg_grbm_descend_packed``, "DVG descent
+    v1"): with ``hs`` / ``Js`` the scaled, clamped float32 fields every draw uses (:func:`grbm_energy_packed`) and ``f_i`` the
+    sampler's float32 local field, a sweep goes through the graph's colour classes in order and flips every unstable spin
+    (``s_i f_i > 0``; ``f_i = 0`` is stable) of the class; a row stops after its first sweep without a flip -- a fixed point --
+    or after ``max_sweeps`` (1 .. 65536) sweeps.  ``bits``: (rows, W) or (C, M, W) int32 on the device, the strides taken from
+    the tensor as in :func:`grbm_fields_packed`; ``graph`` a ``GraphHandle``; ``linear`` (n) and ``quadratic`` (E) float32 on
+    the same device.  ``out``: a contiguous int32 tensor of the input's shape for the final rows -- ``bits`` itself when
+    ``bits`` is contiguous (in place); any other sharing of memory with ``bits`` is refused.  Returns ``Descent(bits, sweeps,
+    flips, unstable)``: the final rows (pad bits 0), and int32 shaped like the leading dimensions the sweeps in which the row
+    flipped something, its flips in all, and the unstable spins left (0 = converged; non-zero only where ``sweeps ==
+    max_sweeps``).  No randomness and no sum across rows: a row's result depends on that row alone, the same bits on every
+    call.  The energy falls strictly with every flip when the float32 field sums are exact; in general ``max_sweeps`` is the
+    only promise of termination.  No workspace, no host sync."""
+    n, E = int(graph.plan.n), int(graph.plan.n_edges)
+    W = (n + 31) // 32
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
+        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
+                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
+    if W > 1 and bits.stride(-1) != 1:
+        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
+    rows = int(bits.shape[-2])
+    rs = int(bits.stride(-2)) if rows > 1 else W
+    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
+    gs = int(bits.stride(0)) if groups > 1 else 0
+    if rs < W:
+        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
+    for name, t, k in (("linear", linear, n), ("quadratic", quadratic, E)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != k:
+            raise _lib.DvgError(f"{name} must be a float32 tensor of the graph's {k} values, got "
+                                f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
+    if isinstance(prefactor, bool) or not isinstance(prefactor, numbers.Real) or not float("-inf") < prefactor < float("inf"):
+        raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
+    hl, hh = _clamp_range(linear_range, "linear_range")
+    jl, jh = _clamp_range(quadratic_range, "quadratic_range")
+    if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, numbers.Integral) or not 1 <= max_sweeps <= DESCEND_MAX_SWEEPS:
+        raise ValueError(f"max_sweeps must be an integer in 1 .. {DESCEND_MAX_SWEEPS}, got {max_sweeps!r}")
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.int32 or out.shape != bits.shape or not out.is_contiguous() or \
+                out.device != bits.device:
+            raise _lib.DvgError(f"out must be a contiguous int32 tensor of shape {tuple(bits.shape)} on {bits.device}, got "
+                                f"{(tuple(out.shape), out.dtype, out.device) if torch.is_tensor(out) else type(out).__name__}")
+        a0, b0 = bits.data_ptr(), out.data_ptr()
+        a1 = a0 + 4 * ((groups - 1) * gs + (rows - 1) * rs + W)
+        if a0 < b0 + 4 * out.numel() and b0 < a1 and not (a0 == b0 and bits.is_contiguous()):
+            raise _lib.DvgError("out shares memory with bits: in place needs out to be bits itself and bits contiguous "
+                                f"(strides {tuple(bits.stride())})")
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    for name, t in (("linear", linear), ("quadratic", quadratic)):
+        if t.device != bits.device:
+            raise _lib.DvgError(f"{name} must be on the device of bits ({bits.device}), got {t.device}")
+    bd, lin, quad = bits.detach(), linear.detach().contiguous(), quadratic.detach().contiguous()
+    T, dev = groups * rows, bd.device
+    shape = (groups, rows) if bits.dim() == 3 else (rows,)
+    res = torch.empty(tuple(bits.shape), dtype=torch.int32, device=dev) if out is None else out.detach()
+    sw, fl, un = (torch.empty((T,), dtype=torch.int32, device=dev) for _ in range(3))
+    with torch.cuda.device(dev):
+        check(lib().dvg_grbm_descend_packed(graph.ptr, lin.data_ptr(), quad.data_ptr() if E else lin.data_ptr(), float(prefactor), hl,
+                                            hh, jl, jh, bd.data_ptr(), rows, rs, groups, gs, int(max_sweeps), res.data_ptr(),
+                                            sw.data_ptr(), fl.data_ptr(), un.data_ptr(), stream_ptr(dev)), "dvg_grbm_descend_packed")
+    return Descent(res if out is None else out, sw.view(shape), fl.view(shape), un.view(shape))
+
+
 Resampled = collections.namedtuple("Resampled", "parents state family weights")
 
 

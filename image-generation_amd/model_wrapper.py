@@ -957,6 +957,31 @@ class ModelWrapper:
         return dict(data=data, prior=prior, gap=data.per_spin - prior.per_spin, local_minimum_share_prior=prior.local_minimum_share)
 
     @torch.no_grad()
+    def prior_minima(self, images: torch.Tensor = None, max_sweeps: int = 1000, **kw) -> dict:
+        """The local minima of the prior's energy that its own draws sit above, and whether given images' latent codes drain
+        into the same ones: the records of one traced draw from the prior (``num_reads``, ``num_sweeps``, ``burn_in``,
+        ``thin``, ``start`` are passed on, ``num_reads`` defaults to NUM_READS) taken by zero-temperature descent to their
+        :class:`~.sampler.Minima` (``GraphRestrictedBoltzmannMachine.descend``).  Returns a dict: ``prior``, those; with
+        ``images`` also ``data``, the ``Minima`` of their hard spins (heaviside, H(0) = 0, as ``prior_log_likelihood`` does),
+        and ``shared``, the share of the data's distinct minima that are also among the prior's (the packed rows compared
+        exactly).  Rank-local and eval-mode, like ``prior_overlap``; of the sampler's counters only ``trace_sweep_count``
+        moves."""
+        self._dvae.eval()
+        self._grbm.eval()
+        ranges = dict(prefactor=self.PREFACTOR, linear_range=self.linear_range, quadratic_range=self.quadratic_range)
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        trace = self._grbm.sample_trace(self.sampler, **ranges, **kw)
+        out = dict(prior=self._grbm.descend(trace.bits, max_sweeps=max_sweeps, **ranges))
+        if images is not None:
+            spins = F.heaviside_latent_to_discrete(self._dvae.encoder(images.to(self._device))).squeeze(1)  # (B, n) +-1
+            out["data"] = data = self._grbm.descend(spins, max_sweeps=max_sweeps, **ranges)
+            mine, theirs = data.unique()[0], out["prior"].unique()[0]
+            _rows, counts = torch.unique(torch.cat([mine, theirs]), dim=0, return_counts=True)  # (each side's rows are distinct)
+            out["shared"] = (counts == 2).sum().to(torch.float64) / float(mine.shape[0])
+        return out
+
+    @torch.no_grad()
     def prior_moments(self, **kw):
         """The prior's moments ``<s_i>``, ``<s_i s_j>`` under the distribution the sampler draws from, over every record of
         one traced draw (``GraphRestrictedBoltzmannMachine.model_moments``; ``num_reads``, ``num_sweeps``, ``burn_in``,

@@ -362,6 +362,27 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         return pl.mean, gl, gq
 
     @torch.no_grad()
+    def descend(self, x_or_bits: torch.Tensor, *, prefactor: float, linear_range=None, quadratic_range=None, max_sweeps: int = 1000):
+        """The :class:`~.sampler.Minima` of spin rows under the prefactor-scaled, clamped ``(h, J)``: every row taken by
+        zero-temperature descent -- colour class by colour class every unstable spin flips -- to a local minimum of the
+        energy, or through ``max_sweeps`` sweeps (``dvg_grbm_descend_packed``), with the energies before and after.
+        ``x_or_bits``: bit-packed rows ((rows, W) or (C, M, W) int32: ``Trace.bits``) or +-1 rows ((..., n), any other dtype;
+        packed with ``sampler.pack_spins``), on the GPU; it is left as it is."""
+        from .sampler import descend, pack_spins
+
+        if not torch.is_tensor(x_or_bits) or not x_or_bits.is_cuda:
+            raise _lib.DvgError("x_or_bits must be a tensor on the GPU (got "
+                                f"{x_or_bits.device if torch.is_tensor(x_or_bits) else type(x_or_bits).__name__}); the HIP path has "
+                                "no CPU fallback")
+        bits = x_or_bits
+        if bits.dtype != torch.int32:
+            if bits.dim() < 2 or bits.shape[-1] != len(self._nodes):
+                raise _lib.DvgError(f"x_or_bits: +-1 rows must be (..., {len(self._nodes)}), got {tuple(bits.shape)}")
+            bits = pack_spins(bits.detach().reshape(-1, bits.shape[-1]) if bits.dim() > 3 else bits.detach())
+        return descend(bits, self.graph_handle(bits.device), self._linear, self._quadratic, prefactor=prefactor,
+                       linear_range=linear_range, quadratic_range=quadratic_range, max_sweeps=max_sweeps)
+
+    @torch.no_grad()
     def replica_overlap(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
         """Which modes the sampler's chains populate on this model: one traced draw (:meth:`sample_trace`, ``**kw`` passed
         on) and the :class:`~.sampler.Overlap` between its distinct chains at equal times (:meth:`Trace.overlap`): ``q2``,

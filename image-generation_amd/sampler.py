@@ -829,6 +829,129 @@ def pseudo_likelihood(bits, graph, linear, quadratic, *, beta, prefactor=1.0, li
     return PseudoLikelihood.from_outputs(f.log_pl, f.unstable, f.cond_sum, f.cond_pair, spin_sum, pair_sum, beta)
 
 
+def _popcount32(words):
+    """The set bits of every int32 word, int64 (the words read as unsigned)."""
+    x = words.to(torch.int64) & 0xFFFFFFFF
+    x = x - ((x >> 1) & 0x55555555)
+    x = (x & 0x33333333) + ((x >> 2) & 0x33333333)
+    x = (x + (x >> 4)) & 0x0F0F0F0F
+    return ((x * 0x01010101) >> 24) & 0xFF
+
+
+class Minima:
+    """What a zero-temperature descent of T +-1 rows arrived at (``dvg_grbm_descend_packed``, "DVG descent v1";
+    :func:`descend`, :meth:`Trace.descend`): ``start_bits`` and ``bits`` (T, W) or (C, M, W) int32, the rows before and after
+    (the pad bits of ``bits`` are 0); ``sweeps``, ``flips``, ``unstable`` int32 of the leading shape -- the sweeps in which
+    the row moved, its flips in all, the unstable spins left (0 = a local minimum); ``energy_start`` and ``energy`` float64 of
+    the same shape (``dvg_grbm_energy_packed`` before and after); ``n`` the number of spins.  Every member is torch on the
+    data's device (CPU tensors too), no host sync except ``count``:
+
+    ``count``: T (a host integer);  ``converged``: bool per row, ``unstable == 0``;  ``converged_share``: its mean;
+    ``energy_drop`` = energy_start - energy;
+    ``distance``: the Hamming distance from a row to where it ended, int32 (pad bits of the start masked);
+    ``mean_flips``, ``mean_sweeps``: float64 means;
+    ``unique()``: ``(rows, counts, index)`` -- the distinct final rows (U, W) int32, their multiplicities (U,) int64 and every
+    row's index into them (leading shape, int64); ordered by falling multiplicity, ties in the order of
+    ``torch.unique(dim=0)`` on the words;
+    ``basin_entropy``: ``-sum p log p`` of the multiplicities over T;
+    ``lowest(k)``: ``(rows, energy, counts)`` of the ``k`` distinct final rows of lowest energy (all of them if fewer), by
+    rising energy, ties in ``unique()``'s order."""
+
+    def __init__(self, start_bits, bits, sweeps, flips, unstable, energy_start, energy, n):
+        self.start_bits, self.bits, self.sweeps, self.flips, self.unstable = start_bits, bits, sweeps, flips, unstable
+        self.energy_start, self.energy, self.n = energy_start, energy, int(n)
+
+    @classmethod
+    def from_outputs(cls, start_bits, bits, sweeps, flips, unstable, energy_start, energy, n) -> "Minima":
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n must be an integer >= 1, got {n!r}")
+        W = (int(n) + 31) // 32
+        if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or bits.numel() < 1:
+            raise ValueError(f"bits must be an int32 tensor of shape (rows >= 1, {W}) or (chains >= 1, records >= 1, {W})")
+        if not torch.is_tensor(start_bits) or start_bits.dtype != torch.int32 or start_bits.shape != bits.shape:
+            raise ValueError(f"start_bits must be an int32 tensor of bits' shape {tuple(bits.shape)}")
+        lead = bits.shape[:-1]
+        for name, t in (("sweeps", sweeps), ("flips", flips), ("unstable", unstable)):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or t.shape != lead:
+                raise ValueError(f"{name} must be an int32 tensor of shape {tuple(lead)}")
+        for name, t in (("energy_start", energy_start), ("energy", energy)):
+            if not torch.is_tensor(t) or t.dtype != torch.float64 or t.shape != lead:
+                raise ValueError(f"{name} must be a float64 tensor of shape {tuple(lead)}")
+        return cls(start_bits, bits, sweeps, flips, unstable, energy_start, energy, n)
+
+    @property
+    def count(self) -> int:
+        return int(self.unstable.numel())
+
+    @property
+    def converged(self):
+        return self.unstable == 0
+
+    @property
+    def converged_share(self):
+        return self.converged.to(torch.float64).mean()
+
+    @property
+    def energy_drop(self):
+        return self.energy_start - self.energy
+
+    @property
+    def distance(self):
+        x = self.start_bits ^ self.bits
+        if self.n % 32:
+            mask = torch.full((x.shape[-1],), -1, dtype=torch.int32, device=x.device)
+            mask[-1] = (1 << (self.n % 32)) - 1
+            x = x & mask
+        return _popcount32(x).sum(-1).to(torch.int32)
+
+    @property
+    def mean_flips(self):
+        return self.flips.to(torch.float64).mean()
+
+    @property
+    def mean_sweeps(self):
+        return self.sweeps.to(torch.float64).mean()
+
+    def unique(self):
+        rows, inverse, counts = torch.unique(self.bits.reshape(-1, self.bits.shape[-1]), dim=0, return_inverse=True, return_counts=True)
+        perm = torch.sort(counts, descending=True, stable=True).indices
+        rank = torch.empty_like(perm)
+        rank[perm] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
+        return rows[perm], counts[perm], rank[inverse.reshape(-1)].view(self.bits.shape[:-1])
+
+    @property
+    def basin_entropy(self):
+        _rows, counts, _index = self.unique()
+        p = counts.to(torch.float64) / float(self.count)
+        return -(p * torch.log(p)).sum()
+
+    def lowest(self, k: int):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"k must be an integer >= 1, got {k!r}")
+        rows, counts, index = self.unique()
+        e = torch.empty((rows.shape[0],), dtype=torch.float64, device=rows.device)
+        e[index.reshape(-1)] = self.energy.reshape(-1)  # (equal rows have equal energies: whichever is written last)
+        pick = torch.sort(e, stable=True).indices[:int(k)]
+        return rows[pick], e[pick], counts[pick]
+
+    def __repr__(self):
+        return f"Minima(n={self.n}, count={self.count})"
+
+
+def descend(bits, graph, linear, quadratic, *, prefactor=1.0, linear_range=None, quadratic_range=None, max_sweeps=1000) -> Minima:
+    """The :class:`Minima` of bit-packed rows ((rows, W) or (C, M, W) int32 on the device, views welcome) under the
+    prefactor-scaled, clamped ``(linear, quadratic)``: one call of ``dvg_grbm_descend_packed`` -- every row taken to a row
+    without an unstable spin, or through ``max_sweeps`` sweeps -- and two of ``dvg_grbm_energy_packed``, before and after; the
+    rows stay packed and ``bits`` is left as it is.  ``graph``: the :class:`GraphHandle` whose edge list ``quadratic``
+    follows."""
+    from . import functional as F  # (functional imports this module)
+
+    kw = dict(prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range)
+    d = F.grbm_descend_packed(bits, graph, linear, quadratic, max_sweeps=max_sweeps, **kw)
+    return Minima.from_outputs(bits.detach(), d.bits, d.sweeps, d.flips, d.unstable, F.grbm_energy_packed(bits, graph, linear, quadratic, **kw),
+                               F.grbm_energy_packed(d.bits, graph, linear, quadratic, **kw), int(graph.plan.n))
+
+
 def trace_sweeps(num_sweeps: int, burn_in: int, thin: int) -> np.ndarray:
     """The recorded sweeps of a traced draw as the numbers k + 1 (k the 0-based sweep of the call), host int64: sweep k is
     recorded iff ``k + 1 > burn_in`` and ``(k + 1 - burn_in) % thin == 0`` -- M = (num_sweeps - burn_in) // thin of them."""
@@ -915,6 +1038,14 @@ class Trace:
         (``dvg_grbm_fields_packed``: the records stay packed)."""
         return pseudo_likelihood(self.bits, graph, linear, quadratic, beta=beta, prefactor=prefactor, linear_range=linear_range,
                                  quadratic_range=quadratic_range)
+
+    def descend(self, graph, linear, quadratic, *, prefactor: float = 1.0, linear_range=None, quadratic_range=None,
+                max_sweeps: int = 1000) -> Minima:
+        """The :class:`Minima` of the C x M records under the prefactor-scaled, clamped ``(linear, quadratic)``: every record
+        quenched to the local minimum below it -- hand in what the draw was given and ``unique()`` counts the distinct minima
+        the chains sat above (``dvg_grbm_descend_packed``: the records stay packed and are left as they are)."""
+        return descend(self.bits, graph, linear, quadratic, prefactor=prefactor, linear_range=linear_range,
+                       quadratic_range=quadratic_range, max_sweeps=max_sweeps)
 
     def correlations(self) -> Correlations:
         """The full pair correlations over all C M records, pooled (``dvg_packed_correlation``: the records stay packed), as

@@ -372,6 +372,47 @@ int dvg_grbm_fields_packed(const dvg_graph_t *g, const float *linear, const floa
                            double *log_pl, int32_t *unstable, double *cond_sum, double *cond_pair,
                            float *field_out, int accumulate,
                            void *ws, size_t ws_bytes, dvg_stream_t stream);
+/* Zero-temperature descent of bit-packed spin rows to local minima of the energy ("DVG descent v1"): what takes the rows that
+ * dvg_grbm_fields_packed counts unstable spins in to a row without any.  Rows are packed as in "DVG trace v1" and addressed by
+ * (rows, row_stride, groups, group_stride) in words exactly as in dvg_grbm_energy_packed; T = groups rows, row r of group g has
+ * the flat index t = g rows + r.  Bits of spins >= n in the input are ignored.
+ *   Fields.  hs, Js: the scaled, clamped float32 fields of "DVG energy v1" (oracle/gibbs.py::scaled_fields).
+ *   Local field.  The sampler's, bit for bit: in float32 f = hs_i, then for each entry of spin i's CSR row in row order
+ *     f = rn(f + (s_j > 0 ? Js : -Js)), no contraction; an isolated spin has f = hs_i.
+ *   Unstable.  A spin is unstable iff s_i f_i > 0 in float32; f_i = 0 is stable: the rule of "DVG fields v1".
+ *   Sweep.  The colour classes k = 0 .. n_colours - 1 in the graph's order (order, class_ptr); in class k every unstable spin
+ *     of the class flips.  A class is an independent set, so flipping together equals flipping one after another in `order`.
+ *   A row runs sweeps 1, 2, .. until a sweep flips none of its spins -- the row is then a fixed point of the rule -- or
+ *   max_sweeps sweeps have run.  A row's result is a function of that row, the fields and the graph alone: never of the other
+ *   rows, their number, or how rows are placed on workgroups.  The rule has no randomness and no floating-point sum across
+ *   rows; two calls return the same bits.
+ *   Outputs, DEVICE pointers:
+ *     bits_out[T W]  required, dense: the final rows; bits of spins >= n are written as 0
+ *     sweeps[T]      int32, optional (NULL): the number of sweeps in which the row flipped at least one spin -- the first
+ *                    sweeps[t] sweeps; a row that starts at a minimum gets 0
+ *     flips[T]       int32, optional: the row's flips in all; a spin may flip in more than one sweep, so this can exceed the
+ *                    Hamming distance moved
+ *     unstable[T]    int32, optional: the unstable spins of the returned row as dvg_grbm_fields_packed counts them; 0 =
+ *                    converged; non-zero only where sweeps[t] == max_sweeps (a row whose last permitted sweep still flipped
+ *                    something is given one more field pass without flips; that pass runs only then)
+ *   In place: bits_out == bits is allowed when the input is itself dense (row_stride == W, and groups == 1 or group_stride ==
+ *   rows W).
+ *   Termination.  A flip lowers the exact energy by 2 s_i F_i, F_i the exact field; the rule tests the rounded f_i, and the
+ *   two can differ in sign only below float32 rounding of the field.  So the energy falls strictly with every flip whenever the
+ *   float32 sums are exact (fields on a coarse binary grid), and every row then ends at a fixed point; otherwise a monotone
+ *   energy is NOT promised and the descent is merely capped by max_sweeps.
+ * linear [n], quadratic [n_edges] and bits are DEVICE pointers.  The call enqueues on `stream`, allocates nothing, takes no
+ * workspace and uses no atomics on global memory.
+ * DVG_E_INVALID, before any HIP call: g, linear, quadratic, bits or bits_out null; rows < 1; groups < 1; row_stride < W;
+ * group_stride < 0; a non-finite prefactor; max_sweeps outside 1 .. 65536 (with n <= 8192 a flip count then fits an int32); the
+ * input's word range overlapping bits_out in any way other than the exact alias above.  DVG_E_UNSUPPORTED: groups rows >= 2^62;
+ * n > 8192 (a tile's bit columns are kept in 64 KiB of LDS).  A rejected call writes nothing. */
+int dvg_grbm_descend_packed(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                            float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                            const uint32_t *bits, int64_t rows, int64_t row_stride,
+                            int64_t groups, int64_t group_stride,
+                            int max_sweeps, uint32_t *bits_out, int32_t *sweeps, int32_t *flips, int32_t *unstable,
+                            dvg_stream_t stream);
 /* Autocorrelation sums of a bit-packed trace, exactly ("DVG acf v1"): bits (n_chains C, n_records M, W = (n + 31) / 32)
  * uint32 in the layout of "DVG trace v1" (bit b of word w = spin 32 w + b is +1; bits of spins >= n are ignored and may hold
  * anything).  With s_i(c, m) = +-1 the spin of chain c at record m, and L = max_lag:

@@ -1,0 +1,453 @@
+"""GPU checks of ``dvg_grbm_descend_packed`` ("DVG descent v1") -- zero-temperature descent of bit-packed rows to local minima
+-- against the numpy definition (``tests/descent_oracle.py``).  The rule has no randomness and no floating-point sum across
+rows, so every output is held to the definition exactly: ``bits_out``, ``sweeps``, ``flips``, ``unstable``.
+
+Graphs and fields as in ``test_gpu_fields_packed.py``: ``pegasus64`` (two whole words a row), ``random77`` (a partial last word,
+spin 3 isolated, degree 34, 12 colours) and ``zephyr1024``; h = 20 U(-1, 1), J = 5 U(-1, 1), prefactor 0.05 (clamps idle) and
+0.3 (both active).  Rows: 1, 63, 64, 65, 130 of random words whose bits of spins >= n are set, and of the traced records of a
+cold draw.  max_sweeps = 64 (the numpy rule converges on these inputs, so every row must report unstable == 0) and 1, 2, 3
+(most random rows are cut off: the counting pass).  The references are computed once per (graph, kind, prefactor, cap) over
+all 130 rows; a row's result depends on that row alone, so a test over the first ``rows`` takes their first ``rows``."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import descent_oracle as do  # noqa: E402
+import trace_oracle  # noqa: E402
+from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
+from oracle import gibbs  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+SEED = 775321899904
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IGUARD = -77
+ROWS = [1, 63, 64, 65, 130]
+GRAPHS = ["pegasus64", "random77", "zephyr1024"]
+H_RANGE, J_RANGE = (-4.0, 4.0), (-1.0, 1.0)
+PREFACTORS, CAPS = (0.05, 0.3), (64, 1, 2, 3)
+OUT = ("bits", "sweeps", "flips", "unstable")
+T_ALL, CHAINS, RECORDS = 130, 26, 5
+
+
+@functools.lru_cache(maxsize=None)
+def _solver_plan(fam, n):
+    g = graphs.pegasus_graph(16) if fam == "pegasus" else graphs.zephyr_graph(12)
+    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, g))
+    nodes, ei, ej = graphs.edges_of(mg)
+    return graphs.build_plan(n, ei, ej), nodes
+
+
+@functools.lru_cache(maxsize=None)
+def _random_plan(n=77, p_edge=0.35):
+    rng = np.random.default_rng(n)
+    iu, ju = np.triu_indices(n, 1)
+    keep = rng.uniform(size=iu.size) < p_edge
+    keep &= (iu != 3) & (ju != 3)
+    plan = graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
+    assert np.diff(plan.adj_ptr)[3] == 0
+    return plan
+
+
+@functools.lru_cache(maxsize=None)
+def _grid_plan(a=8, b=9):
+    idx = np.arange(a * b).reshape(a, b)
+    ei = np.concatenate([idx[:, :-1].ravel(), idx[:-1, :].ravel()]).astype(np.int64)
+    ej = np.concatenate([idx[:, 1:].ravel(), idx[1:, :].ravel()]).astype(np.int64)
+    return graphs.build_plan(a * b, ei, ej)
+
+
+class _Case:
+    """The graph, its handle, 130 rows of each kind on the device -- a traced draw of 26 chains x 5 records, and random words
+    -- and ``generic`` float32 fields whose clamps are active at prefactor 0.3 and idle at 0.05.  Built once per graph."""
+
+    def __init__(self, name, plan=None):
+        self.name = name
+        self.plan = plan = plan or {"pegasus64": lambda: _solver_plan("pegasus", 64)[0], "random77": _random_plan,
+                                    "zephyr1024": lambda: _solver_plan("zephyr", 1024)[0]}[name]()
+        rng = np.random.default_rng(plan.n)
+        self.h = (20.0 * rng.uniform(-1, 1, plan.n)).astype(np.float32)
+        self.J = (5.0 * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)
+        self.lin, self.quad = torch.from_numpy(self.h).cuda(), torch.from_numpy(self.J).cuda()
+        self.gh = gh = smp.GraphHandle(plan, "cuda")
+        self.W = (plan.n + 31) // 32
+        state = torch.empty((CHAINS, plan.n), dtype=torch.int8, device="cuda")
+        traced = torch.empty((T_ALL, self.W), dtype=torch.int32, device="cuda")
+        # (the draw: prefactor 0.3, both clamps active, beta 20 -- cold chains, 1000 sweeps before the 5 records)
+        _lib.check(_lib.lib().dvg_gibbs_sample_traced(gh.ptr, self.lin.data_ptr(), self.quad.data_ptr(), 0.3, -4.0, 4.0, -1.0, 1.0,
+                                                      20.0, state.data_ptr(), CHAINS, 1000, SEED, 6, 1000 + RECORDS, 1, None,
+                                                      traced.data_ptr(), 1000, 1, None, _lib.stream_ptr()), "dvg_gibbs_sample_traced")
+        torch.cuda.synchronize()
+        noise = rng.integers(0, 2 ** 32, size=(T_ALL, self.W), dtype=np.uint64).astype(np.uint32)
+        if plan.n % 32:
+            assert (noise[:, -1] >> np.uint32(plan.n % 32)).any()  # bits of spins >= n are set
+        self.rows = {"trace": traced, "noise": torch.from_numpy(noise.view(np.int32)).cuda()}
+        self.host = {k: v.cpu().numpy().view(np.uint32) for k, v in self.rows.items()}
+        self.pad_noise = rng.integers(0, 2 ** 32, size=(T_ALL, 3), dtype=np.uint64).astype(np.uint32)
+
+    @functools.lru_cache(maxsize=None)
+    def scaled(self, prefactor):
+        return gibbs.scaled_fields(self.h, self.J, prefactor, H_RANGE, J_RANGE)
+
+    @functools.lru_cache(maxsize=None)
+    def want(self, kind, prefactor, cap):
+        hs, Js = self.scaled(prefactor)
+        p = self.plan
+        return do.descend(self.host[kind], p.n, hs, Js, p.edge_i, p.edge_j, p.order, p.class_ptr, cap)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    return _Case(name)
+
+
+class _Got:
+    pass
+
+
+def _run(case, bits, rows, row_stride, groups, group_stride, prefactor, cap, which=OUT, *, lin=None, quad=None, null=None,
+         in_place=False, out_at=None, expect=0):
+    """The C entry on device pointers with a guard word behind every output; returns the outputs as numpy (guards checked).
+    ``which``: the outputs asked for (``bits`` always is); ``in_place``: bits_out = bits (then no guard behind it);
+    ``out_at``: a device address to use as bits_out instead (for calls that must be rejected)."""
+    W, T = case.W, rows * groups
+    dev = {"bits": torch.full((T * W + 1,), IGUARD, dtype=torch.int32, device="cuda")}
+    for k in OUT[1:]:
+        if k in which:
+            dev[k] = torch.full((T + 1,), IGUARD, dtype=torch.int32, device="cuda")
+    before = {k: v.clone() for k, v in dev.items()}
+    bits_before = bits.clone()
+    ptr = dict(g=case.gh.ptr, linear=(lin if lin is not None else case.lin).data_ptr(),
+               quadratic=(quad if quad is not None else case.quad).data_ptr(), bits=bits.data_ptr(),
+               bits_out=out_at if out_at is not None else bits.data_ptr() if in_place else dev["bits"].data_ptr())
+    if null is not None:
+        ptr[null] = None
+    L = _lib.lib()
+    rc = L.dvg_grbm_descend_packed(ptr["g"], ptr["linear"], ptr["quadratic"], prefactor, H_RANGE[0], H_RANGE[1], J_RANGE[0], J_RANGE[1],
+                                   ptr["bits"], rows, row_stride, groups, group_stride, cap, ptr["bits_out"],
+                                   *[_lib.ptr(dev.get(k)) for k in OUT[1:]], _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert rc == expect, (rc, L.dvg_last_error())
+    got = _Got()
+    if rc != 0:
+        for k, v in dev.items():
+            assert torch.equal(v, before[k]), f"a rejected call wrote {k}"
+        assert torch.equal(bits, bits_before), "a rejected call wrote bits"
+        return got
+    if in_place:
+        assert torch.equal(dev["bits"], before["bits"])
+        dev["bits"] = torch.cat([bits.reshape(-1)[:T * W], dev["bits"][-1:]])
+    else:
+        assert torch.equal(bits, bits_before), "the input was written"
+    for k in OUT:
+        a = dev[k].cpu().numpy() if k in dev else None
+        if a is not None:
+            assert a[-1] == IGUARD, f"written past {k}"
+            a = a[:-1]
+        setattr(got, k, a)
+    got.bits = got.bits.view(np.uint32).reshape(T, W)
+    return got
+
+
+def _same(got, want, sel, what=""):
+    for k in OUT:
+        a = getattr(got, k)
+        if a is not None:
+            assert np.array_equal(a, getattr(want, k)[sel]), (what, k, int((a != getattr(want, k)[sel]).sum()))
+
+
+# ------------------------------------------------------------------------------------------------ 1. the definition, exactly
+@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("name", GRAPHS)
+def test_outputs_equal_the_definition(name, rows):
+    case = _case(name)
+    sel = np.arange(rows)
+    for prefactor in PREFACTORS:
+        hs, Js = case.scaled(prefactor)
+        active = bool((np.abs(hs) == 4.0).any() and (np.abs(Js) == 1.0).any())
+        assert active == (prefactor == 0.3)  # the clamps bite at 0.3 and are idle at 0.05
+        for kind in ("trace", "noise"):
+            for cap in CAPS:
+                want = case.want(kind, prefactor, cap)
+                got = _run(case, case.rows[kind][:rows].contiguous(), rows, case.W, 1, 0, prefactor, cap)
+                _same(got, want, sel, (kind, prefactor, cap))
+                assert (got.unstable[got.sweeps < cap] == 0).all() and (got.flips >= got.sweeps).all()
+                if cap == 64:
+                    assert (got.unstable == 0).all() and (got.sweeps < 64).all()  # converged, every row
+            if kind == "noise":  # (teeth: random rows move, need more than one sweep, and cap 1 leaves unstable spins behind)
+                assert (case.want(kind, prefactor, 1).unstable > 0).any() and case.want(kind, prefactor, 64).sweeps.max() > 3
+    w = case.want("noise", 0.3, 64)
+    print(f"DESCENT {name} rows={rows}: noise at 0.3 sweeps up to {w.sweeps.max()}, flips up to {w.flips.max()}, "
+          f"{len(np.unique(w.bits, axis=0))} minima of {T_ALL}; cut off at 1 sweep: {int((case.want('noise', 0.3, 1).unstable > 0).sum())} rows")
+
+
+# ------------------------------------------------------------------------------------------------ 2. cross-checks
+@pytest.mark.parametrize("name", GRAPHS)
+def test_unstable_is_the_fields_count_and_a_second_descent_moves_nothing(name):
+    case = _case(name)
+    for prefactor in PREFACTORS:
+        for kind in ("trace", "noise"):
+            for cap in (1, 2, 64):
+                got = _run(case, case.rows[kind], T_ALL, case.W, 1, 0, prefactor, cap)
+                out = torch.from_numpy(got.bits.view(np.int32)).cuda()
+                f = F.grbm_fields_packed(out, case.gh, case.lin, case.quad, beta=1.0, prefactor=prefactor, linear_range=H_RANGE,
+                                         quadratic_range=J_RANGE, log_pl=False, conditional=False)
+                assert np.array_equal(f.unstable.cpu().numpy(), got.unstable), (kind, prefactor, cap)
+            again = _run(case, out, T_ALL, case.W, 1, 0, prefactor, 64)  # (out: the rows of cap 64)
+            assert np.array_equal(again.bits, got.bits) and not again.sweeps.any() and not again.flips.any() and not again.unstable.any()
+
+
+@pytest.mark.parametrize("name", GRAPHS)
+def test_each_row_alone_gives_the_batch_result(name):
+    """130 calls of one row each, at a cap that cuts some rows off: a row's result does not depend on its tile."""
+    case = _case(name)
+    W, L = case.W, _lib.lib()
+    bits = case.rows["noise"]
+    for cap in (3, 64):
+        want = _run(case, bits, T_ALL, W, 1, 0, 0.3, cap)
+        out = torch.full((T_ALL * W + 1,), IGUARD, dtype=torch.int32, device="cuda")
+        cnt = torch.full((3, T_ALL + 1), IGUARD, dtype=torch.int32, device="cuda")
+        for r in range(T_ALL):
+            _lib.check(L.dvg_grbm_descend_packed(case.gh.ptr, case.lin.data_ptr(), case.quad.data_ptr(), 0.3, -4.0, 4.0, -1.0, 1.0,
+                                                 bits[r].data_ptr(), 1, W, 1, 0, cap, out[r * W:].data_ptr(), cnt[0, r:].data_ptr(),
+                                                 cnt[1, r:].data_ptr(), cnt[2, r:].data_ptr(), _lib.stream_ptr()), "dvg_grbm_descend_packed")
+        torch.cuda.synchronize()
+        assert int(out[-1]) == IGUARD and (cnt[:, -1] == IGUARD).all()
+        assert np.array_equal(out[:-1].cpu().numpy().view(np.uint32).reshape(T_ALL, W), want.bits)
+        for k, name_ in enumerate(OUT[1:]):
+            assert np.array_equal(cnt[k, :-1].cpu().numpy(), getattr(want, name_)), (cap, name_)
+
+
+# ------------------------------------------------------------------------------------------------ 3. layouts
+@pytest.mark.parametrize("C,M", [(1, 5), (26, 5), (65, 2)])
+@pytest.mark.parametrize("name", GRAPHS)
+def test_trace_layout(name, C, M):
+    """groups = C, group_stride = M W, rows = M, row_stride = W: element c M + m is record m of chain c."""
+    case = _case(name)
+    for kind in ("trace", "noise"):
+        bits = case.rows[kind][:C * M].contiguous()
+        got = _run(case, bits, M, case.W, C, M * case.W, 0.3, 3)
+        _same(got, case.want(kind, 0.3, 3), np.arange(C * M), kind)
+        via = F.grbm_descend_packed(bits.view(C, M, case.W), case.gh, case.lin, case.quad, prefactor=0.3, linear_range=H_RANGE,
+                                    quadratic_range=J_RANGE, max_sweeps=3)
+        assert via.bits.shape == (C, M, case.W) and via.bits.dtype == torch.int32 and via.bits.is_contiguous()
+        for k, t in zip(OUT, via):
+            assert t.is_cuda and t.dtype == torch.int32 and (k == "bits" or t.shape == (C, M))
+            assert np.array_equal(t.cpu().numpy().view(np.uint32 if k == "bits" else np.int32).reshape(getattr(got, k).shape), getattr(got, k)), k
+
+
+@pytest.mark.parametrize("name", GRAPHS)
+def test_views_and_padded_rows_need_no_copy(name):
+    case = _case(name)
+    W = case.W
+    call = lambda b, **kw: F.grbm_descend_packed(b, case.gh, case.lin, case.quad, prefactor=0.05, linear_range=H_RANGE,  # noqa: E731
+                                                 quadratic_range=J_RANGE, max_sweeps=2, **kw)
+    for kind in ("trace", "noise"):
+        want = case.want(kind, 0.05, 2)
+        flat, trace = case.rows[kind], case.rows[kind].view(CHAINS, RECORDS, W)
+        idx = np.arange(T_ALL).reshape(CHAINS, RECORDS)
+        padded = torch.from_numpy(np.concatenate([case.host[kind], case.pad_noise], axis=1).view(np.int32)).cuda()  # rows of W + 3 words
+        for view, sel in ((trace[:, 1:], idx[:, 1:]), (trace[::2], idx[::2]), (trace[:, ::3], idx[:, ::3]), (flat[5::7], idx.ravel()[5::7]),
+                          (padded[:, :W], idx.ravel()), (padded.view(CHAINS, RECORDS, W + 3)[:, :, :W], idx),
+                          (trace[:1].expand(3, RECORDS, W), np.tile(idx[:1], (3, 1)))):
+            assert not view.is_contiguous() or view.shape[0] == 1
+            before = view.clone()
+            d = call(view)
+            assert d.bits.shape == view.shape and d.bits.is_contiguous() and d.sweeps.shape == sel.shape
+            assert np.array_equal(d.bits.cpu().numpy().view(np.uint32).reshape(-1, W), want.bits[sel.ravel()])
+            for k, t in zip(OUT[1:], d[1:]):
+                assert np.array_equal(t.cpu().numpy().ravel(), getattr(want, k)[sel.ravel()]), k
+            assert torch.equal(view, before)
+        # a padded output is refused, the padded input's own memory as output too
+        with pytest.raises(_lib.DvgError, match="out must"):
+            call(flat, out=padded[:, :W])
+        with pytest.raises(_lib.DvgError, match="out shares memory"):
+            call(padded[:, :W], out=padded.view(-1)[:T_ALL * W].view(T_ALL, W))
+
+
+@pytest.mark.parametrize("name", GRAPHS)
+def test_in_place_equals_out_of_place(name):
+    case = _case(name)
+    W = case.W
+    for kind in ("trace", "noise"):
+        for cap in (2, 64):
+            want = case.want(kind, 0.3, cap)
+            for rows, groups, gs in ((T_ALL, 1, 0), (RECORDS, CHAINS, RECORDS * W), (1, 65, W)):
+                T = rows * groups
+                bits = case.rows[kind][:T].clone()
+                got = _run(case, bits, rows, W, groups, gs, 0.3, cap, in_place=True)
+                _same(got, want, np.arange(T), (kind, cap, rows, groups))
+            bits = case.rows[kind].clone().view(CHAINS, RECORDS, W)
+            d = F.grbm_descend_packed(bits, case.gh, case.lin, case.quad, prefactor=0.3, linear_range=H_RANGE, quadratic_range=J_RANGE,
+                                      max_sweeps=cap, out=bits)
+            assert d.bits is bits and np.array_equal(bits.cpu().numpy().view(np.uint32).reshape(-1, W), want.bits)
+            assert np.array_equal(d.flips.cpu().numpy().ravel(), want.flips)
+            other = torch.full_like(bits, IGUARD)
+            d = F.grbm_descend_packed(case.rows[kind], case.gh, case.lin, case.quad, prefactor=0.3, linear_range=H_RANGE,
+                                      quadratic_range=J_RANGE, max_sweeps=cap, out=other.view(T_ALL, W))
+            assert torch.equal(other, bits) and d.bits.data_ptr() == other.data_ptr()
+
+
+def test_pad_bits_of_the_output_are_zero_whatever_the_input_holds():
+    case = _case("random77")  # n = 77: 13 spins in the last word
+    noise = case.rows["noise"]
+    assert ((case.host["noise"][:, -1] >> np.uint32(13)) != 0).all()
+    clean = noise.clone()
+    clean[:, -1] &= (1 << 13) - 1
+    full = noise.clone()
+    full[:, -1] |= ~((1 << 13) - 1)
+    outs = [_run(case, b, T_ALL, case.W, 1, 0, 0.3, cap) for cap in (1, 64) for b in (noise, clean, full)]
+    for k in range(0, 6, 3):
+        assert (outs[k].bits[:, -1] >> np.uint32(13) == 0).all()
+        for other in outs[k + 1:k + 3]:
+            for name in OUT:
+                assert np.array_equal(getattr(outs[k], name), getattr(other, name)), name
+
+
+def test_an_exact_zero_field_leaves_the_spin_alone():
+    """An 8 x 9 grid with J = -1/2 and h_i = deg_i / 2 + d (at most 2.5: no clamp bites), rows all up and all down.  All up
+    has f_i = d exactly: at d = 0 every field is 0 and nothing moves; at d = -0.5 it is a minimum; at d = +0.5 every spin is
+    unstable whatever its neighbours do, the first sweep flips all of them and the row ends all down, where f_i = deg_i + d > 0
+    meets s_i = -1.  All down never moves."""
+    plan = _grid_plan()
+    case = _Case("grid72", plan)
+    up = trace_oracle.pack(np.ones((1, plan.n), np.int8))
+    bits = torch.from_numpy(np.concatenate([up, np.zeros_like(up)]).view(np.int32)).cuda()
+    J = torch.full((plan.n_edges,), -0.5, device="cuda")
+    deg = np.diff(plan.adj_ptr).astype(np.float32)
+    for d, moves in ((0.0, False), (-0.5, False), (0.5, True)):
+        h = np.float32(0.5) * deg + np.float32(d)
+        got = _run(case, bits, 2, case.W, 1, 0, 1.0, 64, lin=torch.from_numpy(h).cuda(), quad=J)
+        hs, Js = gibbs.scaled_fields(h, np.full(plan.n_edges, -0.5, np.float32), 1.0, H_RANGE, J_RANGE)
+        assert np.array_equal(hs, h)
+        want = do.descend(bits.cpu().numpy(), plan.n, hs, Js, plan.edge_i, plan.edge_j, plan.order, plan.class_ptr, 64)
+        _same(got, want, np.arange(2), d)
+        assert not got.unstable.any() and got.flips[1] == 0 and np.array_equal(got.bits[1], np.zeros(case.W, np.uint32))
+        if moves:
+            assert got.flips[0] == plan.n and got.sweeps[0] == 1 and np.array_equal(got.bits[0], np.zeros(case.W, np.uint32))
+        else:
+            assert got.flips[0] == 0 and got.sweeps[0] == 0 and np.array_equal(got.bits[0], up[0])
+
+
+# ------------------------------------------------------------------------------------------------ 4. robustness
+@pytest.mark.parametrize("name", GRAPHS)
+def test_each_optional_output_alone_and_two_calls_agree(name):
+    case = _case(name)
+    for kind, rows, cap in (("trace", T_ALL, 64), ("noise", 65, 2)):
+        bits = case.rows[kind][:rows].contiguous()
+        both = [_run(case, bits, rows, case.W, 1, 0, 0.3, cap) for _ in range(2)]
+        for k in OUT:
+            assert np.array_equal(getattr(both[0], k), getattr(both[1], k)), k
+        for which in ((), ("sweeps",), ("flips",), ("unstable",), ("sweeps", "unstable")):
+            alone = _run(case, bits, rows, case.W, 1, 0, 0.3, cap, which)
+            for k in OUT:
+                assert (getattr(alone, k) is None) == (k != "bits" and k not in which)
+                if k == "bits" or k in which:
+                    assert np.array_equal(getattr(alone, k), getattr(both[0], k)), (which, k)
+
+
+def test_rejected_calls_write_nothing():
+    case = _case("random77")
+    W = case.W
+    pool = torch.cat([case.rows["noise"][:35].reshape(-1), torch.full((35 * W + 64,), IGUARD, dtype=torch.int32, device="cuda")])
+    bits = pool[:35 * W].view(35, W)
+    for null in ("g", "linear", "quadratic", "bits", "bits_out"):
+        _run(case, bits, 35, W, 1, 0, 0.3, 8, null=null, expect=-1)
+    _run(case, bits, 0, W, 1, 0, 0.3, 8, expect=-1)
+    _run(case, bits, 35, W, 0, 0, 0.3, 8, expect=-1)
+    _run(case, bits, 35, W - 1, 1, 0, 0.3, 8, expect=-1)
+    _run(case, bits, 5, W, 7, -1, 0.3, 8, expect=-1)
+    _run(case, bits, 35, W, 1, 0, float("nan"), 8, expect=-1)
+    for cap in (0, -1, 65537):
+        _run(case, bits, 35, W, 1, 0, 0.3, cap, expect=-1)
+    for words in (1, W, 35 * W - 1):  # an output that starts inside the input
+        _run(case, bits, 35, W, 1, 0, 0.3, 8, out_at=bits.data_ptr() + 4 * words, expect=-1)
+    _run(case, bits, 5, W, 7, 0, 0.3, 8, in_place=True, expect=-1)  # in place, but every group is the same five rows
+    _run(case, bits, 17, 2 * W, 1, 0, 0.3, 8, in_place=True, expect=-1)  # in place, but padded rows
+    assert "overlap" in _lib.lib().dvg_last_error().decode()
+
+
+# ------------------------------------------------------------------------------------------------ 5. the Python layers
+def test_python_layers_equal_the_c_entry():
+    from image_generation_amd.plugin import GraphRestrictedBoltzmannMachine
+
+    plan, nodes = _solver_plan("zephyr", 128)
+    rng = np.random.default_rng(2)
+    h = (20.0 * rng.uniform(-1, 1, plan.n)).astype(np.float32)
+    J = (5.0 * rng.uniform(-1, 1, plan.n_edges)).astype(np.float32)
+    grbm = GraphRestrictedBoltzmannMachine(nodes, list(zip(np.asarray(nodes)[plan.edge_i].tolist(),
+                                                           np.asarray(nodes)[plan.edge_j].tolist()))).cuda()
+    with torch.no_grad():
+        grbm._linear.copy_(torch.from_numpy(h).cuda())
+        grbm._quadratic.copy_(torch.from_numpy(J).cuda())
+    ranges = dict(prefactor=0.3, linear_range=H_RANGE, quadratic_range=J_RANGE)
+    s = smp.GibbsSampler(plan, nodes, beta=0.2, sweeps=4, seed=SEED, persistent=True, h_range=H_RANGE, j_range=J_RANGE)
+    trace = grbm.sample_trace(s, num_reads=9, num_sweeps=12, burn_in=2, thin=3, **ranges)  # (warm: the records are no minima)
+    gh, lin, quad = grbm.graph_handle("cuda"), grbm._linear.detach(), grbm._quadratic.detach()
+    kept = trace.bits.clone()
+    hs, Js = gibbs.scaled_fields(h, J, 0.3, H_RANGE, J_RANGE)
+    for cap in (2, 1000):
+        d = F.grbm_descend_packed(trace.bits, gh, lin, quad, max_sweeps=cap, **ranges)
+        want = do.descend(kept.cpu().numpy(), plan.n, hs, Js, plan.edge_i, plan.edge_j, plan.order, plan.class_ptr, cap)
+        assert d.sweeps.shape == (9, 3) and np.array_equal(d.bits.cpu().numpy().view(np.uint32).reshape(27, -1), want.bits)
+        for k, t in zip(OUT[1:], d[1:]):
+            assert np.array_equal(t.cpu().numpy().ravel(), getattr(want, k)), (cap, k)
+        assert want.flips.min() > 0 and (cap == 2) == bool(want.unstable.any())
+        e0 = F.grbm_energy_packed(kept, gh, lin, quad, **ranges)
+        e1 = F.grbm_energy_packed(d.bits, gh, lin, quad, **ranges)
+        for m in (trace.descend(gh, lin, quad, max_sweeps=cap, **ranges), smp.descend(trace.bits, gh, lin, quad, max_sweeps=cap, **ranges),
+                  grbm.descend(trace.bits, max_sweeps=cap, **ranges), grbm.descend(trace.unpack(), max_sweeps=cap, **ranges)):
+            assert isinstance(m, smp.Minima) and m.count == 27 and m.n == plan.n
+            assert torch.equal(m.bits, d.bits) and torch.equal(m.sweeps, d.sweeps) and torch.equal(m.flips, d.flips)
+            assert torch.equal(m.unstable, d.unstable) and torch.equal(m.start_bits, kept)
+            assert torch.equal(m.energy_start, e0) and torch.equal(m.energy, e1)
+            assert m.converged_share.is_cuda and float(m.converged_share) == float((want.unstable == 0).mean())
+            est = do.estimates(kept.cpu().numpy(), want.bits, want.sweeps, want.flips, want.unstable, e0.cpu().numpy(), e1.cpu().numpy(), plan.n)
+            assert np.array_equal(m.distance.cpu().numpy().ravel(), est["distance"]) and (m.distance <= m.flips).all()
+            assert abs(float(m.basin_entropy) - est["basin_entropy"]) < 1e-12 and float(m.mean_flips) == est["mean_flips"]
+            rows, counts, index = m.unique()
+            wr, wc, wi = do.unique_minima(want.bits)
+            assert np.array_equal(rows.cpu().numpy(), wr) and np.array_equal(counts.cpu().numpy(), wc) and np.array_equal(index.cpu().numpy().ravel(), wi)
+            lr, le, lc = m.lowest(2)
+            assert lr.shape[0] == min(2, len(wr)) and float(le[0]) == float(e1.min()) and int(lc.sum()) <= 27
+        assert torch.equal(trace.bits, kept)  # the records are left as they are
+    flat = grbm.descend(trace.bits.view(27, -1), **ranges)
+    assert flat.sweeps.shape == (27,) and torch.equal(flat.bits, d.bits.view(27, -1)) and bool(flat.converged.all())
+    assert float(flat.energy_drop.min()) > 0  # every record moved, and (for these fields) moved downhill
+    with pytest.raises(_lib.DvgError, match="device of bits"):
+        F.grbm_descend_packed(trace.bits, gh, lin.cpu(), quad, **ranges)
+
+
+def test_model_wrapper_prior_minima():
+    from image_generation_amd.data import synthetic_images
+    from image_generation_amd.model_wrapper import ModelWrapper
+
+    torch.manual_seed(0)
+    m = ModelWrapper("Advantage_system4", n_latents=64, training_parameter_file=os.path.join(ROOT, "tests", "golden", "step_params.yaml"))
+    m.setup()
+    m.overlap_sampler = False  # (as in the AIS file: this test takes no stream from the process's pool)
+    images = synthetic_images(5, seed=3, device="cuda").reshape(5, 1, 32, 32)
+    res = m.prior_minima(images, num_reads=33, num_sweeps=20, burn_in=6, thin=2)
+    s = m.sampler
+    assert (s.trace_sweep_count, s.sweep_count, s.calls, s.ais_sweep_count) == (20, 0, 0, 0) and s._state is None
+    assert set(res) == {"prior", "data", "shared"}
+    data, prior = res["data"], res["prior"]
+    assert isinstance(data, smp.Minima) and data.sweeps.shape == (5,) and prior.sweeps.shape == (33, 7)
+    assert bool(prior.converged.all()) and bool(data.converged.all()) and float(prior.energy_drop.min()) >= 0.0
+    mine = {tuple(r) for r in data.unique()[0].cpu().tolist()}
+    theirs = {tuple(r) for r in prior.unique()[0].cpu().tolist()}
+    assert float(res["shared"]) == len(mine & theirs) / len(mine)
+    s.reset()  # the same draw again, by hand
+    only = m.prior_minima(num_reads=33, num_sweeps=20, burn_in=6, thin=2, max_sweeps=1)
+    assert set(only) == {"prior"} and (only["prior"].sweeps <= 1).all() and torch.equal(only["prior"].start_bits, prior.start_bits)
+    h, J = m._grbm._linear.detach().cpu().numpy().reshape(-1), m._grbm._quadratic.detach().cpu().numpy().reshape(-1)
+    hs, Js = gibbs.scaled_fields(h, J, m.PREFACTOR, m.linear_range, m.quadratic_range)
+    plan = m._grbm.plan
+    for got, cap in ((prior, 1000), (only["prior"], 1)):
+        want = do.descend(prior.start_bits.cpu().numpy(), plan.n, hs, Js, plan.edge_i, plan.edge_j, plan.order, plan.class_ptr, cap)
+        assert np.array_equal(got.bits.cpu().numpy().view(np.uint32).reshape(-1, want.bits.shape[1]), want.bits)
+        assert np.array_equal(got.flips.cpu().numpy().ravel(), want.flips) and np.array_equal(got.unstable.cpu().numpy().ravel(), want.unstable)

@@ -48,6 +48,11 @@ rows through the sampler's local fields, "DVG fields v1") over the thin=1 trace 
 raw entry with outputs and workspace allocated once; next to it the stock path in torch -- sampler.unpack_spins to float32, x @
 J_dense + h, float64 softplus and tanh, the pooled products over the edge list -- timed with the unpacking and without it; a last line
 gives the largest deviations of the stock path's values (its float32 fields come from a matmul, in another order) from the entry's.
+`descend`: also dvg_grbm_descend_packed (zero-temperature descent of bit-packed rows to local minima, "DVG descent v1") over chains x
+sweeps rows of two kinds -- the thin=1 trace of that draw, and random words -- max_sweeps 1000, the raw entry with its outputs
+allocated once; next to it the stock path in torch with its unpack and repack -- sampler.unpack_spins to float32, per colour class
+x @ J_dense[:, class] + h[class] and a masked sign flip, swept until no row moves (one host read per sweep), sampler.pack_spins
+-- and a last line each that says whether the two paths return equal rows, and what the descent did (sweeps, flips, minima).
 `population`: also population annealing ("DVG PA v1").  (a) dvg_population_resample alone, `resample=PxR,...` (default 8x128,1x65536)
 populations x chains of n spins with normal(0, 3) log weights, states gathered, against the same operation by torch: exp of the
 shifted weights, cumsum, searchsorted, index_select (float64: its parents may differ at near ties; the line says how many do).
@@ -542,6 +547,57 @@ if "fields" in sys.argv:
           f"{int((un != unstable).sum())} of {rows} unstable counts, {float((cs - cond_sum).abs().max()):.3e} in cond_sum, "
           f"{float((cp - cond_pair).abs().max()) if E else 0.0:.3e} in cond_pair  (mean log_pl {float(log_pl.mean()):.6f}, "
           f"local minima {float((unstable == 0).double().mean()):.4f})")
+if "descend" in sys.argv:
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    trace = s.sample_trace(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)  # burn_in 0, thin 1: chains x sweeps records
+    W, M, cap = (n + 31) // 32, sweeps, 1000
+    rows = C * M
+    noise = torch.from_numpy(np.random.default_rng(2).integers(0, 2 ** 32, size=(rows, W), dtype=np.uint64).astype(np.uint32).view(np.int32)).cuda()
+    out = torch.empty((rows, W), dtype=torch.int32, device="cuda")
+    n_sweeps, n_flips, left = (torch.empty((rows,), dtype=torch.int32, device="cuda") for _ in range(3))
+
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:26s} {t:9.1f} us per call  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    hs, Js = (0.05 * lin).clamp(-4.0, 4.0), (0.05 * quad).clamp(-1.0, 1.0)  # (float32: one rounding each, as the kernel's)
+    ei_t, ej_t = torch.from_numpy(np.asarray(plan.edge_i, np.int64)).cuda(), torch.from_numpy(np.asarray(plan.edge_j, np.int64)).cuda()
+    Jd = torch.zeros((n, n), dtype=torch.float32, device="cuda")
+    Jd[ei_t, ej_t] = Js
+    Jd = Jd + Jd.T
+    classes = [torch.from_numpy(np.asarray(plan.order[plan.class_ptr[k]:plan.class_ptr[k + 1]], np.int64)).cuda() for k in range(plan.n_colours)]
+    Jc, hc = [Jd[:, c].contiguous() for c in classes], [hs[c] for c in classes]
+
+    def stock(bits):
+        x = smp.unpack_spins(bits, n)
+        for _ in range(cap):
+            moved = torch.zeros((), dtype=torch.bool, device="cuda")
+            for c, J_c, h_c in zip(classes, Jc, hc):
+                xc = x[:, c]
+                flip = (xc * (x @ J_c + h_c)) > 0
+                x[:, c] = torch.where(flip, -xc, xc)
+                moved |= flip.any()
+            if not bool(moved):
+                break
+        return smp.pack_spins(x)
+
+    for kind, bits in (("trace", trace.bits.view(rows, W)), ("random", noise)):
+        def packed():
+            _lib.check(_lib.lib().dvg_grbm_descend_packed(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0,
+                                                          bits.data_ptr(), rows, W, 1, 0, cap, out.data_ptr(), n_sweeps.data_ptr(),
+                                                          n_flips.data_ptr(), left.data_ptr(), _lib.stream_ptr()), "dvg_grbm_descend_packed")
+            return out
+
+        ts, _ = timed(packed)
+        t_packed = report(f"descend, {kind} rows", ts, f"{rows} rows x {4 * W} B, {n} spins + {2 * plan.n_edges} CSR entries a row and sweep")
+        ts, by_torch = timed(lambda: stock(bits))
+        t_stock = report("unpack + torch + pack", ts, f"{rows} rows x {4 * n} B   {float(np.median(ts)) / t_packed:.1f} x the packed call")
+        packed()
+        print(f"  {'':26s} the two paths return equal rows: {bool(torch.equal(by_torch, out))} ({int((by_torch != out).any(1).sum())} of {rows} "
+              f"differ); sweeps up to {int(n_sweeps.max())} (mean {float(n_sweeps.double().mean()):.2f}), flips a row {float(n_flips.double().mean()):.1f}, "
+              f"{int((left > 0).sum())} rows cut off, {int(torch.unique(out, dim=0).shape[0])} distinct minima; not slower than the stock path: "
+              f"{t_packed <= t_stock}")
 if "population" in sys.argv:
     def report(name, ts, what):
         t = float(np.median(ts))
