@@ -2,6 +2,7 @@
 //   pair_sum[i][j] = sum over the T pooled rows of s_i s_j for EVERY pair of spins, spin_sum[i] = sum of s_i -- the spins x spins
 // product X^T X of the +-1 rows, on their bits.  Two stream-ordered launches, no workgroup waiting on another.
 #include "common.h"
+#include "packed_rows.h"
 
 namespace dvg {
 
@@ -31,21 +32,11 @@ __global__ __launch_bounds__(CT_TILES * 64) void packed_correlation_transpose_ke
   long long plus = 0, seen = 0;
   for (int64_t job = blockIdx.x; job < jobs; job += gridDim.x) {
     const int64_t idx = (job * CT_TILES + wave) * 64 + lane;
-    const uint32_t* row = nullptr;  // (null: a row beyond the last)
-    if (idx < total) {
-      const int64_t g = groups == 1 ? 0 : idx / rows;
-      row = bits + g * group_stride + (idx - g * rows) * row_stride;
-    }
+    const uint32_t* row = packed_row(bits, idx, total, rows, row_stride, groups, group_stride);  // (null: a row beyond the last)
 #pragma unroll
     for (int ww = 0; ww < CT_WORDS; ++ww) {
       const int w = CT_WORDS * (int)blockIdx.y + ww;
-      const uint32_t word = (row && w < W) ? row[w] : 0u;
-      unsigned long long col = 0ull;
-#pragma unroll
-      for (int b = 0; b < 32; ++b) {
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
-        if (lane == b) col = m;
-      }
+      const unsigned long long col = bit_column((row && w < W) ? row[w] : 0u, lane);
       if (lane < 32) cs[wave * CT_STRIDE + 32 * ww + lane] = col;
     }
     __syncthreads();
@@ -187,21 +178,11 @@ extern "C" int dvg_packed_correlation(const uint32_t* bits, int64_t rows, int64_
   DVG_REQUIRE(pair_sum, "packed_correlation: pair_sum is null");
   DVG_REQUIRE(ws, "packed_correlation: ws is null");
   DVG_REQUIRE(((uintptr_t)ws & 15) == 0, "packed_correlation: ws=%p is not aligned to 16 bytes", ws);
-  DVG_REQUIRE(rows >= 1, "packed_correlation: rows=%lld must be at least 1", (long long)rows);
-  DVG_REQUIRE(groups >= 1, "packed_correlation: groups=%lld must be at least 1", (long long)groups);
   DVG_REQUIRE(n >= 1, "packed_correlation: n=%d must be at least 1", n);
   const int64_t W = ((int64_t)n + 31) / 32;
-  DVG_REQUIRE(row_stride >= W, "packed_correlation: row_stride=%lld is less than the %lld words of a row", (long long)row_stride,
-              (long long)W);
-  DVG_REQUIRE(group_stride >= 0, "packed_correlation: group_stride=%lld is negative", (long long)group_stride);
-  if (n > CR_MAX_N) {
-    set_error("packed_correlation: n=%d > %d (the limit of the packed-row entries)", n, CR_MAX_N);
-    return DVG_E_UNSUPPORTED;
-  }
-  if ((__int128)groups * rows >= ((__int128)1 << 62)) {
-    set_error("packed_correlation: groups=%lld x rows=%lld rows are 2^62 or more", (long long)groups, (long long)rows);
-    return DVG_E_UNSUPPORTED;
-  }
+  DVG_TRY(check_row_geometry("packed_correlation", rows, groups, row_stride, W, group_stride));
+  DVG_TRY(check_spin_count("packed_correlation", n, CR_MAX_N, "the limit of the packed-row entries"));
+  DVG_TRY(check_row_count("packed_correlation", rows, groups));
   const int64_t total = groups * rows, Kp = cr_col_words(total), chunks = Kp / CR_KC;
   if (ceil_div(chunks, CR_SLAB_CHUNKS) > 0x7fffffff) {
     set_error("packed_correlation: groups=%lld x rows=%lld is more than one launch takes", (long long)groups, (long long)rows);

@@ -3,13 +3,14 @@
 // max_sweeps have run.  One stream-ordered launch, no workgroup waiting on another, no atomics on global memory.
 #include "common.h"
 #include "graph.h"
+#include "packed_rows.h"
 #include <cmath>
 
 namespace dvg {
 
 // A TILE is 64 consecutive rows of the flattened (group, row) index -- one per lane; workgroup b of DS_WAVES waves takes the
 // tiles b, b + gridDim.x, ..  A row's result depends on that row alone, so the grid cannot show in any output.
-// Per tile: the ballot transpose of grbm_fields_packed_kernel puts the per-spin bit columns in LDS as halves lo[spin] (rows
+// Per tile: the ballot transpose (tile_columns_halves, packed_rows.h) puts the per-spin bit columns in LDS as halves lo[spin] (rows
 // 0..31) and hi[spin] = lo[n + spin] (rows 32..63).  Then the sweeps.  In class k wave v takes the spins order[class_ptr[k] +
 // v], order[class_ptr[k] + v + DS_WAVES], ..: a spin is wave-uniform, its CSR row is loaded 64 entries at a time, entry t by
 // lane t (neighbour, and the coupling scaled and clamped as the sampler's), and handed out with v_readlane; the neighbour's
@@ -37,32 +38,6 @@ namespace dvg {
 constexpr int DS_WAVES = 16, DS_THREADS = DS_WAVES * 64, DS_MAX_N = 8192, DS_MAX_GRID = 1024, DS_MAX_SWEEPS = 65536;
 constexpr int DS_FIXED_LDS = DS_WAVES * 64 * 8 + 2 * DS_WAVES * 8, DS_LDS_MAX = DS_MAX_N * 8 + DS_FIXED_LDS;
 
-__device__ __forceinline__ float ds_clamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-
-// the sampler's float32 local field of the wave-uniform spin i for the 64 rows of the tile, one per lane
-__device__ __forceinline__ float ds_field(int i, int lane, const uint32_t* mine, int to_sign, const int32_t* __restrict__ adj_ptr,
-                                          const int32_t* __restrict__ adj_idx, const int32_t* __restrict__ adj_eid,
-                                          const float* __restrict__ h, const float* __restrict__ J, float prefactor, float h_lo,
-                                          float h_hi, float j_lo, float j_hi) {
-  const int p0 = adj_ptr[i], p1 = adj_ptr[i + 1];
-  float f = ds_clamp(__fmul_rn(prefactor, h[i]), h_lo, h_hi);
-  for (int c0 = p0; c0 < p1; c0 += 64) {
-    const int cnt = p1 - c0 < 64 ? p1 - c0 : 64;
-    int jj = 0;
-    uint32_t Jv = 0u;
-    if (lane < cnt) {
-      jj = adj_idx[c0 + lane];
-      Jv = __float_as_uint(ds_clamp(__fmul_rn(prefactor, J[adj_eid[c0 + lane]]), j_lo, j_hi));
-    }
-    for (int k = 0; k < cnt; ++k) {
-      const int j = __builtin_amdgcn_readlane(jj, k);
-      const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)Jv, k);
-      f = __fadd_rn(f, __uint_as_float(w ^ ((~mine[j] << to_sign) & 0x80000000u)));  // s_j > 0 ? Js : -Js
-    }
-  }
-  return f;
-}
-
 // (bits and bits_out may be the same rows: a tile's rows are read whole, behind a barrier, before any of them is written)
 __global__ __launch_bounds__(DS_THREADS) void grbm_descend_packed_kernel(
     const uint32_t* bits, int64_t rows, int64_t row_stride, int64_t groups, int64_t group_stride, int n, int W, int n_colours,
@@ -82,25 +57,7 @@ __global__ __launch_bounds__(DS_THREADS) void grbm_descend_packed_kernel(
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t idx = tile * 64 + lane;
     const bool live = idx < total;
-    const uint32_t* row = nullptr;  // (null: a row beyond the last)
-    if (live) {
-      const int64_t g = groups == 1 ? 0 : idx / rows;
-      row = bits + g * group_stride + (idx - g * rows) * row_stride;
-    }
-    for (int w = wave; w < W; w += DS_WAVES) {
-      const uint32_t word = row ? row[w] : 0u;
-      unsigned long long col = 0ull;
-#pragma unroll
-      for (int b = 0; b < 32; ++b) {
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
-        if (lane == b) col = m;
-      }
-      const int i = 32 * w + lane;
-      if (lane < 32 && i < n) {
-        lo[i] = (uint32_t)col;
-        lo[n + i] = (uint32_t)(col >> 32);
-      }
-    }
+    tile_columns_halves<DS_WAVES>(packed_row(bits, idx, total, rows, row_stride, groups, group_stride), W, n, wave, lane, lo);
     __syncthreads();
     // ---- the sweeps
     int n_sweeps = 0, n_flips = 0, sweep = 0;
@@ -112,9 +69,9 @@ __global__ __launch_bounds__(DS_THREADS) void grbm_descend_packed_kernel(
         const int u1 = class_ptr[k + 1];
         for (int u = class_ptr[k] + wave; u < u1; u += DS_WAVES) {
           const int i = order[u];
-          const float f = ds_field(i, lane, mine, to_sign, adj_ptr, adj_idx, adj_eid, h, J, prefactor, h_lo, h_hi, j_lo, j_hi);
-          const bool up = ((mine[i] << to_sign) & 0x80000000u) != 0u;  // s_i = +1
-          const bool flip = live && (up ? f > 0.0f : f < 0.0f);
+          const float f = local_field(i, lane, mine, to_sign, adj_ptr, adj_idx, adj_eid, h, J, prefactor, h_lo, h_hi, j_lo, j_hi);
+          const bool up = spin_is_up(mine, i, to_sign);
+          const bool flip = live && spin_is_unstable(up, f);
           const unsigned long long m = __builtin_amdgcn_ballot_w64(flip);
           n_flips += flip ? 1 : 0;
           if (m != 0ull) {
@@ -142,9 +99,9 @@ __global__ __launch_bounds__(DS_THREADS) void grbm_descend_packed_kernel(
     int n_unstable = 0;
     if (unstable_out && any != 0ull) {
       for (int i = wave; i < n; i += DS_WAVES) {
-        const float f = ds_field(i, lane, mine, to_sign, adj_ptr, adj_idx, adj_eid, h, J, prefactor, h_lo, h_hi, j_lo, j_hi);
-        const bool up = ((mine[i] << to_sign) & 0x80000000u) != 0u;
-        n_unstable += (live && (up ? f > 0.0f : f < 0.0f)) ? 1 : 0;
+        const float f = local_field(i, lane, mine, to_sign, adj_ptr, adj_idx, adj_eid, h, J, prefactor, h_lo, h_hi, j_lo, j_hi);
+        const bool up = spin_is_up(mine, i, to_sign);
+        n_unstable += (live && spin_is_unstable(up, f)) ? 1 : 0;
       }
     }
     rowf[wave * 64 + lane] = n_flips;
@@ -196,13 +153,9 @@ extern "C" int dvg_grbm_descend_packed(const dvg_graph_t* g, const float* linear
   DVG_REQUIRE(quadratic, "grbm_descend_packed: quadratic is null");
   DVG_REQUIRE(bits, "grbm_descend_packed: bits is null");
   DVG_REQUIRE(bits_out, "grbm_descend_packed: bits_out is null");
-  DVG_REQUIRE(rows >= 1, "grbm_descend_packed: rows=%lld must be at least 1", (long long)rows);
-  DVG_REQUIRE(groups >= 1, "grbm_descend_packed: groups=%lld must be at least 1", (long long)groups);
   const int n = g->n;
   const int64_t W = ((int64_t)n + 31) / 32;
-  DVG_REQUIRE(row_stride >= W, "grbm_descend_packed: row_stride=%lld is less than the %lld words of a row", (long long)row_stride,
-              (long long)W);
-  DVG_REQUIRE(group_stride >= 0, "grbm_descend_packed: group_stride=%lld is negative", (long long)group_stride);
+  DVG_TRY(check_row_geometry("grbm_descend_packed", rows, groups, row_stride, W, group_stride));
   DVG_REQUIRE(std::isfinite(prefactor), "grbm_descend_packed: prefactor=%g is not finite", (double)prefactor);
   DVG_REQUIRE(max_sweeps >= 1 && max_sweeps <= DS_MAX_SWEEPS, "grbm_descend_packed: max_sweeps=%d must be in 1 .. %d", max_sweeps,
               DS_MAX_SWEEPS);
@@ -217,20 +170,13 @@ extern "C" int dvg_grbm_descend_packed(const dvg_graph_t* g, const float* linear
                 "grbm_descend_packed: bits_out=%p overlaps the words of bits=%p (in place needs bits_out == bits and a dense input: "
                 "row_stride == W, group_stride == rows W)", (const void*)bits_out, (const void*)bits);
   }
-  if ((__int128)groups * rows >= ((__int128)1 << 62)) {
-    set_error("grbm_descend_packed: groups=%lld x rows=%lld rows are 2^62 or more", (long long)groups, (long long)rows);
-    return DVG_E_UNSUPPORTED;
-  }
-  if (n > DS_MAX_N) {
-    set_error("grbm_descend_packed: n=%d > %d (a tile's bit columns are kept in %d KiB of LDS)", n, DS_MAX_N, DS_MAX_N * 8 / 1024);
-    return DVG_E_UNSUPPORTED;
-  }
+  DVG_TRY(check_row_count("grbm_descend_packed", rows, groups));
+  DVG_TRY(check_spin_count("grbm_descend_packed", n, DS_MAX_N));
   const int64_t n_tiles = ceil_div(groups * rows, 64);
   const int grid = (int)(n_tiles < DS_MAX_GRID ? n_tiles : DS_MAX_GRID);
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)n * 8 + (size_t)DS_FIXED_LDS;
-  static std::atomic<uint64_t> attr_done{0};
-  if (lds > 64 * 1024) DVG_TRY(raise_dynamic_lds(attr_done, (const void*)grbm_descend_packed_kernel, DS_LDS_MAX));
+  DVG_RAISE_LDS_ABOVE_64K(lds, grbm_descend_packed_kernel, DS_LDS_MAX);
   DVG_LAUNCH_WORK(K_DESCEND, (double)n * (double)(groups * rows), grbm_descend_packed_kernel, dim3((unsigned)grid),
                   dim3(DS_THREADS), lds, s, bits, rows, row_stride, groups, group_stride, n, (int)W, g->n_colours, g->order,
                   g->class_ptr, g->adj_ptr, g->adj_idx, g->adj_eid, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, max_sweeps,

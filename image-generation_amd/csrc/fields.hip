@@ -3,6 +3,7 @@
 // fields themselves.  Two stream-ordered launches (the second only for the pooled sums), no workgroup waiting on another.
 #include "common.h"
 #include "graph.h"
+#include "packed_rows.h"
 #include <cmath>
 
 namespace dvg {
@@ -11,7 +12,7 @@ namespace dvg {
 // A TILE is 64 consecutive rows of the flattened (group, row) index -- one per lane.  A SLAB is `tiles_per_slab` consecutive
 // tiles; workgroup `blockIdx.x` of FP_WAVES waves takes slab blockIdx.x, tile by tile.  The split into slabs is a function of the
 // number of tiles alone (fp_slabs below), never of the device.
-// Per tile: the ballot transpose of grbm_energy_packed_kernel puts the per-spin bit columns in LDS as halves lo[spin] (rows
+// Per tile: the ballot transpose (tile_columns_halves, packed_rows.h) puts the per-spin bit columns in LDS as halves lo[spin] (rows
 // 0..31) and hi[spin] (rows 32..63); behind the barrier the tile's spins are walked in BLOCKS of 64.
 //   Phase A, lane = row.  Wave v takes the spins i0 + v, i0 + v + FP_WAVES, .. of the block.  A spin is wave-uniform: its CSR
 //   row is loaded 64 entries at a time, entry t by lane t (neighbour, and the coupling scaled and clamped as the sampler's), and
@@ -42,8 +43,6 @@ namespace dvg {
 constexpr int FP_WAVES = 16, FP_THREADS = FP_WAVES * 64, FP_MAX_N = 8192, FP_MAX_SLABS = 512, FP_STRIDE = 65;
 constexpr int FP_PART_LDS = FP_WAVES * 64 * 12, FP_MS_LDS = 64 * FP_STRIDE * 8, FP_FS_LDS = 64 * FP_STRIDE * 4, FP_PTR_LDS = 272;
 constexpr int FP_FIXED_LDS = FP_PART_LDS + FP_MS_LDS + FP_FS_LDS + FP_PTR_LDS, FP_LDS_MAX = FP_MAX_N * 8 + FP_FIXED_LDS;
-
-__device__ __forceinline__ float fp_clamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
 
 // m with the sign of bit `r mod 32` of `word` (set: +m, clear: -m), exactly
 __device__ __forceinline__ double fp_signed(double m, uint32_t word, int r) {
@@ -76,25 +75,8 @@ __global__ __launch_bounds__(FP_THREADS) void grbm_fields_packed_kernel(
   for (int64_t tile = tile0; tile < tile1; ++tile) {
     const bool first = tile == tile0;
     const int64_t idx = tile * 64 + lane;
-    const uint32_t* row = nullptr;  // (null: a row beyond the last)
-    if (idx < total) {
-      const int64_t g = groups == 1 ? 0 : idx / rows;
-      row = bits + g * group_stride + (idx - g * rows) * row_stride;
-    }
-    for (int w = wave; w < W; w += FP_WAVES) {
-      const uint32_t word = row ? row[w] : 0u;
-      unsigned long long col = 0ull;
-#pragma unroll
-      for (int b = 0; b < 32; ++b) {
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
-        if (lane == b) col = m;
-      }
-      const int i = 32 * w + lane;
-      if (lane < 32 && i < n) {
-        lo[i] = (uint32_t)col;
-        lo[n + i] = (uint32_t)(col >> 32);
-      }
-    }
+    const uint32_t* row = packed_row(bits, idx, total, rows, row_stride, groups, group_stride);  // (null: a row beyond the last)
+    tile_columns_halves<FP_WAVES>(row, W, n, wave, lane, lo);
     __syncthreads();
     double nlp_acc = 0.0;
     int unst = 0;
@@ -104,27 +86,12 @@ __global__ __launch_bounds__(FP_THREADS) void grbm_fields_packed_kernel(
       // ---- phase A: lane = row
       for (int u = wave; u < nb; u += FP_WAVES) {
         const int i = i0 + u;
-        const int p0 = adj_ptr[i], p1 = adj_ptr[i + 1];
-        float f = fp_clamp(__fmul_rn(prefactor, h[i]), h_lo, h_hi);
-        for (int c0 = p0; c0 < p1; c0 += 64) {
-          const int cnt = p1 - c0 < 64 ? p1 - c0 : 64;
-          int jj = 0;
-          uint32_t Jv = 0u;
-          if (lane < cnt) {
-            jj = adj_idx[c0 + lane];
-            Jv = __float_as_uint(fp_clamp(__fmul_rn(prefactor, J[adj_eid[c0 + lane]]), j_lo, j_hi));
-          }
-          for (int k = 0; k < cnt; ++k) {
-            const int j = __builtin_amdgcn_readlane(jj, k);
-            const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)Jv, k);
-            f = __fadd_rn(f, __uint_as_float(w ^ ((~mine[j] << to_sign) & 0x80000000u)));  // s_j > 0 ? Js : -Js
-          }
-        }
-        const bool up = ((mine[i] << to_sign) & 0x80000000u) != 0u;  // s_i = +1
-        unst += (up ? f > 0.0f : f < 0.0f) ? 1 : 0;
+        const float f = local_field(i, lane, mine, to_sign, adj_ptr, adj_idx, adj_eid, h, J, prefactor, h_lo, h_hi, j_lo, j_hi);
+        const bool up = spin_is_up(mine, i, to_sign);
+        unst += spin_is_unstable(up, f) ? 1 : 0;
         double m = 0.0;
         if (want_m) {
-          const float z = fp_clamp(__fmul_rn(two_beta, f), -87.0f, 87.0f);
+          const float z = scaled_clamped(two_beta, f, -87.0f, 87.0f);
           const double zd = (double)z, e = exp(-fabs(zd));
           if (want_pl) nlp_acc += fmax(up ? zd : -zd, 0.0) + log1p(e);
           if (want_cond) {
@@ -288,23 +255,13 @@ extern "C" int dvg_grbm_fields_packed(const dvg_graph_t* g, const float* linear,
     DVG_REQUIRE(ws, "grbm_fields_packed: ws is null (the pooled sums need the workspace)");
     DVG_REQUIRE(((uintptr_t)ws & 15) == 0, "grbm_fields_packed: ws=%p is not aligned to 16 bytes", ws);
   }
-  DVG_REQUIRE(rows >= 1, "grbm_fields_packed: rows=%lld must be at least 1", (long long)rows);
-  DVG_REQUIRE(groups >= 1, "grbm_fields_packed: groups=%lld must be at least 1", (long long)groups);
   const int n = g->n;
   const int64_t W = ((int64_t)n + 31) / 32;
-  DVG_REQUIRE(row_stride >= W, "grbm_fields_packed: row_stride=%lld is less than the %lld words of a row", (long long)row_stride,
-              (long long)W);
-  DVG_REQUIRE(group_stride >= 0, "grbm_fields_packed: group_stride=%lld is negative", (long long)group_stride);
+  DVG_TRY(check_row_geometry("grbm_fields_packed", rows, groups, row_stride, W, group_stride));
   DVG_REQUIRE(std::isfinite(prefactor), "grbm_fields_packed: prefactor=%g is not finite", (double)prefactor);
   DVG_REQUIRE(std::isfinite(beta) && beta >= 0.0f, "grbm_fields_packed: beta=%g must be finite and at least 0", (double)beta);
-  if ((__int128)groups * rows >= ((__int128)1 << 62)) {
-    set_error("grbm_fields_packed: groups=%lld x rows=%lld rows are 2^62 or more", (long long)groups, (long long)rows);
-    return DVG_E_UNSUPPORTED;
-  }
-  if (n > FP_MAX_N) {
-    set_error("grbm_fields_packed: n=%d > %d (a tile's bit columns are kept in %d KiB of LDS)", n, FP_MAX_N, FP_MAX_N * 8 / 1024);
-    return DVG_E_UNSUPPORTED;
-  }
+  DVG_TRY(check_row_count("grbm_fields_packed", rows, groups));
+  DVG_TRY(check_spin_count("grbm_fields_packed", n, FP_MAX_N));
   const int64_t n_tiles = ceil_div(groups * rows, 64);
   int64_t tiles_per_slab = 0;
   const int slabs = fp_slabs(n_tiles, &tiles_per_slab);
@@ -318,8 +275,7 @@ extern "C" int dvg_grbm_fields_packed(const dvg_graph_t* g, const float* linear,
   }
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)n * 8 + (size_t)FP_FIXED_LDS;
-  static std::atomic<uint64_t> attr_done{0};
-  if (lds > 64 * 1024) DVG_TRY(raise_dynamic_lds(attr_done, (const void*)grbm_fields_packed_kernel, FP_LDS_MAX));
+  DVG_RAISE_LDS_ABOVE_64K(lds, grbm_fields_packed_kernel, FP_LDS_MAX);
   const float two_beta = 2.0f * beta;
   DVG_LAUNCH_WORK(K_FIELDS_ROWS, (double)n * (double)(groups * rows), grbm_fields_packed_kernel, dim3((unsigned)slabs),
                   dim3(FP_THREADS), lds, s, bits, rows, row_stride, groups, group_stride, n, (int)W, n_adj, g->adj_ptr, g->adj_idx,

@@ -3,6 +3,7 @@
 // /root/reference/src/losses.py:61;  E(x) = x.h + sum_e J_e x_i x_j.
 #include "common.h"
 #include "graph.h"
+#include "packed_rows.h"
 
 namespace dvg {
 
@@ -91,13 +92,7 @@ __global__ __launch_bounds__(MP_WAVES * 64) void grbm_moments_packed_kernel(cons
   for (int job = wave; job < kt * W; job += MP_WAVES) {
     const int k = job / W, w = job - k * W;
     const int64_t r = (tile0 + k) * 64 + lane;
-    const uint32_t word = r < rows ? bits[r * W + w] : 0u;
-    unsigned long long col = 0ull;
-#pragma unroll
-    for (int b = 0; b < 32; ++b) {
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
-      if (lane == b) col = m;
-    }
+    const unsigned long long col = bit_column(r < rows ? bits[r * W + w] : 0u, lane);
     const int i = 32 * w + lane;
     if (lane < 32 && i < n) cols[(size_t)k * n + i] = col;
   }
@@ -160,13 +155,7 @@ __global__ __launch_bounds__(AC_WAVES * 64) void trace_autocorr_kernel(const uin
     for (int job = wave; job < nb * K; job += AC_WAVES) {
       const int j = job / K, k = job - j * K;
       const int m = 64 * k + lane;
-      const uint32_t word = m < M ? bits[((int64_t)(cb + j) * M + m) * W + w] : 0u;
-      unsigned long long column = 0ull;
-#pragma unroll
-      for (int b = 0; b < 32; ++b) {
-        const unsigned long long v = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
-        if (lane == b) column = v;
-      }
+      const unsigned long long column = bit_column(m < M ? bits[((int64_t)(cb + j) * M + m) * W + w] : 0u, lane);
       if (lane < 32) cols[(j * 32 + lane) * Kp + k] = column;
     }
     __syncthreads();
@@ -425,30 +414,12 @@ __global__ __launch_bounds__(EN_WAVES * 64) void grbm_energy_packed_kernel(
   const int64_t total = groups * rows, n_tiles = (total + 63) >> 6;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t idx = tile * 64 + lane;
-    const uint32_t* row = nullptr;  // (null: a row beyond the last)
-    if (idx < total) {
-      const int64_t g = groups == 1 ? 0 : idx / rows;
-      row = bits + g * group_stride + (idx - g * rows) * row_stride;
-    }
-    for (int w = wave; w < W; w += EN_WAVES) {
-      const uint32_t word = row ? row[w] : 0u;
-      unsigned long long col = 0ull;
-#pragma unroll
-      for (int b = 0; b < 32; ++b) {
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(((word >> b) & 1u) != 0u);
-        if (lane == b) col = m;
-      }
-      const int i = 32 * w + lane;
-      if (lane < 32 && i < n) {
-        lo[i] = (uint32_t)col;
-        lo[n + i] = (uint32_t)(col >> 32);
-      }
-    }
+    tile_columns_halves<EN_WAVES>(packed_row(bits, idx, total, rows, row_stride, groups, group_stride), W, n, wave, lane, lo);
     __syncthreads();
     double acc = 0.0;
     for (int b0 = t0; b0 < i1; b0 += 64) {
       const int cnt = i1 - b0 < 64 ? i1 - b0 : 64;
-      const uint32_t hs = lane < cnt ? __float_as_uint(fminf(fmaxf(__fmul_rn(prefactor, h[b0 + lane]), h_lo), h_hi)) : 0u;
+      const uint32_t hs = lane < cnt ? __float_as_uint(scaled_clamped(prefactor, h[b0 + lane], h_lo, h_hi)) : 0u;
       int k = 0;
       for (; k + EN_UNROLL <= cnt; k += EN_UNROLL) {  // (unrolled by hand: the reads of EN_UNROLL terms in flight together)
         uint32_t x[EN_UNROLL];
@@ -461,7 +432,7 @@ __global__ __launch_bounds__(EN_WAVES * 64) void grbm_energy_packed_kernel(
     }
     for (int b0 = e0; b0 < e1; b0 += 64) {
       const int cnt = e1 - b0 < 64 ? e1 - b0 : 64;
-      const uint32_t Js = lane < cnt ? __float_as_uint(fminf(fmaxf(__fmul_rn(prefactor, J[b0 + lane]), j_lo), j_hi)) : 0u;
+      const uint32_t Js = lane < cnt ? __float_as_uint(scaled_clamped(prefactor, J[b0 + lane], j_lo, j_hi)) : 0u;
       int k = 0;
       for (; k + EN_UNROLL <= cnt; k += EN_UNROLL) {
         uint32_t x[EN_UNROLL];
@@ -562,27 +533,16 @@ extern "C" int dvg_grbm_energy_packed(const dvg_graph_t* g, const float* linear,
   DVG_REQUIRE(quadratic, "grbm_energy_packed: quadratic is null");
   DVG_REQUIRE(bits, "grbm_energy_packed: bits is null");
   DVG_REQUIRE(energy_out, "grbm_energy_packed: energy_out is null");
-  DVG_REQUIRE(rows >= 1, "grbm_energy_packed: rows=%lld must be at least 1", (long long)rows);
-  DVG_REQUIRE(groups >= 1, "grbm_energy_packed: groups=%lld must be at least 1", (long long)groups);
   const int n = g->n;
   const int64_t W = ((int64_t)n + 31) / 32;
-  DVG_REQUIRE(row_stride >= W, "grbm_energy_packed: row_stride=%lld is less than the %lld words of a row", (long long)row_stride,
-              (long long)W);
-  DVG_REQUIRE(group_stride >= 0, "grbm_energy_packed: group_stride=%lld is negative", (long long)group_stride);
+  DVG_TRY(check_row_geometry("grbm_energy_packed", rows, groups, row_stride, W, group_stride));
   DVG_REQUIRE(std::isfinite(prefactor), "grbm_energy_packed: prefactor=%g is not finite", (double)prefactor);
-  if ((__int128)groups * rows >= ((__int128)1 << 62)) {
-    set_error("grbm_energy_packed: groups=%lld x rows=%lld energies are 2^62 or more", (long long)groups, (long long)rows);
-    return DVG_E_UNSUPPORTED;
-  }
-  if (n > EN_MAX_N) {
-    set_error("grbm_energy_packed: n=%d > %d (a tile's bit columns are kept in %d KiB of LDS)", n, EN_MAX_N, EN_MAX_N * 8 / 1024);
-    return DVG_E_UNSUPPORTED;
-  }
+  DVG_TRY(check_row_count("grbm_energy_packed", rows, groups));
+  DVG_TRY(check_spin_count("grbm_energy_packed", n, EN_MAX_N));
   hipStream_t s = (hipStream_t)stream;
   const int64_t n_tiles = ceil_div(groups * rows, 64);
   const size_t lds = (size_t)n * 8 + (size_t)EN_PART_LDS;
-  static std::atomic<uint64_t> attr_done{0};
-  if (lds > 64 * 1024) DVG_TRY(raise_dynamic_lds(attr_done, (const void*)grbm_energy_packed_kernel, EN_LDS_MAX));
+  DVG_RAISE_LDS_ABOVE_64K(lds, grbm_energy_packed_kernel, EN_LDS_MAX);
   DVG_LAUNCH(K_GRBM_SUFFSTATS, grbm_energy_packed_kernel, dim3((unsigned)(n_tiles < EN_GRID ? n_tiles : EN_GRID)),
              dim3(EN_WAVES * 64), lds, s, bits, rows, row_stride, groups, group_stride, n, (int)W, g->n_edges, g->edge_i, g->edge_j,
              linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, energy_out);
@@ -629,8 +589,7 @@ extern "C" int dvg_trace_autocorr(const uint32_t* bits, int n_chains, int n_reco
   batch = batch < 1 ? 1 : batch > AC_BATCH ? AC_BATCH : batch;
   batch = batch > per ? per : batch;
   const size_t lds = (size_t)batch * per_chain;
-  static std::atomic<uint64_t> attr_done{0};
-  if (lds > 64 * 1024) DVG_TRY(raise_dynamic_lds(attr_done, (const void*)trace_autocorr_kernel, AC_LDS_MAX));
+  DVG_RAISE_LDS_ABOVE_64K(lds, trace_autocorr_kernel, AC_LDS_MAX);
   DVG_LAUNCH(K_GRBM_SUFFSTATS, trace_autocorr_kernel, dim3((unsigned)W, (unsigned)slabs, (unsigned)chunks), dim3(AC_WAVES * 64),
              lds, s, bits, n_chains, n_records, n, (int)W, max_lag, (int)per, (int)batch, reinterpret_cast<unsigned long long*>(lag_sum),
              reinterpret_cast<unsigned long long*>(spin_sum), chain_sum);

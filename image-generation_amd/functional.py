@@ -298,20 +298,46 @@ def trace_autocorr(bits, n, max_lag, *, chain_sums=True, out=None):
     return lag_sum, spin_sum, chain_sum
 
 
-def _packed_rows(t, name, W):
-    """``(rows, row_stride, groups, group_stride)`` of a 2-D (rows, W) or 3-D (C, M, W) int32 tensor of packed rows, in words."""
+def _packed_rows(t, name, W, groups_first=True):
+    """``(rows, row_stride, groups, group_stride)`` of a 2-D (rows, W) or 3-D (C, M, W) int32 tensor of packed rows, in words.
+    A 3-D tensor is C groups of M rows -- a trace's chains, pooled -- or with ``groups_first=False`` M groups of C rows:
+    :func:`packed_overlap`'s chains at equal times."""
     if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() not in (2, 3) or t.shape[-1] != W or min(t.shape) < 1:
         raise _lib.DvgError(f"{name} must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
                             f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
     if W > 1 and t.stride(-1) != 1:
         raise _lib.DvgError(f"{name}: the last dimension must have stride 1, got strides {tuple(t.stride())}")
-    rows = int(t.shape[0])
-    rs = int(t.stride(0)) if rows > 1 else W
-    groups = int(t.shape[1]) if t.dim() == 3 else 1
-    gs = int(t.stride(1)) if groups > 1 else 0
+    rd, gd = (t.dim() - 2, 0) if groups_first else (0, 1)
+    rows = int(t.shape[rd])
+    rs = int(t.stride(rd)) if rows > 1 else W
+    groups = int(t.shape[gd]) if t.dim() == 3 else 1
+    gs = int(t.stride(gd)) if groups > 1 else 0
     if rs < W or gs < 0:
         raise _lib.DvgError(f"{name}: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(t.stride())})")
     return rows, rs, groups, gs
+
+
+def _model_arguments(graph, linear, quadratic, prefactor, linear_range, quadratic_range):
+    """The early checks of a model's ``linear`` (n) and ``quadratic`` (E) float32 tensors and ``prefactor``;
+    ``(h_lo, h_hi, j_lo, j_hi)`` of the two ranges."""
+    for name, t, k in (("linear", linear, int(graph.plan.n)), ("quadratic", quadratic, int(graph.plan.n_edges))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != k:
+            raise _lib.DvgError(f"{name} must be a float32 tensor of the graph's {k} values, got "
+                                f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
+    if isinstance(prefactor, bool) or not isinstance(prefactor, numbers.Real) or not float("-inf") < prefactor < float("inf"):
+        raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
+    return _clamp_range(linear_range, "linear_range") + _clamp_range(quadratic_range, "quadratic_range")
+
+
+def _on_the_device(bits, linear, quadratic):
+    """The late checks, behind every other argument error: ``bits`` on the GPU, the model on its device.  Returns the three
+    detached, the model's two contiguous."""
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    for name, t in (("linear", linear), ("quadratic", quadratic)):
+        if t.device != bits.device:
+            raise _lib.DvgError(f"{name} must be on the device of bits ({bits.device}), got {t.device}")
+    return bits.detach(), linear.detach().contiguous(), quadratic.detach().contiguous()
 
 
 def packed_overlap(a, b=None, *, n, nearest=False, out=None):
@@ -329,10 +355,10 @@ def packed_overlap(a, b=None, *, n, nearest=False, out=None):
         raise ValueError(f"n must be an integer >= 1, got {n!r}")
     n = int(n)
     W = (n + 31) // 32
-    rows_a, a_rs, groups, a_gs = _packed_rows(a, "a", W)
+    rows_a, a_rs, groups, a_gs = _packed_rows(a, "a", W, groups_first=False)
     rows_b, b_rs, b_gs = 0, 0, 0
     if b is not None:
-        rows_b, b_rs, groups_b, b_gs = _packed_rows(b, "b", W)
+        rows_b, b_rs, groups_b, b_gs = _packed_rows(b, "b", W, groups_first=False)
         if b.dim() == 3 and (a.dim() != 3 or groups_b != groups):
             raise _lib.DvgError(f"b: a 3-D b needs a 3-D a with the same number of records, got a {tuple(a.shape)} and b {tuple(b.shape)}")
         if b.dim() == 2:
@@ -387,32 +413,9 @@ def grbm_energy_packed(bits, graph, linear, quadratic, *, prefactor=1.0, linear_
     on the same device.  Returns ``sum_i hs_i s_i + sum_e Js_e s_i s_j`` per row, float64 (rows,) or (C, M): every addend
     exact, the order of the additions fixed -- the same bits on every call.  No host sync."""
     n, E = int(graph.plan.n), int(graph.plan.n_edges)
-    W = (n + 31) // 32
-    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
-        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
-                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
-    if W > 1 and bits.stride(-1) != 1:
-        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
-    rows = int(bits.shape[-2])
-    rs = int(bits.stride(-2)) if rows > 1 else W
-    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
-    gs = int(bits.stride(0)) if groups > 1 else 0
-    if rs < W:
-        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
-    for name, t, k in (("linear", linear, n), ("quadratic", quadratic, E)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != k:
-            raise _lib.DvgError(f"{name} must be a float32 tensor of the graph's {k} values, got "
-                                f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
-    if isinstance(prefactor, bool) or not isinstance(prefactor, numbers.Real) or not float("-inf") < prefactor < float("inf"):
-        raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
-    hl, hh = _clamp_range(linear_range, "linear_range")
-    jl, jh = _clamp_range(quadratic_range, "quadratic_range")
-    if not bits.is_cuda:
-        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
-    for name, t in (("linear", linear), ("quadratic", quadratic)):
-        if t.device != bits.device:
-            raise _lib.DvgError(f"{name} must be on the device of bits ({bits.device}), got {t.device}")
-    bd, lin, quad = bits.detach(), linear.detach().contiguous(), quadratic.detach().contiguous()
+    rows, rs, groups, gs = _packed_rows(bits, "bits", (n + 31) // 32)
+    hl, hh, jl, jh = _model_arguments(graph, linear, quadratic, prefactor, linear_range, quadratic_range)
+    bd, lin, quad = _on_the_device(bits, linear, quadratic)
     out = torch.empty((groups * rows,), dtype=torch.float64, device=bd.device)
     with torch.cuda.device(bd.device):
         check(lib().dvg_grbm_energy_packed(graph.ptr, lin.data_ptr(), quad.data_ptr() if E else lin.data_ptr(), float(prefactor), hl,
@@ -436,18 +439,7 @@ def packed_correlation(bits, *, n, spin_sums=True, out=None):
     if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
         raise ValueError(f"n must be an integer >= 1, got {n!r}")
     n = int(n)
-    W = (n + 31) // 32
-    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
-        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
-                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
-    if W > 1 and bits.stride(-1) != 1:
-        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
-    rows = int(bits.shape[-2])
-    rs = int(bits.stride(-2)) if rows > 1 else W
-    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
-    gs = int(bits.stride(0)) if groups > 1 else 0
-    if rs < W or gs < 0:
-        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
+    rows, rs, groups, gs = _packed_rows(bits, "bits", (n + 31) // 32)
     spin_sum = pair_sum = None
     if out is not None:
         if not isinstance(out, (tuple, list)) or len(out) != 2:
@@ -493,28 +485,10 @@ def grbm_fields_packed(bits, graph, linear, quadratic, *, beta, prefactor=1.0, l
     cond_pair)`` to add this call's pooled sums onto (needs ``conditional``).  The order of every addition is fixed by the
     shapes alone: the same bits on every call.  It allocates its workspace; no host sync."""
     n, E = int(graph.plan.n), int(graph.plan.n_edges)
-    W = (n + 31) // 32
-    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
-        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
-                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
-    if W > 1 and bits.stride(-1) != 1:
-        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
-    rows = int(bits.shape[-2])
-    rs = int(bits.stride(-2)) if rows > 1 else W
-    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
-    gs = int(bits.stride(0)) if groups > 1 else 0
-    if rs < W:
-        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
-    for name, t, k in (("linear", linear, n), ("quadratic", quadratic, E)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != k:
-            raise _lib.DvgError(f"{name} must be a float32 tensor of the graph's {k} values, got "
-                                f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
-    if isinstance(prefactor, bool) or not isinstance(prefactor, numbers.Real) or not float("-inf") < prefactor < float("inf"):
-        raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
+    rows, rs, groups, gs = _packed_rows(bits, "bits", (n + 31) // 32)
+    hl, hh, jl, jh = _model_arguments(graph, linear, quadratic, prefactor, linear_range, quadratic_range)
     if isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not 0 <= beta < float("inf"):
         raise ValueError(f"beta must be a finite number >= 0, got {beta!r}")
-    hl, hh = _clamp_range(linear_range, "linear_range")
-    jl, jh = _clamp_range(quadratic_range, "quadratic_range")
     for name, v in (("log_pl", log_pl), ("unstable", unstable), ("conditional", conditional), ("fields", fields)):
         if not isinstance(v, bool):
             raise ValueError(f"{name} must be True or False, got {v!r}")
@@ -531,12 +505,7 @@ def grbm_fields_packed(bits, graph, linear, quadratic, *, beta, prefactor=1.0, l
             if not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != (k,) or not t.is_contiguous() or \
                     t.device != bits.device:
                 raise _lib.DvgError(f"out: {name} must be a contiguous ({k},) float64 tensor on {bits.device}")
-    if not bits.is_cuda:
-        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
-    for name, t in (("linear", linear), ("quadratic", quadratic)):
-        if t.device != bits.device:
-            raise _lib.DvgError(f"{name} must be on the device of bits ({bits.device}), got {t.device}")
-    bd, lin, quad = bits.detach(), linear.detach().contiguous(), quadratic.detach().contiguous()
+    bd, lin, quad = _on_the_device(bits, linear, quadratic)
     T, dev = groups * rows, bd.device
     shape = (groups, rows) if bits.dim() == 3 else (rows,)
     lp = torch.empty((T,), dtype=torch.float64, device=dev) if log_pl else None
@@ -577,25 +546,8 @@ def grbm_descend_packed(bits, graph, linear, quadratic, *, prefactor=1.0, linear
     only promise of termination.  No workspace, no host sync."""
     n, E = int(graph.plan.n), int(graph.plan.n_edges)
     W = (n + 31) // 32
-    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or min(bits.shape) < 1:
-        raise _lib.DvgError(f"bits must be (rows >= 1, {W}) or (chains >= 1, records >= 1, {W}) int32, got "
-                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
-    if W > 1 and bits.stride(-1) != 1:
-        raise _lib.DvgError(f"bits: the last dimension must have stride 1, got strides {tuple(bits.stride())}")
-    rows = int(bits.shape[-2])
-    rs = int(bits.stride(-2)) if rows > 1 else W
-    groups = int(bits.shape[0]) if bits.dim() == 3 else 1
-    gs = int(bits.stride(0)) if groups > 1 else 0
-    if rs < W:
-        raise _lib.DvgError(f"bits: a row stride of {rs} words is less than the {W} words of a row (strides {tuple(bits.stride())})")
-    for name, t, k in (("linear", linear, n), ("quadratic", quadratic, E)):
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != k:
-            raise _lib.DvgError(f"{name} must be a float32 tensor of the graph's {k} values, got "
-                                f"{(tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__}")
-    if isinstance(prefactor, bool) or not isinstance(prefactor, numbers.Real) or not float("-inf") < prefactor < float("inf"):
-        raise ValueError(f"prefactor must be a finite number, got {prefactor!r}")
-    hl, hh = _clamp_range(linear_range, "linear_range")
-    jl, jh = _clamp_range(quadratic_range, "quadratic_range")
+    rows, rs, groups, gs = _packed_rows(bits, "bits", W)
+    hl, hh, jl, jh = _model_arguments(graph, linear, quadratic, prefactor, linear_range, quadratic_range)
     if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, numbers.Integral) or not 1 <= max_sweeps <= DESCEND_MAX_SWEEPS:
         raise ValueError(f"max_sweeps must be an integer in 1 .. {DESCEND_MAX_SWEEPS}, got {max_sweeps!r}")
     if out is not None:
@@ -608,12 +560,7 @@ def grbm_descend_packed(bits, graph, linear, quadratic, *, prefactor=1.0, linear
         if a0 < b0 + 4 * out.numel() and b0 < a1 and not (a0 == b0 and bits.is_contiguous()):
             raise _lib.DvgError("out shares memory with bits: in place needs out to be bits itself and bits contiguous "
                                 f"(strides {tuple(bits.stride())})")
-    if not bits.is_cuda:
-        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
-    for name, t in (("linear", linear), ("quadratic", quadratic)):
-        if t.device != bits.device:
-            raise _lib.DvgError(f"{name} must be on the device of bits ({bits.device}), got {t.device}")
-    bd, lin, quad = bits.detach(), linear.detach().contiguous(), quadratic.detach().contiguous()
+    bd, lin, quad = _on_the_device(bits, linear, quadratic)
     T, dev = groups * rows, bd.device
     shape = (groups, rows) if bits.dim() == 3 else (rows,)
     res = torch.empty(tuple(bits.shape), dtype=torch.int32, device=dev) if out is None else out.detach()

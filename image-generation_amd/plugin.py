@@ -330,13 +330,9 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
                                              linear_range, quadratic_range, max_lag=max_lag),
             acceptance_rate=tt.final.acceptance_rate, round_trips=tt.round_trips(), flow=tt.flow())
 
-    @torch.no_grad()
-    def pseudo_likelihood(self, x_or_bits: torch.Tensor, *, beta: float, prefactor: float, linear_range=None, quadratic_range=None):
-        """The :class:`~.sampler.PseudoLikelihood` of spin rows under the prefactor-scaled, clamped ``(h, J)`` at ``beta``:
-        ``sum_i log P(s_i | rest)`` per row -- the likelihood-type score that needs no ``log Z`` -- the rows' unstable spins,
-        and the Rao-Blackwellised moments (``dvg_grbm_fields_packed``).  ``x_or_bits``: bit-packed rows ((rows, W) or (C, M, W)
-        int32: ``Trace.bits``) or +-1 rows ((..., n), any other dtype; packed with ``sampler.pack_spins``), on the GPU."""
-        from .sampler import pack_spins, pseudo_likelihood
+    def _packed_bits(self, x_or_bits):
+        """``x_or_bits`` on the GPU as bit-packed rows: int32 is taken as packed already, any other dtype as +-1 rows (..., n)."""
+        from .sampler import pack_spins
 
         if not torch.is_tensor(x_or_bits) or not x_or_bits.is_cuda:
             raise _lib.DvgError("x_or_bits must be a tensor on the GPU (got "
@@ -347,6 +343,17 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
             if bits.dim() < 2 or bits.shape[-1] != len(self._nodes):
                 raise _lib.DvgError(f"x_or_bits: +-1 rows must be (..., {len(self._nodes)}), got {tuple(bits.shape)}")
             bits = pack_spins(bits.detach().reshape(-1, bits.shape[-1]) if bits.dim() > 3 else bits.detach())
+        return bits
+
+    @torch.no_grad()
+    def pseudo_likelihood(self, x_or_bits: torch.Tensor, *, beta: float, prefactor: float, linear_range=None, quadratic_range=None):
+        """The :class:`~.sampler.PseudoLikelihood` of spin rows under the prefactor-scaled, clamped ``(h, J)`` at ``beta``:
+        ``sum_i log P(s_i | rest)`` per row -- the likelihood-type score that needs no ``log Z`` -- the rows' unstable spins,
+        and the Rao-Blackwellised moments (``dvg_grbm_fields_packed``).  ``x_or_bits``: bit-packed rows ((rows, W) or (C, M, W)
+        int32: ``Trace.bits``) or +-1 rows ((..., n), any other dtype; packed with ``sampler.pack_spins``), on the GPU."""
+        from .sampler import pseudo_likelihood
+
+        bits = self._packed_bits(x_or_bits)
         return pseudo_likelihood(bits, self.graph_handle(bits.device), self._linear, self._quadratic, beta=beta, prefactor=prefactor,
                                  linear_range=linear_range, quadratic_range=quadratic_range)
 
@@ -368,17 +375,9 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         energy, or through ``max_sweeps`` sweeps (``dvg_grbm_descend_packed``), with the energies before and after.
         ``x_or_bits``: bit-packed rows ((rows, W) or (C, M, W) int32: ``Trace.bits``) or +-1 rows ((..., n), any other dtype;
         packed with ``sampler.pack_spins``), on the GPU; it is left as it is."""
-        from .sampler import descend, pack_spins
+        from .sampler import descend
 
-        if not torch.is_tensor(x_or_bits) or not x_or_bits.is_cuda:
-            raise _lib.DvgError("x_or_bits must be a tensor on the GPU (got "
-                                f"{x_or_bits.device if torch.is_tensor(x_or_bits) else type(x_or_bits).__name__}); the HIP path has "
-                                "no CPU fallback")
-        bits = x_or_bits
-        if bits.dtype != torch.int32:
-            if bits.dim() < 2 or bits.shape[-1] != len(self._nodes):
-                raise _lib.DvgError(f"x_or_bits: +-1 rows must be (..., {len(self._nodes)}), got {tuple(bits.shape)}")
-            bits = pack_spins(bits.detach().reshape(-1, bits.shape[-1]) if bits.dim() > 3 else bits.detach())
+        bits = self._packed_bits(x_or_bits)
         return descend(bits, self.graph_handle(bits.device), self._linear, self._quadratic, prefactor=prefactor,
                        linear_range=linear_range, quadratic_range=quadratic_range, max_sweeps=max_sweeps)
 
