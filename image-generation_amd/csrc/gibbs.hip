@@ -1215,6 +1215,16 @@ extern "C" int dvg_gibbs_sample_ais(const dvg_graph_t* g, const float* linear, c
   return gibbs_draw<false, GIBBS_WEIGH>(g, a, (hipStream_t)stream);
 }
 
+// What both traced draws check of the sweeps they record, under the entry point's name `who`; `plain`: the draw without a trace.
+static int gibbs_record_check(const char* who, const char* plain, int n_sweeps, int burn_in, int thin) {
+  DVG_REQUIRE(burn_in >= 0, "%s: burn_in=%d must be at least 0", who, burn_in);
+  DVG_REQUIRE(thin >= 1, "%s: thin=%d must be at least 1", who, thin);
+  DVG_REQUIRE(burn_in <= n_sweeps && n_sweeps - burn_in >= thin,  // (n_sweeps >= burn_in + thin, without the sum's overflow)
+              "%s: n_sweeps=%d, burn_in=%d, thin=%d record nothing (a draw that records nothing is %s)", who, n_sweeps, burn_in, thin,
+              plain);
+  return DVG_OK;
+}
+
 // The exchange draw ("DVG PT v1", include/dvg.h): ladders of n_replicas chains, each at the beta of the rung it holds; every
 // swap_every sweeps the chains of neighbouring rungs of a ladder exchange them on a Metropolis coin.
 // what both exchange draws check, under the entry point's name `who`; `missing`: the entry point's own null argument, if any
@@ -1264,12 +1274,7 @@ extern "C" int dvg_gibbs_sample_tempered_traced(const dvg_graph_t* g, const floa
   DVG_TRY(gibbs_exchange_check("gibbs_tempered_traced", g, linear, quadratic, ladder, n_replicas, swap_every, state, rung, n_chains,
                                n_sweeps, trace_out ? nullptr : "null trace_out (a draw that records nothing is dvg_gibbs_sample_tempered)",
                                dyn));
-  DVG_REQUIRE(burn_in >= 0, "gibbs_tempered_traced: burn_in=%d must be at least 0", burn_in);
-  DVG_REQUIRE(thin >= 1, "gibbs_tempered_traced: thin=%d must be at least 1", thin);
-  // (n_sweeps - burn_in >= thin, without the overflow of burn_in + thin)
-  DVG_REQUIRE(burn_in <= n_sweeps && n_sweeps - burn_in >= thin,
-              "gibbs_tempered_traced: n_sweeps=%d, burn_in=%d, thin=%d record nothing (a draw that records nothing is "
-              "dvg_gibbs_sample_tempered)", n_sweeps, burn_in, thin);
+  DVG_TRY(gibbs_record_check("gibbs_tempered_traced", "dvg_gibbs_sample_tempered", n_sweeps, burn_in, thin));
   GibbsExchangeTraceArgs a;
   gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
                   n_sweeps, init, samples_out, nullptr);
@@ -1291,12 +1296,7 @@ extern "C" int dvg_gibbs_sample_traced(const dvg_graph_t* g, const float* linear
   DVG_TRY(gibbs_check("gibbs_traced", g, linear && quadratic && state,
                       trace_out ? nullptr : "null trace_out (a draw that records nothing is dvg_gibbs_sample)", n_chains, n_sweeps,
                       false, nullptr));
-  DVG_REQUIRE(burn_in >= 0, "gibbs_traced: burn_in=%d must be at least 0", burn_in);
-  DVG_REQUIRE(thin >= 1, "gibbs_traced: thin=%d must be at least 1", thin);
-  // (n_sweeps - burn_in >= thin, without the overflow of burn_in + thin)
-  DVG_REQUIRE(burn_in <= n_sweeps && n_sweeps - burn_in >= thin,
-              "gibbs_traced: n_sweeps=%d, burn_in=%d, thin=%d record nothing (a draw that records nothing is dvg_gibbs_sample)", n_sweeps,
-              burn_in, thin);
+  DVG_TRY(gibbs_record_check("gibbs_traced", "dvg_gibbs_sample", n_sweeps, burn_in, thin));
   DVG_REQUIRE(!dyn, "gibbs_traced: dyn must be NULL (the draw is one-off: the recorded sweeps are counted from the host's sweep0)");
   GibbsTraceArgs a;
   gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, beta, state, n_chains, chain_id0, seed, sweep0,

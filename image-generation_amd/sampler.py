@@ -10,6 +10,7 @@ returns ``(sampler, sampler_kwargs, graph, linear_range, quadratic_range)`` wher
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 from typing import Dict, Optional, Sequence, Tuple
 
 import networkx as nx
@@ -1155,6 +1156,26 @@ class TemperedTrace:
         return f"TemperedTrace({Q} ladders x {R} rungs x {M} records, n={self.n})"
 
 
+def _whole(name: str, v, low: int = 1) -> int:
+    """``v`` as an int, if it is a whole number of at least ``low`` (a bool is none, nor is anything that is not a number)."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < low:
+        raise ValueError(f"{name} must be an integer >= {low}, got {v!r}")
+    return int(v)
+
+
+def _ranges(linear_range, quadratic_range) -> Tuple[float, float, float, float]:
+    """``(h_lo, h_hi, j_lo, j_hi)`` as the library takes them; None: no clamp."""
+    inf = float("inf")
+    hl, hh = linear_range if linear_range is not None else (-inf, inf)
+    jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+    return float(hl), float(hh), float(jl), float(jh)
+
+
+def _on_gpu(name: str, t: torch.Tensor) -> None:
+    if not t.is_cuda:
+        raise _lib.DvgError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
+
+
 class GibbsSampler:
     """``sample_ising``-compatible local solver running on the MI355X.
 
@@ -1253,15 +1274,59 @@ class GibbsSampler:
                                                     ctypes.byref(lds)), "dvg_gibbs_launch_info")
         return {"workgroups": wg.value, "threads": th.value, "lds_bytes": lds.value}
 
+    # -- what the draws share: a draw checks its arguments, allocates its outputs, makes one library call, advances one counter
+    def _check_start(self, start, *, count=None, count_name: str = "num_reads", per: int = 1, rungs=None) -> int:
+        """The host-side checks of a draw's ``start``, in the one order every draw has: a tensor, its dtype, its shape, the
+        chain count the caller named (``count`` groups of ``per`` chains), on the GPU.  The exchange draws' ``rungs`` go
+        beside it.  That it lives where the parameters do is :meth:`_parameters`' to check.  Returns the chains."""
+        n, named = self.plan.n, (("start", start),) + ((("rungs", rungs),) if per > 1 else ())
+        for name, t in named:
+            if not torch.is_tensor(t):
+                raise _lib.DvgError(f"{name} must be a tensor, got {type(t).__name__}")
+        if start.dtype not in (torch.float32, torch.int8):
+            raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
+        if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1 or start.shape[0] % per:
+            raise _lib.DvgError(f"start must be ({'chains' if per == 1 else f'ladders x {per}'}, {n}), got {tuple(start.shape)}")
+        C = int(start.shape[0])
+        if per > 1 and (rungs.dtype not in (torch.int32, torch.int64) or tuple(rungs.shape) != (C,)):
+            raise _lib.DvgError(f"rungs must be ({C},) int32 or int64, got {tuple(rungs.shape)} {rungs.dtype}")
+        if count is not None and count != C // per:
+            raise _lib.DvgError(f"{count_name}={count!r} but start has {C} chains" + (f" ({per} per ladder)" if per > 1 else ""))
+        for name, t in named:
+            _on_gpu(name, t)
+        return C
+
+    def _parameters(self, linear, quadratic, **beside):
+        """``(lin, quad)``: the detached parameters, on the GPU, contiguous and of the graph's sizes.  ``beside``: the draw's
+        other tensors by name (None and host values pass); one on another GPU than the parameters' is an error."""
+        lin = _lib.require_cuda(linear.detach(), "linear")
+        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
+        if lin.numel() != self.plan.n or quad.numel() != self.plan.n_edges:
+            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
+        for name, t in beside.items():
+            if torch.is_tensor(t) and t.is_cuda and t.device != lin.device:
+                raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
+        return lin, quad
+
+    def _own_chains(self, start, C: int, device):
+        """``(state, init)`` of a one-off draw, never the persistent chains: an empty buffer the INIT stream fills, or the
+        call's own contiguous int8 copy of ``start``."""
+        if start is None:
+            return torch.empty((C, self.plan.n), dtype=torch.int8, device=device), 1
+        return start.detach().to(torch.int8, copy=True).contiguous(), 0
+
+    def _call(self, name: str, lin, quad, prefactor, linear_range, quadratic_range, *rest) -> None:
+        """One library call on the parameters' device and current stream: the graph and the model arguments every draw's entry
+        point begins with, then ``rest`` (which ends with ``dyn``), then the stream."""
+        head = (lin.data_ptr(), quad.data_ptr(), float(prefactor)) + _ranges(linear_range, quadratic_range)
+        with torch.cuda.device(lin.device):
+            _lib.check(getattr(_lib.lib(), name)(self.graph.ptr, *head, *rest, _lib.stream_ptr(lin.device)), name)
+
     def sample_native(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float,
                       linear_range=None, quadratic_range=None, num_reads: int = 256) -> torch.Tensor:
         """Device tensors in, (num_reads, n) float32 +-1 device tensor out; no host sync."""
-        L = _lib.lib()
-        lin = _lib.require_cuda(linear.detach(), "linear")
-        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
+        lin, quad = self._parameters(linear, quadratic)
         n = self.plan.n
-        if lin.numel() != n or quad.numel() != self.plan.n_edges:
-            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
         init = 0
         if self._state is None or not self.persistent or self._state.shape[0] != num_reads:
             self._state = torch.empty((num_reads, n), dtype=torch.int8, device=lin.device)
@@ -1269,31 +1334,16 @@ class GibbsSampler:
             if not self.persistent:
                 pass  # fresh chains every call; the sweep counter keeps the random stream moving
         out = torch.empty((num_reads, n), dtype=torch.float32, device=lin.device)
-        inf = float("inf")
-        hl, hh = linear_range if linear_range is not None else (-inf, inf)
-        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
         betas = self._betas
         if betas is not None and (betas.device != lin.device or int(betas.shape[0]) != self.sweeps):
             raise _lib.DvgError(f"the beta schedule ({tuple(betas.shape)} on {betas.device}) does not match the draw "
                                 f"({self.sweeps} sweeps on {lin.device}); set it again with set_beta_schedule")
-        with torch.cuda.device(lin.device):
-            if betas is None:
-                _lib.check(
-                    L.dvg_gibbs_sample(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
-                                       float(hh), float(jl), float(jh), self.beta, self._state.data_ptr(), num_reads,
-                                       self.chain_offset & 0xFFFFFFFF, self.seed, self.sweep_count & 0xFFFFFFFF,
-                                       self.sweeps, init, out.data_ptr(), _lib.DYN, _lib.stream_ptr(lin.device)),
-                    "dvg_gibbs_sample",
-                )
-            else:
-                _lib.check(
-                    L.dvg_gibbs_sample_annealed(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor),
-                                                float(hl), float(hh), float(jl), float(jh), betas.data_ptr(), 0,
-                                                self._state.data_ptr(), num_reads, self.chain_offset & 0xFFFFFFFF,
-                                                self.seed, self.sweep_count & 0xFFFFFFFF, self.sweeps, init,
-                                                out.data_ptr(), _lib.DYN, _lib.stream_ptr(lin.device)),
-                    "dvg_gibbs_sample_annealed",
-                )
+        tail = (self._state.data_ptr(), num_reads, self.chain_offset & 0xFFFFFFFF, self.seed, self.sweep_count & 0xFFFFFFFF,
+                self.sweeps, init, out.data_ptr(), _lib.DYN)
+        if betas is None:
+            self._call("dvg_gibbs_sample", lin, quad, prefactor, linear_range, quadratic_range, self.beta, *tail)
+        else:
+            self._call("dvg_gibbs_sample_annealed", lin, quad, prefactor, linear_range, quadratic_range, betas.data_ptr(), 0, *tail)
         self.sweep_count += self.sweeps
         self.calls += 1
         return out
@@ -1311,51 +1361,29 @@ class GibbsSampler:
         Apart from the graph handle it shares nothing with the training draws: it leaves the persistent chains,
         ``sweep_count`` and ``calls`` alone, counts its sweeps in ``cond_sweep_count`` and draws its random words under
         its own key ``cond_seed``; chain ids are ``chain_offset + arange(C)``."""
-        L = _lib.lib()
-        lin = _lib.require_cuda(linear.detach(), "linear")
-        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
         n = self.plan.n
-        if lin.numel() != n or quad.numel() != self.plan.n_edges:
-            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
-        for name, t in (("start", start), ("clamp", clamp)):
-            if not t.is_cuda:
-                raise _lib.DvgError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
-            if t.device != lin.device:
-                raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
-        if start.dtype not in (torch.float32, torch.int8):
-            raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
-        if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1:
-            raise _lib.DvgError(f"start must be (chains, {n}), got {tuple(start.shape)}")
-        C = int(start.shape[0])
+        C = self._check_start(start)
         if tuple(clamp.shape) not in ((C, n), (n,)):
             raise _lib.DvgError(f"clamp must be ({C}, {n}) or ({n},), got {tuple(clamp.shape)}")
         if clamp.dtype not in (torch.bool, torch.uint8):
             raise _lib.DvgError(f"clamp must be bool or uint8, got {clamp.dtype}")
-        state = start.detach().to(torch.int8, copy=True).contiguous()  # the call's own chains, never the persistent ones
+        _on_gpu("clamp", clamp)
+        lin, quad = self._parameters(linear, quadratic, start=start, clamp=clamp)
+        state, _init = self._own_chains(start, C, lin.device)
         flags = clamp.detach().to(torch.uint8).contiguous()
         stride = n if flags.dim() == 2 else 0
         n_sweeps = self.sweeps if sweeps is None else int(sweeps)
         out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
-        inf = float("inf")
-        hl, hh = linear_range if linear_range is not None else (-inf, inf)
-        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
-        with torch.cuda.device(lin.device):
-            _lib.check(
-                L.dvg_gibbs_sample_clamped(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
-                                           float(hh), float(jl), float(jh), self.beta, state.data_ptr(), C,
-                                           self.chain_offset & 0xFFFFFFFF, self.cond_seed,
-                                           self.cond_sweep_count & 0xFFFFFFFF, n_sweeps, int(bool(init_free)),
-                                           flags.data_ptr(), stride, out.data_ptr(), None, _lib.stream_ptr(lin.device)),
-                "dvg_gibbs_sample_clamped",
-            )
+        self._call("dvg_gibbs_sample_clamped", lin, quad, prefactor, linear_range, quadratic_range, self.beta, state.data_ptr(), C,
+                   self.chain_offset & 0xFFFFFFFF, self.cond_seed, self.cond_sweep_count & 0xFFFFFFFF, n_sweeps,
+                   int(bool(init_free)), flags.data_ptr(), stride, out.data_ptr(), None)
         self.cond_sweep_count += n_sweeps
         return out
 
-    def _annealed_arguments(self, linear, quadratic, linear_range, quadratic_range, betas, num_reads, start, beta_from=None):
+    def _annealed_arguments(self, linear, quadratic, betas, num_reads, start, beta_from=None):
         """The argument checks and buffers :meth:`sample_annealed` and :meth:`sample_ais` share; every check comes before
-        the first library call.  Returns (lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh))."""
-        n = self.plan.n
-        # every argument check comes before the first library call (the table's upload included)
+        the first library call (the table's upload included).  Returns them by name: ``lin``, ``quad``, the device ``table``
+        of ``S`` sweeps and its chain ``stride``, the ``C`` chains' ``state`` and ``init``, and ``out``."""
         if beta_from is not None:  # (sample_ais)
             bf = float(beta_from)
             with np.errstate(over="ignore"):
@@ -1366,21 +1394,9 @@ class GibbsSampler:
                 raise ValueError(f"beta_from={beta_from!r} with fresh chains: they are uniform, a sample at beta 0 and at no "
                                  "other; give the chains' states as `start`")
         if start is not None:
-            if not torch.is_tensor(start):
-                raise _lib.DvgError(f"start must be a tensor, got {type(start).__name__}")
-            if start.dtype not in (torch.float32, torch.int8):
-                raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
-            if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1:
-                raise _lib.DvgError(f"start must be (chains, {n}), got {tuple(start.shape)}")
-            if not start.is_cuda:
-                raise _lib.DvgError(f"start must live on the GPU (got {start.device}); the HIP path has no CPU fallback")
-            if num_reads is not None and num_reads != int(start.shape[0]):
-                raise _lib.DvgError(f"num_reads={num_reads!r} but start has {int(start.shape[0])} chains")
-            C = int(start.shape[0])
+            C = self._check_start(start, count=num_reads)
         elif num_reads is not None:
-            if isinstance(num_reads, bool) or int(num_reads) != num_reads or int(num_reads) < 1:
-                raise ValueError(f"num_reads must be an integer >= 1, got {num_reads!r}")
-            C = int(num_reads)
+            C = _whole("num_reads", num_reads)
         else:
             try:
                 shape = tuple(betas.shape) if hasattr(betas, "shape") else np.shape(betas)
@@ -1390,25 +1406,13 @@ class GibbsSampler:
                 raise ValueError("an annealed draw needs num_reads, start or a (chains, sweeps) table to know how many chains to draw")
             C = int(shape[0])
         _check_beta_table(betas, "betas", rows=C)
-        lin = _lib.require_cuda(linear.detach(), "linear")
-        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
-        if lin.numel() != n or quad.numel() != self.plan.n_edges:
-            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
-        for name, t in (("start", start), ("betas", betas)):
-            if torch.is_tensor(t) and t.is_cuda and t.device != lin.device:
-                raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
+        lin, quad = self._parameters(linear, quadratic, start=start, betas=betas)
         table = _beta_table(betas, lin.device, "betas", rows=C)
         S = int(table.shape[-1])
-        stride = S if table.dim() == 2 else 0
-        if start is None:
-            state, init = torch.empty((C, n), dtype=torch.int8, device=lin.device), 1
-        else:
-            state, init = start.detach().to(torch.int8, copy=True).contiguous(), 0  # the call's own chains
-        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
-        inf = float("inf")
-        hl, hh = linear_range if linear_range is not None else (-inf, inf)
-        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
-        return lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh)
+        state, init = self._own_chains(start, C, lin.device)
+        out = torch.empty((C, self.plan.n), dtype=torch.float32, device=lin.device)
+        return SimpleNamespace(lin=lin, quad=quad, table=table, S=S, stride=S if table.dim() == 2 else 0, C=C, state=state,
+                               init=init, out=out)
 
     def sample_annealed(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
                         quadratic_range, betas, *, num_reads: Optional[int] = None,
@@ -1424,20 +1428,12 @@ class GibbsSampler:
         ``sweep_count``, ``calls`` and any schedule set with :meth:`set_beta_schedule` alone, counts its sweeps in
         ``anneal_sweep_count`` and draws its random words under its own key ``anneal_seed``; chain ids are
         ``chain_offset + arange(C)``."""
-        lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh) = self._annealed_arguments(
-            linear, quadratic, linear_range, quadratic_range, betas, num_reads, start)
-        C = int(out.shape[0])
-        with torch.cuda.device(lin.device):
-            _lib.check(
-                _lib.lib().dvg_gibbs_sample_annealed(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor),
-                                                     float(hl), float(hh), float(jl), float(jh), table.data_ptr(), stride,
-                                                     state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF, self.anneal_seed,
-                                                     self.anneal_sweep_count & 0xFFFFFFFF, S, init, out.data_ptr(), None,
-                                                     _lib.stream_ptr(lin.device)),
-                "dvg_gibbs_sample_annealed",
-            )
-        self.anneal_sweep_count += S
-        return out
+        a = self._annealed_arguments(linear, quadratic, betas, num_reads, start)
+        self._call("dvg_gibbs_sample_annealed", a.lin, a.quad, prefactor, linear_range, quadratic_range, a.table.data_ptr(), a.stride,
+                   a.state.data_ptr(), a.C, self.chain_offset & 0xFFFFFFFF, self.anneal_seed, self.anneal_sweep_count & 0xFFFFFFFF,
+                   a.S, a.init, a.out.data_ptr(), None)
+        self.anneal_sweep_count += a.S
+        return a.out
 
     def sample_ais(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
                    betas, *, num_reads: Optional[int] = None, start: Optional[torch.Tensor] = None, beta_from: float = 0.0):
@@ -1453,22 +1449,14 @@ class GibbsSampler:
 
         Its own key ``ais_seed`` and counter ``ais_sweep_count``: the training, conditional and annealed streams are
         left alone."""
-        lin, quad, table, S, stride, state, init, out, (hl, hh, jl, jh) = self._annealed_arguments(
-            linear, quadratic, linear_range, quadratic_range, betas, num_reads, start, beta_from=beta_from)
-        C = int(out.shape[0])
-        log_w = torch.empty((C,), dtype=torch.float64, device=lin.device)
-        energy = torch.empty((C,), dtype=torch.float64, device=lin.device)
-        with torch.cuda.device(lin.device):
-            _lib.check(
-                _lib.lib().dvg_gibbs_sample_ais(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
-                                                float(hh), float(jl), float(jh), table.data_ptr(), stride, float(beta_from),
-                                                state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF, self.ais_seed,
-                                                self.ais_sweep_count & 0xFFFFFFFF, S, init, out.data_ptr(),
-                                                log_w.data_ptr(), energy.data_ptr(), None, _lib.stream_ptr(lin.device)),
-                "dvg_gibbs_sample_ais",
-            )
-        self.ais_sweep_count += S
-        return out, log_w, energy
+        a = self._annealed_arguments(linear, quadratic, betas, num_reads, start, beta_from=beta_from)
+        log_w = torch.empty((a.C,), dtype=torch.float64, device=a.lin.device)
+        energy = torch.empty((a.C,), dtype=torch.float64, device=a.lin.device)
+        self._call("dvg_gibbs_sample_ais", a.lin, a.quad, prefactor, linear_range, quadratic_range, a.table.data_ptr(), a.stride,
+                   float(beta_from), a.state.data_ptr(), a.C, self.chain_offset & 0xFFFFFFFF, self.ais_seed,
+                   self.ais_sweep_count & 0xFFFFFFFF, a.S, a.init, a.out.data_ptr(), log_w.data_ptr(), energy.data_ptr(), None)
+        self.ais_sweep_count += a.S
+        return a.out, log_w, energy
 
     def log_partition(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
                       *, beta: Optional[float] = None, num_sweeps: int = 1000, num_reads: int = 1024,
@@ -1480,12 +1468,10 @@ class GibbsSampler:
         plain torch ops on the device, no host sync."""
         if schedule not in ("linear", "geometric"):
             raise ValueError(f"schedule must be 'linear' or 'geometric', got {schedule!r}")
-        if isinstance(num_sweeps, bool) or int(num_sweeps) != num_sweeps or int(num_sweeps) < 2:
-            raise ValueError(f"num_sweeps must be an integer >= 2, got {num_sweeps!r}")
+        num_sweeps = _whole("num_sweeps", num_sweeps, 2)
         b = float(self.beta if beta is None else beta)
         if not np.isfinite(b) or b <= 0.0:
             raise ValueError(f"beta={beta!r} must be finite and > 0")
-        num_sweeps = int(num_sweeps)
         if schedule == "linear":
             betas = beta_schedule(0.0, b, num_sweeps, "linear")
         else:
@@ -1518,18 +1504,13 @@ class GibbsSampler:
         sched = _check_beta_table(betas, "betas")
         if sched.ndim != 1:
             raise _lib.DvgError(f"betas must be (steps,), got {tuple(sched.shape)}")
-        for name, v in (("num_reads", num_reads), ("num_populations", num_populations), ("sweeps_per_beta", sweeps_per_beta)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < 1:
-                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
-        C, P, theta, T = int(num_reads), int(num_populations), int(sweeps_per_beta), int(sched.size)
+        C, P = _whole("num_reads", num_reads), _whole("num_populations", num_populations)
+        theta, T = _whole("sweeps_per_beta", sweeps_per_beta), int(sched.size)
         if C % P:
             raise ValueError(f"num_populations={num_populations!r} does not divide num_reads={num_reads!r}")
         if C // P > 2 ** 20:
             raise ValueError(f"num_reads={num_reads!r} / num_populations={num_populations!r}: more than 2^20 chains per population")
-        lin = _lib.require_cuda(linear.detach(), "linear")
-        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
-        if lin.numel() != n or quad.numel() != self.plan.n_edges:
-            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
+        lin, quad = self._parameters(linear, quadratic)
         dev = lin.device
         L = _lib.lib()
         table = torch.from_numpy(np.repeat(sched, theta)).to(dev)  # (T theta,) float32: each call points into it
@@ -1542,9 +1523,6 @@ class GibbsSampler:
         parents = torch.empty((T if history else 1, C), dtype=torch.int32, device=dev)
         log_z = torch.full((P,), n * float(np.log(2.0)), dtype=torch.float64, device=dev)
         ess = torch.empty((T, P), dtype=torch.float64, device=dev)
-        inf = float("inf")
-        hl, hh = linear_range if linear_range is not None else (-inf, inf)
-        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
         with torch.cuda.device(dev):
             ws = torch.empty((int(L.dvg_population_resample_workspace_bytes(C)),), dtype=torch.uint8, device=dev)
             stream = _lib.stream_ptr(dev)
@@ -1552,13 +1530,9 @@ class GibbsSampler:
                 lw = log_w.data_ptr() + 8 * C * (t % rows)
                 par = parents.data_ptr() + (4 * C * t if history else 0)
                 sweep0 = self.pa_sweep_count + t * theta
-                _lib.check(
-                    L.dvg_gibbs_sample_ais(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl), float(hh),
-                                           float(jl), float(jh), table.data_ptr() + 4 * t * theta, 0,
-                                           float(sched[t - 1]) if t else 0.0, state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF,
-                                           self.pa_seed, sweep0 & 0xFFFFFFFF, theta, int(t == 0), None, lw, None, None, stream),
-                    "dvg_gibbs_sample_ais",
-                )
+                self._call("dvg_gibbs_sample_ais", lin, quad, prefactor, linear_range, quadratic_range, table.data_ptr() + 4 * t * theta,
+                           0, float(sched[t - 1]) if t else 0.0, state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF, self.pa_seed,
+                           sweep0 & 0xFFFFFFFF, theta, int(t == 0), None, lw, None, None)
                 _lib.check(
                     L.dvg_population_resample(lw, C, P, self.chain_offset & 0xFFFFFFFF, self.pa_seed,
                                               (sweep0 + theta) & 0xFFFFFFFF, state.data_ptr(), other.data_ptr(), n,
@@ -1593,107 +1567,63 @@ class GibbsSampler:
 
         Its own key ``pt_seed`` and counter ``pt_sweep_count`` (which also numbers the exchanges): the training,
         conditional, annealed and AIS streams are left alone.  Chain ids are ``chain_offset + arange(Q R)``."""
-        ladder, R, Q, S, swap_every, _M, lin, quad = self._tempered_arguments(linear, quadratic, betas, num_ladders, num_sweeps,
-                                                                              swap_every, start, rungs)
-        return self._tempered_draw(lin, quad, prefactor, linear_range, quadratic_range, ladder, R, Q, S, swap_every, start, rungs)
+        a = self._tempered_arguments(linear, quadratic, betas, num_ladders, num_sweeps, swap_every, start, rungs)
+        return self._tempered_draw(a, prefactor, linear_range, quadratic_range)[0]
 
-    def _tempered_arguments(self, linear, quadratic, betas, num_ladders, num_sweeps, swap_every, start, rungs, record=None):
+    def _tempered_arguments(self, linear, quadratic, betas, num_ladders, num_sweeps, swap_every, start, rungs, traced=False,
+                            burn_in=0, thin=1):
         """The argument checks of the exchange draws, every one before the first library call (the ladder's upload included).
-        ``record``: the traced draw's ``(burn_in, thin)``, checked as :meth:`sample_trace` does.  Returns the ladder (host
-        float32), R, Q, the sweeps, ``swap_every``, the records M (None without ``record``) and the parameters."""
-        n = self.plan.n
+        ``traced``: ``burn_in`` and ``thin`` count, checked as :meth:`sample_trace` does.  Returns by name the ``ladder`` (host
+        float32), ``R``, ``Q``, the sweeps ``S``, ``swap_every``, ``burn_in``, ``thin``, the records ``M`` (None unless
+        ``traced``), ``start``, ``rungs`` and the parameters ``lin``, ``quad``."""
         if torch.is_tensor(betas) and betas.is_cuda:
             raise _lib.DvgError("betas: the ladder is a host sequence, array or CPU tensor (it is checked, then uploaded)")
         ladder = _check_beta_table(betas, "betas")
         if ladder.ndim != 1 or not 2 <= ladder.size <= 16:
             raise _lib.DvgError(f"betas must be (replicas,) with 2 to 16 replicas, got {tuple(ladder.shape)}")
-        R = int(ladder.size)
-        for name, v in (("num_ladders", num_ladders), ("swap_every", swap_every),
-                        ("num_sweeps", self.sweeps if num_sweeps is None else num_sweeps)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < 1:
-                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
-        Q, S, swap_every = int(num_ladders), int(self.sweeps if num_sweeps is None else num_sweeps), int(swap_every)
-        M = None
-        if record is not None:
-            for name, v, low in (("burn_in", record[0], 0), ("thin", record[1], 1)):
-                if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < low:
-                    raise ValueError(f"{name} must be an integer >= {low}, got {v!r}")
-            M = (S - int(record[0])) // int(record[1])
+        R, Q, swap_every = int(ladder.size), _whole("num_ladders", num_ladders), _whole("swap_every", swap_every)
+        S, M = _whole("num_sweeps", self.sweeps if num_sweeps is None else num_sweeps), None
+        if traced:
+            burn_in, thin = _whole("burn_in", burn_in, 0), _whole("thin", thin)
+            M = (S - burn_in) // thin
             if M < 1:
-                raise ValueError(f"num_sweeps={S}, burn_in={int(record[0])}, thin={int(record[1])} record nothing (a draw without "
-                                 "a trace is sample_tempered)")
+                raise ValueError(f"num_sweeps={S}, burn_in={burn_in}, thin={thin} record nothing (a draw without a trace is "
+                                 "sample_tempered)")
         if (start is None) != (rungs is None):
             raise ValueError("start and rungs go together: give both (to continue a draw) or neither (fresh chains)")
         if start is not None:
-            for name, t in (("start", start), ("rungs", rungs)):
-                if not torch.is_tensor(t):
-                    raise _lib.DvgError(f"{name} must be a tensor, got {type(t).__name__}")
-            if start.dtype not in (torch.float32, torch.int8):
-                raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
-            if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1 or start.shape[0] % R:
-                raise _lib.DvgError(f"start must be (ladders x {R}, {n}), got {tuple(start.shape)}")
-            if rungs.dtype not in (torch.int32, torch.int64) or tuple(rungs.shape) != (int(start.shape[0]),):
-                raise _lib.DvgError(f"rungs must be ({int(start.shape[0])},) int32 or int64, got {tuple(rungs.shape)} {rungs.dtype}")
-            if int(start.shape[0]) != Q * R:
-                raise _lib.DvgError(f"num_ladders={num_ladders!r} but start has {int(start.shape[0])} chains ({R} per ladder)")
-            for name, t in (("start", start), ("rungs", rungs)):
-                if not t.is_cuda:
-                    raise _lib.DvgError(f"{name} must live on the GPU (got {t.device}); the HIP path has no CPU fallback")
-        lin = _lib.require_cuda(linear.detach(), "linear")
-        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
-        if lin.numel() != n or quad.numel() != self.plan.n_edges:
-            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
-        for name, t in (("start", start), ("rungs", rungs)):
-            if t is not None and t.device != lin.device:
-                raise _lib.DvgError(f"{name} is on {t.device}, the model parameters on {lin.device}")
-        return ladder, R, Q, S, swap_every, M, lin, quad
+            self._check_start(start, count=num_ladders, count_name="num_ladders", per=R, rungs=rungs)
+        lin, quad = self._parameters(linear, quadratic, start=start, rungs=rungs)
+        return SimpleNamespace(ladder=ladder, R=R, Q=Q, S=S, swap_every=swap_every, burn_in=burn_in, thin=thin, M=M, start=start,
+                               rungs=rungs, lin=lin, quad=quad)
 
-    def _tempered_draw(self, lin, quad, prefactor, linear_range, quadratic_range, ladder, R, Q, S, swap_every, start, rungs,
-                       record=None):
-        """The exchange draw on checked arguments.  ``record``: None, or the traced draw's ``(burn_in, thin, M, energies,
-        rung_walk)`` -- then ``(Tempered, bits, energies or None, walk or None)`` is returned."""
-        n, C = self.plan.n, Q * R
-        table = torch.from_numpy(ladder).to(lin.device)
-        if start is None:
-            state, rung, init = (torch.empty((C, n), dtype=torch.int8, device=lin.device),
-                                 torch.empty((C,), dtype=torch.int32, device=lin.device), 1)
-        else:  # the call's own chains
-            state, rung, init = start.detach().to(torch.int8, copy=True).contiguous(), rungs.detach().to(torch.int32, copy=True).contiguous(), 0
-        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
-        energy = torch.empty((C,), dtype=torch.float64, device=lin.device)
-        accept = torch.empty((C,), dtype=torch.int32, device=lin.device)  # (uint32 counts; a draw has fewer than 2^31 exchanges)
-        inf = float("inf")
-        hl, hh = linear_range if linear_range is not None else (-inf, inf)
-        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
+    def _tempered_draw(self, a, prefactor, linear_range, quadratic_range, energies=False, rung_walk=False):
+        """The exchange draw on checked arguments (:meth:`_tempered_arguments`' ``a``); with records (``a.M``) the traced entry
+        point, which takes the same arguments and five more.  Returns ``(Tempered, bits, energies, walk)``: the last three
+        are the trace's buffers, None where there is none."""
+        n, R, C, dev = self.plan.n, a.R, a.Q * a.R, a.lin.device
+        table = torch.from_numpy(a.ladder).to(dev)
+        state, init = self._own_chains(a.start, C, dev)
+        if a.rungs is None:
+            rung = torch.empty((C,), dtype=torch.int32, device=dev)
+        else:
+            rung = a.rungs.detach().to(torch.int32, copy=True).contiguous()
+        out = torch.empty((C, n), dtype=torch.float32, device=dev)
+        energy = torch.empty((C,), dtype=torch.float64, device=dev)
+        accept = torch.empty((C,), dtype=torch.int32, device=dev)  # (uint32 counts; a draw has fewer than 2^31 exchanges)
         sweep0 = self.pt_sweep_count & 0xFFFFFFFF
-        if record is not None:
-            burn_in, thin, M, with_energies, with_walk = record
-            bits = torch.empty((Q, R, M, (n + 31) // 32), dtype=torch.int32, device=lin.device)
-            e_trace = torch.empty((Q, R, M), dtype=torch.float64, device=lin.device) if with_energies else None
-            walk = torch.empty((Q, R, M), dtype=torch.uint8, device=lin.device) if with_walk else None
-            with torch.cuda.device(lin.device):
-                _lib.check(
-                    _lib.lib().dvg_gibbs_sample_tempered_traced(
-                        self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl), float(hh), float(jl), float(jh),
-                        table.data_ptr(), R, swap_every, state.data_ptr(), rung.data_ptr(), C, self.chain_offset & 0xFFFFFFFF,
-                        self.pt_seed, sweep0, S, init, out.data_ptr(), energy.data_ptr(), accept.data_ptr(), bits.data_ptr(),
-                        None if e_trace is None else e_trace.data_ptr(), None if walk is None else walk.data_ptr(), burn_in, thin,
-                        None, _lib.stream_ptr(lin.device)),
-                    "dvg_gibbs_sample_tempered_traced",
-                )
-            self.pt_sweep_count += S
-            return Tempered.from_draw(n, R, out, energy, accept, sweep0, S, swap_every, state, rung), bits, e_trace, walk
-        with torch.cuda.device(lin.device):
-            _lib.check(
-                _lib.lib().dvg_gibbs_sample_tempered(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
-                                                     float(hh), float(jl), float(jh), table.data_ptr(), R, swap_every,
-                                                     state.data_ptr(), rung.data_ptr(), C, self.chain_offset & 0xFFFFFFFF,
-                                                     self.pt_seed, sweep0, S, init, out.data_ptr(), energy.data_ptr(),
-                                                     accept.data_ptr(), None, _lib.stream_ptr(lin.device)),
-                "dvg_gibbs_sample_tempered",
-            )
-        self.pt_sweep_count += S
-        return Tempered.from_draw(n, R, out, energy, accept, sweep0, S, swap_every, state, rung)
+        name, bits, e_trace, walk = "dvg_gibbs_sample_tempered", None, None, None
+        args = [table.data_ptr(), R, a.swap_every, state.data_ptr(), rung.data_ptr(), C, self.chain_offset & 0xFFFFFFFF, self.pt_seed,
+                sweep0, a.S, init, out.data_ptr(), energy.data_ptr(), accept.data_ptr()]
+        if a.M is not None:
+            name = "dvg_gibbs_sample_tempered_traced"
+            bits = torch.empty((a.Q, R, a.M, (n + 31) // 32), dtype=torch.int32, device=dev)
+            e_trace = torch.empty((a.Q, R, a.M), dtype=torch.float64, device=dev) if energies else None
+            walk = torch.empty((a.Q, R, a.M), dtype=torch.uint8, device=dev) if rung_walk else None
+            args += [bits.data_ptr(), _lib.ptr(e_trace), _lib.ptr(walk), a.burn_in, a.thin]
+        self._call(name, a.lin, a.quad, prefactor, linear_range, quadratic_range, *args, None)
+        self.pt_sweep_count += a.S
+        return Tempered.from_draw(n, R, out, energy, accept, sweep0, a.S, a.swap_every, state, rung), bits, e_trace, walk
 
     def sample_tempered_trace(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
                               quadratic_range, betas, *, num_ladders: int, num_sweeps: Optional[int] = None, swap_every: int = 1,
@@ -1711,13 +1641,10 @@ class GibbsSampler:
 
         The stream is :meth:`sample_tempered`'s: the key ``pt_seed``, and ``pt_sweep_count`` advances by ``num_sweeps``;
         every other stream and counter is left alone."""
-        ladder, R, Q, S, swap_every, M, lin, quad = self._tempered_arguments(linear, quadratic, betas, num_ladders, num_sweeps,
-                                                                             swap_every, start, rungs, record=(burn_in, thin))
-        burn_in, thin = int(burn_in), int(thin)
-        final, bits, e_trace, walk = self._tempered_draw(lin, quad, prefactor, linear_range, quadratic_range, ladder, R, Q, S,
-                                                         swap_every, start, rungs,
-                                                         record=(burn_in, thin, M, bool(energies), bool(rung_walk)))
-        return TemperedTrace(bits, e_trace, walk, trace_sweeps(S, burn_in, thin), final, ladder, self.plan.n)
+        a = self._tempered_arguments(linear, quadratic, betas, num_ladders, num_sweeps, swap_every, start, rungs, traced=True,
+                                     burn_in=burn_in, thin=thin)
+        final, bits, e_trace, walk = self._tempered_draw(a, prefactor, linear_range, quadratic_range, bool(energies), bool(rung_walk))
+        return TemperedTrace(bits, e_trace, walk, trace_sweeps(a.S, a.burn_in, a.thin), final, a.ladder, self.plan.n)
 
     def sample_trace(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range, *,
                      num_reads: Optional[int] = None, start: Optional[torch.Tensor] = None, num_sweeps: Optional[int] = None,
@@ -1735,57 +1662,24 @@ class GibbsSampler:
         arange(C)``."""
         n = self.plan.n
         # every argument check comes before the first library call
-        for name, v, low in (("num_sweeps", self.sweeps if num_sweeps is None else num_sweeps, 1), ("burn_in", burn_in, 0),
-                             ("thin", thin, 1)):
-            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or int(v) < low:
-                raise ValueError(f"{name} must be an integer >= {low}, got {v!r}")
-        S, burn_in, thin = int(self.sweeps if num_sweeps is None else num_sweeps), int(burn_in), int(thin)
+        S = _whole("num_sweeps", self.sweeps if num_sweeps is None else num_sweeps)
+        burn_in, thin = _whole("burn_in", burn_in, 0), _whole("thin", thin)
         M = (S - burn_in) // thin
         if M < 1:
             raise ValueError(f"num_sweeps={S}, burn_in={burn_in}, thin={thin} record nothing (a draw without a trace is sample_native)")
         if start is not None:
-            if not torch.is_tensor(start):
-                raise _lib.DvgError(f"start must be a tensor, got {type(start).__name__}")
-            if start.dtype not in (torch.float32, torch.int8):
-                raise _lib.DvgError(f"start must be float32 or int8 (+-1), got {start.dtype}")
-            if start.dim() != 2 or start.shape[1] != n or start.shape[0] < 1:
-                raise _lib.DvgError(f"start must be (chains, {n}), got {tuple(start.shape)}")
-            if num_reads is not None and num_reads != int(start.shape[0]):
-                raise _lib.DvgError(f"num_reads={num_reads!r} but start has {int(start.shape[0])} chains")
-            if not start.is_cuda:
-                raise _lib.DvgError(f"start must live on the GPU (got {start.device}); the HIP path has no CPU fallback")
-            C = int(start.shape[0])
+            C = self._check_start(start, count=num_reads)
         elif num_reads is not None:
-            if isinstance(num_reads, bool) or not isinstance(num_reads, (int, float, np.integer, np.floating)) or \
-                    int(num_reads) != num_reads or int(num_reads) < 1:
-                raise ValueError(f"num_reads must be an integer >= 1, got {num_reads!r}")
-            C = int(num_reads)
+            C = _whole("num_reads", num_reads)
         else:
             raise ValueError("a traced draw needs num_reads (fresh chains) or start to know how many chains to draw")
-        lin = _lib.require_cuda(linear.detach(), "linear")
-        quad = _lib.require_cuda(quadratic.detach(), "quadratic")
-        if lin.numel() != n or quad.numel() != self.plan.n_edges:
-            raise _lib.DvgError("linear/quadratic do not match the sampler's graph")
-        if start is not None and start.device != lin.device:
-            raise _lib.DvgError(f"start is on {start.device}, the model parameters on {lin.device}")
-        if start is None:
-            state, init = torch.empty((C, n), dtype=torch.int8, device=lin.device), 1
-        else:
-            state, init = start.detach().to(torch.int8, copy=True).contiguous(), 0  # the call's own chains
+        lin, quad = self._parameters(linear, quadratic, start=start)
+        state, init = self._own_chains(start, C, lin.device)
         out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
         bits = torch.empty((C, M, (n + 31) // 32), dtype=torch.int32, device=lin.device)
-        inf = float("inf")
-        hl, hh = linear_range if linear_range is not None else (-inf, inf)
-        jl, jh = quadratic_range if quadratic_range is not None else (-inf, inf)
-        with torch.cuda.device(lin.device):
-            _lib.check(
-                _lib.lib().dvg_gibbs_sample_traced(self.graph.ptr, lin.data_ptr(), quad.data_ptr(), float(prefactor), float(hl),
-                                                   float(hh), float(jl), float(jh), self.beta, state.data_ptr(), C,
-                                                   self.chain_offset & 0xFFFFFFFF, self.trace_seed,
-                                                   self.trace_sweep_count & 0xFFFFFFFF, S, init, out.data_ptr(), bits.data_ptr(),
-                                                   burn_in, thin, None, _lib.stream_ptr(lin.device)),
-                "dvg_gibbs_sample_traced",
-            )
+        self._call("dvg_gibbs_sample_traced", lin, quad, prefactor, linear_range, quadratic_range, self.beta, state.data_ptr(), C,
+                   self.chain_offset & 0xFFFFFFFF, self.trace_seed, self.trace_sweep_count & 0xFFFFFFFF, S, init, out.data_ptr(),
+                   bits.data_ptr(), burn_in, thin, None)
         self.trace_sweep_count += S
         return Trace(bits, out, state, trace_sweeps(S, burn_in, thin), n)
 
@@ -1826,9 +1720,7 @@ class GibbsSampler:
         elif num_sweeps is not None:
             raise ValueError("num_sweeps needs beta_range (or a beta_schedule): a fixed-beta draw runs the sampler's own sweeps")
         if betas is not None:
-            if isinstance(num_reads, bool) or int(num_reads) != num_reads or int(num_reads) < 1:
-                raise ValueError(f"num_reads must be an integer >= 1, got {num_reads!r}")
-            _check_beta_table(betas, "beta_schedule", rows=int(num_reads))  # (before anything is built or uploaded)
+            _check_beta_table(betas, "beta_schedule", rows=_whole("num_reads", num_reads))  # (before anything is built or uploaded)
             if num_sweeps is not None and beta_schedule is not None and int(num_sweeps) != int(np.shape(betas)[-1]):
                 raise ValueError(f"num_sweeps={num_sweeps} does not match the beta_schedule given ({np.shape(betas)[-1]} sweeps)")
         idx = {v: k for k, v in enumerate(self.nodes)}
