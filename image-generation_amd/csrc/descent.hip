@@ -26,10 +26,8 @@ namespace dvg {
 // sweeps whose OR has its bit; its flips are counted in the lane, per wave, and the waves' counts meet in LDS at the end, as
 // the fields kernel's partial sums do.  Only when the last permitted sweep still flipped something (and `unstable` is asked
 // for) one more pass over all spins, wave v the spins v, v + DS_WAVES, .., counts the unstable spins without flipping.
-// The way back: wave v takes the row pairs (r, r + 32), r = v, v + DS_WAVES, ..; for word w lane l reads column half
-// lo[32 w + l] (l < 32) or hi[32 w + l - 32] (0 for spins >= n: the pad bits), the ballot of bit r is word w of row r (low
-// half) and of row r + 32 (high half), kept by lane w mod 32 of either half; after 32 words (or the last) lanes 0..31 store
-// consecutive words of row r, lanes 32..63 of row r + 32.
+// The way back (tile_rows_from_halves, packed_rows.h): wave v takes the row pairs (r, r + 32), r = v, v + DS_WAVES, .., and
+// ballots the column halves back into the rows' words.
 // LDS: 8 n bytes of columns + DS_WAVES 512 bytes of row counts + 2 DS_WAVES 8 bytes of slots: 8.25 KiB + 8 n bytes, 72.25 KiB at
 // n = 8192.  Banks (ds_read_b32 / ds_write_b32: dword mod 32 in 32-lane halves): the transpose writes 32 consecutive dwords;
 // the sweeps read one column address per half (a broadcast) and one lane writes; the way back reads 32 consecutive dwords per
@@ -119,22 +117,7 @@ __global__ __launch_bounds__(DS_THREADS) void grbm_descend_packed_kernel(
       if (unstable_out) unstable_out[idx] = un;
     }
     // ---- the way back: column bits to the rows' words
-    const int half = lane & 31;
-    for (int r = wave; r < 32; r += DS_WAVES) {
-      const int64_t ridx = tile * 64 + r + (lane < 32 ? 0 : 32);
-      uint32_t* dst = bits_out + ridx * W;
-      for (int w0 = 0; w0 < W; w0 += 32) {
-        const int nw = W - w0 < 32 ? W - w0 : 32;
-        uint32_t word = 0u;
-        for (int w = 0; w < nw; ++w) {
-          const int i = 32 * (w0 + w) + half;
-          const uint32_t c = i < n ? mine[i] : 0u;
-          const unsigned long long m = __builtin_amdgcn_ballot_w64(((c >> r) & 1u) != 0u);
-          if (half == w) word = lane < 32 ? (uint32_t)m : (uint32_t)(m >> 32);
-        }
-        if (half < nw && ridx < total) dst[w0 + half] = word;
-      }
-    }
+    tile_rows_from_halves<DS_WAVES>(mine, W, n, wave, lane, tile, total, bits_out);
     __syncthreads();  // (the columns, the counts and the slots are rewritten by the next tile)
   }
 }

@@ -1,6 +1,6 @@
-// What the entries on bit-packed spin rows share (grbm.hip, correlation.hip, fields.hip, descent.hip): the ballot transpose from
-// rows to per-spin bit columns, the address of a strided row, the sampler's float32 local field on such columns, and the
-// checks of the C entries' row arguments.  A new packed-row entry starts from here.
+// What the entries on bit-packed spin rows share (grbm.hip, correlation.hip, fields.hip, descent.hip, quantum.hip): the ballot
+// transpose from rows to per-spin bit columns and back, the address of a strided row, the sampler's float32 local field on such
+// columns, and the checks of the C entries' row arguments.  A new packed-row entry starts from here.
 // The column convention, once: a TILE is 64 rows, one per lane of a wave; bit r of a spin's 64-bit column is the spin's bit in
 // row r of the tile; rows beyond the last (pad rows) read as 0; columns of spins >= n are never stored.
 // No device function in here holds a barrier: the callers keep their own.
@@ -43,6 +43,32 @@ __device__ __forceinline__ void tile_columns_halves(const uint32_t* row, int W, 
     if (lane < 32 && i < n) {
       lo[i] = (uint32_t)col;
       lo[n + i] = (uint32_t)(col >> 32);
+    }
+  }
+}
+
+// The way back: the column halves of the tile `tile` to the words of its rows, dense in bits_out ([total][W]).  Wave `wave` of
+// WAVES takes the row pairs (r, r + 32), r = wave, wave + WAVES, ..; for word w lane l reads column half lo[32 w + l] (l < 32) or
+// lo[n + 32 w + l - 32] (0 for spins >= n: the pad bits), the ballot of bit r is word w of row r (low half) and of row r + 32
+// (high half), kept by lane w mod 32 of either half; after 32 words (or the last) lanes 0..31 store consecutive words of row
+// r, lanes 32..63 of row r + 32.  `mine`: the halves that hold the lane's bit.  Rows beyond `total` are not stored.
+template <int WAVES>
+__device__ __forceinline__ void tile_rows_from_halves(const uint32_t* mine, int W, int n, int wave, int lane, int64_t tile,
+                                                      int64_t total, uint32_t* bits_out) {
+  const int half = lane & 31;
+  for (int r = wave; r < 32; r += WAVES) {
+    const int64_t ridx = tile * 64 + r + (lane < 32 ? 0 : 32);
+    uint32_t* dst = bits_out + ridx * W;
+    for (int w0 = 0; w0 < W; w0 += 32) {
+      const int nw = W - w0 < 32 ? W - w0 : 32;
+      uint32_t word = 0u;
+      for (int w = 0; w < nw; ++w) {
+        const int i = 32 * (w0 + w) + half;
+        const uint32_t c = i < n ? mine[i] : 0u;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(((c >> r) & 1u) != 0u);
+        if (half == w) word = lane < 32 ? (uint32_t)m : (uint32_t)(m >> 32);
+      }
+      if (half < nw && ridx < total) dst[w0 + half] = word;
     }
   }
 }

@@ -224,6 +224,17 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         self._need_local_sampler(sampler, "sample_tempered")
         return sampler.sample_tempered(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, betas, **kw)
 
+    def sample_quantum(self, sampler, beta_slice, kappa, *, slices: int, prefactor: float, linear_range=None,
+                       quadratic_range=None, **kw):
+        """A simulated-quantum-annealing draw from the model under the prefactor-scaled, clamped ``(h, J)``: chains of
+        ``slices`` Trotter slices under the per-sweep tables ``beta_slice`` and ``kappa`` -- ``sampler.transverse_schedule``
+        makes them from a transverse-field schedule (:meth:`GibbsSampler.sample_quantum`; ``num_reads``, ``start`` are passed
+        on).  Returns its :class:`~.sampler.Sliced`; ``.samples`` holds slice 0 of every chain.  The local
+        :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "sample_quantum")
+        return sampler.sample_quantum(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, beta_slice, kappa,
+                                      slices=slices, **kw)
+
     def sample_trace(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
         """A traced draw from the model under the prefactor-scaled, clamped ``(h, J)``: the chains' states after every
         ``thin``-th sweep behind ``burn_in``, bit-packed inside the kernel (:meth:`GibbsSampler.sample_trace`; ``num_reads``,

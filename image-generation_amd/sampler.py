@@ -79,6 +79,49 @@ def beta_schedule(beta_start: float, beta_end: float, num_sweeps: int, kind: str
 _make_beta_schedule = beta_schedule  # (sample_ising has a keyword of that name)
 
 
+def _slice_count(slices) -> int:
+    """``slices`` as an int, if it is a power of two in 2 .. 64 (the Trotter slices of a :meth:`GibbsSampler.sample_quantum` chain)."""
+    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 2 <= slices <= 64 or slices & (slices - 1):
+        raise ValueError(f"slices must be a power of two in 2 .. 64, got {slices!r}")
+    return int(slices)
+
+
+def transverse_schedule(beta: float, gamma_start: float, gamma_end: float, num_sweeps: int, slices: int,
+                        kind: str = "linear") -> Tuple[np.ndarray, np.ndarray]:
+    """The two tables of a simulated-quantum-annealing draw (:meth:`GibbsSampler.sample_quantum`, "DVG SQA v1") at inverse
+    temperature ``beta`` with ``slices`` = P Trotter slices, the transverse field going from ``gamma_start`` to ``gamma_end``
+    over ``num_sweeps`` sweeps, ``kind`` "linear" or "geometric" (``np.linspace`` / ``np.geomspace`` in float64; ``num_sweeps
+    == 1`` gives ``gamma_end`` alone).  Returns ``(beta_slice, kappa)``, two (num_sweeps,) float32 arrays: ``beta_slice = beta /
+    P`` throughout, ``kappa[k] = -1/2 ln tanh(beta Gamma_k / P)`` computed in float64 and rounded once -- it falls as Gamma
+    grows: a strong field decouples the slices, a vanishing one locks them together.  Both fields must be finite and > 0
+    and ``beta`` finite and > 0; a field so small that ``kappa`` overflows float32 is an error."""
+    if kind not in ("geometric", "linear"):
+        raise ValueError(f"transverse schedule kind must be 'geometric' or 'linear', got {kind!r}")
+    num_sweeps, P = _whole("num_sweeps", num_sweeps), _slice_count(slices)
+    try:
+        b, g0, g1 = float(beta), float(gamma_start), float(gamma_end)
+    except (TypeError, ValueError):
+        raise ValueError(f"beta={beta!r}, gamma_start={gamma_start!r}, gamma_end={gamma_end!r} must be numbers") from None
+    if not (np.isfinite(b) and b > 0.0):
+        raise ValueError(f"beta={beta!r} must be finite and > 0")
+    for name, g in (("gamma_start", g0), ("gamma_end", g1)):
+        if not (np.isfinite(g) and g > 0.0):
+            raise ValueError(f"{name}={g!r} must be finite and > 0 (kappa = -1/2 ln tanh(beta Gamma / P))")
+    gammas = np.array([g1]) if num_sweeps == 1 else (np.geomspace if kind == "geometric" else np.linspace)(g0, g1, num_sweeps)
+    if num_sweeps > 1:
+        gammas[0], gammas[-1] = g0, g1
+    with np.errstate(divide="ignore", over="ignore"):
+        kappa = (-0.5 * np.log(np.tanh(b * gammas / P)) + 0.0).astype(np.float32)
+        beta_slice = np.full(num_sweeps, b / P, dtype=np.float64).astype(np.float32)
+    if not np.isfinite(kappa).all():
+        k = int(np.flatnonzero(~np.isfinite(kappa))[0])
+        raise ValueError(f"kappa overflows float32 at sweep {k} (Gamma = {gammas[k]!r}): gamma_start={g0!r} / gamma_end={g1!r} "
+                         f"is too small for beta / slices = {b / P!r}")
+    if not np.isfinite(beta_slice).all():
+        raise ValueError(f"beta={beta!r} / slices overflows float32")
+    return beta_slice, kappa
+
+
 def _check_beta_table(betas, what: str, rows: Optional[int] = None):
     """The host-side checks of a table of betas, no device work: shape (S,) or (rows, S) with S >= 1; a CUDA tensor must
     be float32 (its values are the caller's business: looking would be a host sync); host values -- a sequence, an
@@ -953,6 +996,59 @@ def descend(bits, graph, linear, quadratic, *, prefactor=1.0, linear_range=None,
                                F.grbm_energy_packed(d.bits, graph, linear, quadratic, **kw), int(graph.plan.n))
 
 
+class Sliced:
+    """What :meth:`GibbsSampler.sample_quantum` returns, for C chains of P Trotter slices ("DVG SQA v1").  ``bits`` (C, P, W) int32
+    on the device: the slices one bit per spin ("DVG trace v1": bit b of word w = spin 32 w + b is +1, pad bits 0) -- hand it
+    back as ``start`` to continue, or to any packed-row function as ``groups = C``, ``rows = P``; ``samples`` (C, n) float32 +-1:
+    slice 0 of every chain; ``slices`` = P; ``n`` the spin count."""
+
+    def __init__(self, bits, samples, n):
+        self.bits, self.samples, self.n = bits, samples, int(n)
+
+    @property
+    def slices(self) -> int:
+        return int(self.bits.shape[1])
+
+    def energy(self, graph, linear, quadratic, prefactor: float = 1.0, linear_range=None, quadratic_range=None) -> torch.Tensor:
+        """The (C, P) float64 classical energies of the slices under the prefactor-scaled, clamped ``(linear, quadratic)`` --
+        hand in what the draw was given (``dvg_grbm_energy_packed``: the slices stay packed).  ``graph``: the
+        :class:`GraphHandle` whose edge list ``quadratic`` follows."""
+        from . import functional as F  # (functional imports this module)
+
+        return F.grbm_energy_packed(self.bits, graph, linear, quadratic, prefactor=prefactor, linear_range=linear_range,
+                                    quadratic_range=quadratic_range)
+
+    def best(self, graph=None, linear=None, quadratic=None, prefactor: float = 1.0, linear_range=None, quadratic_range=None, *,
+             energies: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """(C, n) float32 +-1: of each chain the slice of lowest classical energy, ties to the lowest slice index.  The
+        energies are :meth:`energy`'s of the same arguments, or ``energies`` (C, P) given (then plain torch, CPU tensors too)."""
+        C, P, _W = self.bits.shape
+        e = self.energy(graph, linear, quadratic, prefactor, linear_range, quadratic_range) if energies is None else energies
+        if not torch.is_tensor(e) or tuple(e.shape) != (C, P):
+            raise ValueError(f"energies must be a ({C}, {P}) tensor, got {tuple(e.shape) if torch.is_tensor(e) else type(e).__name__}")
+        first = torch.argmax((e == e.min(1, keepdim=True).values).to(torch.int8), 1)  # (the first of the minima)
+        rows = self.bits[torch.arange(C, device=self.bits.device), first.to(self.bits.device)]
+        return unpack_spins(rows, self.n)
+
+    def slice_overlap(self) -> torch.Tensor:
+        """The mean over chains and over the P pairs of neighbouring slices (k, k + 1 mod P) of ``(1 / n) sum_i s[k][i]
+        s[k+1][i]``, a float64 scalar on ``bits``' device (plain torch, CPU tensors too): 1 when the slices of every chain
+        agree, about 0 when kappa = 0 leaves them independent.  Pad bits are ignored."""
+        n, W = self.n, int(self.bits.shape[-1])
+        words = self.bits.to(torch.int64) & 0xFFFFFFFF
+        diff = words ^ torch.roll(words, -1, 1)
+        if n % 32:
+            mask = torch.full((W,), 0xFFFFFFFF, dtype=torch.int64, device=self.bits.device)
+            mask[-1] = (1 << (n % 32)) - 1
+            diff = diff & mask
+        d = _popcount32(diff).sum(-1).to(torch.float64)  # Hamming distance of every neighbouring pair
+        return (1.0 - 2.0 * d / n).mean()
+
+    def __repr__(self):
+        C, P, _W = self.bits.shape
+        return f"Sliced({C} chains x {P} slices, n={self.n})"
+
+
 def trace_sweeps(num_sweeps: int, burn_in: int, thin: int) -> np.ndarray:
     """The recorded sweeps of a traced draw as the numbers k + 1 (k the 0-based sweep of the call), host int64: sweep k is
     recorded iff ``k + 1 > burn_in`` and ``(k + 1 - burn_in) % thin == 0`` -- M = (num_sweeps - burn_in) // thin of them."""
@@ -1227,6 +1323,9 @@ class GibbsSampler:
         # ... and the population-annealing draws (sample_population), whose counter also numbers the resamplings
         self.pa_seed = self.seed ^ 0x70613031
         self.pa_sweep_count = 0
+        # ... and the simulated-quantum-annealing draws (sample_quantum)
+        self.sqa_seed = self.seed ^ 0x73716131
+        self.sqa_sweep_count = 0
         # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
         self._betas: Optional[torch.Tensor] = None
         self._fixed_sweeps = self.sweeps
@@ -1247,6 +1346,7 @@ class GibbsSampler:
         self.pt_sweep_count = 0
         self.trace_sweep_count = 0
         self.pa_sweep_count = 0
+        self.sqa_sweep_count = 0
 
     def set_beta_schedule(self, betas) -> None:
         """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
@@ -1317,7 +1417,7 @@ class GibbsSampler:
 
     def _call(self, name: str, lin, quad, prefactor, linear_range, quadratic_range, *rest) -> None:
         """One library call on the parameters' device and current stream: the graph and the model arguments every draw's entry
-        point begins with, then ``rest`` (which ends with ``dyn``), then the stream."""
+        point begins with, then ``rest`` (which ends with ``dyn`` where the entry point has one), then the stream."""
         head = (lin.data_ptr(), quad.data_ptr(), float(prefactor)) + _ranges(linear_range, quadratic_range)
         with torch.cuda.device(lin.device):
             _lib.check(getattr(_lib.lib(), name)(self.graph.ptr, *head, *rest, _lib.stream_ptr(lin.device)), name)
@@ -1683,10 +1783,65 @@ class GibbsSampler:
         self.trace_sweep_count += S
         return Trace(bits, out, state, trace_sweeps(S, burn_in, thin), n)
 
+    def sample_quantum(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                       beta_slice, kappa, *, slices: int, num_reads: Optional[int] = None,
+                       start: Optional[torch.Tensor] = None) -> "Sliced":
+        """A simulated-quantum-annealing draw (``dvg_gibbs_sample_quantum``, "DVG SQA v1" in include/dvg.h): chains of
+        ``slices`` = P Trotter slices of the n spins (P a power of two in 2 .. 64), Gibbs-sampled for S sweeps under
+        ``p(s) ~ exp(-beta_slice[k] sum_slices E + kappa[k] sum s[slice][i] s[slice + 1][i])`` in sweep k -- path-integral
+        Monte Carlo of the transverse-field Ising model; :func:`transverse_schedule` makes the two tables from a field
+        schedule.  ``beta_slice``, ``kappa``: (S,) each, host sequences, arrays or CPU tensors (checked here: finite, >= 0,
+        equal length; then uploaded) or CUDA float32 tensors, used as they are.  ``start=None``: ``num_reads`` fresh chains
+        from the INIT stream; ``start`` (C, P, W) int32 on the device (a :class:`Sliced`'s ``bits``): the chains continue
+        from the call's own copy of it.  Returns a :class:`Sliced`; no host sync.
+
+        Its own key ``sqa_seed`` and counter ``sqa_sweep_count``: every other stream, the persistent chains, ``sweep_count``
+        and ``calls`` are left alone.  Chain ids are ``chain_offset + arange(C)``."""
+        n = self.plan.n
+        W = (n + 31) // 32
+        # every argument check comes before the first library call (the tables' upload included)
+        P = _slice_count(slices)
+        if start is not None:
+            if not torch.is_tensor(start):
+                raise _lib.DvgError(f"start must be a tensor, got {type(start).__name__}")
+            if start.dtype != torch.int32:
+                raise _lib.DvgError(f"start must be int32 packed slices, got {start.dtype}")
+            if start.dim() != 3 or start.shape[0] < 1 or tuple(start.shape[1:]) != (P, W):
+                raise _lib.DvgError(f"start must be (chains, {P}, {W}), got {tuple(start.shape)}")
+            C = int(start.shape[0])
+            if num_reads is not None and num_reads != C:
+                raise _lib.DvgError(f"num_reads={num_reads!r} but start has {C} chains")
+            _on_gpu("start", start)
+        elif num_reads is not None:
+            C = _whole("num_reads", num_reads)
+        else:
+            raise ValueError("a quantum draw needs num_reads (fresh chains) or start to know how many chains to draw")
+        if C * P >= 2 ** 31:
+            raise ValueError(f"num_reads={C} x slices={P} must stay below 2^31")
+        hosts = [_check_beta_table(t, name) for name, t in (("beta_slice", beta_slice), ("kappa", kappa))]
+        lengths = [int(np.shape(t)[-1]) if h is None else int(h.shape[-1]) for t, h in zip((beta_slice, kappa), hosts)]
+        if lengths[0] != lengths[1]:
+            raise ValueError(f"beta_slice has {lengths[0]} sweeps, kappa {lengths[1]}: an entry of each per sweep")
+        lin, quad = self._parameters(linear, quadratic, start=start, beta_slice=beta_slice, kappa=kappa)
+        tb = _beta_table(beta_slice, lin.device, "beta_slice")
+        tk = _beta_table(kappa, lin.device, "kappa")
+        S = lengths[0]
+        if start is None:
+            bits, init = torch.empty((C, P, W), dtype=torch.int32, device=lin.device), 1
+        else:
+            bits, init = start.detach().clone(memory_format=torch.contiguous_format), 0
+        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
+        self._call("dvg_gibbs_sample_quantum", lin, quad, prefactor, linear_range, quadratic_range, tb.data_ptr(), tk.data_ptr(),
+                   bits.data_ptr(), C, P, self.chain_offset & 0xFFFFFFFF, self.sqa_seed, self.sqa_sweep_count & 0xFFFFFFFF, S, init,
+                   out.data_ptr())
+        self.sqa_sweep_count += S
+        return Sliced(bits, out, n)
+
     # -- dimod-style entry point -----------------------------------------------------------
     def sample_ising(self, h: Dict, J: Dict, num_reads: int = 1, answer_mode: str = "raw", auto_scale: bool = False,
                      annealing_time: float = 1.0, label: str = "", beta_schedule=None, beta_range=None,
-                     num_sweeps: Optional[int] = None, beta_schedule_type: str = "geometric", **_unused) -> SampleSet:
+                     num_sweeps: Optional[int] = None, beta_schedule_type: str = "geometric", transverse_field_range=None,
+                     num_slices: Optional[int] = None, **_unused) -> SampleSet:
         """Same call the reference makes on its QPU sampler (kwargs built at
         /root/reference/src/utils/common.py:130-138).  ``h``/``J`` are already
         scaled by the prefactor and clamped by the caller (plugin ``to_ising``).
@@ -1698,12 +1853,29 @@ class GibbsSampler:
         are left alone).  ``annealing_time`` is accepted, as the reference passes it, and unused: nothing maps a QPU's
         microseconds to a schedule.
 
+        Simulated-quantum-annealing reads: ``transverse_field_range=(Gamma_start, Gamma_end)`` with ``num_slices`` Trotter
+        slices and ``num_sweeps`` (default: the sampler's ``sweeps``) build the linear :func:`transverse_schedule` at the
+        sampler's ``beta`` and return slice 0 of ``num_reads`` FRESH chains of :meth:`sample_quantum` (its key and counter);
+        they do not go together with ``beta_range`` / ``beta_schedule``.
+
         The returned set carries the per-read Ising energy ``h.s + sum J s_i s_j`` of the ``(h, J)`` given, computed on
         the device (``dvg_grbm_energy``) and brought to the host when ``.record`` is read."""
         if auto_scale:
             raise ValueError("auto_scale=True is not supported: the sampler draws from the distribution it is given")
-        betas = None
-        if beta_schedule is not None:
+        betas = tables = None
+        if transverse_field_range is not None or num_slices is not None:
+            if beta_schedule is not None or beta_range is not None:
+                raise ValueError("transverse_field_range / num_slices (a quantum draw) do not go with beta_range / beta_schedule "
+                                 "(an annealed one)")
+            if transverse_field_range is None or num_slices is None:
+                raise ValueError("a quantum draw needs both transverse_field_range and num_slices")
+            try:
+                g0, g1 = transverse_field_range
+            except (TypeError, ValueError):
+                raise ValueError(f"transverse_field_range must be (gamma_start, gamma_end), got {transverse_field_range!r}") from None
+            _whole("num_reads", num_reads)
+            tables = transverse_schedule(self.beta, g0, g1, self.sweeps if num_sweeps is None else num_sweeps, num_slices)
+        elif beta_schedule is not None:
             if beta_range is not None:
                 raise ValueError("give beta_schedule or beta_range, not both")
             if beta_schedule_type not in ("custom", "geometric", "linear"):
@@ -1737,7 +1909,9 @@ class GibbsSampler:
             quad[edge_pos[key]] = float(val)
         dev = self.device
         lin, quad = lin.to(dev), quad.to(dev)
-        if betas is None:
+        if tables is not None:
+            t = self.sample_quantum(lin, quad, 1.0, None, None, *tables, slices=num_slices, num_reads=num_reads).samples
+        elif betas is None:
             t = self.sample_native(lin, quad, 1.0, None, None, num_reads)
         else:
             t = self.sample_annealed(lin, quad, 1.0, None, None, betas, num_reads=num_reads)

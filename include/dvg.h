@@ -277,6 +277,45 @@ int dvg_gibbs_sample_tempered_traced(const dvg_graph_t *g, const float *linear, 
                                      double *energy_out, uint32_t *accept_out,
                                      uint32_t *trace_out, double *energy_trace_out, uint8_t *rung_trace_out, int burn_in, int thin,
                                      const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The simulated-quantum-annealing draw ("DVG SQA v1"): path-integral (Trotter-slice) Monte Carlo of the transverse-field Ising
+ * model, the closest classical stand-in for a quantum annealer's read.  A chain is P = n_slices copies ("slices") of the n
+ * spins, s[k][i] = +-1; P is a power of two, 2 <= P <= 64; the slices are periodic, the neighbours of slice k are (k +- 1) mod P
+ * (for P = 2 the other slice counts twice).  With hs, Js the scaled, clamped float32 fields of dvg_gibbs_sample, sweep q of the
+ * call reads two float32 numbers from DEVICE tables shared by all chains:
+ *   beta_slice[q] >= 0  multiplies the classical energy of every slice (beta / P times whatever ramp the caller wants);
+ *   kappa[q] >= 0       the dimensionless ferromagnetic coupling between neighbouring slices of the same spin,
+ *                       -1/2 ln tanh(beta Gamma_q / P) for a transverse field Gamma_q.
+ * One sweep at fixed tables is Gibbs sampling of
+ *   p(s) ~ exp(-beta_slice sum_k E(s[k]) + kappa sum_k sum_i s[k][i] s[k+1][i]),   E(s) = hs.s + sum_e Js_e s_i s_j.
+ * The decision for site (i, k) of chain id c in global sweep t = sweep0 + q; every operation float32, round to nearest, no
+ * contraction:
+ *   f   the v1 local field of spin i in slice k: hs_i, then for each entry of spin i's CSR row in row order rn(f +- Js);
+ *   nb  = s[k-1][i] + s[k+1][i], in {-2, 0, 2};
+ *   z0  = rn(rn(beta_slice[q] f) - rn(kappa[q] nb));   z = clamp(rn(2 z0), -87, 87);   tt = spec_exp(z);
+ *   u   = u32_to_unit(w),  w = word .x of philox4x32_10(i, c, t, STREAM_SQA | (k << 8), key = seed),  STREAM_SQA = 6 -- the
+ *         full sweep index, not t >> 2;
+ *   s[k][i] = +1  iff  rn(u rn(1 + tt)) < 1   (the last two lines of v1's decision, unchanged).
+ * Order inside a sweep: for colour class 0 .. n_colours - 1, first every (i in the class, k even), then every (i in the class,
+ * k odd); each such set is an independent set of the product graph, so together equals one after another.  f does not depend
+ * on spin i's other slices: one sum serves both half-steps.
+ * Start state with init != 0: s[k][i] = +1 iff bit 31 of philox4x32_10(i, c, sweep0, STREAM_INIT | (k << 8)).x is set -- slice
+ * 0 is dvg_gibbs_sample's start state; otherwise the chains start from `slices` as given.
+ *   slices: DEVICE, in/out, [n_chains][n_slices][W = (n + 31) / 32] uint32 in the layout of "DVG trace v1" (bit b of word w = spin
+ *     32 w + b is +1): packed rows with groups = n_chains, rows = n_slices for every packed-row entry below.  Bits of spins >= n
+ *     are ignored on input and written as 0.
+ *   samples_out: DEVICE, [n_chains][n] float32 +-1, slice 0 of every chain, or NULL.
+ *   Chain ids are chain_id0 + 0 .. n_chains - 1.  A chain's result is a function of its id, the tables, the fields and the
+ *   graph alone, never of the other chains or of how chains are placed on workgroups.
+ * DVG_E_INVALID, before any HIP call: g, linear, quadratic, beta_slice, kappa or slices null; n_chains < 1; n_sweeps < 1;
+ * n_slices not a power of two in 2 .. 64; a non-finite prefactor.  DVG_E_UNSUPPORTED: n > 8192 (a tile's bit columns are kept
+ * in 64 KiB of LDS); n_chains n_slices >= 2^31.  A rejected call writes nothing.  The table values are NOT checked on the
+ * device.  No dyn: the draw is not part of a captured training step.  The call enqueues on `stream`, allocates nothing and
+ * uses no atomics. */
+int dvg_gibbs_sample_quantum(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                             float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                             const float *beta_slice, const float *kappa,
+                             uint32_t *slices, int n_chains, int n_slices, uint32_t chain_id0, uint64_t seed,
+                             uint32_t sweep0, int n_sweeps, int init, float *samples_out, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and
