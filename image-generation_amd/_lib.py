@@ -156,6 +156,10 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
          c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p],
     ),
+    "dvg_gibbs_cluster_move": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p],
+    ),
     "dvg_packed_correlation_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "dvg_packed_correlation": (
         c_int,

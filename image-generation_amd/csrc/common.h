@@ -88,6 +88,7 @@ enum KernelId : int {
   K_FIELDS_REDUCE,  // grbm_fields_reduce_kernel: the slabs' pooled sums in slab order
   K_DESCEND,        // grbm_descend_packed_kernel (descent.hip): zero-temperature descent of packed rows to local minima (work = n T spins)
   K_QUANTUM,        // gibbs_quantum_kernel (quantum.hip): Trotter-slice Gibbs chains under a transverse-field schedule (work = site updates)
+  K_CLUSTER,        // gibbs_cluster_kernel (cluster.hip): isoenergetic cluster moves between twin ladders (work = spins x jobs x passes, an upper bound: n per job)
   K_COUNT
 };
 

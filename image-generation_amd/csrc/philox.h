@@ -7,7 +7,7 @@
 
 namespace dvg {
 
-enum : uint32_t { STREAM_GIBBS = 0, STREAM_INIT = 1, STREAM_GUMBEL = 2, STREAM_DROPOUT = 3, STREAM_SWAP = 4, STREAM_RESAMPLE = 5, STREAM_SQA = 6 };
+enum : uint32_t { STREAM_GIBBS = 0, STREAM_INIT = 1, STREAM_GUMBEL = 2, STREAM_DROPOUT = 3, STREAM_SWAP = 4, STREAM_RESAMPLE = 5, STREAM_SQA = 6, STREAM_ICM = 7 };
 
 struct u32x4 { uint32_t x, y, z, w; };
 

@@ -27,7 +27,7 @@ static const char* kNames[K_COUNT] = {
     "mse", "adam", "misc", "conv_igemm_weight_space", "conv_wino_kernel", "conv_wino_wgrad_kernel",
     "conv_wino4_kernel", "conv_wino4_wgrad_kernel", "packed_correlation_transpose_kernel", "packed_correlation_kernel",
     "grbm_fields_packed_kernel", "grbm_fields_reduce_kernel", "grbm_descend_packed_kernel",
-    "gibbs_quantum_kernel"};
+    "gibbs_quantum_kernel", "gibbs_cluster_kernel"};
 
 struct EvPair { hipEvent_t a, b; float share = 1.0f; };
 static uint64_t g_mask = 0;

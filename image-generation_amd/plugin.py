@@ -224,6 +224,15 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         self._need_local_sampler(sampler, "sample_tempered")
         return sampler.sample_tempered(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, betas, **kw)
 
+    def sample_tempered_cluster(self, sampler, betas, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """A parallel-tempering draw of twin ladders with isoenergetic cluster moves between the twins' equal rungs, from
+        the model under the prefactor-scaled, clamped ``(h, J)`` (:meth:`GibbsSampler.sample_tempered_cluster`;
+        ``num_ladders``, ``num_sweeps``, ``swap_every``, ``cluster_every``, ``rung_from``, ``start``, ``rungs`` are passed
+        on).  Returns its :class:`~.sampler.TemperedCluster`; ``.tempered.target`` holds the samples at ``betas[-1]``.  The
+        local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "sample_tempered_cluster")
+        return sampler.sample_tempered_cluster(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, betas, **kw)
+
     def sample_quantum(self, sampler, beta_slice, kappa, *, slices: int, prefactor: float, linear_range=None,
                        quadratic_range=None, **kw):
         """A simulated-quantum-annealing draw from the model under the prefactor-scaled, clamped ``(h, J)``: chains of

@@ -255,6 +255,58 @@ class Tempered:
         return f"Tempered({Q} ladders x {R} rungs, n={n}, attempts={self.attempts.tolist()})"
 
 
+class ClusterMoves:
+    """What :meth:`GibbsSampler.cluster_move` returns, for P twin pairs of R rungs ("DVG ICM v1"); device tensors.  ``sizes``
+    (P, R) int64: the spins each pair exchanged at each rung, 0 where nothing moved (rungs below ``rung_from``, identical
+    twins); ``differ`` (P, R) int64: the sites where the pair's two holders of the rung disagreed.  ``moved_share`` (R,)
+    float64: exchanged sites over disagreeing sites, summed over the pairs -- 1 where every cluster is the whole of D, the move
+    then only renames the twins; ``mean_size`` (R,) float64: the mean cluster over the pairs that disagreed anywhere.  Both
+    NaN for a rung without a disagreeing pair."""
+
+    def __init__(self, sizes, differ):
+        self.sizes, self.differ = sizes, differ
+
+    @classmethod
+    def from_outputs(cls, sizes: torch.Tensor, differ: torch.Tensor, R: int) -> "ClusterMoves":
+        return cls(sizes.view(-1, R).to(torch.int64), differ.view(-1, R).to(torch.int64))
+
+    @property
+    def moved_share(self):
+        return self.sizes.sum(0).to(torch.float64) / self.differ.sum(0).to(torch.float64)
+
+    @property
+    def mean_size(self):
+        return self.sizes.sum(0).to(torch.float64) / (self.differ > 0).sum(0).to(torch.float64)
+
+    def __repr__(self):
+        P, R = self.sizes.shape
+        return f"ClusterMoves({P} twin pairs x {R} rungs)"
+
+
+def cluster_schedule(sweep0: int, num_sweeps: int, cluster_every: int, fresh: bool):
+    """The segments of a :meth:`GibbsSampler.sample_tempered_cluster` call of ``num_sweeps`` sweeps from global sweep
+    ``sweep0``: a list of ``(move, first_sweep, sweeps)`` -- ``move``: the index t / cluster_every of the cluster move in front
+    of the segment's first sweep t (t % cluster_every == 0), or None for a first segment without one: ``sweep0`` is no
+    multiple of ``cluster_every``, or the chains are ``fresh``.  Every segment is one exchange draw of ``sweeps`` >= 1."""
+    cuts = [t for t in range(sweep0, sweep0 + num_sweeps) if t % cluster_every == 0 and not (fresh and t == sweep0)]
+    firsts = ([] if cuts and cuts[0] == sweep0 else [sweep0]) + cuts
+    ends = firsts[1:] + [sweep0 + num_sweeps]
+    return [(t // cluster_every if t in cuts else None, t, e - t) for t, e in zip(firsts, ends)]
+
+
+class TemperedCluster:
+    """What :meth:`GibbsSampler.sample_tempered_cluster` returns.  ``tempered``: the :class:`Tempered` of the call's last
+    sweeps (samples, energies, state and rungs after them; ``accepted`` and ``attempts`` summed over the call); ``sizes`` and
+    ``differ`` (moves, pairs, R) int64 device tensors: per cluster move of the call what :class:`ClusterMoves` holds;
+    ``moves`` (moves,) host int64: their indices t / cluster_every."""
+
+    def __init__(self, tempered, sizes, differ, moves):
+        self.tempered, self.sizes, self.differ, self.moves = tempered, sizes, differ, moves
+
+    def __repr__(self):
+        return f"TemperedCluster({self.tempered!r}, moves={self.moves.tolist()})"
+
+
 class Population:
     """What :meth:`GibbsSampler.sample_population` returns, for P populations of R chains annealed over T temperature steps;
     tensors live where the draw's do.  ``samples`` (C, n) float32 +-1 and ``state`` (C, n) int8: the final population,
@@ -1724,6 +1776,108 @@ class GibbsSampler:
         self._call(name, a.lin, a.quad, prefactor, linear_range, quadratic_range, *args, None)
         self.pt_sweep_count += a.S
         return Tempered.from_draw(n, R, out, energy, accept, sweep0, a.S, a.swap_every, state, rung), bits, e_trace, walk
+
+    def _cluster_arguments(self, state, rungs, replicas, rung_from, move):
+        """The argument checks of :meth:`cluster_move`, every one before the first library call.  Returns ``(R, rung_from, move,
+        rung)``, ``rung`` the (C,) int32 contiguous table or None."""
+        n = self.plan.n
+        R = _whole("replicas", replicas)
+        if R > 16:
+            raise ValueError(f"replicas must be an integer in 1 .. 16, got {replicas!r}")
+        rung_from, move = _whole("rung_from", rung_from, 0), _whole("move", move, 0)
+        if rung_from >= R:
+            raise ValueError(f"rung_from must be an integer in 0 .. {R - 1}, got {rung_from!r}")
+        if move >= 2 ** 32:
+            raise ValueError(f"move must stay below 2^32, got {move!r}")
+        if rungs is None and R > 1:
+            raise ValueError(f"replicas={R} ladders need their rungs (only single chains, replicas=1, go without)")
+        for name, t in (("state", state),) + ((("rungs", rungs),) if rungs is not None else ()):
+            if not torch.is_tensor(t):
+                raise _lib.DvgError(f"{name} must be a tensor, got {type(t).__name__}")
+        if state.dtype != torch.int8 or not state.is_contiguous():
+            raise _lib.DvgError(f"state must be a contiguous int8 tensor (it is changed in place), got {state.dtype}")
+        if state.dim() != 2 or state.shape[1] != n or state.shape[0] < 2 or state.shape[0] % (2 * R):
+            raise _lib.DvgError(f"state must be (twin pairs x {2 * R}, {n}), got {tuple(state.shape)}")
+        C = int(state.shape[0])
+        if rungs is not None and (rungs.dtype not in (torch.int32, torch.int64) or tuple(rungs.shape) != (C,)):
+            raise _lib.DvgError(f"rungs must be ({C},) int32 or int64, got {tuple(rungs.shape)} {rungs.dtype}")
+        _on_gpu("state", state)
+        if rungs is not None:
+            _on_gpu("rungs", rungs)
+            if rungs.device != state.device:
+                raise _lib.DvgError(f"rungs is on {rungs.device}, state on {state.device}")
+        return R, rung_from, move, None if rungs is None else rungs.detach().to(torch.int32).contiguous()
+
+    def cluster_move(self, state: torch.Tensor, rungs: Optional[torch.Tensor] = None, *, replicas: int = 1, rung_from: int = 0,
+                     move: int) -> "ClusterMoves":
+        """One isoenergetic cluster move (``dvg_gibbs_cluster_move``, "DVG ICM v1" in include/dvg.h) on ``state`` (C, n) int8
+        +-1 on the device, IN PLACE: ladders of R = ``replicas`` consecutive chains, the ladders 2p and 2p + 1 twins; for
+        every rung r >= ``rung_from`` the twins' holders of r exchange their spins on one connected cluster of the sites
+        where they disagree, rooted at a random such site.  The pair's total energy does not change: no acceptance test.
+        ``rungs`` (C,) integer on the device, the rung each chain holds (a :class:`Tempered`'s ``state`` and ``rungs`` fit);
+        None with ``replicas=1``: chains 2p and 2p + 1 are twins.  ``move``: the number of the move, the third word of its
+        Philox counter -- the same number again undoes the move.  Returns a :class:`ClusterMoves`; no host sync.
+
+        Its key is the exchange draw's ``pt_seed``; no counter advances and no stream of sweeps is touched.  Chain ids are
+        ``chain_offset + arange(C)``."""
+        R, rung_from, move, rung = self._cluster_arguments(state, rungs, replicas, rung_from, move)
+        jobs = int(state.shape[0]) // 2
+        sizes = torch.empty((jobs,), dtype=torch.int32, device=state.device)  # (uint32 counts of at most n spins)
+        differ = torch.empty((jobs,), dtype=torch.int32, device=state.device)
+        with torch.cuda.device(state.device):
+            _lib.check(_lib.lib().dvg_gibbs_cluster_move(self.graph.ptr, state.data_ptr(), _lib.ptr(rung), int(state.shape[0]), R,
+                                                         rung_from, self.chain_offset & 0xFFFFFFFF, self.pt_seed, move,
+                                                         sizes.data_ptr(), differ.data_ptr(), _lib.stream_ptr(state.device)),
+                       "dvg_gibbs_cluster_move")
+        return ClusterMoves.from_outputs(sizes, differ, R)
+
+    def sample_tempered_cluster(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
+                                quadratic_range, betas, *, num_ladders: int, num_sweeps: Optional[int] = None, swap_every: int = 1,
+                                cluster_every: int, rung_from: int = 0, start: Optional[torch.Tensor] = None,
+                                rungs: Optional[torch.Tensor] = None) -> "TemperedCluster":
+        """A parallel-tempering draw of TWIN ladders with isoenergetic cluster moves between them: BY DEFINITION a composition
+        of :meth:`sample_tempered` calls ("DVG PT v1") and :meth:`cluster_move` calls ("DVG ICM v1") on the exchange draw's key
+        ``pt_seed`` and counter ``pt_sweep_count``.  ``num_ladders`` is even: the ladders 2p and 2p + 1 are twins.  In front of
+        every sweep of global index t with ``t % cluster_every == 0`` -- the call's first sweep included when ``start`` is
+        given, never in front of the first sweep of fresh chains -- move number ``t // cluster_every`` takes place at the rungs
+        ``rung_from`` .. R - 1; the sweeps between two moves are one exchange draw that is handed ``state`` and ``rungs``
+        (:func:`cluster_schedule` lists the segments).  A call ends on sweeps: the energies are the kernel's own.  One call of
+        S sweeps and two calls of S1 + S2 sweeps that hand ``state`` and ``rungs`` on are the same draw, as for
+        :meth:`sample_tempered`, whose other arguments and checks these are; every check comes before the first library
+        call.  Returns a :class:`TemperedCluster`; no host sync.
+
+        ``pt_sweep_count`` advances by ``num_sweeps``; every other stream and counter is left alone."""
+        import copy
+
+        if isinstance(num_ladders, bool) or not isinstance(num_ladders, (int, np.integer)) or num_ladders < 2 or num_ladders % 2:
+            raise ValueError(f"num_ladders must be an even integer >= 2 (twin ladders), got {num_ladders!r}")
+        every = _whole("cluster_every", cluster_every)
+        rung_from = _whole("rung_from", rung_from, 0)
+        rungs_of_ladder = int(betas.numel()) if torch.is_tensor(betas) else int(np.size(betas))
+        if 2 <= rungs_of_ladder <= rung_from:  # (a ladder of another size is _tempered_arguments' to reject)
+            raise ValueError(f"rung_from must be an integer in 0 .. {rungs_of_ladder - 1}, got {rung_from!r}")
+        a = self._tempered_arguments(linear, quadratic, betas, num_ladders, num_sweeps, swap_every, start, rungs)
+        P = a.Q // 2
+        parts, sizes, differ, moves = [], [], [], []
+        for move, _first, sweeps in cluster_schedule(self.pt_sweep_count, a.S, every, a.start is None):
+            seg = copy.copy(a)
+            seg.S = sweeps
+            if parts:
+                seg.start, seg.rungs = parts[-1].state, parts[-1].rungs
+            if move is not None:
+                if not parts:
+                    seg.start = seg.start.detach().to(torch.int8, copy=True).contiguous()  # (the caller's start stays as it was)
+                m = self.cluster_move(seg.start, seg.rungs, replicas=a.R, rung_from=rung_from, move=move & 0xFFFFFFFF)
+                sizes.append(m.sizes)
+                differ.append(m.differ)
+                moves.append(move)
+            parts.append(self._tempered_draw(seg, prefactor, linear_range, quadratic_range)[0])
+        last, dev = parts[-1], a.lin.device
+        total = Tempered(last.samples, last.energies, sum(p.accepted for p in parts[1:]) + parts[0].accepted,
+                         sum(p.attempts for p in parts[1:]) + parts[0].attempts, last.state, last.rungs)
+        empty = torch.zeros((0, P, a.R), dtype=torch.int64, device=dev)
+        return TemperedCluster(total, torch.stack(sizes) if sizes else empty, torch.stack(differ) if differ else empty.clone(),
+                               np.asarray(moves, dtype=np.int64))
 
     def sample_tempered_trace(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range,
                               quadratic_range, betas, *, num_ladders: int, num_sweeps: Optional[int] = None, swap_every: int = 1,

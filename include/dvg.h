@@ -316,6 +316,38 @@ int dvg_gibbs_sample_quantum(const dvg_graph_t *g, const float *linear, const fl
                              const float *beta_slice, const float *kappa,
                              uint32_t *slices, int n_chains, int n_slices, uint32_t chain_id0, uint64_t seed,
                              uint32_t sweep0, int n_sweeps, int init, float *samples_out, dvg_stream_t stream);
+/* The isoenergetic cluster move ("DVG ICM v1"): Houdayer's move on any topology (Zhu, Ochoa, Katzgraber 2015).  Two replicas at
+ * the same temperature exchange their spins on one connected cluster of the sites where they disagree: the pair's total
+ * energy does not change, so the move has no acceptance test, and it carries whole domains from one replica to the other.
+ * Integers only: spins, the graph, one Philox word.
+ *   Layout.  state (n_chains, n) int8 +-1, DEVICE, changed in place, and rung [n_chains] int32, DEVICE, read only, both BY
+ *     CHAIN as "DVG PT v1" hands them on; R = n_replicas; ladder q = chains q R .. q R + R - 1.  Ladders 2p and 2p + 1 are
+ *     TWINS: their chain ids differ, so they are independent draws of the same ladder.  n_replicas == 1 with rung == NULL:
+ *     chains 2p and 2p + 1 are twins and both hold rung 0.
+ *   Holder.  The holder of rung r in a ladder is its lowest-numbered chain whose rung, clamped into 0 .. R-1, equals r.  A
+ *     ladder without a holder for r: the job (p, r) does nothing and reports 0, 0.  Distinct r give distinct chains whatever
+ *     the table holds; nothing is read or written out of bounds.
+ *   Job.  For every twin pair p = 0 .. n_chains / (2 R) - 1 and every rung r with rung_from <= r < R, with a the holder in
+ *     ladder 2p and b the holder in ladder 2p + 1:
+ *       D    = { i : state[a][i] < 0  differs from  state[b][i] < 0 }, in ascending spin order;  k = |D|;
+ *              differ_out[p R + r] = k;  k == 0: nothing moves, size_out[p R + r] = 0;  otherwise
+ *       word = philox4x32_10(ctr = (r, chain_id0 + 2 p R, move, STREAM_ICM = 7), key = seed).x   (the id mod 2^32);
+ *       root = element number ((uint64)word * k) >> 32 of D;
+ *       the cluster = the connected component of root in the subgraph of g induced on D -- every edge of the graph counts,
+ *              whatever its coupling;
+ *       for every i of the cluster state[a][i] and state[b][i] change places (both change sign there);
+ *       size_out[p R + r] = the size of the cluster.
+ *     Elements with r < rung_from are written as 0.  size_out, differ_out: DEVICE, uint32 [n_chains / 2], each may be NULL.
+ *   What follows: D is the same before and after the move; the same call again with the same `move` restores state;
+ *     E(a) + E(b) is unchanged for any (h, J) on this graph.  Energies are no argument: "DVG PT v1" sums a chain's start
+ *     energy afresh at every call.
+ * DVG_E_INVALID, before any HIP call: g or state null; n_replicas outside 1 .. 16; rung null with n_replicas > 1;
+ * n_chains < 2 or not a multiple of 2 n_replicas; rung_from outside 0 .. R-1.  DVG_E_UNSUPPORTED: n > 65536 (a job's two bit
+ * sets, D and the cluster, are kept in 16 KiB of LDS).  A rejected call writes nothing.  One stream-ordered launch on `stream`,
+ * no allocation, no atomics, no workgroup waiting on another; a job's result is a function of that job alone. */
+int dvg_gibbs_cluster_move(const dvg_graph_t *g, int8_t *state, const int32_t *rung, int n_chains,
+                           int n_replicas, int rung_from, uint32_t chain_id0, uint64_t seed, uint32_t move,
+                           uint32_t *size_out, uint32_t *differ_out, dvg_stream_t stream);
 /* The launch geometry dvg_gibbs_sample uses for n_chains chains on this graph (nothing is launched; any out pointer may
  * be NULL): workgroups, threads per workgroup, LDS bytes per workgroup.  For callers that size what runs BESIDE the draw
  * (tools and A/B measurements; since round 5 the Winograd grids beside the draw deal their tile blocks dynamically and
