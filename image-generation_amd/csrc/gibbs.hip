@@ -371,25 +371,150 @@ __device__ __forceinline__ void gibbs_exchange_record(const GibbsExchangeTraceAr
   if (a.rung_trace && l == 0) a.rung_trace[(size_t)chain * M + m] = (uint8_t)rung;
 }
 
+// ---------------------------------------------------------------- the sweep loop's control (gibbs_kernel, gibbs_fast_kernel)
+// What a draw mode does around the neighbour sums is the same in both chain-per-lanes kernels and is written here once; the
+// kernels keep the field code, its schedule and the start-energy walk.  The modes of SCHED:
+//   0: the plain draw (and, HELD, the conditional one) at the fixed beta of the argument block.
+//   GIBBS_TABLE: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead (one load per sweep and lane;
+//     with the shared row every lane of a wave reads one address, with a row per chain the LPC lanes of a chain).
+//   GIBBS_WEIGH: the AIS draw -- the table, and a lane keeps its share `e` of the chain's energy (the start addends of its
+//     spins, then every update it makes) and its share `lw` of the log weight; lane 0 of the chain stores the sums.
+//   GIBBS_EXCHANGE: the energy share as above, beta the ladder's entry of the rung the chain holds; at an exchange the
+//     workgroup meets at a barrier (gibbs_exchange_post / _decide).  The exchanges are counted from (sweep0, swap_every) alone.
+//   GIBBS_TRACE: the plain draw; behind a recorded sweep's last fence the chain's lanes pack its row (gibbs_record).  Which
+//     sweeps: a countdown in scalar registers (`rec_at`, the next recorded k + 1), no division per sweep.
+//   GIBBS_EXCHANGE_TRACE: the exchange draw (EXCH); behind the exchange block of a recorded sweep the lanes of a valid chain
+//     write its record to the row of the rung it NOW holds (gibbs_exchange_record), on the same countdown.
+// What the exchange modes rest on, in either kernel:
+//   * EVERY wave of a workgroup reaches EVERY barrier: the ones in gibbs_sweep_tail and the one in gibbs_finish.  The kernels
+//     let no wave leave or skip the sweep loop under EXCH -- the lanes of an idle slot run it without a spin to update;
+//   * idle slots count the records down as the others do and record nothing;
+//   * the traced exchange draw sums `e` from a COPY (gibbs_exchange_record): the shares go on as in the draw without records.
+template <int SCHED>
+struct GibbsMode {
+  static constexpr bool AIS = SCHED == GIBBS_WEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE;
+  static constexpr bool EXCH = SCHED == GIBBS_EXCHANGE || XTRACE, ENERGY = AIS || EXCH;
+  static constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
+};
+// a lane's control registers; a mode leaves those of the others at zero and the compiler drops them
+struct GibbsControl {
+  const float* bt;        // TABLE: this chain's row of the table
+  float beta_next;        // TABLE: the entry of the coming sweep, read a sweep ahead of its first use; EXCH: the rung's beta
+  float beta_prev;        // AIS: the beta of the sweep before (first: beta_from)
+  int rung;               // EXCH: the rung the chain holds
+  double e, lw;           // ENERGY, AIS: the lane's shares of the chain's energy and log weight
+  uint32_t rec_at, rec_m;  // TRACE, XTRACE: the next recorded sweep (as k + 1) and its record
+};
+// before the first sweep (and the start-energy walk): the lanes of a valid chain or, EXCH, of any slot
+template <int SCHED, typename Args>
+__device__ __forceinline__ GibbsControl gibbs_begin(const Args& a, const GibbsExchangeLds& X, const GibbsSlot& slot) {
+  using M = GibbsMode<SCHED>;
+  GibbsControl c{};
+  if constexpr (M::EXCH) {
+    if (slot.valid) c.rung = a.init ? slot.j : min(max(a.rung[slot.chain], 0), a.n_replicas - 1);
+    c.beta_next = X.ladder[c.rung];
+  } else if constexpr (M::TABLE) {
+    c.bt = a.betas + (int64_t)slot.chain * a.beta_stride;
+    c.beta_next = c.bt[0];
+  }
+  if constexpr (M::AIS) c.beta_prev = a.beta_from;
+  if constexpr (M::TRACE || M::XTRACE) c.rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
+  return c;
+}
+// head of sweep t: its two_beta; AIS: the weight step on the energy before the sweep
+template <int SCHED, typename Args>
+__device__ __forceinline__ float gibbs_sweep_head(const Args& a, uint32_t t, uint32_t sweep0, GibbsControl& c) {
+  using M = GibbsMode<SCHED>;
+  if constexpr (M::EXCH) {
+    return __fmul_rn(2.0f, c.beta_next);
+  } else if constexpr (M::TABLE) {
+    const float two_beta = __fmul_rn(2.0f, c.beta_next);
+    if constexpr (M::AIS) {
+      c.lw -= ((double)c.beta_next - (double)c.beta_prev) * c.e;
+      c.beta_prev = c.beta_next;
+    }
+    const uint32_t kn = t - sweep0 + 1u;
+    if (kn < (uint32_t)a.n_sweeps) c.beta_next = c.bt[kn];
+    return two_beta;
+  } else {
+    return a.two_beta;
+  }
+}
+// tail of sweep t, behind its last class's fence.  `st`: the chain's row, `l` the lane's index in the chain; A16: gibbs_record's.
+template <int LPC, int SLOTS, int SCHED, bool A16, typename Args>
+__device__ __forceinline__ void gibbs_sweep_tail(const Args& a, const GibbsExchangeLds& X, const GibbsSlot& slot, const _Float16* st,
+                                                 int l, uint32_t t, uint32_t sweep0, GibbsControl& c) {
+  using M = GibbsMode<SCHED>;
+  const int n = a.n, n_pad = (n + 15) & ~15;
+  if constexpr (M::TRACE) {  // (every lane here is a valid chain's)
+    if (t - sweep0 + 1u == c.rec_at && c.rec_m < (uint32_t)a.n_records) {
+      gibbs_record<LPC, A16>(st, n, n_pad, l, a.trace + ((size_t)slot.chain * a.n_records + c.rec_m) * gibbs_held_words(n));
+      c.rec_at += (uint32_t)a.thin;
+      ++c.rec_m;
+    }
+  }
+  if constexpr (M::EXCH) {
+    // (t, swap_every: kernel arguments -- the same in every wave of every workgroup)
+    if ((t + 1u) % (uint32_t)a.swap_every == 0u) {
+      const uint32_t x = (t + 1u) / (uint32_t)a.swap_every;
+      if (slot.valid) gibbs_exchange_post<LPC, SLOTS>(X, a.n_replicas, x, slot.lq, c.rung, l, c.e);
+      __syncthreads();
+      if (slot.valid)
+        gibbs_exchange_decide(a, X, SLOTS, a.n_replicas, x, slot.lq, a.chain_id0 + (uint32_t)(slot.chain - slot.j), l, c.rung,
+                              c.beta_next);
+    }
+  }
+  if constexpr (M::XTRACE) {
+    if (t - sweep0 + 1u == c.rec_at && c.rec_m < (uint32_t)a.n_records) {
+      if (slot.valid)
+        gibbs_exchange_record<LPC, A16>(a, st, n, n_pad, l, slot.chain, (size_t)(slot.chain - slot.j + c.rung), c.rec_m, c.rung, c.e);
+      c.rec_at += (uint32_t)a.thin;
+      ++c.rec_m;
+    }
+  }
+}
+// the way out, behind the last sweep: state (and EXCH: rung) by chain; samples, energies and counters by chain or, EXCH, by rung
+template <int LPC, int SCHED, typename Args>
+__device__ __forceinline__ void gibbs_finish(const Args& a, const GibbsExchangeLds& X, const GibbsSlot& slot, const _Float16* st, int l,
+                                             const GibbsControl& c) {
+  using M = GibbsMode<SCHED>;
+  const int n = a.n, chain = slot.chain;
+  size_t row = (size_t)chain;
+  if constexpr (M::EXCH) {
+    __syncthreads();  // the counters are final
+    if (!slot.valid) return;
+    row = (size_t)(chain - slot.j + c.rung);
+  }
+  int8_t* dst = a.state + (size_t)chain * n;
+  for (int i = l; i < n; i += LPC) {
+    const float v = (float)st[i];
+    dst[i] = (int8_t)v;
+    if (a.samples_out) a.samples_out[row * n + i] = v;
+  }
+  if constexpr (M::EXCH) {
+    const double e = gibbs_chain_sum<LPC>(c.e);
+    if (l == 0) {
+      a.rung[chain] = c.rung;
+      if (a.energy_out) a.energy_out[row] = e;
+      if (a.accept_out) a.accept_out[chain] = X.acc[slot.lq * a.n_replicas + slot.j];
+    }
+  } else if constexpr (M::AIS) {
+    const double e = gibbs_chain_sum<LPC>(c.e), lw = gibbs_chain_sum<LPC>(c.lw);
+    if (l == 0) {
+      a.log_weight_out[chain] = lw;
+      if (a.energy_out) a.energy_out[chain] = e;
+    }
+  }
+}
+
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
-// HELD: the conditional draw -- the chain's held flags sit behind the state rows, one bit per spin, and a held spin is
-// passed over in its class.  SCHED: the annealed draw -- a lane reads its chain's beta of a sweep one sweep ahead.
-// SCHED == GIBBS_WEIGH: a lane also keeps its share `e` of the chain's energy (the start addends of spins l, l + LPC, ...,
-// then every update it makes) and its share `lw` of the log weight; lane 0 of the chain stores the sums.
-// SCHED == GIBBS_EXCHANGE: the energy share as above, beta the entry of the rung the chain holds; at an exchange the
-// workgroup meets at a barrier (gibbs_exchange_post / _decide).  EVERY wave runs the sweep loop and reaches every barrier --
-// lanes of an idle slot with empty classes; the exchanges are counted from (sweep0, n_sweeps, swap_every) alone.
-// SCHED == GIBBS_TRACE: the plain draw at its fixed beta; behind a recorded sweep's last fence the chain's lanes pack its row
-// (gibbs_record).  Which sweeps: a countdown in scalar registers (`rec_at`, the next recorded k + 1), no division per sweep.
-// SCHED == GIBBS_EXCHANGE_TRACE: the exchange draw (EXCH); behind the exchange block of a recorded sweep the lanes of a valid
-// chain write its record to the row of the rung it NOW holds (gibbs_exchange_record), on the same countdown.  Idle slots count
-// down too and record nothing; they still reach every barrier.
+// HELD: the chain's held flags sit behind the state rows, one bit per spin, and a held spin is passed over in its class.
+// EXCH: the lanes of an idle slot find every class empty.  The rows are aligned to 4 bytes (gibbs_record's A16 = false).
 template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
-  constexpr bool AIS = SCHED == GIBBS_WEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE, EXCH = SCHED == GIBBS_EXCHANGE || XTRACE;
-  constexpr bool ENERGY = AIS || EXCH;
-  constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
+  using M = GibbsMode<SCHED>;
+  constexpr bool EXCH = M::EXCH;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n;
   const GibbsLds L = gibbs_carve(smem, n, a.n_batches, a.n_colours);
@@ -434,45 +559,16 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
   __builtin_amdgcn_wave_barrier();
 
   if (valid || EXCH) {
-    // SCHED: this chain's row of the table; the entry of the coming sweep, read a sweep ahead of its first use
-    [[maybe_unused]] const float* bt = nullptr;
-    [[maybe_unused]] float beta_next = 0.0f;
-    [[maybe_unused]] int rung = 0;  // EXCH: the rung the chain holds, and (beta_next) its beta
-    if constexpr (EXCH) {
-      const int R = a.n_replicas;
-      if (valid) rung = a.init ? slot.j : min(max(a.rung[chain], 0), R - 1);
-      beta_next = X.ladder[rung];
-    } else if constexpr (TABLE) {
-      bt = a.betas + (int64_t)chain * a.beta_stride;
-      beta_next = bt[0];
-    }
-    [[maybe_unused]] double e = 0.0, lw = 0.0;
-    [[maybe_unused]] float beta_prev = 0.0f;
-    if constexpr (AIS) beta_prev = a.beta_from;
-    [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE, XTRACE: the next recorded sweep (as k + 1) and its record
-    if constexpr (TRACE || XTRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
-    if constexpr (ENERGY) {
+    GibbsControl ctl = gibbs_begin<SCHED>(a, X, slot);
+    if constexpr (M::ENERGY) {
       for (int i = l; i < (valid ? n : 0); i += LPC) {
         const float hsi = L.hs[i];
-        e += gibbs_start_energy(st[i], hsi, gibbs_field(hsi, L.row[i], L, st, a.n_batches, a.max_batches));
+        ctl.e += gibbs_start_energy(st[i], hsi, gibbs_field(hsi, L.row[i], L, st, a.n_batches, a.max_batches));
       }
     }
     for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
       const uint32_t tq = t >> 2, tw = t & 3u;
-      float two_beta;
-      if constexpr (EXCH) {
-        two_beta = __fmul_rn(2.0f, beta_next);
-      } else if constexpr (TABLE) {
-        two_beta = __fmul_rn(2.0f, beta_next);
-        if constexpr (AIS) {
-          lw -= ((double)beta_next - (double)beta_prev) * e;
-          beta_prev = beta_next;
-        }
-        const uint32_t kn = t - sweep0 + 1u;
-        if (kn < (uint32_t)a.n_sweeps) beta_next = bt[kn];
-      } else {
-        two_beta = a.two_beta;
-      }
+      const float two_beta = gibbs_sweep_head<SCHED>(a, t, sweep0, ctl);
       for (int k = 0; k < a.n_colours; ++k) {
         const int lo = L.cls[k], hi = (EXCH && !valid) ? lo : L.cls[k + 1];  // (an idle slot: every class empty)
         for (int p = lo + l; p < hi; p += LPC) {
@@ -483,71 +579,16 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
           const float f = gibbs_field(L.hs[i], L.row[i], L, st, a.n_batches, a.max_batches);
           const u32x4 r = philox4x32_10((uint32_t)i, cid, tq, STREAM_GIBBS, a.k0, a.k1);
           const _Float16 s_new = gibbs_decide(f, two_beta, pick(r, tw));
-          if constexpr (ENERGY) e += gibbs_energy_step((float)s_new, (float)st[i], f);
+          if constexpr (M::ENERGY) ctl.e += gibbs_energy_step((float)s_new, (float)st[i], f);
           st[i] = s_new;
         }
         // the next class reads what this one wrote (same wave): order LDS traffic
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
       }
-      if constexpr (TRACE) {
-        if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
-          gibbs_record<LPC, false>(st, n, n_pad, l, a.trace + ((size_t)chain * a.n_records + rec_m) * gibbs_held_words(n));
-          rec_at += (uint32_t)a.thin;
-          ++rec_m;
-        }
-      }
-      if constexpr (EXCH) {
-        // (t, swap_every: kernel arguments -- the same in every wave of every workgroup)
-        if ((t + 1u) % (uint32_t)a.swap_every == 0u) {
-          const uint32_t x = (t + 1u) / (uint32_t)a.swap_every;
-          if (valid) gibbs_exchange_post<LPC, WAVES * CPW>(X, a.n_replicas, x, slot.lq, rung, l, e);
-          __syncthreads();
-          if (valid)
-            gibbs_exchange_decide(a, X, WAVES * CPW, a.n_replicas, x, slot.lq, cid - (uint32_t)slot.j, l, rung, beta_next);
-        }
-      }
-      if constexpr (XTRACE) {
-        if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
-          if (valid) gibbs_exchange_record<LPC, false>(a, st, n, n_pad, l, chain, (size_t)(chain - slot.j + rung), rec_m, rung, e);
-          rec_at += (uint32_t)a.thin;
-          ++rec_m;
-        }
-      }
+      gibbs_sweep_tail<LPC, WAVES * CPW, SCHED, false>(a, X, slot, st, l, t, sweep0, ctl);
     }
-    if constexpr (EXCH) {
-      __syncthreads();  // the counters are final
-      if (valid) {
-        const size_t row = (size_t)(chain - slot.j + rung);  // the outputs by rung; state and rung by chain
-        int8_t* dst = a.state + (size_t)chain * n;
-        for (int i = l; i < n; i += LPC) {
-          const float v = (float)st[i];
-          dst[i] = (int8_t)v;
-          if (a.samples_out) a.samples_out[row * n + i] = v;
-        }
-        e = gibbs_chain_sum<LPC>(e);
-        if (l == 0) {
-          a.rung[chain] = rung;
-          if (a.energy_out) a.energy_out[row] = e;
-          if (a.accept_out) a.accept_out[chain] = X.acc[slot.lq * a.n_replicas + slot.j];
-        }
-      }
-      return;
-    }
-    int8_t* dst = a.state + (size_t)chain * n;
-    for (int i = l; i < n; i += LPC) {
-      const float v = (float)st[i];
-      dst[i] = (int8_t)v;
-      if (a.samples_out) a.samples_out[(size_t)chain * n + i] = v;
-    }
-    if constexpr (AIS) {
-      e = gibbs_chain_sum<LPC>(e);
-      lw = gibbs_chain_sum<LPC>(lw);
-      if (l == 0) {
-        a.log_weight_out[chain] = lw;
-        if (a.energy_out) a.energy_out[chain] = e;
-      }
-    }
+    gibbs_finish<LPC, SCHED>(a, X, slot, st, l, ctl);
   }
 }
 
@@ -750,24 +791,19 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
   }
 }
 
-// HELD: the conditional draw -- a lane owns the same spin in a slot for the whole draw, so its held flags are one bit
-// per slot in a register; a held slot draws no random word and stores to the sink.
-// SCHED: the annealed draw -- two_beta is the lane's chain's table entry of the sweep, read one sweep ahead (one load per
-// sweep and lane; with the shared row every lane of a wave reads one address, with a row per chain the LPC lanes of a chain).
-// SCHED == GIBBS_WEIGH: the AIS draw -- one walk over the steps before the first sweep for the start energy (the fields of
-// the start state; no decision, no store), then one convert and one float64 add per update; the value a slot's spin has
-// is one bit per slot in a register, like `held`.
-// SCHED == GIBBS_EXCHANGE: the energy share of the AIS draw, two_beta from the rung the chain holds, and the workgroup's
-// barrier at every exchange.  No wave leaves before the last barrier: the lanes of an idle slot own no spin in any row (every
-// store of theirs goes to the sink), and a wave of idle slots alone passes over the sweep, not over the barrier.
-// SCHED == GIBBS_TRACE: the plain draw; gibbs_record behind a recorded sweep's last fence (the rows are 16-byte aligned here).
-// SCHED == GIBBS_EXCHANGE_TRACE: the exchange draw; gibbs_exchange_record behind a recorded sweep's exchange block.
+// The modes are those of the sweep loop's control above.  What is this form's own:
+// HELD: a lane owns the same spin in a slot for the whole draw, so its held flags are one bit per slot in a register; a
+// held slot draws no random word and stores to the sink.
+// ENERGY: one walk over the steps before the first sweep for the start energy (the fields of the start state; no decision,
+// no store), then one convert and one float64 add per update; the value a slot's spin has is one bit per slot in a
+// register (`up`), like `held`.
+// EXCH: the lanes of an idle slot own no spin in any row (every store of theirs goes to the sink), and a wave of idle slots
+// alone passes over the steps (`rows_on`), not over the barriers.  The rows are 16-byte aligned (gibbs_record's A16 = true).
 template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
-  constexpr bool AIS = SCHED == GIBBS_WEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE, EXCH = SCHED == GIBBS_EXCHANGE || XTRACE;
-  constexpr bool ENERGY = AIS || EXCH;
-  constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
+  using M = GibbsMode<SCHED>;
+  constexpr bool EXCH = M::EXCH, ENERGY = M::ENERGY;
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = a.n, n_pad = (n + 15) & ~15;
   const int n_rows = a.n_rows;
@@ -867,22 +903,8 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
 #pragma unroll
     for (int j = 0; j < MB; ++j) o[r][j] = *reinterpret_cast<const gu32x2*>(ol + (size_t)(r * MB + j) * LPC * 8);
   }
-  [[maybe_unused]] const float* bt = nullptr;
-  [[maybe_unused]] float beta_next = 0.0f;
-  [[maybe_unused]] int rung = 0;  // EXCH: the rung the chain holds, and (beta_next) its beta
-  if constexpr (EXCH) {
-    if (valid) rung = a.init ? slot.j : min(max(a.rung[chain], 0), a.n_replicas - 1);
-    beta_next = X.ladder[rung];
-  } else if constexpr (TABLE) {
-    bt = a.betas + (int64_t)chain * a.beta_stride;
-    beta_next = bt[0];
-  }
-  [[maybe_unused]] double e = 0.0, lw = 0.0;
-  [[maybe_unused]] float beta_prev = 0.0f;
-  [[maybe_unused]] uint32_t up = 0u;  // AIS: bit k = the spin of slot k is +1
-  if constexpr (AIS) beta_prev = a.beta_from;
-  [[maybe_unused]] uint32_t rec_at = 0u, rec_m = 0u;  // TRACE, XTRACE: the next recorded sweep (as k + 1) and its record
-  if constexpr (TRACE || XTRACE) rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
+  GibbsControl ctl = gibbs_begin<SCHED>(a, X, slot);
+  [[maybe_unused]] uint32_t up = 0u;  // ENERGY: bit k = the spin of slot k is +1
   if constexpr (ENERGY) {
     // the sweep loop's walk over the steps, on the start state (it leaves `o` at step 0's offsets again)
 #pragma unroll
@@ -902,7 +924,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
       for (int r = 0; r < NR; ++r) {  // (a row the step left out has no spin in any lane of the wave)
         if (sp[k0 + r] >= 0) {
           const _Float16 s = st[sp[k0 + r]];
-          e += gibbs_start_energy(s, hs[k0 + r], f[r]);
+          ctl.e += gibbs_start_energy(s, hs[k0 + r], f[r]);
           if ((float)s > 0.0f) up |= 1u << (k0 + r);
         }
       }
@@ -913,25 +935,12 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
   if constexpr (ENERGY) {                                                                                    \
     const bool fr = DVG_GIBBS_FREE(K);                                                                      \
     const float sn = (float)(S), so = ((up >> (K)) & 1u) ? 1.0f : -1.0f;                                    \
-    e += gibbs_energy_step(fr ? sn : so, so, F);                                                            \
+    ctl.e += gibbs_energy_step(fr ? sn : so, so, F);                                                        \
     if (fr) up = (up & ~(1u << (K))) | (sn > 0.0f ? 1u << (K) : 0u);                                        \
   }
   for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
     const uint32_t tq = t >> 2, tw = t & 3u;
-    float two_beta;
-    if constexpr (EXCH) {
-      two_beta = __fmul_rn(2.0f, beta_next);
-    } else if constexpr (TABLE) {
-      two_beta = __fmul_rn(2.0f, beta_next);
-      if constexpr (AIS) {
-        lw -= ((double)beta_next - (double)beta_prev) * e;
-        beta_prev = beta_next;
-      }
-      const uint32_t kn = t - sweep0 + 1u;
-      if (kn < (uint32_t)a.n_sweeps) beta_next = bt[kn];
-    } else {
-      two_beta = a.two_beta;
-    }
+    const float two_beta = gibbs_sweep_head<SCHED>(a, t, sweep0, ctl);
     if (t == sweep0 || tw == 0u) {
 #pragma unroll
       for (int k = 0; k < MAXS; ++k)
@@ -974,68 +983,12 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD,
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       __builtin_amdgcn_wave_barrier();
     }
-    if constexpr (TRACE) {
-      // (every lane still here is a valid chain's; the words of the held-flag helper: one bit per spin)
-      if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
-        gibbs_record<LPC, true>(st, n, n_pad, l, a.trace + ((size_t)chain * a.n_records + rec_m) * gibbs_held_words(n));
-        rec_at += (uint32_t)a.thin;
-        ++rec_m;
-      }
-    }
-    if constexpr (EXCH) {
-      // (t, swap_every: kernel arguments -- the same in every wave of every workgroup)
-      if ((t + 1u) % (uint32_t)a.swap_every == 0u) {
-        const uint32_t x = (t + 1u) / (uint32_t)a.swap_every;
-        if (valid) gibbs_exchange_post<LPC, WAVES * CPW>(X, a.n_replicas, x, slot.lq, rung, l, e);
-        __syncthreads();
-        if (valid) gibbs_exchange_decide(a, X, WAVES * CPW, a.n_replicas, x, slot.lq, cid - (uint32_t)slot.j, l, rung, beta_next);
-      }
-    }
-    if constexpr (XTRACE) {
-      // (the rows are 16-byte aligned here, as the plain trace's; the lanes of an idle slot only count)
-      if (t - sweep0 + 1u == rec_at && rec_m < (uint32_t)a.n_records) {
-        if (valid) gibbs_exchange_record<LPC, true>(a, st, n, n_pad, l, chain, (size_t)(chain - slot.j + rung), rec_m, rung, e);
-        rec_at += (uint32_t)a.thin;
-        ++rec_m;
-      }
-    }
+    gibbs_sweep_tail<LPC, WAVES * CPW, SCHED, true>(a, X, slot, st, l, t, sweep0, ctl);
   }
 #undef DVG_GIBBS_WORD
 #undef DVG_GIBBS_WEIGH
 #undef DVG_GIBBS_FREE
-  if constexpr (EXCH) {
-    __syncthreads();  // the counters are final
-    if (valid) {
-      const size_t row = (size_t)(chain - slot.j + rung);  // the outputs by rung; state and rung by chain
-      int8_t* dst = a.state + (size_t)chain * n;
-      for (int i = l; i < n; i += LPC) {
-        const float v = (float)st[i];
-        dst[i] = (int8_t)v;
-        if (a.samples_out) a.samples_out[row * n + i] = v;
-      }
-      e = gibbs_chain_sum<LPC>(e);
-      if (l == 0) {
-        a.rung[chain] = rung;
-        if (a.energy_out) a.energy_out[row] = e;
-        if (a.accept_out) a.accept_out[chain] = X.acc[slot.lq * a.n_replicas + slot.j];
-      }
-    }
-    return;
-  }
-  int8_t* dst = a.state + (size_t)chain * n;
-  for (int i = l; i < n; i += LPC) {
-    const float v = (float)st[i];
-    dst[i] = (int8_t)v;
-    if (a.samples_out) a.samples_out[(size_t)chain * n + i] = v;
-  }
-  if constexpr (AIS) {
-    e = gibbs_chain_sum<LPC>(e);
-    lw = gibbs_chain_sum<LPC>(lw);
-    if (l == 0) {
-      a.log_weight_out[chain] = lw;
-      if (a.energy_out) a.energy_out[chain] = e;
-    }
-  }
+  gibbs_finish<LPC, SCHED>(a, X, slot, st, l, ctl);
 }
 
 // ---------------------------------------------------------------- host: plan (gibbs_plan.h), fill arguments, launch
@@ -1081,15 +1034,22 @@ static int gibbs_launch(void (*kern)(A...), const GibbsDrawPlan& p, const GibbsA
 
 using namespace dvg;
 
+// Every draw: plan, attach the lane image, launch.  The exchange draws have a planner of their own (the replica count is an
+// input) and the same tables; with the records (GIBBS_EXCHANGE_TRACE) the same plan, the same forms, the same LDS.
 template <bool HELD, int SCHED = 0>
 static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStream_t s) {
-  constexpr GibbsDrawKind KIND = HELD                   ? GK_HELD
-                                 : SCHED == GIBBS_WEIGH ? GK_WEIGH
-                                 : SCHED == GIBBS_TABLE ? GK_TABLE
-                                 : SCHED == GIBBS_TRACE ? GK_TRACE
-                                                        : GK_PLAIN;
+  constexpr GibbsDrawKind KIND = HELD                     ? GK_HELD
+                                 : GibbsMode<SCHED>::EXCH ? GK_EXCHANGE
+                                 : SCHED == GIBBS_WEIGH   ? GK_WEIGH
+                                 : SCHED == GIBBS_TABLE   ? GK_TABLE
+                                 : SCHED == GIBBS_TRACE   ? GK_TRACE
+                                                          : GK_PLAIN;
   GibbsDrawPlan p;
-  DVG_TRY(gibbs_draw_plan(g->shape, a.n_chains, KIND, opt(OPT_GIBBS_GENERIC), &p));
+  if constexpr (KIND == GK_EXCHANGE) {
+    DVG_TRY(gibbs_exchange_plan(g->shape, a.n_chains / a.n_replicas, a.n_replicas, opt(OPT_GIBBS_GENERIC), &p, nullptr));
+  } else {
+    DVG_TRY(gibbs_draw_plan(g->shape, a.n_chains, KIND, opt(OPT_GIBBS_GENERIC), &p));
+  }
   if (p.form == GF_LANE) {
     a.lane_spin = g->lane_spin; a.lane_eid = g->lane_eid; a.lane_off = g->lane_off; a.n_rows = g->shape.lane_rows;
   }
@@ -1097,18 +1057,6 @@ static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStrea
     if (p.form == GF_SLOTS) return gibbs_launch(gibbs_slot_kernel_of(p), p, a, s, a, p.slots);
   }
   return gibbs_launch(gibbs_kernel_of<HELD, SCHED>(p), p, a, s, a);
-}
-
-// the exchange draw: its own plan (the replica count is an input), the same tables.  SCHED: GIBBS_EXCHANGE or, with the
-// records, GIBBS_EXCHANGE_TRACE -- the same plan, the same forms, the same LDS.
-template <int SCHED>
-static int gibbs_draw_exchange(const dvg_graph_t* g, GibbsArgsT<false, SCHED>& a, hipStream_t s) {
-  GibbsDrawPlan p;
-  DVG_TRY(gibbs_exchange_plan(g->shape, a.n_chains / a.n_replicas, a.n_replicas, opt(OPT_GIBBS_GENERIC), &p, nullptr));
-  if (p.form == GF_LANE) {
-    a.lane_spin = g->lane_spin; a.lane_eid = g->lane_eid; a.lane_off = g->lane_off; a.n_rows = g->shape.lane_rows;
-  }
-  return gibbs_launch(gibbs_kernel_of<false, SCHED>(p), p, a, s, a);
 }
 
 // What every draw checks, under its entry point's name `who`.  `missing`: the entry point's own null argument, if any
@@ -1258,7 +1206,7 @@ extern "C" int dvg_gibbs_sample_tempered(const dvg_graph_t* g, const float* line
                   n_sweeps, init, samples_out, nullptr);
   a.ladder = ladder; a.n_replicas = n_replicas; a.swap_every = swap_every;
   a.rung = rung; a.energy_out = energy_out; a.accept_out = accept_out;
-  return gibbs_draw_exchange<GIBBS_EXCHANGE>(g, a, (hipStream_t)stream);
+  return gibbs_draw<false, GIBBS_EXCHANGE>(g, a, (hipStream_t)stream);
 }
 
 // The traced exchange draw ("DVG PT trace v1", include/dvg.h): dvg_gibbs_sample_tempered, with a history by rung -- packed
@@ -1282,7 +1230,7 @@ extern "C" int dvg_gibbs_sample_tempered_traced(const dvg_graph_t* g, const floa
   a.rung = rung; a.energy_out = energy_out; a.accept_out = accept_out;
   a.trace = trace_out; a.energy_trace = energy_trace_out; a.rung_trace = rung_trace_out;
   a.burn_in = burn_in; a.thin = thin; a.n_records = (n_sweeps - burn_in) / thin;
-  return gibbs_draw_exchange<GIBBS_EXCHANGE_TRACE>(g, a, (hipStream_t)stream);
+  return gibbs_draw<false, GIBBS_EXCHANGE_TRACE>(g, a, (hipStream_t)stream);
 }
 
 // The traced draw ("DVG trace v1", include/dvg.h): dvg_gibbs_sample, with the chains' states after the recorded sweeps
