@@ -102,6 +102,11 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int,
          c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     ),
+    "dvg_gibbs_sample_fields": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int,
+         c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
+    ),
     "dvg_gibbs_sample_annealed": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_int,

@@ -91,16 +91,26 @@ struct GibbsExchangeTraceArgs : GibbsExchangeArgs {
   int burn_in, thin;       // the rule of GibbsTraceArgs
   int n_records;           // (n_sweeps - burn_in) / thin
 };
-constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3, GIBBS_TRACE = 4, GIBBS_EXCHANGE_TRACE = 5;
+// Per-chain-field draws (dvg_gibbs_sample_fields, "DVG field v1" in include/dvg.h): the plain draw, with chain c sampling the
+// model whose linear vector is rn(linear + its row of `fields`) -- soft evidence, where HELD is the hard kind.  A seventh mode
+// of SCHED, GIBBS_FIELD: the plain block plus the rows.  The rolled kernel alone carries it: a chain's scaled, clamped hs row
+// lives in LDS behind the state rows and stands in for the image's shared one; the update is the plain draw's.
+struct GibbsFieldArgs : GibbsArgs {
+  const float* fields;    // [n_chains or 1][n]: added to `linear`, in its raw units (finite: not checked)
+  int64_t field_stride;   // n (a row per chain) or 0 (one row for all chains)
+};
+constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3, GIBBS_TRACE = 4, GIBBS_EXCHANGE_TRACE = 5, GIBBS_FIELD = 6;
 template <bool HELD, int SCHED = 0>
 using GibbsArgsT = std::conditional_t<
-    SCHED == GIBBS_EXCHANGE_TRACE, GibbsExchangeTraceArgs,
+    SCHED == GIBBS_FIELD, GibbsFieldArgs,
     std::conditional_t<
-        SCHED == GIBBS_TRACE, GibbsTraceArgs,
-        std::conditional_t<SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
-                           std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
-                                              std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs,
-                                                                 std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>>>;
+        SCHED == GIBBS_EXCHANGE_TRACE, GibbsExchangeTraceArgs,
+        std::conditional_t<
+            SCHED == GIBBS_TRACE, GibbsTraceArgs,
+            std::conditional_t<SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
+                               std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
+                                                  std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs,
+                                                                     std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>>>>;
 
 // A chain's start state, its LPC lanes each taking spins l, l + LPC, ...: from the INIT stream (init) or from `state`.
 // HELD (a conditional draw): held spins from `state` always, free ones as above.
@@ -385,6 +395,8 @@ __device__ __forceinline__ void gibbs_exchange_record(const GibbsExchangeTraceAr
 //     sweeps: a countdown in scalar registers (`rec_at`, the next recorded k + 1), no division per sweep.
 //   GIBBS_EXCHANGE_TRACE: the exchange draw (EXCH); behind the exchange block of a recorded sweep the lanes of a valid chain
 //     write its record to the row of the rung it NOW holds (gibbs_exchange_record), on the same countdown.
+//   GIBBS_FIELD: the plain draw's control -- the fixed beta, nothing at the head or the tail of a sweep; what differs is where
+//     the rolled kernel reads a spin's hs (FIELD: the chain's own row).  The lane-major kernel has no such instantiation.
 // What the exchange modes rest on, in either kernel:
 //   * EVERY wave of a workgroup reaches EVERY barrier: the ones in gibbs_sweep_tail and the one in gibbs_finish.  The kernels
 //     let no wave leave or skip the sweep loop under EXCH -- the lanes of an idle slot run it without a spin to update;
@@ -395,6 +407,7 @@ struct GibbsMode {
   static constexpr bool AIS = SCHED == GIBBS_WEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE;
   static constexpr bool EXCH = SCHED == GIBBS_EXCHANGE || XTRACE, ENERGY = AIS || EXCH;
   static constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
+  static constexpr bool FIELD = SCHED == GIBBS_FIELD;
 };
 // a lane's control registers; a mode leaves those of the others at zero and the compiler drops them
 struct GibbsControl {
@@ -510,6 +523,9 @@ __device__ __forceinline__ void gibbs_finish(const Args& a, const GibbsExchangeL
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
 // HELD: the chain's held flags sit behind the state rows, one bit per spin, and a held spin is passed over in its class.
 // EXCH: the lanes of an idle slot find every class empty.  The rows are aligned to 4 bytes (gibbs_record's A16 = false).
+// FIELD: the chain's row of hs = clamp(rn(prefactor * rn(linear + field))) sits behind the state rows, float32 [n_pad] per chain
+// slot, written once when the chain is loaded by the lanes that read it (one wave: the fence below orders it); every read of
+// the image's shared hs goes to it instead.
 template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
@@ -539,6 +555,13 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
   [[maybe_unused]] uint32_t* hb = nullptr;
   if constexpr (HELD)
     hb = reinterpret_cast<uint32_t*>(L.state + (size_t)WAVES * CPW * n_pad) + (size_t)(wave * CPW + sub) * gibbs_held_words(n);
+  // where a spin's hs is read: the image's row, or (FIELD) the chain's own
+  const float* hsv = L.hs;
+  [[maybe_unused]] float* hc = nullptr;
+  if constexpr (M::FIELD) {
+    hc = reinterpret_cast<float*>(L.state + (size_t)WAVES * CPW * n_pad) + (size_t)(wave * CPW + sub) * n_pad;
+    hsv = hc;
+  }
 
   // (read before the chains start: a fresh chain's start configuration is keyed by the sweep index it starts at, so
   // non-persistent draws do not all restart from one configuration)
@@ -554,6 +577,11 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
         hb[w] = bits;
       }
     }
+    if constexpr (M::FIELD) {
+      const float* fr = a.fields + (int64_t)chain * a.field_stride;
+      for (int i = l; i < n; i += LPC)
+        hc[i] = clampf(__fmul_rn(a.prefactor, __fadd_rn(a.linear[i], fr[i])), a.h_lo, a.h_hi);
+    }
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   __builtin_amdgcn_wave_barrier();
@@ -562,7 +590,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
     GibbsControl ctl = gibbs_begin<SCHED>(a, X, slot);
     if constexpr (M::ENERGY) {
       for (int i = l; i < (valid ? n : 0); i += LPC) {
-        const float hsi = L.hs[i];
+        const float hsi = hsv[i];
         ctl.e += gibbs_start_energy(st[i], hsi, gibbs_field(hsi, L.row[i], L, st, a.n_batches, a.max_batches));
       }
     }
@@ -576,7 +604,7 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
           if constexpr (HELD) {
             if ((hb[i >> 5] >> (i & 31)) & 1u) continue;
           }
-          const float f = gibbs_field(L.hs[i], L.row[i], L, st, a.n_batches, a.max_batches);
+          const float f = gibbs_field(hsv[i], L.row[i], L, st, a.n_batches, a.max_batches);
           const u32x4 r = philox4x32_10((uint32_t)i, cid, tq, STREAM_GIBBS, a.k0, a.k1);
           const _Float16 s_new = gibbs_decide(f, two_beta, pick(r, tw));
           if constexpr (M::ENERGY) ctl.e += gibbs_energy_step((float)s_new, (float)st[i], f);
@@ -802,6 +830,7 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
 template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
+  static_assert(SCHED != GIBBS_FIELD, "the per-chain-field draw takes the rolled form alone: this image keeps h in registers");
   using M = GibbsMode<SCHED>;
   constexpr bool EXCH = M::EXCH, ENERGY = M::ENERGY;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -998,11 +1027,13 @@ using GibbsKernelT = void (*)(GibbsArgsT<HELD, SCHED>);
 // the instantiation a plan names; null: it has none.  The tables expand from the lists the plan chose from.
 template <bool HELD, int SCHED>
 static GibbsKernelT<HELD, SCHED> gibbs_kernel_of(const GibbsDrawPlan& p) {
+  if constexpr (SCHED != GIBBS_FIELD) {  // (the field kind is planned rolled on every graph and has no lane-major instantiation)
 #define DVG_GIBBS_LANE_ENTRY(LPC, W, MB, NR, MAXS)                                                      \
   if (p.form == GF_LANE && p.lpc == LPC && p.waves == W && p.mb == MB && p.nr == NR && p.maxs == MAXS)  \
     return gibbs_fast_kernel<LPC, W, MB, NR, MAXS, HELD, SCHED>;
-  DVG_GIBBS_LANE_KERNELS(DVG_GIBBS_LANE_ENTRY)
+    DVG_GIBBS_LANE_KERNELS(DVG_GIBBS_LANE_ENTRY)
 #undef DVG_GIBBS_LANE_ENTRY
+  }
 #define DVG_GIBBS_ROLLED_ENTRY(LPC, W) \
   if (p.form == GF_ROLLED && p.lpc == LPC && p.waves == W) return gibbs_kernel<LPC, W, HELD, SCHED>;
   DVG_GIBBS_ROLLED_KERNELS(DVG_GIBBS_ROLLED_ENTRY)
@@ -1043,6 +1074,7 @@ static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStrea
                                  : SCHED == GIBBS_WEIGH   ? GK_WEIGH
                                  : SCHED == GIBBS_TABLE   ? GK_TABLE
                                  : SCHED == GIBBS_TRACE   ? GK_TRACE
+                                 : SCHED == GIBBS_FIELD   ? GK_FIELD
                                                           : GK_PLAIN;
   GibbsDrawPlan p;
   if constexpr (KIND == GK_EXCHANGE) {
@@ -1251,6 +1283,25 @@ extern "C" int dvg_gibbs_sample_traced(const dvg_graph_t* g, const float* linear
                   n_sweeps, init, samples_out, nullptr);
   a.trace = trace_out; a.burn_in = burn_in; a.thin = thin; a.n_records = (n_sweeps - burn_in) / thin;
   return gibbs_draw<false, GIBBS_TRACE>(g, a, (hipStream_t)stream);
+}
+
+// The per-chain-field draw ("DVG field v1", include/dvg.h): chain c samples the model whose linear vector is
+// rn(linear + fields[c * field_chain_stride + .]); everything behind that add is dvg_gibbs_sample's.
+extern "C" int dvg_gibbs_sample_fields(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                       float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                       float beta, int8_t* state, int n_chains, uint32_t chain_id0,
+                                       uint64_t seed, uint32_t sweep0, int n_sweeps, int init,
+                                       const float* fields, int64_t field_chain_stride,
+                                       float* samples_out, const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  const GibbsStride stride{"field_chain_stride", field_chain_stride, "n", g ? g->n : 0};
+  DVG_TRY(gibbs_check("gibbs_fields", g, linear && quadratic && state,
+                      fields ? nullptr : "null fields (a draw without fields is dvg_gibbs_sample)", n_chains, n_sweeps, false, &stride));
+  DVG_REQUIRE(!dyn, "gibbs_fields: dyn must be NULL (the draw is one-off, not part of a captured step)");
+  GibbsFieldArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, beta, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, nullptr);
+  a.fields = fields; a.field_stride = field_chain_stride;
+  return gibbs_draw<false, GIBBS_FIELD>(g, a, (hipStream_t)stream);
 }
 
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,

@@ -71,26 +71,49 @@ static int gibbs_plan_slots(const GibbsGraphShape& g, int n_chains, int ch, Gibb
   return gibbs_plan_finish(g, n_chains, p, "");
 }
 
-static int gibbs_plan_rolled(const GibbsGraphShape& g, int n_chains, bool held, int lpc, int waves, GibbsDrawPlan* p) {
+// what a chain slot of the rolled form keeps in LDS behind the state rows: the held kind a row of flag bits, the field kind a
+// float32 row of hs
+static size_t gibbs_rolled_extra(const GibbsGraphShape& g, GibbsDrawKind kind) {
+  return kind == GK_HELD ? sizeof(uint32_t) * (size_t)gibbs_held_words(g.n) : kind == GK_FIELD ? gibbs_field_row_bytes(g.n) : 0;
+}
+static size_t gibbs_rolled_lds(const GibbsGraphShape& g, GibbsDrawKind kind, int lpc, int waves) {
+  const int chains = waves * (64 / lpc);
+  return gibbs_lds_bytes(g.n, g.n_batches, g.n_colours, chains) + (size_t)chains * gibbs_rolled_extra(g, kind);
+}
+
+static int gibbs_plan_rolled(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, int lpc, int waves, GibbsDrawPlan* p) {
+  if (kind == GK_FIELD) {
+    // The hs rows triple a chain's LDS: the largest WAVES of the list at this LPC, no larger than the one chosen, that fits
+    // (1024 spins: ~105 KB of tables and 6 KB per chain -- 4 chains, not 16).  Nothing fits: the chosen one, reported below.
+    int fit = 0;
+#define DVG_GIBBS_ROLLED_FIT(LPC, W) \
+  if (LPC == lpc && W <= waves && W > fit && gibbs_rolled_lds(g, kind, LPC, W) <= GIBBS_LDS_MAX) fit = W;
+    DVG_GIBBS_ROLLED_KERNELS(DVG_GIBBS_ROLLED_FIT)
+#undef DVG_GIBBS_ROLLED_FIT
+    if (fit) waves = fit;
+  }
   p->form = GF_ROLLED;
   p->lpc = lpc; p->waves = waves;
   p->chains_per_block = waves * (64 / lpc); p->threads = waves * 64;
-  // (held: a row of flag bits per chain behind the state rows)
-  p->lds = gibbs_lds_bytes(g.n, g.n_batches, g.n_colours, p->chains_per_block) +
-           (held ? sizeof(uint32_t) * (size_t)p->chains_per_block * gibbs_held_words(g.n) : 0);
-  return gibbs_plan_finish(g, n_chains, p, held ? " (the held flags of a conditional draw included)" : "");
+  p->lds = gibbs_rolled_lds(g, kind, lpc, waves);
+  return gibbs_plan_finish(g, n_chains, p,
+                           kind == GK_HELD    ? " (the held flags of a conditional draw included)"
+                           : kind == GK_FIELD ? " (the field rows of a per-chain-field draw included)"
+                                              : "");
 }
 
 // The held draw takes the plain draw's choices, with two exceptions: it has no chains-side-by-side form, so the large
 // graphs' many-chain draws run the rolled kernel in 16-wave workgroups, and the A/B forms 3 and 4 count as 0.
 // The annealed draw, weighed or not, and the traced draw: the same two exceptions.
+// The per-chain-field draw: the table kind's plan under gibbs_generic = 1, whatever the option -- the rolled form alone keeps
+// hs where a row per chain can stand in for it -- with the workgroup stepped down to what fits (gibbs_plan_rolled).
 int gibbs_draw_plan(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, int64_t generic_option, GibbsDrawPlan* out) {
   GibbsDrawPlan& p = *out;
   p = GibbsDrawPlan{};
   const bool variant = kind != GK_PLAIN;
   // (option gibbs_generic = 1 forces the rolled reference schedule: A/B runs and the bit-exactness test of the fast one;
   // 2 = the fast schedule without its two-passes-side-by-side form)
-  const int64_t form = (variant && generic_option >= 3) ? 0 : generic_option;
+  const int64_t form = kind == GK_FIELD ? 1 : (variant && generic_option >= 3) ? 0 : generic_option;
   // (4: the chains-side-by-side schedule in 8-chain workgroups whatever the size: A/B runs; graphs whose classes do not
   // make slots take what 0 gives them)
   if (!variant && form == 4 && gibbs_make_slots(g, 8, &p.slots)) return gibbs_plan_slots(g, n_chains, 8, &p);
@@ -134,12 +157,12 @@ int gibbs_draw_plan(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, 
     // ... with static (class, pass) slots when the classes make at most 20 of them (gibbs_slot_kernel; option
     // gibbs_generic = 1 keeps the plain rolled kernel: the reference of the bit-exactness tests)
     if (!variant && form != 1 && gibbs_make_slots(g, 16, &p.slots)) return gibbs_plan_slots(g, n_chains, 16, &p);
-    return gibbs_plan_rolled(g, n_chains, kind == GK_HELD, 64, 16, &p);
+    return gibbs_plan_rolled(g, n_chains, kind, 64, 16, &p);
   }
   // Lanes per chain: the smallest of 16 / 32 / 64 that covers the largest colour class in one pass, else 64; one wave per
   // workgroup for small graphs with few chains, as above.
   const bool small = gibbs_lds_bytes(g.n, g.n_batches, g.n_colours, 0) <= 16 * 1024 && n_chains <= 1024;
-  return gibbs_plan_rolled(g, n_chains, kind == GK_HELD, g.max_class <= 16 ? 16 : g.max_class <= 32 ? 32 : 64, small ? 1 : 4, &p);
+  return gibbs_plan_rolled(g, n_chains, kind, g.max_class <= 16 ? 16 : g.max_class <= 32 ? 32 : 64, small ? 1 : 4, &p);
 }
 
 int gibbs_exchange_plan(const GibbsGraphShape& g, int n_ladders, int n_replicas, int64_t generic_option, GibbsDrawPlan* out,
@@ -156,7 +179,7 @@ int gibbs_exchange_plan(const GibbsGraphShape& g, int n_ladders, int n_replicas,
                                 : gibbs_lds_bytes(g.n, g.n_batches, g.n_colours, p.chains_per_block);
     } else {
       p = GibbsDrawPlan{};
-      DVG_TRY(gibbs_plan_rolled(g, n_chains, false, 64, 16, &p));
+      DVG_TRY(gibbs_plan_rolled(g, n_chains, GK_TABLE, 64, 16, &p));
     }
   }
   const int per_block = p.chains_per_block / R;

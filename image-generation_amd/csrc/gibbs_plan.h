@@ -32,6 +32,8 @@ __host__ __device__ __forceinline__ size_t gibbs_lds_bytes(int n, int n_batches,
 }
 // words of one chain's row of held flags in LDS (the rolled form of a conditional draw), one bit per spin
 __host__ __device__ __forceinline__ int gibbs_held_words(int n) { return (n + 31) >> 5; }
+// bytes of one chain's row of scaled, clamped linear terms in LDS (the rolled form of a per-chain-field draw): float32, n_pad entries
+__host__ __device__ __forceinline__ size_t gibbs_field_row_bytes(int n) { return sizeof(float) * (size_t)((n + 15) & ~15); }
 
 // LDS of the fixed-row image (slots form, FIX): h [n] | couplings [n][20] | state offsets [n][20] | order [n] | state [n_pad][CH]
 __host__ __device__ __forceinline__ size_t gibbs_fix_layout(int n, size_t off[5]) {
@@ -99,8 +101,11 @@ GibbsGraphShape gibbs_graph_shape(int n, int n_colours, const int32_t* class_ptr
 // exchange: _tempered (GIBBS_EXCHANGE) and _tempered_traced (GIBBS_EXCHANGE_TRACE: the same plan, a record is packed from the
 // chain's own row and registers) -- planned by gibbs_exchange_plan, which needs the replica count as well;
 // trace: _traced (GIBBS_TRACE) -- the table kind's choices (no slots form), the table kind's LDS: a record is packed from the
-// state rows where they lie
-enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE, GK_TRACE };
+// state rows where they lie;
+// field: _fields (GIBBS_FIELD) -- the rolled form on every graph: the instantiation the table kind takes under gibbs_generic = 1,
+// its WAVES stepped down within DVG_GIBBS_ROLLED_KERNELS until the image fits with a float32 row of hs per chain slot behind the
+// state rows (6 bytes per spin and chain where the other kinds keep 2)
+enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE, GK_TRACE, GK_FIELD };
 //   GF_ROLLED  gibbs_kernel<lpc, waves, HELD, SCHED>: any graph
 //   GF_LANE    gibbs_fast_kernel<lpc, waves, mb, nr, maxs, HELD, SCHED>: graphs with a lane-major image
 //   GF_SLOTS   gibbs_slot_kernel<maxs, ch, fix>: ch chains of a 16-wave workgroup side by side; the plain draw only
@@ -117,7 +122,7 @@ struct GibbsDrawPlan {
   bool fix;          // slots: the fixed-row image (at most 20 neighbours per spin and it fits)
   GibbsSlots slots;  // slots
   int chains_per_block, grid, threads;
-  size_t lds;        // dynamic LDS bytes (held rolled form: the flag words included)
+  size_t lds;        // dynamic LDS bytes (held rolled form: the flag words included; field kind: the hs rows included)
 };
 
 // Pure: the same arguments give the same plan.  generic_option: option gibbs_generic as the call read it.

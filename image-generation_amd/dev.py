@@ -133,14 +133,16 @@ def mmd_plan(nx, ny, d):
 
 GIBBS_FORMS = ("rolled", "lane", "slots")            # csrc/gibbs_plan.h: GibbsForm
 GIBBS_KINDS = ("plain", "held", "table", "weigh")    # GibbsDrawKind
-# ... by name: "trace" (dvg_gibbs_sample_traced) is GK_TRACE = 5, behind GK_EXCHANGE, which dvg_dev_gibbs_exchange_plan plans
-GIBBS_KIND_IDS = dict({k: i for i, k in enumerate(GIBBS_KINDS)}, trace=5)
+# ... by name: "trace" (dvg_gibbs_sample_traced) is GK_TRACE = 5, behind GK_EXCHANGE, which dvg_dev_gibbs_exchange_plan plans;
+# "field" (dvg_gibbs_sample_fields) is GK_FIELD = 6
+GIBBS_KIND_IDS = dict({k: i for i, k in enumerate(GIBBS_KINDS)}, trace=5, field=6)
 
 
 def gibbs_draw_plan(plan, n_chains, kind="plain"):
     """The kernel form a Gibbs draw of ``n_chains`` chains takes on the graph of ``plan`` (a ``graphs.GibbsPlan``) under
     the current option ``gibbs_generic`` (no device needed).  ``kind``: ``"plain"`` (``dvg_gibbs_sample``), ``"held"``
-    (``_clamped``), ``"table"`` (``_annealed``), ``"weigh"`` (``_ais``) or ``"trace"`` (``_traced``: the table kind's plan).  ``form``: ``"rolled"`` (``gibbs_kernel``),
+    (``_clamped``), ``"table"`` (``_annealed``), ``"weigh"`` (``_ais``), ``"trace"`` (``_traced``: the table kind's plan) or ``"field"`` (``_fields``: rolled on every graph,
+    ``lds_bytes`` with the chains' rows of hs).  ``form``: ``"rolled"`` (``gibbs_kernel``),
     ``"lane"`` (``gibbs_fast_kernel``) or ``"slots"`` (``gibbs_slot_kernel``), ``params`` its template parameters;
     ``workgroups``, ``threads``, ``lds_bytes``: the launch, what ``dvg_gibbs_launch_info`` reports for the plain kind;
     ``lane_image``: the shape of the graph's lane-major image (csrc/graph.h), ``None`` for a graph that gets none."""

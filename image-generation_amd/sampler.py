@@ -79,6 +79,29 @@ def beta_schedule(beta_start: float, beta_end: float, num_sweeps: int, kind: str
 _make_beta_schedule = beta_schedule  # (sample_ising has a keyword of that name)
 
 
+def logit_fields(logits, beta: float, prefactor: float):
+    """The ``fields`` of :meth:`GibbsSampler.sample_fields` that multiply the prior by factorial evidence: with
+    ``fields = -logits / (2 * beta * prefactor)`` chain c draws from
+
+        ``p(z) * prod_i sigmoid(logits[c, i])^[z_i = +1] * sigmoid(-logits[c, i])^[z_i = -1]``,  normalised,
+
+    ``p`` being the sampler's distribution without fields -- e.g. a GRBM prior times an encoder's logits for one image per
+    chain (``logits`` = the log odds of ``z_i = +1``).  Derivation: the draw samples ``exp(-beta (hs_c . z + z Js z))`` with
+    ``hs_c = prefactor * (linear + fields[c])`` where no range clamps, i.e. ``p(z) * exp(-beta * prefactor * fields[c] . z)``.
+    The evidence of spin i is ``sigmoid(l z_i)`` with ``l = logits[c, i]``, and ``sigmoid(l) / sigmoid(-l) = e^l`` makes it
+    ``exp(l z_i / 2)`` up to a factor that does not depend on ``z_i``.  Matching exponents, ``-beta * prefactor * field =
+    l / 2``.  A ``linear_range`` that clamps ``prefactor * (linear + fields)`` caps the evidence with it.
+
+    ``logits``: a tensor (any device; the result stays there, float32) or an array (the result is a float32 array);
+    ``beta`` and ``prefactor`` must be finite and nonzero."""
+    scale = 2.0 * float(beta) * float(prefactor)
+    if not np.isfinite(scale) or scale == 0.0:
+        raise ValueError(f"beta={beta!r}, prefactor={prefactor!r}: both must be finite and nonzero")
+    if torch.is_tensor(logits):
+        return (-logits.detach().to(torch.float32) / scale).contiguous()
+    return (-np.asarray(logits, dtype=np.float32) / np.float32(scale)).astype(np.float32)
+
+
 def _slice_count(slices) -> int:
     """``slices`` as an int, if it is a power of two in 2 .. 64 (the Trotter slices of a :meth:`GibbsSampler.sample_quantum` chain)."""
     if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 2 <= slices <= 64 or slices & (slices - 1):
@@ -1378,6 +1401,9 @@ class GibbsSampler:
         # ... and the simulated-quantum-annealing draws (sample_quantum)
         self.sqa_seed = self.seed ^ 0x73716131
         self.sqa_sweep_count = 0
+        # ... and the draws with a field per chain (sample_fields)
+        self.field_seed = self.seed ^ 0x666C6431
+        self.field_sweep_count = 0
         # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
         self._betas: Optional[torch.Tensor] = None
         self._fixed_sweeps = self.sweeps
@@ -1399,6 +1425,7 @@ class GibbsSampler:
         self.trace_sweep_count = 0
         self.pa_sweep_count = 0
         self.sqa_sweep_count = 0
+        self.field_sweep_count = 0
 
     def set_beta_schedule(self, betas) -> None:
         """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
@@ -1530,6 +1557,56 @@ class GibbsSampler:
                    self.chain_offset & 0xFFFFFFFF, self.cond_seed, self.cond_sweep_count & 0xFFFFFFFF, n_sweeps,
                    int(bool(init_free)), flags.data_ptr(), stride, out.data_ptr(), None)
         self.cond_sweep_count += n_sweeps
+        return out
+
+    def sample_fields(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                      fields: torch.Tensor, *, start: Optional[torch.Tensor] = None, sweeps: Optional[int] = None,
+                      num_reads: Optional[int] = None) -> torch.Tensor:
+        """A draw with a linear field of its own per chain (``dvg_gibbs_sample_fields``, "DVG field v1" in include/dvg.h):
+        chain c samples the model ``(linear + fields[c], quadratic)`` -- soft evidence, where :meth:`sample_conditional`
+        holds spins outright.  :func:`logit_fields` makes the fields of factorial logits (posterior refinement: a prior times
+        an encoder's logits, one image per chain); a batch of Ising problems that share their couplings is ``fields =
+        h_batch - linear``.
+
+        ``fields``: float32, on the parameters' GPU, in the raw units of ``linear`` (``prefactor`` and ``linear_range`` apply
+        to the sum); (C, n), a row per chain, or (n,), one row for all chains, with ``start`` or ``num_reads`` naming C.  Its
+        values must be finite (not checked: that would be a host sync).  ``start``: (C, n) float32 or int8 +-1 to start the
+        chains from; None: the INIT stream.  ``sweeps``: default the sampler's.  Returns (C, n) float32 +-1 on the device;
+        no host sync.
+
+        Like :meth:`sample_conditional` it leaves the persistent chains, ``sweep_count`` and ``calls`` alone; it counts its
+        sweeps in ``field_sweep_count`` and draws its random words under its own key ``field_seed``; chain ids are
+        ``chain_offset + arange(C)``."""
+        n = self.plan.n
+        if not torch.is_tensor(fields):
+            raise _lib.DvgError(f"fields must be a tensor, got {type(fields).__name__}")
+        if fields.dtype != torch.float32:
+            raise _lib.DvgError(f"fields must be float32, got {fields.dtype}")
+        if fields.dim() not in (1, 2) or fields.shape[-1] != n or fields.shape[0] < 1:
+            raise _lib.DvgError(f"fields must be (chains, {n}) or ({n},), got {tuple(fields.shape)}")
+        rows = int(fields.shape[0]) if fields.dim() == 2 else None
+        if num_reads is not None:
+            num_reads = _whole("num_reads", num_reads)
+        if start is not None:
+            C = self._check_start(start, count=num_reads)
+        elif num_reads is not None:
+            C = num_reads
+        elif rows is not None:
+            C = rows
+        else:
+            raise ValueError(f"fields of shape ({n},) need start or num_reads to know how many chains to draw")
+        if rows is not None and rows != C:
+            raise _lib.DvgError(f"fields has {rows} rows but the draw has {C} chains")
+        n_sweeps = self.sweeps if sweeps is None else _whole("sweeps", sweeps, low=0)
+        _on_gpu("fields", fields)
+        lin, quad = self._parameters(linear, quadratic, start=start, fields=fields)
+        state, init = self._own_chains(start, C, lin.device)
+        rows_dev = fields.detach().contiguous()
+        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
+        self._call("dvg_gibbs_sample_fields", lin, quad, prefactor, linear_range, quadratic_range, self.beta, state.data_ptr(), C,
+                   self.chain_offset & 0xFFFFFFFF, self.field_seed, self.field_sweep_count & 0xFFFFFFFF, n_sweeps, init,
+                   rows_dev.data_ptr(), n if rows is not None else 0, out.data_ptr(), None)
+        self.field_sweep_count += n_sweeps
         return out
 
     def _annealed_arguments(self, linear, quadratic, betas, num_reads, start, beta_from=None):

@@ -135,6 +135,32 @@ int dvg_gibbs_sample_clamped(const dvg_graph_t *g, const float *linear, const fl
                              uint32_t sweep0, int n_sweeps, int init,
                              const uint8_t *clamp, int64_t clamp_chain_stride, float *samples_out,
                              const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The per-chain-field draw ("DVG field v1"): dvg_gibbs_sample with a linear field of its own per chain -- soft evidence,
+ * where dvg_gibbs_sample_clamped is the hard kind: a chain is leaned towards a configuration, not nailed to it.  Chain c
+ * samples the model whose linear vector is
+ *     lin_c[i] = rn(linear[i] + fields[c * field_chain_stride + i])      one float32 add,
+ * and everything behind that add is "DVG block-Gibbs v1" unchanged: hs_c[i] = clamp(rn(prefactor * lin_c[i]), h_lo, h_hi), the
+ * CSR-order signed adds starting from hs_c[i], two_beta, spec_exp, the decision, the Philox counter (spin, chain id,
+ * sweep >> 2, STREAM_GIBBS), the INIT stream.  So oracle/gibbs.py::gibbs_sweeps called once per chain with
+ * scaled_fields(linear + fields[c], ...) and that chain's id is the draw, bit for bit.
+ *   fields: DEVICE pointer, float32, in the raw units of `linear` (the prefactor and the range apply to the sum).
+ *     field_chain_stride = n: one row of n entries per chain; = 0: one row shared by all chains; anything else, or
+ *     fields == NULL, is DVG_E_INVALID (a draw without fields is dvg_gibbs_sample).  The values are NOT checked on the device: a
+ *     field that is not finite gives that chain a draw without meaning, never an access out of bounds.
+ *   With all fields zero the draw is dvg_gibbs_sample's, bit for bit; with stride 0 it is dvg_gibbs_sample's on
+ *     rn(linear + row), bit for bit.  A chain's result is a function of its id, its row, the model and the graph alone: not
+ *     of the other chains, not of the launch geometry.
+ *   DVG_E_INVALID, before any launch: what dvg_gibbs_sample rejects; fields == NULL; a stride that is neither 0 nor n;
+ *     dyn != NULL (the draw is one-off, not part of a captured step).  It takes the rolled kernel form on every graph
+ *     (csrc/gibbs_plan.h), a float32 row of hs_c per chain beside the state rows in LDS -- workgroups of fewer chains on large
+ *     graphs; DVG_E_UNSUPPORTED if the graph's image does not fit the LDS with one chain's rows beside it.  Every other argument as
+ *     for dvg_gibbs_sample.  No held, annealed, weighed, exchange or traced form of this draw. */
+int dvg_gibbs_sample_fields(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                            float prefactor, float h_lo, float h_hi, float j_lo, float j_hi, float beta,
+                            int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                            uint32_t sweep0, int n_sweeps, int init,
+                            const float *fields, int64_t field_chain_stride, float *samples_out,
+                            const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The annealed draw: dvg_gibbs_sample with beta looked up per sweep, and optionally per chain, as
  * neal.SimulatedAnnealingSampler's beta_range / num_sweeps / beta_schedule_type offer it.  Sweep k of the call (global
  * index sweep0 + k) on chain c runs at  beta = betas[c * beta_chain_stride + k];  everything else is "DVG block-Gibbs v1"

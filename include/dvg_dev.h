@@ -44,7 +44,8 @@ int dvg_dev_mmd_plan(int64_t nx, int64_t ny, int dim, int64_t out[24]);
 /* The kernel form a Gibbs draw of n_chains chains takes on a graph under the current option gibbs_generic
  * (csrc/gibbs_plan.h; reads the host arrays of the graph's colouring and CSR only, needs no device).  kind: 0 plain
  * (dvg_gibbs_sample), 1 held (_clamped), 2 table (_annealed), 3 weigh (_ais), 5 trace (_traced: the table kind's plan; 4, the
- * exchange draw, is planned by dvg_dev_gibbs_exchange_plan).  out[0] form: 0 rolled (gibbs_kernel<out[1],
+ * exchange draw, is planned by dvg_dev_gibbs_exchange_plan), 6 field (_fields: rolled on every graph, out[12] with the
+ * chains' rows of hs).  out[0] form: 0 rolled (gibbs_kernel<out[1],
  * out[2], ..>), 1 lane-major (gibbs_fast_kernel<out[1], out[2], out[3], out[4], out[5], ..>), 2 chains side by side
  * (gibbs_slot_kernel<out[5], out[6], out[7]>); out[1..7] = LPC, WAVES, MB, NR, MAXS, CH, FIX (0 where the form has no such
  * parameter); out[8] the slots form's (class, pass) slots; out[9] chains per workgroup; out[10] workgroups, out[11] threads

@@ -61,6 +61,9 @@ dvg_gibbs_sample_ais call of the same sweeps, against the draw's AIS calls alone
 start-energy walk each call repeats) and its resample calls alone: the per-step overhead and the resample's share of it.  (c)
 std_err of log Z at equal sweeps, `seeds=K` (default 4) seeds each: population annealing (between its 8 populations), AIS by its
 effective sample size, and AIS between 8 groups of its chains -- the populations' formula on the same footing.
+`chain_fields`: also the draw with a linear field per chain (dvg_gibbs_sample_fields, "DVG field v1"), timed as the ais rows are -- the
+raw call on persistent chains -- with N(0, 1) fields, a row per chain, and with one shared row; it runs the rolled kernel, so the
+row to hold it against is `rolled reference`; a second line gives the plans of the two (workgroup, LDS).
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -117,6 +120,31 @@ if "clamped" in sys.argv:
         clamp = torch.from_numpy((rng.uniform(size=(C, n)) < frac).astype(np.uint8)).cuda()
         ts, out = timed(lambda: s.sample_conditional(lin, quad, 0.05, (-4, 4), (-1, 1), start, clamp))
         row("cond. call, %.0f %% held" % (100 * frac), ts, (C * n - int(clamp.sum())) * sweeps, out)
+if "chain_fields" in sys.argv:
+    from image_generation_amd import dev
+
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    per_chain = torch.from_numpy(rng.standard_normal((C, n)).astype(np.float32)).cuda()
+    for name, rows, stride in (("fields, a row per chain", per_chain, n), ("fields, one shared row", per_chain[0].contiguous(), 0)):
+        state = torch.empty((C, n), dtype=torch.int8, device="cuda")
+        out = torch.empty((C, n), dtype=torch.float32, device="cuda")
+        at = [0]
+
+        def with_fields():
+            _lib.check(_lib.lib().dvg_gibbs_sample_fields(s.graph.ptr, lin.data_ptr(), quad.data_ptr(), 0.05, -4.0, 4.0, -1.0, 1.0, 20.0,
+                                                          state.data_ptr(), C, 0, seed, at[0], sweeps, int(at[0] == 0), rows.data_ptr(),
+                                                          stride, out.data_ptr(), None, _lib.stream_ptr()), "dvg_gibbs_sample_fields")
+            at[0] += sweeps
+            return out
+
+        ts, out = timed(with_fields)
+        row(name, ts, C * n * sweeps, out)
+    with _lib.option_scope(gibbs_generic=1):
+        rolled = dev.gibbs_draw_plan(plan, C, "plain")
+    field = dev.gibbs_draw_plan(plan, C, "field")
+    for name, p in (("rolled reference", rolled), ("fields", field)):
+        print(f"  {'':26s} {name}: gibbs_kernel<{p['params']['LPC']}, {p['params']['WAVES']}>, {p['workgroups']} workgroups of "
+              f"{p['chains_per_workgroup']} chains, {p['lds_bytes']} B of LDS")
 if "annealed" in sys.argv:
     shared = smp.beta_schedule(0.05, 20.0, sweeps)
     s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
