@@ -222,6 +222,9 @@ struct ConvArgs {
   // Winograd launches of the decoder's Upsample(x2) + 3x3 layers: 1 = forward (`in` is the source map, M / L of the output
   // grid: 9 of 16 transform positions), 2 = data gradient (`out` = the source map's gradient, one row per output quad)
   int wino_um = 0;
+  // F(4x4,3x3) launches (launch_conv_wino4, wino_um = 0): 1 = the block shape of 32 tiles x 64 output channels instead of
+  // 64 x 32 (conv_wino4_block64_shape; same bits, half the input transforms per matrix operation)
+  int wino4_block64 = 0;
 };
 // CU budgets of the Winograd launches of a TRAINING call (whole-CU persistent grids: a launch is sized to the CUs its
 // neighbours leave).  Measured at c3, both wave forms: the encoder's data gradient and weight gradient side
@@ -250,6 +253,7 @@ int launch_wino_weight_pack(const float* w, const WeightMap& map, float* u, hipS
 // Winograd F(4x4,3x3) form of the same layers (conv_wino4.hip): `wp` = the pack of a PackJob with wino = 2 (36 Cin Cout
 // floats: wino4_pack_entry), stats rows = conv_wino4_stats_blocks (tile blocks of 1024 pixels)
 bool conv_wino4_shape(int64_t M, int Cin, int Cout, int L);
+bool conv_wino4_block64_shape(int64_t M, int Cin, int Cout, int L);  // ... in the 64-channel block shape (ConvArgs.wino4_block64)
 int conv_wino4_stats_blocks(int64_t M);
 int launch_conv_wino4(const ConvArgs& a, hipStream_t s);
 int launch_wino4_weight_pack(const float* w, const WeightMap& map, float* u, hipStream_t s, int ups = 0);  // ups: the 25-position pack

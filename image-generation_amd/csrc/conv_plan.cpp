@@ -43,6 +43,14 @@ bool enc_wino_wanted(const PlanOptions& o, int64_t M, int Cout, ConvPass pass, b
 // enc_wino4_mask / dec_wino4_mask, measured per launch inside the c3 step: options.cpp says why each bit is what it is).
 bool wino4_bit(const PlanOptions& o, int64_t mask, int bit) { return o.v[OPT_ENC_WINO4] != 0 && ((mask >> bit) & 1); }
 
+// The F(4x4,3x3) block shape of 32 tiles x 64 channels halves the input transforms per matrix operation and deals items of
+// twice the work: a launch takes it where its mask bit is set, the shape allows and every workgroup of its CU budget still
+// gets two items or more (below that the coarser deal costs what the transforms save).  `Cout`: of the launch.
+bool wino4_block64(const PlanOptions& o, int l, bool dgrad, int64_t M, int Cin, int Cout, int L, int cus) {
+  if (!wino4_bit(o, o.v[OPT_ENC_WINO4_MASK], enc_wino4_block64_bit(l, dgrad)) || !conv_wino4_block64_shape(M, Cin, Cout, L)) return false;
+  return (int64_t)conv_wino4_stats_blocks(M) * (Cout / 64) >= 2 * (int64_t)(cus > 0 && cus < 256 ? cus : 256);
+}
+
 bool is_wino(ConvForm f) { return f == CF_WINO2 || f == CF_WINO4; }
 // checkpoint layout of the layer's 9-tap weight, forward / data-gradient orientation
 WeightMap map9(const ConvLayer& y, bool dgrad) {
@@ -55,17 +63,32 @@ bool plan_enc_wino_fwd(int64_t M, int Cin, int Cout, int L, bool training, const
   return conv_wino_shape(M, Cin, Cout, L) && enc_wino_wanted(o, M, Cout, PASS_FWD, training);
 }
 
+int plan_enc_wino_cus(const PlanOptions& o, ConvPass pass, bool training) {
+  // (a training call's forward runs beside the step's sampler draw, which holds its CUs: the tile blocks are dealt
+  // dynamically, so the grid is sized to the chip and the workgroups that get their CU late, when the draw ends,
+  // take what is left; under option wino_dynamic = 0 -- the static deal, A/B -- a quarter of the chip is left out)
+  if (pass == PASS_FWD) return (training && o.v[OPT_WINO_DYNAMIC] == 0) ? 192 : 0;
+  // (the layer's weight-gradient chain runs beside its data gradient on the side stream)
+  if (pass == PASS_DGRAD) return o.v[OPT_ENC_DGRAD_CUS] > 0 ? (int)o.v[OPT_ENC_DGRAD_CUS] : WINO_CUS_ENC_DGRAD;
+  return (int)o.v[OPT_ENC_WGRAD_CUS];
+}
+
 void plan_encoder_layers(int64_t B, int n, bool training, const PlanOptions& o, ConvLayer y[4]) {
   const int ch[5] = {1, 32, 64, 128, n};
   for (int l = 1; l < 4; ++l) {
     ConvLayer& c = y[l];
     c.M = B * (1024 >> (2 * l)); c.Cin = ch[l]; c.Cout = ch[l + 1]; c.L = 5 - l; c.ups = false; c.convt = false;
     c.form[PASS_FWD] = c.form[PASS_DGRAD] = c.form[PASS_WGRAD] = CF_DIRECT;
+    c.block64[PASS_FWD] = c.block64[PASS_DGRAD] = false;
     if (plan_enc_wino_fwd(c.M, c.Cin, c.Cout, c.L, training, o))
       c.form[PASS_FWD] = wino4_bit(o, o.v[OPT_ENC_WINO4_MASK], l - 1) && conv_wino4_shape(c.M, c.Cin, c.Cout, c.L) ? CF_WINO4 : CF_WINO2;
+    c.block64[PASS_FWD] = c.form[PASS_FWD] == CF_WINO4 &&
+                          wino4_block64(o, l, false, c.M, c.Cin, c.Cout, c.L, plan_enc_wino_cus(o, PASS_FWD, training));
     if (!training) continue;  // (no backward follows an evaluation-mode forward)
     if (conv_wino_shape(c.M, c.Cout, c.Cin, c.L) && enc_wino_wanted(o, c.M, c.Cin, PASS_DGRAD, true))
       c.form[PASS_DGRAD] = wino4_bit(o, o.v[OPT_ENC_WINO4_MASK], 2 + l) && conv_wino4_shape(c.M, c.Cout, c.Cin, c.L) ? CF_WINO4 : CF_WINO2;
+    c.block64[PASS_DGRAD] = c.form[PASS_DGRAD] == CF_WINO4 &&
+                            wino4_block64(o, l, true, c.M, c.Cout, c.Cin, c.L, plan_enc_wino_cus(o, PASS_DGRAD, true));
     // (the weight gradient takes the form with the layer's other training launches: the size rule counts the FORWARD's
     // tile blocks, so under it the forward's shape has to qualify too)
     if (conv_wino_wgrad_shape(c.M, c.Cin, c.Cout, c.L) && enc_wino_wanted(o, c.M, c.Cout, PASS_WGRAD, true) &&
@@ -79,6 +102,7 @@ void plan_decoder_layers(int64_t N, int n, const PlanOptions& o, ConvLayer y[3])
   for (int l = 0; l < 3; ++l) {
     ConvLayer& c = y[l];
     c.M = N * ((int64_t)4 << (2 * l)); c.Cin = ch[l]; c.Cout = ch[l + 1]; c.L = l + 1; c.ups = l > 0; c.convt = true;
+    c.block64[PASS_FWD] = c.block64[PASS_DGRAD] = false;  // (the decoder's F(4x4,3x3) launches have 32 output channels or 8-16 chunks)
     ConvForm base = CF_DIRECT;
     // Option dec_d22 = 0 keeps the 9-tap form for the first layer (A/B runs, tests).  Option dec_lc0: 0 never compose
     // the Linear layer with it, 1 always (tests), -1 (default) from 4096 rows up at c3's 256 latent spins -- measured
@@ -139,6 +163,7 @@ void conv_layer_geometry(const ConvLayer& y, ConvPass pass, ConvArgs& a) {
   a.M = y.M; a.Cin = d ? y.Cout : y.Cin; a.Cout = d ? y.Cin : y.Cout; a.L = y.L; a.ntaps = 9;
   a.ups = !d && y.ups; a.poolsum = d && y.ups;  // (data gradient behind the upsample: each 2x2 quad summed in the epilogue)
   a.fold = 0; a.wino_um = 0; a.bias_mod = 0;
+  a.wino4_block64 = f == CF_WINO4 && !y.ups && y.block64[pass];
   if (f == CF_FOLD) { a.M = y.M / 4; a.L = y.L - 1; a.ntaps = d ? 16 : 4; a.ups = a.poolsum = 0; a.fold = d ? 2 : 1; }  // rows = SOURCE pixels
   if (f == CF_D22 || f == CF_LC0) {
     // rows = images, columns = (pixel, channel): the same memory as [M][C]; composed: straight from / to the spins

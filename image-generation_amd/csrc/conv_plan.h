@@ -34,6 +34,9 @@ struct ConvLayer {
   int Cin, Cout, L;
   bool ups, convt;
   ConvForm form[3];
+  // CF_WINO4 forward / data-gradient launches of the encoder: the block shape of 32 tiles x 64 output channels instead of
+  // 64 x 32 (conv_wino4.hip; same bits -- no part of the signature)
+  bool block64[2] = {false, false};
 };
 
 // The planners (pure functions).  Encoder: y[1..3] (y[0], the VALU layer, is left alone); an evaluation-mode plan has no
@@ -42,6 +45,11 @@ void plan_encoder_layers(int64_t B, int n, bool training, const PlanOptions& o, 
 void plan_decoder_layers(int64_t N, int n, const PlanOptions& o, ConvLayer y[3]);
 // policy + shape of one encoder forward launch of a training call (dvg_dev_conv_wino_ok)
 bool plan_enc_wino_fwd(int64_t M, int Cin, int Cout, int L, bool training, const PlanOptions& o);
+// CUs an encoder Winograd launch of the pass is sized for (ConvArgs.wino_cus; 0: the launcher's default)
+int plan_enc_wino_cus(const PlanOptions& o, ConvPass pass, bool training);
+// the bit of dev option enc_wino4_mask that gives encoder layer l's (1..3) F(4x4,3x3) forward / data-gradient launch the
+// 64-channel block shape: the bit of the form itself, 16 higher
+inline int enc_wino4_block64_bit(int l, bool dgrad) { return 16 + (dgrad ? 2 + l : l - 1); }
 
 // workspace layouts: the offset (in floats) of a buffer of `count` floats, in 256-byte granules
 inline size_t bump(size_t& o, size_t count) {

@@ -24,6 +24,22 @@ __device__ __forceinline__ void wino4_in6(float& x0, float& x1, float& x2, float
   x0 = t0; x1 = p + q; x2 = p - q; x3 = __builtin_fmaf(2.f, s, r); x4 = __builtin_fmaf(-2.f, s, r); x5 = t5;
 }
 
+// Half of it: rows 0-2 (HI = 0: from x0 .. x4) or rows 3-5 (HI = 1: from x1 .. x5) of B^T x, the same operations per row
+template <bool ZE, bool HI>
+__device__ __forceinline__ void wino4_in3(float x0, float x1, float x2, float x3, float x4, float x5, float& o0, float& o1, float& o2) {
+  if constexpr (!HI) {
+    const float p = __builtin_fmaf(-4.f, x2, x4), q = __builtin_fmaf(-4.f, x1, x3);
+    if constexpr (ZE) o0 = __builtin_fmaf(-5.f, x2, x4);
+    else o0 = __builtin_fmaf(4.f, x0, __builtin_fmaf(-5.f, x2, x4));
+    o1 = p + q; o2 = p - q;
+  } else {
+    const float r = x4 - x2, s = x3 - x1;
+    o0 = __builtin_fmaf(2.f, s, r); o1 = __builtin_fmaf(-2.f, s, r);
+    if constexpr (ZE) o2 = __builtin_fmaf(-5.f, x3, 4.f * x1);
+    else o2 = __builtin_fmaf(4.f, x1, __builtin_fmaf(-5.f, x3, x5));
+  }
+}
+
 __device__ __forceinline__ f32x4 vfma(float k, const f32x4& a, const f32x4& b) {
   f32x4 o;
 #pragma unroll

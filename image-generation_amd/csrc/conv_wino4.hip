@@ -30,6 +30,10 @@
 // pack), the transformed input [k][tile][36], written by waves 0-3 (a patch per thread and chunk, under the MFMAs).
 // Two stages of each, one barrier per chunk, the chunk sequence runs on across the tile blocks a workgroup owns
 // (persistent grid, dynamic deal: conv_wino.hip).
+//
+// Raw pieces, patch transforms and transformed-entry writes scale with the TILES of a stage, the matrix work with tiles x
+// channels: the second block shape (Wino4Cfg, W = 1: work items of 64 tiles x 64 channels as two passes of 32 tiles x 64
+// channels) halves the former per MFMA and computes the same bits.  Which launches take it: conv_plan.cpp.
 #include <atomic>
 
 #include "conv.h"
@@ -43,6 +47,8 @@ typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
 typedef __attribute__((address_space(3))) const f32x4 lds_cf32x4;
 typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
 typedef __attribute__((address_space(3))) const float lds_cf32;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
 
 struct Wino4Args {
   const float* in;    // [16 tiles][Cin]  (Morton pixel order: tile t = rows 16t .. 16t+15)
@@ -73,9 +79,15 @@ struct Wino4Args {
 // pictures), the input transform keeps rows / columns {0,1,3,4,5}, and the output transform sums each 2x2 quad of the 4x4
 // tile, (Q A^T) M (Q A^T)^T with Q A^T = [1 2 0 3 -1 0; 0 2 0 12 -4 1] -- column 2 is zero there too: the same 25 positions;
 // `out` is the source map's gradient, four rows per tile.
-template <int L, int UM = 0>
+// W = 1: the 64-channel block shape (UM = 0 only): a work item is still a 64-tile block, now with 64 output channels, run as
+// two consecutive passes of 32 tiles x 64 channels -- the same 8 waves (2 tile groups x 4 channel groups), 144 accumulators
+// per wave and 72 MFMAs per SIMD and chunk, but HALF the raw-pixel pieces, patch transforms and transformed-entry writes
+// per MFMA (they scale with the tiles of a stage, the weights -- contiguous and L2-resident -- with its channels).  A pass
+// is a tile block of its own in everything below (TILES tiles, CH channels); what knows of the pair is the work loop.
+template <int L, int UM = 0, int W = 0>
 struct Wino4Cfg {
-  static constexpr int H = 1 << L, HW = H * H, TPI = HW / 16, IPB = 64 / TPI;  // tiles per image, images per tile block
+  static constexpr int TILES = W ? 32 : 64, CH = W ? 64 : 32;  // tiles and output channels of a stage
+  static constexpr int H = 1 << L, HW = H * H, TPI = HW / 16, IPB = TILES / TPI;  // tiles per image, images per stage
   static constexpr int NPOS = UM ? 25 : 36, EF = UM ? 28 : 36, EB = 4 * EF, NQ = EF / 4;  // positions, floats / bytes / quads per entry
   // The raw pictures, in 16-byte cells (a pixel's 4 channels).  4x4 images: one tile per image, the halo is known at
   // compile time -- 16 cells in Morton order + 1 (an ODD image stride: the 8 images of a 32-lane read pass start in 8
@@ -89,16 +101,19 @@ struct Wino4Cfg {
   static constexpr int ROWC = SRC ? 6 : (L == 3 ? 10 : 23), ROWS_IMG = L == 3 ? 10 : 17;
   static constexpr int CELLS_IMG = SRC ? (L == 2 ? 5 : 37) : (L == 2 ? 17 : (L == 3 ? 101 : ROWS_IMG * ROWC));
   static constexpr int NCELL = (L == 4 && !SRC) ? (IPB * ROWS_IMG + 1) * ROWC : IPB * CELLS_IMG;
-  static constexpr int SRC_PIX = SRC ? 256 : 1024;  // input pixels of a tile block
-  static constexpr int OUT_PIX = UM == 2 ? 256 : 1024;  // output pixels of a tile block (UM = 2: the source map's gradient)
+  static constexpr int SRC_PIX = SRC ? 256 : TILES * 16;  // input pixels of a stage's tiles
+  static constexpr int OUT_PIX = UM == 2 ? 256 : TILES * 16;  // output pixels (UM = 2: the source map's gradient)
   static constexpr int RAW_B = NCELL * 16;
   static constexpr int NRAWP = (NCELL + 63) / 64;   // 1 KiB DMA pieces (the last one is moved back to end at NCELL)
   // transformed input: [k][entry][36 floats], 32 bytes between the k planes (see the bank notes in the kernel)
-  static constexpr int VPL = 64 * EB + 32, V_B = 4 * VPL;
-  static constexpr int U_B = 4 * 32 * EB, U_PIECES = U_B / 1024;
-  static constexpr int OFF_RAW = 0, OFF_V = 2 * RAW_B, OFF_U = OFF_V + 2 * V_B, OFF_RED = OFF_U + 2 * U_B, OFF_NEXT = OFF_RED + 1024;
+  static constexpr int VPL = TILES * EB + 32, V_B = 4 * VPL;
+  static constexpr int U_B = 4 * CH * EB, U_PIECES = U_B / 1024;
+  // (the BatchNorm partials of the stage's waves, 1 KiB; W = 1: + the first pass's sums [64][2], waiting for the second)
+  static constexpr int OFF_RAW = 0, OFF_V = 2 * RAW_B, OFF_U = OFF_V + 2 * V_B, OFF_RED = OFF_U + 2 * U_B, OFF_HOLD = OFF_RED + 1024;
+  static constexpr int OFF_NEXT = OFF_HOLD + (W ? 512 : 0);
   static constexpr int LDS_BYTES = OFF_NEXT + 16;
-  static_assert(L >= 2 && L <= 4 && (!UM || L <= 3) && NCELL >= 64 && U_B % 1024 == 0 && LDS_BYTES <= 160 * 1024, "unsupported shape");
+  static_assert(L >= 2 && L <= 4 && (!UM || L <= 3) && (!W || !UM) && NCELL >= 64 && U_B % 1024 == 0 && V_B % 16 == 0 && RAW_B % 16 == 0, "unsupported shape");
+  static_assert(LDS_BYTES <= 160 * 1024, "two stages of the raw pictures, the transformed input and the weights: 160 KiB of LDS");
   // cell offset of patch element (i, j) from the thread's base cell
   static constexpr int poff(int i, int j) {
     if (SRC) return L == 2 ? (int)(((unsigned)(j - 1) & 1u) | (((unsigned)(i - 1) & 1u) << 1)) : i * ROWC + j;  // (4x4 source patch)
@@ -114,36 +129,43 @@ struct Wino4Cfg {
 // hold 4 planes x 2 entries) the two halves of a group then fall on the even and the odd 16-byte bank groups.
 __device__ __forceinline__ constexpr int wino4_entry(int r) { return r < 4 ? 2 * r : (r < 12 ? 2 * (r - 4) + 1 : 2 * (r - 8)); }
 
-template <int L, int UM>
+template <int L, int UM, int W>
 __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned char* wsm) {
-  using C = Wino4Cfg<L, UM>;
+  using C = Wino4Cfg<L, UM, W>;
   constexpr int EB = C::EB, NQ = C::NQ, NPOS = C::NPOS;
   constexpr int H = C::H, HW = C::HW;
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_byte_t*)wsm;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wt = wave & 3, wc = wave >> 2;  // the wave's 16 tiles and 16 channels of the block's 64 x 32
+  // the wave's 16 tiles and 16 channels of the stage's 64 x 32 (W = 1: 32 x 64)
+  const int wt = W ? wave & 1 : wave & 3, wc = W ? wave >> 1 : wave >> 2;
   const int kq = lane >> 4, r16 = lane & 15;
-  const int n0 = blockIdx.y * 32;
+  const int n0 = blockIdx.y * C::CH;
   const int nch = a.Cin / 4;
 
   // ---- the patch a thread of waves 0-3 transforms per chunk: channel t_k of tile tl.  Lane bits: k (2), then three tile
   // bits p, a, b, then c; wave bits w.  (1) The 32 lanes of a raw read pass (k, p, a, b) hold 4 channels x 8 cells that
   // start in 8 different bank groups; (2) the 8 lanes of a ds_write_b128 group (k, p) hold 4 planes x 2 entries of
   // different parity (p flips bit 2 of the tile's MFMA row: wino4_entry), 8 different bank groups.
+  // W = 1: four waves transform HALF a patch each -- waves 0-1 rows 0-2 of B^T d (the patch's rows 0-4), waves 2-3 rows 3-5
+  // (its rows 1-5): 30 of the 36 taps read, 18 of the 36 entries written, one transform wave per SIMD as before; a stage's
+  // 32 tiles take the lane's four tile bits and ONE wave bit.
+  constexpr int NP = W ? 2 : 1;   // stages (passes) per work item
+  constexpr bool HALF = W == 1;
+  const int xw = W ? wave & 1 : wt;
   const int t_k = lane & 3, bp = (lane >> 2) & 1, ba = (lane >> 3) & 1, bb = (lane >> 4) & 1, bc = lane >> 5;
   int t_img, t_ty = 0, t_tx = 0, cell0;
   if constexpr (UM == 1 && L == 3) {  // (source cells: tile x-step 2, y-step 12, image stride 37: p, a = image bits, b = y)
-    t_img = bp | (ba << 1) | ((wt & 1) << 2) | ((wt >> 1) << 3); t_ty = bb; t_tx = bc;
+    t_img = bp | (ba << 1) | ((xw & 1) << 2) | ((xw >> 1) << 3); t_ty = bb; t_tx = bc;
     cell0 = t_img * C::CELLS_IMG + 2 * t_ty * C::ROWC + 2 * t_tx;
   } else if constexpr (L == 2) {
-    t_img = ba | (bb << 1) | (bp << 2) | (bc << 3) | (wt << 4);
+    t_img = ba | (bb << 1) | (bp << 2) | (bc << 3) | (xw << 4);
     cell0 = t_img * C::CELLS_IMG;
   } else if constexpr (L == 3) {
-    t_img = bp | (ba << 1) | (bc << 2) | ((wt & 1) << 3); t_tx = bb; t_ty = wt >> 1;
+    t_img = bp | (ba << 1) | (bc << 2) | (W ? 0 : (xw & 1) << 3); t_tx = bb; t_ty = W ? xw : xw >> 1;
     cell0 = t_img * C::CELLS_IMG + 4 * t_ty * C::ROWC + 4 * t_tx;
   } else {
-    t_img = wt; t_tx = ba | (bp << 1); t_ty = bb | (bc << 1);
+    t_img = xw; t_tx = ba | (bp << 1); t_ty = bb | (bc << 1);
     cell0 = (t_img * C::ROWS_IMG + 4 * t_ty) * C::ROWC + 5 * t_tx;
   }
   const int tl = t_img * C::TPI + (int)morton((uint32_t)t_ty, (uint32_t)t_tx);
@@ -157,13 +179,14 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
     vst[st] = lds0 + C::OFF_V + st * C::V_B + (uint32_t)(t_k * C::VPL + t_entry * EB);
     // MFMA operands: entry (k, row) of 144 bytes; lane (kq, r16) reads k = kq of its row / column
     aaddr[st] = lds0 + C::OFF_V + st * C::V_B + (uint32_t)(kq * C::VPL + (16 * wt + wino4_entry(r16)) * EB);
-    baddr[st] = lds0 + C::OFF_U + st * C::U_B + (uint32_t)((kq * 32 + 16 * wc + r16) * EB);
+    // (W = 1: the two [4][32][36] pieces of the 64 channels lie behind each other, as in the pack)
+    baddr[st] = lds0 + C::OFF_U + st * C::U_B + (uint32_t)(((wc >> 1) * 128 + kq * 32 + 16 * (wc & 1) + r16) * EB);
     asm volatile("" : "+v"(rbase[st]), "+v"(vst[st]), "+v"(aaddr[st]), "+v"(baddr[st]));  // (kept apart: not base + constant again)
   }
 
   // ---- DMA of one chunk's images: 1 KiB pieces; raw piece p by wave p % 8, weight piece q by wave 4 + q % 4
   const __amdgpu_buffer_rsrc_t rsrc_in = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(a.in), 0, (int)((int64_t)a.nblk * C::SRC_PIX * a.Cin * 4), 0x00020000);
+      const_cast<float*>(a.in), 0, (int)((int64_t)a.nblk * NP * C::SRC_PIX * a.Cin * 4), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_u = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(a.u), 0, (int)((int64_t)a.Cin * a.Cout * EB), 0x00020000);
   // Every wave of a role issues the SAME number of pieces, unconditionally (a piece index past the end repeats the last
@@ -213,7 +236,7 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
     const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)(rdst[q] + (uint32_t)(st * C::RAW_B)));
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_in, (lds_void_t*)(uintptr_t)dst, 16, rvoff[q], soff, 0, 0);
   };
-  const int ustride = a.Cout / 32 * C::U_B;  // bytes between two chunks of the pack
+  const int ustride = a.Cout / 32 * (4 * 32 * EB);  // bytes between two chunks of the pack
   auto u_sbase = [&](int ch) { return __builtin_amdgcn_readfirstlane(ch * ustride + (int)blockIdx.y * C::U_B); };
   auto issue_u_piece = [&](int sbase, int st, int q) {  // (waves 4-7; pieces 18, 19 repeat pieces 0, 1)
     int p = ((wave - 4) & 3) + 4 * q;
@@ -264,6 +287,50 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
     for (int q = q0; q < q0 + 3; ++q) {
       const f32x4 o = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
       *reinterpret_cast<lds_f32x4*>((uintptr_t)(vst[vs] + (uint32_t)(q * 16))) = o;
+    }
+  };
+
+  // W = 1, half a patch (HI: rows 3-5 of B^T d): t[3][6] = those rows, v[18] = their entries (positions 18 HI ..), written
+  // as they complete: the straddling pair 16-17 / 18-19 as a ds_write_b64
+  auto load_half = [&](auto hic, int rs, float (&d)[36]) {
+    constexpr int R0 = decltype(hic)::value ? 1 : 0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) d[(R0 ? 0 : 30) + j] = 0.f;  // (the row this half never reads)
+#pragma unroll
+    for (int i = (R0 > I0 ? R0 : I0); i < (R0 + 5 < I1 ? R0 + 5 : I1); ++i)
+#pragma unroll
+      for (int j = I0; j < I1; ++j) {
+        d[i * 6 + j] = *reinterpret_cast<lds_cf32*>((uintptr_t)(rbase[rs] + (uint32_t)(C::poff(i, j) * 16)));
+      }
+    if constexpr (L == 2) {
+#pragma unroll
+      for (int e = 0; e < 36; ++e)
+        if (e / 6 == 0 || e / 6 == 5 || e % 6 == 0 || e % 6 == 5) d[e] = 0.f;
+    }
+  };
+  auto xform_half_col = [&](auto hic, int j, const float (&d)[36], float (&t)[18]) {
+    if (L == 2 && (j == 0 || j == 5)) { t[j] = t[6 + j] = t[12 + j] = 0.f; return; }
+    wino4_in3<L == 2, decltype(hic)::value != 0>(d[j], d[6 + j], d[12 + j], d[18 + j], d[24 + j], d[30 + j], t[j], t[6 + j], t[12 + j]);
+  };
+  auto xform_half_row = [&](auto hic, int vs, int i, float (&t)[18]) {  // row 3 HI + i, and the entry quads it completes
+    constexpr bool HI = decltype(hic)::value != 0;
+    wino4_in6<L == 2>(t[6 * i], t[6 * i + 1], t[6 * i + 2], t[6 * i + 3], t[6 * i + 4], t[6 * i + 5]);
+    auto st4 = [&](int pos, int j) {
+      const f32x4 o = {t[j], t[j + 1], t[j + 2], t[j + 3]};
+      *reinterpret_cast<lds_f32x4*>((uintptr_t)(vst[vs] + (uint32_t)(pos * 4))) = o;
+    };
+    auto st2 = [&](int pos, int j) {
+      const f32x2 o = {t[j], t[j + 1]};
+      *reinterpret_cast<lds_f32x2*>((uintptr_t)(vst[vs] + (uint32_t)(pos * 4))) = o;
+    };
+    if constexpr (!HI) {
+      if (i == 0) st4(0, 0);
+      if (i == 1) { st4(4, 4); st4(8, 8); }
+      if (i == 2) { st4(12, 12); st2(16, 16); }
+    } else {
+      if (i == 0) { st2(18, 0); st4(20, 2); }
+      if (i == 1) st4(24, 6);
+      if (i == 2) { st4(28, 10); st4(32, 14); }
     }
   };
 
@@ -327,11 +394,25 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
   }
   bool has_next = blk_nxt < a.nblk;
   if (blk_cur >= a.nblk) { finish(); return; }
-  if (wave < 4) { issue_all(std::integral_constant<int, 1>{}, blk_cur, 0, 0, true); issue_all(std::integral_constant<int, 1>{}, blk_cur, 1, 1, false); }
-  else { issue_all(std::integral_constant<int, 0>{}, blk_cur, 0, 0, true); issue_all(std::integral_constant<int, 0>{}, blk_cur, 1, 1, false); }
+  // the stage in work and the one behind it (W = 1: the item's two passes, stages 2 blk and 2 blk + 1)
+  int sb_cur = blk_cur * NP, sb_nxt = W ? sb_cur + 1 : blk_nxt;
+  bool sb_has = W ? true : has_next;
+  if (wave < 4) { issue_all(std::integral_constant<int, 1>{}, sb_cur, 0, 0, true); issue_all(std::integral_constant<int, 1>{}, sb_cur, 1, 1, false); }
+  else { issue_all(std::integral_constant<int, 0>{}, sb_cur, 0, 0, true); issue_all(std::integral_constant<int, 0>{}, sb_cur, 1, 1, false); }
   __syncthreads();  // (the workgroup fence waits for the LDS-DMA pieces)
   if (wave < 4) {
-    if constexpr (UM == 1) {
+    if constexpr (HALF) {
+      float d[36], t[18];
+      auto half = [&](auto hic) {
+        load_half(hic, 0, d);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) xform_half_col(hic, j, d, t);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) xform_half_row(hic, 0, i, t);
+      };
+      if (wave < 2) half(std::integral_constant<int, 0>{});
+      else half(std::integral_constant<int, 1>{});
+    } else if constexpr (UM == 1) {
       float sv[16], t[30], v[28] = {};
       load_patch_u(0, sv);
       xform_u_cols(sv, t);
@@ -358,7 +439,7 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
   __syncthreads();
 
   const __amdgpu_buffer_rsrc_t rsrc_out = __builtin_amdgcn_make_buffer_rsrc(
-      a.out, 0, (int)((int64_t)a.nblk * C::OUT_PIX * a.Cout * 4), 0x00020000);
+      a.out, 0, (int)((int64_t)a.nblk * NP * C::OUT_PIX * a.Cout * 4), 0x00020000);
   const int ch_out = n0 + 16 * wc + r16;
   constexpr int PPT = UM == 2 ? 4 : 16;  // output pixels per tile
   const int ovoff = (4 * kq * PPT * a.Cout + ch_out) * 4;  // tile 4 kq of the wave's sixteen, pixel 0, the lane's channel
@@ -376,7 +457,7 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
     const int i = idx & 3;
     const int b = UM == 2 ? idx >> 3 : idx >> 4, aa = UM == 2 ? (idx >> 2) & 1 : (idx >> 2) & 3;
     // (the row index is kept opaque: its products with the 64 constant row offsets would each take a scalar register)
-    int row0 = __builtin_amdgcn_readfirstlane((pblk * 64 + 16 * wt) * PPT);
+    int row0 = __builtin_amdgcn_readfirstlane((pblk * C::TILES + 16 * wt) * PPT);
     asm volatile("" : "+s"(row0));
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(yp[idx]), rsrc_out, ovoff,
                                           (row0 + i * PPT + (int)morton((uint32_t)aa, (uint32_t)b)) * a.Cout * 4, WINO4_STORE_AUX);
@@ -434,15 +515,20 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
       float* red = reinterpret_cast<float*>(wsm + C::OFF_RED);
       s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64);
       s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
-      if (kq == 0) { red[(wt * 32 + 16 * wc + r16) * 2] = s1; red[(wt * 32 + 16 * wc + r16) * 2 + 1] = s2; }
+      if (kq == 0) { red[(wt * C::CH + 16 * wc + r16) * 2] = s1; red[(wt * C::CH + 16 * wc + r16) * 2 + 1] = s2; }
     }
   };
-  auto stats_finish = [&](int blk) {
-    if (a.stats && tid < 32) {
+  // the block's sums over its four 16-tile groups, ((g0 + g1) + g2) + g3 from zero in both block shapes: W = 1 has g0, g1 in
+  // its first pass -- their sum waits in LDS (written and read by the same thread) -- and g2, g3 in the second
+  auto stats_finish = [&](int blk, int pass) {
+    if (a.stats && tid < C::CH) {
       const float* red = reinterpret_cast<const float*>(wsm + C::OFF_RED);
+      float* hold = reinterpret_cast<float*>(wsm + C::OFF_HOLD);
       float t1 = 0.f, t2 = 0.f;
+      if (W && pass) { t1 = hold[tid * 2]; t2 = hold[tid * 2 + 1]; }
 #pragma unroll
-      for (int w = 0; w < 4; ++w) { t1 += red[(w * 32 + tid) * 2]; t2 += red[(w * 32 + tid) * 2 + 1]; }
+      for (int w = 0; w < 4 / NP; ++w) { t1 += red[(w * C::CH + tid) * 2]; t2 += red[(w * C::CH + tid) * 2 + 1]; }
+      if (W && !pass) { hold[tid * 2] = t1; hold[tid * 2 + 1] = t2; return; }
       float* dst = a.stats + ((size_t)blk * a.Cout + n0 + tid) * 2;
       dst[0] = t1; dst[1] = t2;
     }
@@ -453,32 +539,36 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
   // beside the MFMAs: the six columns, then the six rows, the entries stored as they complete.
   auto chunk = [&](int cix, auto stc, auto xfc, auto firstc, auto pendc) {
     constexpr int st = decltype(stc)::value;
-    constexpr bool XF = decltype(xfc)::value != 0, FIRST = decltype(firstc)::value != 0, PEND = decltype(pendc)::value != 0;
+    // the wave's role: 0 LDS-DMA pieces, 1 the input transform (W = 1: rows 0-2 of B^T d), 2 its rows 3-5 (W = 1)
+    constexpr int ROLE = decltype(xfc)::value;
+    constexpr bool XF = ROLE == 1 || ROLE == 2, FIRST = decltype(firstc)::value != 0, PEND = decltype(pendc)::value != 0;
+    using HIc = std::integral_constant<int, ROLE == 2>;
     const int u_ch = cix + 1 < nch ? cix + 1 : 0;
     const bool over = cix + 2 >= nch;
-    const int r_ch = !over ? cix + 2 : (has_next ? cix + 2 - nch : nch - 1);
-    const int r_blk = over && has_next ? blk_nxt : blk_cur;
+    const int r_ch = !over ? cix + 2 : (sb_has ? cix + 2 - nch : nch - 1);
+    const int r_blk = over && sb_has ? sb_nxt : sb_cur;
     // the chunk's LDS-DMA pieces first (they have the whole chunk to land): the next chunk's weights (waves 4-7), then the
     // raw pixels of the chunk after next
     {
       const int usb = u_sbase(u_ch), rso = raw_soff(r_blk, r_ch);
-      if constexpr (!XF) {
+      if constexpr (ROLE == 0) {
 #pragma unroll
         for (int q = 0; q < UPW; ++q) issue_u_piece(usb, st ^ 1, q);
       }
 #pragma unroll
-      for (int q = 0; q < (XF ? RX : RN); ++q) issue_raw_piece(rso, st, q);
+      for (int q = 0; q < (ROLE ? RX : RN); ++q) issue_raw_piece(rso, st, q);
     }
     f32x4 qa[3], qb[3];
     auto load_quad = [&](int q) {
       qa[q % 3] = *reinterpret_cast<lds_cf32x4*>((uintptr_t)(aaddr[st] + (uint32_t)(q * 16)));
       qb[q % 3] = *reinterpret_cast<lds_cf32x4*>((uintptr_t)(baddr[st] + (uint32_t)(q * 16)));
     };
-    float d[36], su[16], tu[30], vu[28];  // (the plain form's patch; behind the upsample: source patch, T s / B^T d, V)
+    float d[36], su[16], tu[30], vu[28], th[18];  // (the plain form's patch; behind the upsample: source patch, T s / B^T d, V; W = 1: half of B^T d)
     load_quad(0);
     load_quad(1);
     if constexpr (XF) {
       if constexpr (UM == 1) load_patch_u(st ^ 1, su);
+      else if constexpr (HALF) load_half(HIc{}, st ^ 1, d);
       else load_patch(st ^ 1, d);
       if constexpr (UM) {
 #pragma unroll
@@ -500,6 +590,10 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
         if (q == 1) xform_u_cols(su, tu);
         if (q == 2) { xform_u_row(0, tu, vu); xform_u_row(1, tu, vu); xform_u_row(2, tu, vu); store_quads_u(st ^ 1, 0, 3, vu); }
         if (q == 3) { xform_u_row(3, tu, vu); xform_u_row(4, tu, vu); store_quads_u(st ^ 1, 3, NQ, vu); }
+      } else if constexpr (XF && HALF) {
+        // pieces: q = 1..3 two columns each, q = 4..6 a row each and the entry quads it completes
+        if (q >= 1 && q <= 3) { xform_half_col(HIc{}, 2 * q - 2, d, th); xform_half_col(HIc{}, 2 * q - 1, d, th); }
+        if (q >= 4 && q <= 6) xform_half_row(HIc{}, st ^ 1, q - 4, th);
       } else if constexpr (XF) {
         // pieces: q = 1..3 two columns each, q = 4..6 two rows each and their three entry quads
         if (q >= 1 && q <= 3) { xform_col(2 * q - 2, d); xform_col(2 * q - 1, d); }
@@ -532,9 +626,10 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
     bool go = true, pend = false;
     using I0c = std::integral_constant<int, 0>;
     using I1c = std::integral_constant<int, 1>;
+    int pass = 0;  // (W = 1: the stage is the item's first / second pass)
     while (go) {
       int fetched = 0;
-      if (dynq && tid == 0 && has_next) fetched = atomicAdd(a.dyn + blockIdx.y, 1);
+      if (dynq && tid == 0 && has_next && pass == NP - 1) fetched = atomicAdd(a.dyn + blockIdx.y, 1);
       if (pend) chunk(0, I0c{}, xfc, I1c{}, I1c{});
       else chunk(0, I0c{}, xfc, I1c{}, I0c{});
       for (int ch = 2; ch < nch; ch += 2) {
@@ -542,8 +637,16 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
         chunk(ch, I0c{}, xfc, I0c{}, I0c{});
       }
       chunk(nch - 1, I1c{}, xfc, I0c{}, I0c{});
-      epilogue(blk_cur);
+      epilogue(sb_cur);
       pend = true;
+      if (W && pass == 0) {
+        // (between the passes: the barrier hands the first pass's BatchNorm partials over, the chunk sequence runs on)
+        __syncthreads();
+        stats_finish(blk_cur, 0);
+        pass = 1;
+        sb_cur = sb_nxt; sb_nxt = blk_nxt * NP; sb_has = has_next;
+        continue;
+      }
       // ONE barrier per tile block behind the epilogue: the per-wave BatchNorm partials are in LDS, the next block's id is
       // handed round (dynamic deal: two slots in turn)
       if (dynq) {
@@ -551,26 +654,34 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
         if (tid == 0) nslot[par] = fetched;
       }
       __syncthreads();
-      stats_finish(blk_cur);
+      stats_finish(blk_cur, pass);
+      pass = 0;
       go = has_next;
       blk_cur = blk_nxt;
       if (dynq) blk_nxt = __builtin_amdgcn_readfirstlane(nslot[par]);
       else blk_nxt = blk_cur + (int)gridDim.x;
       has_next = blk_nxt < a.nblk;
+      sb_cur = blk_cur * NP; sb_nxt = W ? sb_cur + 1 : blk_nxt; sb_has = W ? true : has_next;
     }
 #pragma unroll
     for (int idx = 0; idx < NSTORE; ++idx) store_pending(idx);  // (the last block's)
   };
   // (one instantiation per role: waves 0-3 carry the input transform)
-  if (wave < 4) run(std::integral_constant<int, 1>{});
-  else run(std::integral_constant<int, 0>{});
+  if constexpr (W == 1) {
+    if (wave < 2) run(std::integral_constant<int, 1>{});
+    else if (wave < 4) run(std::integral_constant<int, 2>{});
+    else run(std::integral_constant<int, 0>{});
+  } else {
+    if (wave < 4) run(std::integral_constant<int, 1>{});
+    else run(std::integral_constant<int, 0>{});
+  }
   finish();
 }
 
-template <int L, int UM = 0>
+template <int L, int UM = 0, int W = 0>
 __global__ __launch_bounds__(512) void conv_wino4_kernel(Wino4Args a) {
   extern __shared__ __align__(16) unsigned char wino4_smem[];
-  conv_wino4_body<L, UM>(a, wino4_smem);
+  conv_wino4_body<L, UM, W>(a, wino4_smem);
 }
 
 bool wino4_shape_ok(int64_t M, int Cin, int Cout, int L) {
@@ -580,13 +691,13 @@ bool wino4_shape_ok(int64_t M, int Cin, int Cout, int L) {
   return true;
 }
 
-template <int L, int UM = 0>
+template <int L, int UM = 0, int W = 0>
 int launch_wino4_cfg(const Wino4Args& a, double flops, hipStream_t s) {
-  using C = Wino4Cfg<L, UM>;
-  auto kern = conv_wino4_kernel<L, UM>;
+  using C = Wino4Cfg<L, UM, W>;
+  auto kern = conv_wino4_kernel<L, UM, W>;
   static std::atomic<uint64_t> attr_done{0};
   DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, C::LDS_BYTES));
-  const int ny = a.Cout / 32;
+  const int ny = a.Cout / C::CH;
   int cus = a.cus > 0 ? a.cus : 256;
   if (cus < ny) cus = ny;
   if (cus > 256) cus = 256;
@@ -602,12 +713,14 @@ int launch_wino4_cfg(const Wino4Args& a, double flops, hipStream_t s) {
 
 bool conv_wino4_shape(int64_t M, int Cin, int Cout, int L) { return wino4_shape_ok(M, Cin, Cout, L); }
 
+bool conv_wino4_block64_shape(int64_t M, int Cin, int Cout, int L) { return wino4_shape_ok(M, Cin, Cout, L) && Cout % 64 == 0; }
+
 int conv_wino4_stats_blocks(int64_t M) { return (int)(M / 1024); }
 
 // a.wp must be the F(4x4, 3x3) pack of a PackJob with wino = 2 ([Cin / 4][Cout / 32][4][32][36] floats: wino4_pack_entry)
 int launch_conv_wino4(const ConvArgs& a, hipStream_t s) {
   DVG_REQUIRE(wino4_shape_ok(a.M, a.Cin, a.Cout, a.L) && a.ntaps == 9 && !a.ups && !a.poolsum && !a.fold && a.wino_um >= 0 &&
-                  a.wino_um <= 2 && (a.wino_um == 0 || a.L <= 3),
+                  a.wino_um <= 2 && (a.wino_um == 0 || a.L <= 3) && (!a.wino4_block64 || !a.wino_um),
               "conv_wino4: unsupported launch (M=%lld Cin=%d Cout=%d L=%d um=%d)", (long long)a.M, a.Cin, a.Cout, a.L, a.wino_um);
   Wino4Args w;
   w.in = a.in; w.u = a.wp; w.bias = a.bias; w.out = a.out; w.stats = a.stats;
@@ -623,6 +736,14 @@ int launch_conv_wino4(const ConvArgs& a, hipStream_t s) {
     return a.L == 2 ? launch_wino4_cfg<2, 2>(w, flops_u, s) : launch_wino4_cfg<3, 2>(w, flops_u, s);
   }
   const double flops = 2.0 * (double)(a.M / 16) * 36.0 * a.Cin * a.Cout;
+  if (a.wino4_block64) {
+    DVG_REQUIRE(a.Cout % 64 == 0, "conv_wino4: the 64-channel block shape needs Cout %% 64 == 0 (Cout=%d)", a.Cout);
+    switch (a.L) {
+      case 2: return launch_wino4_cfg<2, 0, 1>(w, flops, s);
+      case 3: return launch_wino4_cfg<3, 0, 1>(w, flops, s);
+      default: return launch_wino4_cfg<4, 0, 1>(w, flops, s);
+    }
+  }
   switch (a.L) {
     case 2: return launch_wino4_cfg<2>(w, flops, s);
     case 3: return launch_wino4_cfg<3>(w, flops, s);

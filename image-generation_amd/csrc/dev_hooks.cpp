@@ -32,7 +32,10 @@ extern "C" int dvg_dev_conv_wino(const float* in, const float* w, int mode, floa
   return launch_conv_wino(a, s);
 }
 // The same layer in the Winograd F(4x4,3x3) form (conv_wino4.hip): `u` takes the 36 Cin Cout transformed weights; stats rows =
-// M / 1024.  DVG_E_INVALID when the shape does not qualify (dvg_dev_conv_wino4_shape).
+// M / 1024.  DVG_E_INVALID when the shape does not qualify (dvg_dev_conv_wino4_shape).  The launch stands for the encoder layer
+// of its image side (L = 4, 3, 2: layers 1, 2, 3; mode 0 the forward, 1 the data gradient): with that launch's block-shape bit
+// of dev option enc_wino4_mask set it runs in the 64-channel block shape wherever the shape allows (the product's item-count
+// rule is policy, not shape: conv_plan.cpp).
 extern "C" int dvg_dev_conv_wino4(const float* in, const float* w, int mode, float* u, const float* bias, float* out,
                                   float* stats, int64_t M, int Cin, int Cout, int L, int cus, int um, dvg_stream_t stream) {
   DVG_REQUIRE(in && w && u && out, "dev_conv_wino4: null argument");
@@ -42,6 +45,8 @@ extern "C" int dvg_dev_conv_wino4(const float* in, const float* w, int mode, flo
   a.in = in; a.wp = u; a.bias = bias; a.out = out; a.stats = stats;
   a.M = M; a.Cin = Cin; a.Cout = Cout; a.L = L; a.ntaps = 9; a.ups = 0; a.poolsum = 0;
   a.splitk_ws = nullptr; a.wino_cus = cus; a.wino_um = um;
+  const int64_t mask = opt(OPT_ENC_WINO4_MASK);
+  a.wino4_block64 = um == 0 && L >= 2 && L <= 4 && ((mask >> enc_wino4_block64_bit(5 - L, mode != 0)) & 1) && conv_wino4_block64_shape(M, Cin, Cout, L);
   return launch_conv_wino4(a, s);
 }
 extern "C" int dvg_dev_conv_wino4_shape(int64_t M, int Cin, int Cout, int L) { return conv_wino4_shape(M, Cin, Cout, L) ? 1 : 0; }

@@ -34,12 +34,9 @@ EncPlan enc_plan(int64_t B, int n, int training, const PlanOptions& o) {
   EncPlan p{};
   p.B = B; p.n = n;
   p.l0_fused = o.v[OPT_ENC_L0_FUSED] != 0; p.bn_reduce_pooled = o.v[OPT_ENC_BN_REDUCE_POOLED] != 0;
-  // (a training call's forward runs beside the step's sampler draw, which holds its CUs: the tile blocks are dealt
-  // dynamically, so the grid is sized to the chip and the workgroups that get their CU late, when the draw ends,
-  // take what is left; under option wino_dynamic = 0 -- the static deal, A/B -- a quarter of the chip is left out)
-  p.cus_fwd = (training && o.v[OPT_WINO_DYNAMIC] == 0) ? 192 : 0;
-  p.cus_dgrad = o.v[OPT_ENC_DGRAD_CUS] > 0 ? (int)o.v[OPT_ENC_DGRAD_CUS] : WINO_CUS_ENC_DGRAD;  // (the layer's weight-gradient chain runs beside it on the side stream)
-  p.cus_wgrad = (int)o.v[OPT_ENC_WGRAD_CUS];
+  p.cus_fwd = plan_enc_wino_cus(o, PASS_FWD, training != 0);
+  p.cus_dgrad = plan_enc_wino_cus(o, PASS_DGRAD, true);
+  p.cus_wgrad = plan_enc_wino_cus(o, PASS_WGRAD, true);
   plan_encoder_layers(B, n, training != 0, o, p.conv);
   p.signature = plan_signature(p.conv + 1, 3, o, PlanKey{false, p.l0_fused, training != 0, false});
   const int ch[5] = {1, 32, 64, 128, n};

@@ -33,7 +33,7 @@ const OptDef kDefs[OPT_COUNT] = {
     {"dec_tail_fused", 1, "decoder: 1 = the 8x8x32 stage's BatchNorm / Dropout / LeakyReLU (forward and backward) run inside the 32 -> 1 layer's kernels, its activated map and that map's gradient are never stored (default), 0 = separate passes (rounds 1-2)", true},
     {"wino_dynamic", 1, "Winograd forward / data-gradient launches deal their tile blocks dynamically (an atomic counter per grid row) instead of round-robin: a workgroup that gets its CU late takes fewer blocks (1 default, 0 = the static deal of rounds 3-4)", true},
     {"enc_wino4", 1, "every launch of the Winograd F(4x4,3x3) form -- forward, data gradient and weight gradient, encoder and decoder: 1 (default) the launches that run in the Winograd domain take it where the shape qualifies and their bit of the dev options enc_wino4_mask / dec_wino4_mask is set (36 position GEMMs per 4x4 output tile: 2.25 multiplies per output instead of 4.0; behind the decoder's upsample 25 of the 36), 0 none: the F(2x2,3x3) form everywhere"},
-    {"enc_wino4_mask", 0x13c, "which encoder launches option enc_wino4 covers: bit l-1 the forward of layer l (1..3), bit 2+l its data gradient, bit 5+l its weight gradient (default 0x13c: layer 3's forward, every data gradient, layer 3's weight gradient -- the forwards of layers 1-2 gain nothing inside the step and their 7x float32 noise in front of two more max-pool stages moved the B = 1024 full-size gradient test from 4.6e-3 to 5.4e-3 of its 5e-3 bar; the weight gradients of layers 1-2 are level with the F(2x2,3x3) kernel)", true},
+    {"enc_wino4_mask", 0x14013c, "which encoder launches option enc_wino4 covers: bit l-1 the forward of layer l (1..3), bit 2+l its data gradient, bit 5+l its weight gradient (default 0x13c in these bits: layer 3's forward, every data gradient, layer 3's weight gradient -- the forwards of layers 1-2 gain nothing inside the step and their 7x float32 noise in front of two more max-pool stages moved the B = 1024 full-size gradient test from 4.6e-3 to 5.4e-3 of its 5e-3 bar; the weight gradients of layers 1-2 are level with the F(2x2,3x3) kernel); bits 16-21: the BLOCK SHAPE of a forward / data-gradient launch that takes the form -- bit 15+l layer l's forward, bit 18+l its data gradient: set, the launch runs work items of 64 tiles x 64 output channels as two passes of 32 tiles x 64 channels (half the raw-pixel pieces, input transforms and transformed-entry writes per matrix operation, the same bits) where Cout % 64 == 0 and every workgroup of its CU budget gets two items or more; clear, blocks of 64 tiles x 32 channels (the A/B reference); default bits 18 and 20: layer 3's forward and layer 2's data gradient, each measured faster inside the c3 step -- at c3 no other launch of the form qualifies", true},
     {"enc_dgrad_cus", 0, "CUs the encoder's Winograd data-gradient launches are sized for (0: the measured constant of conv.h)", true},
     {"enc_wgrad_cus", 0, "CUs the encoder's Winograd weight-gradient launches are sized for (0: the measured constant of conv.h)", true},
     {"dec_wino4_mask", 0x2, "which of the decoder's Winograd launches behind the upsample take the F(4x4,3x3) form with 25 of 36 positions (option enc_wino4 != 0): bit 0 / 1 the forward of the 128 -> 64 / 64 -> 32 layer (bit 0 off: with it the full-size decoder's reconstruction is 2.97e-6 from float64, the bar is 2e-6), bit 2 / 3 their data gradients", true},

@@ -67,7 +67,10 @@ int dvg_dev_gibbs_exchange_plan(int n, int n_colours, const int32_t *class_ptr, 
 int dvg_dev_conv_wino4(const float *in, const float *w, int mode, float *u, const float *bias, float *out, float *stats,
                        int64_t M, int Cin, int Cout, int L, int cus, int um, dvg_stream_t stream);
 /* (um = 1: Upsample(x2) + 3x3 forward, `in` = the source map ([M / 4][Cin]), 25 of 36 positions; um = 2: its data gradient,
- * `in` = the fine-grid gradient, `out` = the source map's gradient ([M / 4][Cout])) */
+ * `in` = the fine-grid gradient, `out` = the source map's gradient ([M / 4][Cout]))
+ * (um = 0: the launch stands for the encoder layer of its image side -- L = 4, 3, 2: layers 1, 2, 3; mode 0 the forward, 1 the
+ * data gradient -- and follows that launch's block-shape bit of dev option enc_wino4_mask (bits 16-21): set and Cout % 64 == 0,
+ * it runs blocks of 32 tiles x 64 output channels instead of 64 x 32; same bits) */
 int dvg_dev_conv_wino4_shape(int64_t M, int Cin, int Cout, int L);
 /* ... and the layer's weight gradient in that form (csrc/conv_wino4_wgrad.hip): slabs of dvg_dev_wino4_wgrad_slab_floats()
  * floats (0 = the shape does not qualify); cus: CUs the grid is sized for (0 = the training step's budget). */
