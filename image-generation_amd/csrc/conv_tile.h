@@ -1,4 +1,5 @@
-// MFMA tile helpers shared by the convolution translation units (conv_igemm.hip, conv_wgrad.hip).
+// MFMA tile helpers shared by the convolution translation units (conv_igemm.hip, conv_wgrad.hip, and through
+// conv_wino_common.h the four Winograd ones: conv_wino.hip, conv_wino4.hip, conv_wino_wgrad.hip, conv_wino4_wgrad.hip).
 #pragma once
 #include "conv.h"
 

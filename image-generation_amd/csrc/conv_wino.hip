@@ -18,23 +18,17 @@
 // chunk three LDS images: the raw input pixels of the block's images [pixel][KC] and the transformed weights
 // [k][co][16] arrive by LDS-DMA, the transformed input [k][quad][16] is written by the block itself (each thread
 // transforms one patch per chunk, under the previous chunk's MFMAs).  Two stages of each, one barrier per chunk, and
-// the chunk sequence runs on across the tile blocks a workgroup owns (persistent grid), so the staging pipeline is
-// filled once per workgroup, not once per tile.  A 64-byte entry (16 transform positions of one (k, row)) is read as
-// ds_read_b128 whose 16-byte slots are XOR-ed with bits 2-3 of the row: conflict-free for the 16 lanes of a read pass.
+// the chunk sequence runs on across the tile blocks a workgroup owns (persistent grid; its size: conv_wino_common.h), so
+// the staging pipeline is filled once per workgroup, not once per tile.  A 64-byte entry (16 transform positions of one
+// (k, row)) is read as ds_read_b128 whose 16-byte slots are XOR-ed with bits 2-3 of the row: conflict-free for the 16
+// lanes of a read pass.
 // (Rounds 3-4 ran one wave per SIMD with all 16 positions -- 256 accumulator registers -- and left the matrix pipe idle
 // for every exposed wait: deleted in round 5, see DESIGN.md.)
 #include <atomic>
 
-#include "conv.h"
-#include "conv_tile.h"
+#include "conv_wino_common.h"
 
 namespace dvg {
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-typedef __attribute__((address_space(3))) const f32x4 lds_cf32x4;
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-typedef __attribute__((address_space(3))) const float lds_cf32;
 
 struct WinoArgs {
   const float* in;    // [4 tiles][Cin]  (Morton pixel order: quad t = rows 4t .. 4t+3)
@@ -585,10 +579,7 @@ __global__ __launch_bounds__(256) void wino_weight_pack_kernel(const float* __re
 }
 
 int launch_wino_weight_pack(const float* w, const WeightMap& map, float* u, hipStream_t s) {
-  int64_t gx = ceil_div((int64_t)map.Ca * map.Cb, 256);
-  if (gx > 1024) gx = 1024;
-  DVG_LAUNCH(K_WEIGHT_PACK, wino_weight_pack_kernel, dim3((unsigned)gx), dim3(256), 0, s, w, map, u);
-  return DVG_OK;
+  return launch_wino_pack(wino_weight_pack_kernel, w, map, u, s);
 }
 
 // Which tile shape serves a layer: 64 quads x 64 channels (8-channel chunks) or 128 quads x 32 channels (4-channel chunks)
@@ -618,20 +609,11 @@ static int launch_wino8_cfg(const WinoArgs& a, double flops, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
   DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, C::LDS_BYTES));
   const int ny = a.Cout / C::CB;
-  int cus = a.cus > 0 ? a.cus : 256;
-  if (cus < ny) cus = ny;
-  if (cus > 256) cus = 256;
-  int gx = cus / ny;
-  if (gx < 1) gx = 1;
-  if (gx > a.nblk) gx = a.nblk;
+  // (the dynamic deal needs a next chunk to prefetch across the block boundary and a counter per column block)
+  const WinoGrid g = wino_persistent_grid(a.cus, ny, a.nblk, a.Cin / KC >= 2 && ny <= 16);
   WinoArgs ad = a;
-  // (the dynamic deal hands every workgroup TWO blocks up front: a launch of fewer than about three rounds keeps the
-  // static deal, where the grid is shrunk to its round count -- an evaluation forward at the 256-block threshold would
-  // otherwise be done by half the grid in two rounds.  Dynamic launches of one device must be ordered on ONE stream:
-  // the counters are a per-device pool that the launch's last workgroup re-zeroes.)
-  ad.dyn = (opt(OPT_WINO_DYNAMIC) != 0 && a.Cin / KC >= 2 && ny <= 16 && a.nblk >= 3 * gx) ? dyn_tile_counters() : nullptr;
-  if (!ad.dyn) gx = (a.nblk + (a.nblk + gx - 1) / gx - 1) / ((a.nblk + gx - 1) / gx);
-  DVG_LAUNCH_WORK_SHARE(K_IGEMM_WINO, flops, (float)(gx * ny > 256 ? 256 : gx * ny) / 256.0f, kern, dim3((unsigned)gx, (unsigned)ny), dim3(512), C::LDS_BYTES, s, ad);
+  ad.dyn = g.dyn;
+  DVG_LAUNCH_WORK_SHARE(K_IGEMM_WINO, flops, wino_work_share((unsigned)(g.gx * ny)), kern, dim3((unsigned)g.gx, (unsigned)ny), dim3(512), C::LDS_BYTES, s, ad);
   return DVG_OK;
 }
 

@@ -4,7 +4,7 @@
 //   A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
 //   G   = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]   (conv.h: wino4_pack_entry)
 #pragma once
-#include "conv_tile.h"
+#include "conv_wino_common.h"
 
 namespace dvg {
 
@@ -22,6 +22,34 @@ __device__ __forceinline__ void wino4_in6(float& x0, float& x1, float& x2, float
     t5 = __builtin_fmaf(4.f, x1, __builtin_fmaf(-5.f, x3, x5));
   }
   x0 = t0; x1 = p + q; x2 = p - q; x3 = __builtin_fmaf(2.f, s, r); x4 = __builtin_fmaf(-2.f, s, r); x5 = t5;
+}
+
+// The whole 6x6 patch d of a thread, in place: V = B^T d B as six columns, then six rows; ZE: a 4x4 image, whose patch has the
+// zero padding as its ring 0 / 5 (a zero column stays zero)
+template <bool ZE>
+__device__ __forceinline__ void wino4_zero_ring(float (&d)[36]) {
+  if constexpr (ZE) {
+#pragma unroll
+    for (int e = 0; e < 36; ++e)
+      if (e / 6 == 0 || e / 6 == 5 || e % 6 == 0 || e % 6 == 5) d[e] = 0.f;
+  }
+}
+template <bool ZE>
+__device__ __forceinline__ void wino4_patch_col(int j, float (&d)[36]) {  // B^T d, column j
+  if (ZE && (j == 0 || j == 5)) return;
+  wino4_in6<ZE>(d[j], d[6 + j], d[12 + j], d[18 + j], d[24 + j], d[30 + j]);
+}
+template <bool ZE>
+__device__ __forceinline__ void wino4_patch_row(int i, float (&d)[36]) {  // (.) B, row i
+  wino4_in6<ZE>(d[6 * i], d[6 * i + 1], d[6 * i + 2], d[6 * i + 3], d[6 * i + 4], d[6 * i + 5]);
+}
+// entry quads q0 .. q0 + 2 (positions 4 q0 .. 4 q0 + 11: two transformed rows) of the entry at LDS address `entry`
+__device__ __forceinline__ void wino4_store_quads(uint32_t entry, int q0, const float (&d)[36]) {
+#pragma unroll
+  for (int q = q0; q < q0 + 3; ++q) {
+    const f32x4 o = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
+    *reinterpret_cast<lds_f32x4*>((uintptr_t)(entry + (uint32_t)(q * 16))) = o;
+  }
 }
 
 // Half of it: rows 0-2 (HI = 0: from x0 .. x4) or rows 3-5 (HI = 1: from x1 .. x5) of B^T x, the same operations per row

@@ -29,26 +29,17 @@
 // base register + an immediate), the transformed weights [k][co][36] (LDS-DMA of a contiguous 18 KiB piece of the
 // pack), the transformed input [k][tile][36], written by waves 0-3 (a patch per thread and chunk, under the MFMAs).
 // Two stages of each, one barrier per chunk, the chunk sequence runs on across the tile blocks a workgroup owns
-// (persistent grid, dynamic deal: conv_wino.hip).
+// (persistent grid: its size and the dynamic-deal decision are wino_persistent_grid of conv_wino_common.h, the deal is
+// described in conv_wino.hip).
 //
 // Raw pieces, patch transforms and transformed-entry writes scale with the TILES of a stage, the matrix work with tiles x
 // channels: the second block shape (Wino4Cfg, W = 1: work items of 64 tiles x 64 channels as two passes of 32 tiles x 64
 // channels) halves the former per MFMA and computes the same bits.  Which launches take it: conv_plan.cpp.
 #include <atomic>
 
-#include "conv.h"
-#include "conv_tile.h"
 #include "conv_wino4.h"
 
 namespace dvg {
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-typedef __attribute__((address_space(3))) const f32x4 lds_cf32x4;
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
-typedef __attribute__((address_space(3))) const float lds_cf32;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) f32x2 lds_f32x2;
 
 struct Wino4Args {
   const float* in;    // [16 tiles][Cin]  (Morton pixel order: tile t = rows 16t .. 16t+15)
@@ -269,26 +260,9 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
       for (int j = I0; j < I1; ++j) {
         d[i * 6 + j] = *reinterpret_cast<lds_cf32*>((uintptr_t)(rbase[rs] + (uint32_t)(C::poff(i, j) * 16)));
       }
-    if constexpr (L == 2) {
-#pragma unroll
-      for (int e = 0; e < 36; ++e)
-        if (e / 6 == 0 || e / 6 == 5 || e % 6 == 0 || e % 6 == 5) d[e] = 0.f;
-    }
+    wino4_zero_ring<L == 2>(d);
   };
-  auto xform_col = [&](int j, float (&d)[36]) {  // B^T d, column j
-    if (L == 2 && (j == 0 || j == 5)) return;    // (a zero column stays zero)
-    wino4_in6<L == 2>(d[j], d[6 + j], d[12 + j], d[18 + j], d[24 + j], d[30 + j]);
-  };
-  auto xform_row = [&](int i, float (&d)[36]) {  // (.) B, row i
-    wino4_in6<L == 2>(d[6 * i], d[6 * i + 1], d[6 * i + 2], d[6 * i + 3], d[6 * i + 4], d[6 * i + 5]);
-  };
-  auto store_quads = [&](int vs, int q0, const float (&d)[36]) {  // entries 4 q0 .. 4 q0 + 11 (two transformed rows)
-#pragma unroll
-    for (int q = q0; q < q0 + 3; ++q) {
-      const f32x4 o = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-      *reinterpret_cast<lds_f32x4*>((uintptr_t)(vst[vs] + (uint32_t)(q * 16))) = o;
-    }
-  };
+  // (the whole patch's columns, rows and entry stores: wino4_patch_col, wino4_patch_row, wino4_store_quads of conv_wino4.h)
 
   // W = 1, half a patch (HI: rows 3-5 of B^T d): t[3][6] = those rows, v[18] = their entries (positions 18 HI ..), written
   // as they complete: the straddling pair 16-17 / 18-19 as a ds_write_b64
@@ -302,11 +276,7 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
       for (int j = I0; j < I1; ++j) {
         d[i * 6 + j] = *reinterpret_cast<lds_cf32*>((uintptr_t)(rbase[rs] + (uint32_t)(C::poff(i, j) * 16)));
       }
-    if constexpr (L == 2) {
-#pragma unroll
-      for (int e = 0; e < 36; ++e)
-        if (e / 6 == 0 || e / 6 == 5 || e % 6 == 0 || e % 6 == 5) d[e] = 0.f;
-    }
+    wino4_zero_ring<L == 2>(d);
   };
   auto xform_half_col = [&](auto hic, int j, const float (&d)[36], float (&t)[18]) {
     if (L == 2 && (j == 0 || j == 5)) { t[j] = t[6 + j] = t[12 + j] = 0.f; return; }
@@ -430,10 +400,10 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
       float d[36];
       load_patch(0, d);
 #pragma unroll
-      for (int j = 0; j < 6; ++j) xform_col(j, d);
+      for (int j = 0; j < 6; ++j) wino4_patch_col<L == 2>(j, d);
 #pragma unroll
-      for (int i = 0; i < 6; ++i) xform_row(i, d);
-      store_quads(0, 0, d); store_quads(0, 3, d); store_quads(0, 6, d);
+      for (int i = 0; i < 6; ++i) wino4_patch_row<L == 2>(i, d);
+      wino4_store_quads(vst[0], 0, d); wino4_store_quads(vst[0], 3, d); wino4_store_quads(vst[0], 6, d);
     }
   }
   __syncthreads();
@@ -596,8 +566,8 @@ __device__ __forceinline__ void conv_wino4_body(const Wino4Args& a, unsigned cha
         if (q >= 4 && q <= 6) xform_half_row(HIc{}, st ^ 1, q - 4, th);
       } else if constexpr (XF) {
         // pieces: q = 1..3 two columns each, q = 4..6 two rows each and their three entry quads
-        if (q >= 1 && q <= 3) { xform_col(2 * q - 2, d); xform_col(2 * q - 1, d); }
-        if (q >= 4 && q <= 6) { xform_row(2 * q - 8, d); xform_row(2 * q - 7, d); store_quads(st ^ 1, 3 * (q - 4), d); }
+        if (q >= 1 && q <= 3) { wino4_patch_col<L == 2>(2 * q - 2, d); wino4_patch_col<L == 2>(2 * q - 1, d); }
+        if (q >= 4 && q <= 6) { wino4_patch_row<L == 2>(2 * q - 8, d); wino4_patch_row<L == 2>(2 * q - 7, d); wino4_store_quads(vst[st ^ 1], 3 * (q - 4), d); }
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -698,16 +668,11 @@ int launch_wino4_cfg(const Wino4Args& a, double flops, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
   DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, C::LDS_BYTES));
   const int ny = a.Cout / C::CH;
-  int cus = a.cus > 0 ? a.cus : 256;
-  if (cus < ny) cus = ny;
-  if (cus > 256) cus = 256;
-  int gx = cus / ny;
-  if (gx < 1) gx = 1;
-  if (gx > a.nblk) gx = a.nblk;
+  // (every shape may take the dynamic deal: wino4_shape_ok implies two or more chunks and at most 16 column blocks)
+  const WinoGrid g = wino_persistent_grid(a.cus, ny, a.nblk, true);
   Wino4Args ad = a;
-  ad.dyn = (opt(OPT_WINO_DYNAMIC) != 0 && a.nblk >= 3 * gx) ? dyn_tile_counters() : nullptr;
-  if (!ad.dyn) gx = (a.nblk + (a.nblk + gx - 1) / gx - 1) / ((a.nblk + gx - 1) / gx);
-  DVG_LAUNCH_WORK_SHARE(K_IGEMM_WINO4, flops, (float)(gx * ny > 256 ? 256 : gx * ny) / 256.0f, kern, dim3((unsigned)gx, (unsigned)ny), dim3(512), C::LDS_BYTES, s, ad);
+  ad.dyn = g.dyn;
+  DVG_LAUNCH_WORK_SHARE(K_IGEMM_WINO4, flops, wino_work_share((unsigned)(g.gx * ny)), kern, dim3((unsigned)g.gx, (unsigned)ny), dim3(512), C::LDS_BYTES, s, ad);
   return DVG_OK;
 }
 
@@ -757,10 +722,7 @@ __global__ __launch_bounds__(256) void wino4_weight_pack_kernel(const float* __r
 }
 
 int launch_wino4_weight_pack(const float* w, const WeightMap& map, float* u, hipStream_t s, int ups) {
-  int64_t gx = ceil_div((int64_t)map.Ca * map.Cb, 256);
-  if (gx > 1024) gx = 1024;
-  DVG_LAUNCH(K_WEIGHT_PACK, wino4_weight_pack_kernel, dim3((unsigned)gx), dim3(256), 0, s, w, map, u, ups);
-  return DVG_OK;
+  return launch_wino_pack(wino4_weight_pack_kernel, w, map, u, s, ups);
 }
 
 }  // namespace dvg

@@ -19,15 +19,9 @@
 // The loads of a chunk are issued behind the transform of the chunk before it: a chunk and a half ahead of their use.
 #include <atomic>
 
-#include "conv.h"
-#include "conv_tile.h"
 #include "conv_wino4.h"
 
 namespace dvg {
-
-typedef __attribute__((address_space(3))) unsigned char lds_byte_t;
-typedef __attribute__((address_space(3))) const f32x4 lds_cf32x4;
-typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
 
 struct Wino4WgradArgs {
   const float* in;   // [16 tiles][Cin]  (Morton pixel order)
@@ -169,32 +163,14 @@ __global__ __launch_bounds__(512) void conv_wino4_wgrad_kernel(Wino4WgradArgs a)
           }
       }
     };
-    auto zero_ring = [&]() {
-      if constexpr (L == 2) {
-#pragma unroll
-        for (int e = 0; e < 36; ++e)
-          if (e / 6 == 0 || e / 6 == 5 || e % 6 == 0 || e % 6 == 5) d[e] = 0.f;
-      }
-    };
-    auto xform_col = [&](int j) {
-      if (L == 2 && (j == 0 || j == 5)) return;
-      wino4_in6<L == 2>(d[j], d[6 + j], d[12 + j], d[18 + j], d[24 + j], d[30 + j]);
-    };
-    auto xform_row = [&](int i) { wino4_in6<L == 2>(d[6 * i], d[6 * i + 1], d[6 * i + 2], d[6 * i + 3], d[6 * i + 4], d[6 * i + 5]); };
-    auto store_quads = [&](int vs, int q0) {
-#pragma unroll
-      for (int q = q0; q < q0 + 3; ++q) {
-        const f32x4 o = {d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]};
-        *reinterpret_cast<lds_f32x4*>((uintptr_t)(vst[vs] + (uint32_t)(q * 16))) = o;
-      }
-    };
+    constexpr bool ZE = L == 2;  // (the forward's whole-patch transform: conv_wino4.h)
     auto xform_all = [&](int vs) {
-      zero_ring();
+      wino4_zero_ring<ZE>(d);
 #pragma unroll
-      for (int j = 0; j < 6; ++j) xform_col(j);
+      for (int j = 0; j < 6; ++j) wino4_patch_col<ZE>(j, d);
 #pragma unroll
-      for (int i = 0; i < 6; ++i) xform_row(i);
-      store_quads(vs, 0); store_quads(vs, 3); store_quads(vs, 6);
+      for (int i = 0; i < 6; ++i) wino4_patch_row<ZE>(i, d);
+      wino4_store_quads(vst[vs], 0, d); wino4_store_quads(vst[vs], 3, d); wino4_store_quads(vst[vs], 6, d);
     };
     // prologue: chunk 0 transformed, chunk 1 loaded
     load_patch(chunk0);
@@ -207,9 +183,9 @@ __global__ __launch_bounds__(512) void conv_wino4_wgrad_kernel(Wino4WgradArgs a)
       mfma_chunk(stc, [&](int q) {
         // the NEXT chunk's patch (loaded behind the previous transform): columns beside quads 3-5, rows and stores 6-8
         if (!more) return;
-        if (q == 3) zero_ring();
-        if (q >= 3 && q <= 5) { xform_col(2 * q - 6); xform_col(2 * q - 5); }
-        if (q >= 6) { xform_row(2 * q - 12); xform_row(2 * q - 11); store_quads(st ^ 1, 3 * (q - 6)); }
+        if (q == 3) wino4_zero_ring<ZE>(d);
+        if (q >= 3 && q <= 5) { wino4_patch_col<ZE>(2 * q - 6, d); wino4_patch_col<ZE>(2 * q - 5, d); }
+        if (q >= 6) { wino4_patch_row<ZE>(2 * q - 12, d); wino4_patch_row<ZE>(2 * q - 11, d); wino4_store_quads(vst[st ^ 1], 3 * (q - 6), d); }
       });
       if (c + 2 < nchunks) load_patch(chunk0 + c + 2);
       __syncthreads();
@@ -244,13 +220,7 @@ __global__ __launch_bounds__(512) void conv_wino4_wgrad_kernel(Wino4WgradArgs a)
     // columns: (A dY)[xi][b] over the tile's rows a; rows: (.) A^T over b
     auto xf_col = [&](int b) { wino4_dy6(z[b], z[6 + b], z[12 + b], z[18 + b], z[24 + b], z[30 + b]); };
     auto xf_row = [&](int i) { wino4_dy6(z[6 * i], z[6 * i + 1], z[6 * i + 2], z[6 * i + 3], z[6 * i + 4], z[6 * i + 5]); };
-    auto store_quads = [&](int vs, int q0) {
-#pragma unroll
-      for (int q = q0; q < q0 + 3; ++q) {
-        const f32x4 o = {z[4 * q], z[4 * q + 1], z[4 * q + 2], z[4 * q + 3]};
-        *reinterpret_cast<lds_f32x4*>((uintptr_t)(zst[vs] + (uint32_t)(q * 16))) = o;
-      }
-    };
+    auto store_quads = [&](int vs, int q0) { wino4_store_quads(zst[vs], q0, z); };
     load_tile(chunk0);
 #pragma unroll
     for (int b = 0; b < 4; ++b) xf_col(b);
@@ -293,27 +263,8 @@ __global__ __launch_bounds__(512) void conv_wino4_wgrad_kernel(Wino4WgradArgs a)
   for (int p = 0; p < 36; ++p) *reinterpret_cast<f32x4*>(dst + (size_t)p * a.Cin * a.Cout) = acc[p];
 }
 
-// (1) every (position, ci, co) element summed over the slabs by 8 lanes (strided over the slabs, fixed-shape shuffle tree:
-// deterministic), in place into slab 0 (conv_wino_wgrad.hip: the same two-pass form)
-__global__ __launch_bounds__(256) void wino4_wgrad_slabsum_kernel(float* __restrict__ slabs, int nslabs, int64_t total) {
-  const int sub = threadIdx.x & 7;
-  for (int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3; e < total; e += ((int64_t)gridDim.x * 256) >> 3) {
-    float s = 0.f;
-    for (int k0 = sub; k0 < nslabs; k0 += 64) {  // eight loads in flight, summed in the same order
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = k0 + 8 * u < nslabs ? slabs[(size_t)(k0 + 8 * u) * total + e] : 0.f;
-#pragma unroll
-      for (int u = 0; u < 8; ++u) if (k0 + 8 * u < nslabs) s += v[u];
-    }
-    s += __shfl_xor(s, 1, 64);
-    s += __shfl_xor(s, 2, 64);
-    s += __shfl_xor(s, 4, 64);
-    if (sub == 0) slabs[e] = s;
-  }
-}
-
-// (2) dg = G^T dU G per channel pair from slab 0, written in the checkpoint layout
+// The slabs are reduced in the two passes of conv_wino_wgrad.hip: (1) the slab sum in place into slab 0
+// (launch_wino_wgrad_slabsum), (2) dg = G^T dU G per channel pair from slab 0, written in the checkpoint layout
 __global__ __launch_bounds__(256) void wino4_wgrad_reduce_kernel(const float* __restrict__ du, WeightMap map, float* __restrict__ grad_w) {
   const int64_t pairs = (int64_t)map.Ca * map.Cb;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < pairs; e += (int64_t)gridDim.x * 256) {
@@ -355,13 +306,9 @@ Wino4WgradGeom wino4_wgrad_geom(int64_t M, int Cin, int Cout, int cus) {
   g.cfg = Cin % 64 == 0 ? 0 : 1;  // 0: 64 x 32 channel tile, 1: 32 x 64
   g.nx = Cin / (g.cfg == 0 ? 64 : 32);
   g.ny = Cout / (g.cfg == 0 ? 32 : 64);
-  const int chunks = (int)(M / 64);
-  // one workgroup per CU of the budget, every workgroup at least 8 chunks deep; the last slab may be shorter
-  int want = cus / (g.nx * g.ny);
-  if (want < 1) want = 1;
-  if (want > chunks / 8) want = chunks / 8 > 0 ? chunks / 8 : 1;
-  g.per = (chunks + want - 1) / want;
-  g.nsplit = (chunks + g.per - 1) / g.per;
+  const WinoSlabs sl = wino_slab_split((int)(M / 64), g.nx * g.ny, cus);
+  g.per = sl.per;
+  g.nsplit = sl.nsplit;
   return g;
 }
 
@@ -371,8 +318,7 @@ int launch_wino4_wgrad_cfg(const Wino4WgradArgs& a, double flops, dim3 grid, hip
   auto kern = conv_wino4_wgrad_kernel<L, WA, WB>;
   static std::atomic<uint64_t> attr_done{0};
   DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, C::LDS_BYTES));
-  const unsigned wgs = grid.x * grid.y * grid.z;
-  DVG_LAUNCH_WORK_SHARE(K_WGRAD_WINO4, flops, (float)(wgs > 256u ? 256u : wgs) / 256.0f, kern, grid, dim3(512), C::LDS_BYTES, s, a);
+  DVG_LAUNCH_WORK_SHARE(K_WGRAD_WINO4, flops, wino_work_share(grid.x * grid.y * grid.z), kern, grid, dim3(512), C::LDS_BYTES, s, a);
   return DVG_OK;
 }
 
@@ -399,11 +345,7 @@ int launch_conv_wino4_wgrad(const float* in, const float* dy, int64_t M, int Cin
   else rc = L == 2 ? launch_wino4_wgrad_cfg<2, 2, 4>(a, flops, grid, s) : L == 3 ? launch_wino4_wgrad_cfg<3, 2, 4>(a, flops, grid, s) : launch_wino4_wgrad_cfg<4, 2, 4>(a, flops, grid, s);
   DVG_TRY(rc);
   const int64_t pairs = (int64_t)Cin * Cout;
-  if (g.nsplit > 1) {
-    int64_t blocks = (36 * pairs * 8 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    DVG_LAUNCH(K_WGRAD_REDUCE, wino4_wgrad_slabsum_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slabs, g.nsplit, 36 * pairs);
-  }
+  if (g.nsplit > 1) DVG_TRY(launch_wino_wgrad_slabsum(slabs, g.nsplit, pairs, 36, 0, s));  // (one slab: it is the sum)
   DVG_LAUNCH(K_WGRAD_REDUCE, wino4_wgrad_reduce_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, (const float*)slabs, map, grad_w);
   return DVG_OK;
 }

@@ -21,10 +21,10 @@
 // Nine MFMAs per k-step instead of the folded form's sixteen (class, tap) pairs, from a 3x3 SOURCE patch.
 // K order: a thread keeps ONE quad position (its 16 patch offsets are constants of the kernel) and walks the images, so
 // the split over workgroups is (position group) x (image range); slabs are reduced in fixed order (no float atomics).
+#include <atomic>
 #include <type_traits>
 
-#include "conv.h"
-#include "conv_tile.h"
+#include "conv_wino_common.h"
 
 namespace dvg {
 
@@ -59,14 +59,10 @@ struct WinoWgrad8Cfg {
 template <int WA, int WB, bool UPS = false>
 __global__ __launch_bounds__(512) void conv_wino_wgrad8_kernel(WinoWgradArgs a) {
   using C = WinoWgrad8Cfg<WA, WB>;
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   constexpr int NE = UPS ? 9 : 16;  // raw rows of an input item: the 3x3 source patch, or the 4x4 patch
   constexpr int CIB = C::CIB, COB = C::COB, QC = C::QC, NQ = C::NQ, NV = C::NV, NZ = C::NZ;
-  typedef __attribute__((address_space(3))) unsigned char lds_byte;
-  typedef __attribute__((address_space(3))) const f32x4 lds_cf32x4;
-  typedef __attribute__((address_space(3))) f32x4 lds_f32x4;
   extern __shared__ __align__(16) unsigned char wwg_smem[];
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_byte*)wwg_smem;
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_byte_t*)wwg_smem;
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, c = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ps = wave >> 2, wr = wave & 3;  // position set (transform rows 2 ps, 2 ps + 1); place of the pair in the tile
@@ -341,12 +337,15 @@ __global__ __launch_bounds__(512) void conv_wino_wgrad8_kernel(WinoWgradArgs a) 
 // item per channel pair had 64 workgroups for the decoder's 64 -> 32 layer, whose 512 slabs it then read for 405 us
 // in-situ, with the next layer's weight gradient waiting for the slab buffer behind it.  (2) dg = G^T dU G per channel
 // pair from slab 0, written in the checkpoint layout.  G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1].
-__global__ __launch_bounds__(256) void wino_wgrad_slabsum_kernel(float* __restrict__ slabs, int nslabs, int64_t pairs, int ups) {
-  const int64_t total = 16 * pairs;
+// Pass (1) serves the F(4x4) weight gradient too (conv_wino4_wgrad.hip: 36 positions per channel pair).
+__global__ __launch_bounds__(256) void wino_wgrad_slabsum_kernel(float* __restrict__ slabs, int nslabs, int64_t pairs, int positions, int ups) {
+  const int64_t total = positions * pairs;
   const int sub = threadIdx.x & 7;
   for (int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3; e < total; e += ((int64_t)gridDim.x * 256) >> 3) {
-    const int p = (int)(e / pairs);
-    if (ups && ((p >> 2) == 2 || (p & 3) == 2)) continue;  // (upsampled layers: identically zero, never written)
+    if (ups) {  // (upsampled layers, 16 positions: the vanishing ones are identically zero, never written)
+      const int p = (int)(e / pairs);
+      if ((p >> 2) == 2 || (p & 3) == 2) continue;
+    }
     float s = 0.f;
     for (int k0 = sub; k0 < nslabs; k0 += 64) {  // eight loads in flight, summed in the same order
       float v[8];
@@ -360,6 +359,13 @@ __global__ __launch_bounds__(256) void wino_wgrad_slabsum_kernel(float* __restri
     s += __shfl_xor(s, 4, 64);
     if (sub == 0) slabs[e] = s;
   }
+}
+
+int launch_wino_wgrad_slabsum(float* slabs, int nslabs, int64_t pairs, int positions, int ups, hipStream_t s) {
+  int64_t blocks = (positions * pairs * 8 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  DVG_LAUNCH(K_WGRAD_REDUCE, wino_wgrad_slabsum_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slabs, nslabs, pairs, positions, ups);
+  return DVG_OK;
 }
 
 __global__ __launch_bounds__(256) void wino_wgrad_reduce_kernel(const float* __restrict__ du, WeightMap map, float* __restrict__ grad_w, int ups) {
@@ -411,11 +417,7 @@ static WinoWgradGeom wino_wgrad_geom(int64_t M, int Cin, int Cout, int L, int cu
   const int ipc = qi >= nq ? 1 : nq / qi;
   const int n_img = (int)(M >> (2 * L));
   const int ichunks = (n_img + ipc - 1) / ipc;
-  // one workgroup per CU of the budget; every workgroup at least 8 chunks deep
-  int want = cus / (g.tiles * g.pgn);
-  if (want < 1) want = 1;
-  if (want > ichunks / 8) want = ichunks / 8 > 0 ? ichunks / 8 : 1;
-  g.isplit = want;
+  g.isplit = wino_slab_split(ichunks, g.tiles * g.pgn, cus).want;  // (the kernel takes its own share of the image chunks)
   g.nslabs = g.pgn * g.isplit * g.wk;
   return g;
 }
@@ -429,9 +431,9 @@ template <int WA, int WB, bool UPS>
 static int launch_wino_wgrad8_cfg(const WinoWgradArgs& a, double flops, dim3 grid, hipStream_t s) {
   using C = WinoWgrad8Cfg<WA, WB>;
   auto kern = conv_wino_wgrad8_kernel<WA, WB, UPS>;
-  DVG_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
-  const unsigned wgs = grid.x * grid.y * grid.z;  // (one workgroup per CU)
-  DVG_LAUNCH_WORK_SHARE(K_WGRAD_WINO, flops, (float)(wgs > 256u ? 256u : wgs) / 256.0f, kern, grid, dim3(512), C::LDS_BYTES, s, a);
+  static std::atomic<uint64_t> attr_done{0};
+  DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, C::LDS_BYTES));
+  DVG_LAUNCH_WORK_SHARE(K_WGRAD_WINO, flops, wino_work_share(grid.x * grid.y * grid.z), kern, grid, dim3(512), C::LDS_BYTES, s, a);
   return DVG_OK;
 }
 
@@ -459,9 +461,7 @@ int launch_conv_wino_wgrad(const float* in, const float* dy, int64_t M, int Cin,
   }
   DVG_TRY(rc);
   const int64_t pairs = (int64_t)Cin * Cout;
-  int64_t blocks = (16 * pairs * 8 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  DVG_LAUNCH(K_WGRAD_REDUCE, wino_wgrad_slabsum_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slabs, g.nslabs, pairs, ups);
+  DVG_TRY(launch_wino_wgrad_slabsum(slabs, g.nslabs, pairs, 16, ups, s));  // (with one slab too)
   DVG_LAUNCH(K_WGRAD_REDUCE, wino_wgrad_reduce_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, (const float*)slabs, map, grad_w, ups);
   return DVG_OK;
 }
