@@ -243,6 +243,7 @@ SIGNATURES = {
         [POINTER(DecoderParams), c_int, c_void_p, c_int64, c_void_p, c_int, c_float, POINTER(DecoderGrads), c_void_p,
          c_void_p, c_size_t, c_int, c_void_p],
     ),
+    "dvg_decoder_declare_spins": (c_int, [c_void_p, c_int]),
     "dvg_mse_workspace_bytes": (c_size_t, []),
     "dvg_mse_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dvg_adam_step": (

@@ -82,6 +82,8 @@ enum KernelId : int {
   K_WGRAD_WINO,     // conv_wino_wgrad8_kernel (profiler name "conv_wino_wgrad_kernel"): Winograd form of the encoder's 3x3 weight gradients (work = executed FLOPs)
   K_IGEMM_WINO4,    // conv_wino4_kernel: Winograd F(4x4,3x3) form of the encoder's 3x3 layers (work = executed FLOPs: 1/4 of the direct form's)
   K_WGRAD_WINO4,    // conv_wino4_wgrad_kernel: F(4x4,3x3) form of the encoder's 3x3 weight gradients (work = executed FLOPs)
+  K_IGEMM_SPIN,     // conv_igemm_kernel<..., 6> launches (profiler name "conv_igemm_spin_kernel"): the decoder's input layer on declared +-1 spins, A as bf16, B as three bf16 pieces (work = algorithmic FLOPs, as the split form's launches)
+  K_WGRAD_SPIN,     // conv_wgrad1_dma_kernel<true> (profiler name "conv_wgrad_kernel_spin"): that layer's weight gradient, the same arithmetic
   K_CORR_TRANSPOSE, // packed_correlation_transpose_kernel (correlation.hip): packed rows -> bit columns
   K_CORR_PRODUCT,   // packed_correlation_kernel: the spins x spins product on bit columns (work = n n T spin products)
   K_FIELDS_ROWS,    // grbm_fields_packed_kernel (fields.hip): local fields of packed rows, per-row outputs, per-slab pooled sums (work = n T spins)
@@ -96,7 +98,7 @@ enum KernelId : int {
 enum Opt : int {
   OPT_IGEMM_DMA = 0, OPT_IGEMM_POSMAJOR, OPT_IGEMM_THR128, OPT_WGRAD_DMA, OPT_DEC_FOLD, OPT_DEC_D22, OPT_DEC_LC0, OPT_MMD_W128,
   OPT_MMD_D256, OPT_GIBBS_GENERIC, OPT_SIDE_STREAM, OPT_ENC_WINO, OPT_DEC_WINO, OPT_ENC_L0_FUSED, OPT_DEC_TAIL_FUSED,
-  OPT_WINO_DYNAMIC, OPT_ENC_WINO4, OPT_ENC_WINO4_MASK, OPT_ENC_DGRAD_CUS, OPT_ENC_WGRAD_CUS, OPT_DEC_WINO4_MASK, OPT_WGRAD_REDUCE_TILED, OPT_ENC_BN_REDUCE_POOLED, OPT_MMD_GRAM_FP4, OPT_COUNT
+  OPT_WINO_DYNAMIC, OPT_ENC_WINO4, OPT_ENC_WINO4_MASK, OPT_ENC_DGRAD_CUS, OPT_ENC_WGRAD_CUS, OPT_DEC_WINO4_MASK, OPT_WGRAD_REDUCE_TILED, OPT_ENC_BN_REDUCE_POOLED, OPT_MMD_GRAM_FP4, OPT_DEC_SPIN_GEMM, OPT_DEV_SPIN_OPERAND, OPT_COUNT
 };
 int64_t opt(Opt id);
 

@@ -202,11 +202,17 @@ struct ConvArgs {
   // operand form of the launch (set by launch_conv_igemm from conv_launch_mode; the PM argument of conv_igemm_kernel):
   // 0 float32 staged through registers (`wp` = [tap][Cin][Cout]); 3 float32 by LDS-DMA; 4 float32 operands as three bf16
   // pieces, split at operand-read time ("f32x3"); 5 operands rounded to bf16 at operand-read time ("bf16 inputs").
-  // 3 / 4 / 5 read the same float32 K-major pack `wp` = [tap][Cout][Cin].
+  // 6 (chosen by launch_conv_igemm from spin_a, never by conv_launch_mode): A rounded to bf16, B as three pieces.
+  // 3 / 4 / 5 / 6 read the same float32 K-major pack `wp` = [tap][Cout][Cin].
   int bf16 = 0;
   // force_f32 = 1: this launch runs in float32 (form 3 or 0) whatever the process-wide mode: the weight-space products of
   // the composed decoder layers (their operands are weights, not activations of the network)
   int force_f32 = 0;
+  // spin_a = 1: the caller's PROMISE that every element of `in` is +1 or -1 (the decoder's input layer on the spins of
+  // a forward call that declared them so: dvg_decoder_declare_spins).  Launches of form 3 or 4 then run form 6: A
+  // rounded to bf16 (exact for +-1), B as three bf16 pieces, three exact products per k-step.  A false promise rounds
+  // A to bf16.  Ignored under option dec_spin_gemm = 0.
+  int spin_a = 0;
   // bias_perm = n > 0: column j = p*n + c takes bias[c*4 + p] (the decoder's Linear(n, 4n) bias in checkpoint order)
   int bias_perm = 0;
   // bias_mod = C > 0: column j = p*C + c takes bias[c] (the dense 2x2 form: one bias per channel, four pixels per row)
@@ -241,6 +247,11 @@ bool plan_forward_flag(const void* ws, uint32_t bit);   // the forward noted on 
 bool plan_matches_forward(const void* ws, uint32_t signature);   // backward calls: the same plan as the forward's?
 void conv_precision_note_forward(const void* ws);      // forward calls: remember the mode that wrote the packs
 bool conv_precision_matches_forward(const void* ws);   // backward calls: same mode as the forward on this workspace?
+// The +-1 promise of the decoder's spins (dvg_decoder_declare_spins): declared for the NEXT forward call on `ws`, which
+// takes it (spin_promise_note_forward: returns it and records it for the backward call; one declaration, one forward)
+void spin_promise_declare(const void* ws, bool pm1);
+bool spin_promise_note_forward(const void* ws);
+bool spin_promise_of_forward(const void* ws);          // backward calls: what the forward on this workspace was promised
 int launch_conv_igemm(const ConvArgs& a, hipStream_t s);
 // Winograd F(2x2,3x3) form of a stride-1 3x3 layer (conv_wino.hip): same ConvArgs, `wp` = the transformed pack of
 // launch_wino_weight_pack ([Cin][Cout][16] floats), stats rows = conv_wino_stats_blocks
@@ -291,6 +302,10 @@ struct WgradArgs {
   // pixels, side 2^L), `dy` has 4*M rows, ntaps = 16 and the slabs hold the 16 (class, tap) pairs; the reduce pass
   // (launch_wgrad_reduce with fold = true) sums the 4 classes back onto the 9 checkpoint taps.
   int fold = 0;
+  // spin_x = 1: the caller's PROMISE that every element of `in` is +1 or -1 (as ConvArgs.spin_a): 1-tap launches served by
+  // the 128 x 128 LDS-DMA kernel run its spin form (X as exact bf16 values, dY as three bf16 pieces); a false promise
+  // rounds X to bf16.  Ignored under option dec_spin_gemm = 0.
+  int spin_x = 0;
 };
 int wgrad_ksplit(int64_t M, int Cin, int Cout, int ntaps);
 int wgrad_fold_ksplit(int64_t Msrc, int Cin, int Cout);

@@ -39,6 +39,11 @@ namespace dvg {
 //     the f32 MFMA's matrix time.  ~5 VALU instructions per operand element, issued under the MFMAs.
 //   PM = 5 ("bf16 inputs"): every operand is rounded to bf16 (round to nearest even, v_cvt_pk_bf16_f32): the product of
 //     the bf16-rounded operands, accumulated in float32.
+//   PM = 6 ("spin A"): the caller has PROMISED that the A operand (the rows of `in`) holds only +-1 (ConvArgs.spin_a: the
+//     decoder's input layer, whose rows are the spins).  A is rounded to bf16 -- exact for +-1 -- and only B is split, so
+//     each k-step issues three products, lo, mid, hi, each of them exact: the float32 weights times the spins at 3/16 of
+//     the f32 MFMA's matrix time and a quarter of form 4's A-side conversions.  On a false promise A is rounded to bf16
+//     (finite, but no longer float32-class).
 // A lane's 16 floats of a chunk (k = 16 hh .. 16 hh + 15) feed two k-steps of 8; A and B are converted by the same code
 // in the same element order, so the pairing of k indices is the f32 form's.  (Rounds 1-2 staged these two modes through
 // registers, converting on the way INTO LDS; they could not use the LDS-DMA path, the position-major tiles or the composed
@@ -46,7 +51,8 @@ namespace dvg {
 
 template <int BM, int BN, int WM, int WN, int WK, int PM = 0>
 __global__ __launch_bounds__(WM* WN* WK * 64) void conv_igemm_kernel(ConvArgs a) {
-  static_assert(PM == 0 || PM == 3 || PM == 4 || PM == 5, "operand forms: 0 register-staged f32, 3 / 4 / 5 LDS-DMA");
+  static_assert(PM == 0 || (PM >= 3 && PM <= 6), "operand forms: 0 register-staged f32, 3 / 4 / 5 / 6 LDS-DMA");
+  constexpr bool BFM = PM >= 4;  // arithmetic on the bf16 MFMA
   constexpr bool DMA = PM >= 3;
   static_assert(!DMA || WK == 1, "LDS-DMA form: no K wave groups");
   // (A dedicated loader wave per block -- every buffer_load ... lds of the block issued by a fifth wave -- was built and
@@ -317,18 +323,49 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv_igemm_kernel(ConvArgs a)
       issue(0);
       if (it_beg + 1 < it_end) fetch_nbr();
     }
-    constexpr int NPC = PM == 4 ? 3 : 1;  // bf16 pieces per operand (forms 4 / 5)
-    bf16x8v pa[NPC][TM], pb[NPC][TN];     // converted operands of the pending k-step (forms 4 / 5)
-    if constexpr (PM == 4 || PM == 5) {
+    constexpr int NPA = PM == 4 ? 3 : 1, NPB = PM == 4 || PM == 6 ? 3 : 1;  // bf16 pieces per A / B operand (forms 4 / 5 / 6)
+    bf16x8v pa[NPA][TM], pb[NPB][TN];     // converted operands of the pending k-step (forms 4 / 5 / 6)
+    if constexpr (BFM) {
       const bf16x8v zero8 = __builtin_bit_cast(bf16x8v, (u32x4v){0u, 0u, 0u, 0u});
 #pragma unroll
-      for (int pc = 0; pc < NPC; ++pc) {
+      for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int i = 0; i < TM; ++i) pa[pc][i] = zero8;
+        for (int pc = 0; pc < NPA; ++pc) pa[pc][i] = zero8;
 #pragma unroll
-        for (int j = 0; j < TN; ++j) pb[pc][j] = zero8;
-      }
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int pc = 0; pc < NPB; ++pc) pb[pc][j] = zero8;
     }
+    // one k-step's MFMAs on converted operands (forms 4 / 5 / 6)
+    auto mfma_step = [&](const bf16x8v (&xa)[NPA][TM], const bf16x8v (&xb)[NPB][TN]) {
+      if constexpr (PM == 4) {
+        // six piece products, smallest first (lo hi, hi lo, mid mid, mid hi, hi mid, hi hi), into ONE accumulator
+        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+        for (int t = 0; t < 6; ++t)
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[PA[t]][i], xb[PB[t]][j], acc[i][j], 0, 0, 0);
+      } else if constexpr (PM == 6) {
+        // three products of the (exact) +-1 operand with the pieces of B, smallest first (lo, mid, hi), into ONE accumulator
+#pragma unroll
+        for (int t = 2; t >= 0; --t)
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0][i], xb[t][j], acc[i][j], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0][i], xb[0][j], acc[i][j], 0, 0, 0);
+      }
+    };
+    (void)mfma_step;
     for (int it = it_beg; it < it_end; ++it) {
       const int buf = (it - it_beg) & 1;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of chunk `it` have landed ...
@@ -339,7 +376,7 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv_igemm_kernel(ConvArgs a)
       }
       const unsigned char* Ab = stg + buf * STAGE + wm * TM * 32 * 128;
       const unsigned char* Bb = stg + buf * STAGE + BM * 128 + wn * TN * 32 * 128;
-      if constexpr (PM == 4 || PM == 5) {
+      if constexpr (BFM) {
         // bf16 MFMA on the float32 LDS image: two k-steps of 16 per chunk; step st takes this lane's floats
         // 16 hh + 8 st .. + 7 (logical slots 4 hh + 2 st, + 1) of every row / column and converts them in registers.
         // Software pipeline INSIDE the wave, one k-step deep and across the chunk barrier: the MFMAs of k-step t run
@@ -347,33 +384,13 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv_igemm_kernel(ConvArgs a)
         // so VALU work of one wave does not land under the MFMAs of another by itself: measured 37 % matrix-pipe use
         // with convert -> MFMA in sequence).  `pa / pb` carry the converted operands of the pending k-step into the
         // next iteration; they start as zeros (one k-step of MFMAs on zeros per block instead of a peeled first pass).
-        constexpr int NMF = TM * TN * (PM == 4 ? 6 : 1);  // MFMAs per k-step
+        constexpr int NMF = TM * TN * (PM == 4 ? 6 : PM == 6 ? 3 : 1);  // MFMAs per k-step
         // VALU instructions of one k-step's conversions (measured on the ISA: 11 per pair of elements of the split, the
         // round-to-nearest form one v_cvt_pk per pair) spread over the gaps between that phase's MFMAs
-        constexpr int NVT = (PM == 4 ? 44 : 4) * (TM + TN);
+        constexpr int NVT = PM == 4 ? 44 * (TM + TN) : PM == 6 ? 4 * TM + 44 * TN : 4 * (TM + TN);
         constexpr int NVA = (NVT + NMF - 1) / NMF;
         constexpr int LEAD = NMF >= 8 ? 3 : 1;  // MFMAs issued ahead of the first conversion (they cover the LDS read latency)
-        auto mfma_step = [&](const bf16x8v (&xa)[NPC][TM], const bf16x8v (&xb)[NPC][TN]) {
-          if constexpr (PM == 4) {
-            // six piece products, smallest first (lo hi, hi lo, mid mid, mid hi, hi mid, hi hi), into ONE accumulator
-            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-            constexpr int NT6 = 6;
-#pragma unroll
-            for (int t = 0; t < NT6; ++t)
-#pragma unroll
-              for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[PA[t]][i], xb[PB[t]][j], acc[i][j], 0, 0, 0);
-          } else {
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-              for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[0][i], xb[0][j], acc[i][j], 0, 0, 0);
-          }
-        };
-        auto convert_step = [&](const f32x4 (&xa)[TM][2], const f32x4 (&xb)[TN][2], bf16x8v (&oa)[NPC][TM], bf16x8v (&ob)[NPC][TN]) {
+        auto convert_step = [&](const f32x4 (&xa)[TM][2], const f32x4 (&xb)[TN][2], bf16x8v (&oa)[NPA][TM], bf16x8v (&ob)[NPB][TN]) {
 #pragma unroll
           for (int i = 0; i < TM; ++i) {
             if constexpr (PM == 4) f32x8_split3(xa[i][0], xa[i][1], oa[0][i], oa[1][i], oa[2][i]);
@@ -381,7 +398,7 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv_igemm_kernel(ConvArgs a)
           }
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
-            if constexpr (PM == 4) f32x8_split3(xb[j][0], xb[j][1], ob[0][j], ob[1][j], ob[2][j]);
+            if constexpr (NPB == 3) f32x8_split3(xb[j][0], xb[j][1], ob[0][j], ob[1][j], ob[2][j]);
             else ob[0][j] = f32x8_to_bf16(xb[j][0], xb[j][1]);
           }
         };
@@ -401,7 +418,7 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv_igemm_kernel(ConvArgs a)
           }
         }
         __builtin_amdgcn_sched_barrier(0);  // (the reads and their address arithmetic: a scheduling region of their own)
-        bf16x8v na[NPC][TM], nb[NPC][TN];
+        bf16x8v na[NPA][TM], nb[NPB][TN];
         // phase A: MFMAs of the pending k-step (the previous chunk's second) over the conversion of this chunk's first
         mfma_step(pa, pb);
         convert_step(ra[0], rb[0], na, nb);
@@ -458,24 +475,7 @@ __global__ __launch_bounds__(WM* WN* WK * 64) void conv_igemm_kernel(ConvArgs a)
         }
       }
     }
-    if constexpr (PM == 4 || PM == 5) {  // the last k-step's MFMAs
-      if constexpr (PM == 4) {
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[PA[t]][i], pb[PB[t]][j], acc[i][j], 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[0][i], pb[0][j], acc[i][j], 0, 0, 0);
-      }
-    }
+    if constexpr (BFM) mfma_step(pa, pb);  // the last k-step's MFMAs
   } else {
     f32x4 aA[KH][RA], bA[KH][RB];
     float mA[KH][RA];
@@ -711,6 +711,10 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
   // (the packs were written in the matching format: launch_weight_pack_multi makes the same decision per job)
   a.bf16 = conv_launch_mode(a.fold == 1 ? a.M * 4 : a.M, a.Cout);
   if (a.force_f32 && a.bf16 > 3) a.bf16 = 3;
+  // the caller's promise that the rows of `in` hold only +-1 (ConvArgs.spin_a): form 6 instead of the float32 or the
+  // split form, unless option dec_spin_gemm = 0 ignores it.  (Forms 0 and 5 never switch.)
+  const bool spin = a.spin_a && !a.force_f32 && (a.bf16 == 3 || a.bf16 == 4) && opt(OPT_DEC_SPIN_GEMM) != 0;
+  if (spin) a.bf16 = 6;
   const bool taps_ok = a.fold == 1 ? a.ntaps == 4 : a.fold == 2 ? a.ntaps == 16 : (a.ntaps == 9 || a.ntaps == 1);
   if (a.fold && (a.ups || a.poolsum || !conv_fold_ok(a.M))) {
     set_error("conv_igemm: fold=%d needs ups=poolsum=0 and whole 128-row blocks (M=%lld)", a.fold, (long long)a.M);
@@ -762,19 +766,22 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
   const int bm = igemm_bm(cfg), bn = igemm_bn(cfg);
   const dim3 grid(cm * (unsigned)ceil_div(a.M, bm), (unsigned)(a.Cout / bn), kz);
   int rc;
-  // (weight-space products of the composed decoder layers: their own profiler id, always float32)
+  // (weight-space products of the composed decoder layers: their own profiler id, always float32; the spin-operand
+  // launches: an id of their own too, carrying the algorithmic FLOPs as the split form's launches do)
   const bool wspace = a.force_f32 != 0;
+  const int own_id = wspace ? K_IGEMM_WSPACE : spin ? K_IGEMM_SPIN : -1;
 #define IGEMM_LAUNCH_PM(PMV, FL)                                                                                        \
   switch (cfg) {                                                                                                        \
-    case 0: rc = launch_igemm_cfg<128, 64, 2, 2, 1, PMV>(wspace ? K_IGEMM_WSPACE : K_IGEMM_128x64, FL, grid, a, s); break;   \
-    case 1: rc = launch_igemm_cfg<64, 64, 2, 2, 1, PMV>(wspace ? K_IGEMM_WSPACE : K_IGEMM_64x64, FL, grid, a, s); break;     \
-    case 3: rc = launch_igemm_cfg<32, 64, 1, 2, 1, PMV>(wspace ? K_IGEMM_WSPACE : K_IGEMM_32x64, FL, grid, a, s); break;     \
-    case 4: rc = launch_igemm_cfg<128, 128, 2, 2, 1, PMV>(wspace ? K_IGEMM_WSPACE : K_IGEMM_128x128, FL, grid, a, s); break; \
-    default: rc = launch_igemm_cfg<128, 32, 4, 1, 1, PMV>(wspace ? K_IGEMM_WSPACE : K_IGEMM_128x32, FL, grid, a, s); break;  \
+    case 0: rc = launch_igemm_cfg<128, 64, 2, 2, 1, PMV>(own_id >= 0 ? own_id : K_IGEMM_128x64, FL, grid, a, s); break;   \
+    case 1: rc = launch_igemm_cfg<64, 64, 2, 2, 1, PMV>(own_id >= 0 ? own_id : K_IGEMM_64x64, FL, grid, a, s); break;     \
+    case 3: rc = launch_igemm_cfg<32, 64, 1, 2, 1, PMV>(own_id >= 0 ? own_id : K_IGEMM_32x64, FL, grid, a, s); break;     \
+    case 4: rc = launch_igemm_cfg<128, 128, 2, 2, 1, PMV>(own_id >= 0 ? own_id : K_IGEMM_128x128, FL, grid, a, s); break; \
+    default: rc = launch_igemm_cfg<128, 32, 4, 1, 1, PMV>(own_id >= 0 ? own_id : K_IGEMM_128x32, FL, grid, a, s); break;  \
   }
   if (a.bf16 == 3) { IGEMM_LAUNCH_PM(3, flops_exec) }
   else if (a.bf16 == 4) { IGEMM_LAUNCH_PM(4, flops_exec) }
   else if (a.bf16 == 5) { IGEMM_LAUNCH_PM(5, flops_exec) }
+  else if (a.bf16 == 6) { IGEMM_LAUNCH_PM(6, flops_exec) }
   else { IGEMM_LAUNCH_PM(0, flops) }
 #undef IGEMM_LAUNCH_PM
   DVG_TRY(rc);

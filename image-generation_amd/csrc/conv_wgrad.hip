@@ -440,6 +440,13 @@ __global__ __launch_bounds__(WA* WB* WT * 64) void conv_wgrad9_dma_kernel(WgradA
 // dW[ci][co] = sum_m X[m][ci] dY[m][co] (the decoder's Linear layer): a plain TN GEMM over the rows.  128 x 128 channel
 // tile per block, 4 waves with a 64 x 64 wave tile (4 accumulator tiles), 32 rows per stage by LDS-DMA, two stages, one
 // barrier per stage; rows past the slab carry an out-of-range offset (zeros).
+// SPIN = true (WgradArgs.spin_x: the caller has promised that X holds only +-1 -- the decoder's input layer): the SAME
+// staging and stage image, the arithmetic on the bf16 MFMA as in form 6 of conv_igemm_kernel.  A 32-row stage is two k-steps
+// of 16 rows; lane (c, hh) takes rows 16 st + 8 hh .. + 7 of its columns (eight ds_read_b32 per tile operand and k-step:
+// the read count per 32 rows of the float32 form), packs X with v_cvt_pk_bf16_f32 (exact for +-1), splits dY into three
+// bf16 pieces (hi + mid + lo == dY bit for bit) and issues three exact products per accumulator tile, smallest piece first.
+// One k-step deep software pipeline across the stage barrier: the conversions of k-step t+1 ride under the MFMAs of t.
+template <bool SPIN>
 __global__ __launch_bounds__(256) void conv_wgrad1_dma_kernel(WgradArgs a) {
   constexpr int BA = 128, BB = 128, XB = 32 * BA * 4, STAGE = 2 * XB;  // X rows then dY rows, 16 KB each
   typedef __attribute__((address_space(3))) void lds_void;
@@ -486,11 +493,74 @@ __global__ __launch_bounds__(256) void conv_wgrad1_dma_kernel(WgradArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = (f32x16){0};
   if (nchunks > 0) issue(0, 0);
+  // (spin form) converted operands of the pending k-step: they start as zeros -- one k-step of MFMAs on zeros per block
+  bf16x8v px[2], py[3][2];
+  auto spin_mfma = [&](const bf16x8v (&xa)[2], const bf16x8v (&yb)[3][2]) {
+#pragma unroll
+    for (int t = 2; t >= 0; --t)  // lo, mid, hi
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xa[i], yb[t][j], acc[i][j], 0, 0, 0);
+  };
+  auto spin_convert = [&](const f32x4 (&rx)[2][2], const f32x4 (&ry)[2][2], bf16x8v (&ox)[2], bf16x8v (&oy)[3][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) ox[i] = f32x8_to_bf16(rx[i][0], rx[i][1]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) f32x8_split3(ry[j][0], ry[j][1], oy[0][j], oy[1][j], oy[2][j]);
+  };
+  (void)spin_mfma; (void)spin_convert;
+  if constexpr (SPIN) {
+    const bf16x8v zero8 = __builtin_bit_cast(bf16x8v, (u32x4v){0u, 0u, 0u, 0u});
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      px[i] = zero8;
+#pragma unroll
+      for (int t = 0; t < 3; ++t) py[t][i] = zero8;
+    }
+  }
   for (int it = 0; it < nchunks; ++it) {
     const int buf = it & 1;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (it + 1 < nchunks) issue(it + 1, buf ^ 1);
+    if constexpr (SPIN) {
+      constexpr int NMF = 12, NVA = (4 * 2 + 44 * 2 + NMF - 1) / NMF, LEAD = 3;  // MFMAs, conversion VALU per MFMA gap (conv_igemm.hip)
+      const float* xq = reinterpret_cast<const float*>(wg_smem + buf * STAGE) + 8 * hh * BA + wa * 64 + c;
+      const float* yq = reinterpret_cast<const float*>(wg_smem + buf * STAGE + XB) + 8 * hh * BB + wb * 64 + c;
+      f32x4 rx[2][2][2], ry[2][2][2];  // [k-step][tile][rows 0-3 / 4-7 of the lane's eight]
+#pragma unroll
+      for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            rx[st][i][e >> 2][e & 3] = xq[(16 * st + e) * BA + i * 32];
+            ry[st][i][e >> 2][e & 3] = yq[(16 * st + e) * BB + i * 32];
+          }
+      __builtin_amdgcn_sched_barrier(0);
+      bf16x8v nx[2], ny[3][2];
+      // phase A: MFMAs of the pending k-step (the previous stage's second) over the conversion of this stage's first
+      spin_mfma(px, py);
+      spin_convert(rx[0], ry[0], nx, ny);
+      __builtin_amdgcn_sched_group_barrier(0x008, LEAD, 0);
+#pragma unroll
+      for (int g = LEAD; g < NMF; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x002, NVA + 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // phase B: MFMAs of this stage's first k-step over the conversion of its second (pending into the next iteration)
+      spin_mfma(nx, ny);
+      spin_convert(rx[1], ry[1], px, py);
+#pragma unroll
+      for (int g = 0; g < NMF; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, NVA, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      continue;
+    }
     const float* xp = reinterpret_cast<const float*>(wg_smem + buf * STAGE) + hh * BA + wa * 64 + c;
     const float* yp = reinterpret_cast<const float*>(wg_smem + buf * STAGE + XB) + hh * BB + wb * 64 + c;
     float av[2][2], bv[2][2];
@@ -512,6 +582,7 @@ __global__ __launch_bounds__(256) void conv_wgrad1_dma_kernel(WgradArgs a) {
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
     }
   }
+  if constexpr (SPIN) spin_mfma(px, py);  // the last k-step's MFMAs
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -784,10 +855,21 @@ int launch_conv_wgrad(const WgradArgs& a, hipStream_t s) {
     return DVG_OK;
   }
   if (a.ntaps == 1 && wgrad1_dma_ok(a.M, a.Cin, a.Cout)) {
-    auto kern = conv_wgrad1_dma_kernel;
+    const dim3 g1((unsigned)((a.Cin / 128) * (a.Cout / 128)), (unsigned)a.ksplit);
+    // the caller's promise that `in` holds only +-1 (WgradArgs.spin_x): the spin form, unless option dec_spin_gemm = 0
+    // ignores it (2: the forward GEMM alone takes the form, A/B runs); never under bf16 GEMM inputs (as the forward
+    // kernel's form 5 never switches)
+    if (a.spin_x && opt(OPT_DEC_SPIN_GEMM) == 1 && conv_precision_mode() != 1) {
+      auto kern = conv_wgrad1_dma_kernel<true>;
+      static std::atomic<uint64_t> attr_done{0};
+      DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, 65536));
+      DVG_LAUNCH_WORK(K_WGRAD_SPIN, flops, kern, g1, dim3(256), 65536, s, a);
+      return DVG_OK;
+    }
+    auto kern = conv_wgrad1_dma_kernel<false>;
     static std::atomic<uint64_t> attr_done{0};
     DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, 65536));
-    DVG_LAUNCH_WORK(K_WGRAD_2x2, flops, kern, dim3((unsigned)((a.Cin / 128) * (a.Cout / 128)), (unsigned)a.ksplit), dim3(256), 65536, s, a);
+    DVG_LAUNCH_WORK(K_WGRAD_2x2, flops, kern, g1, dim3(256), 65536, s, a);
     return DVG_OK;
   }
   const dim3 grid((unsigned)((a.Cin / ba) * (a.Cout / bb)), (unsigned)a.ntaps, (unsigned)a.ksplit);

@@ -211,6 +211,9 @@ int decoder_fwd_impl(const dvg_decoder_params_t* p, int n, const float* spins, i
                      const float* const dropout_keep[4], uint64_t seed, uint64_t offset, float* out, const MseTail* mt,
                      void* ws, size_t ws_bytes, const dvg_step_state_t* dyn, int prepared, dvg_stream_t stream) {
   const DecPlan pl = dec_plan(N > 0 ? N : 1, (n >= 32 && n % 32 == 0) ? n : 32, plan_options());
+  // the caller's declaration for THIS call that `spins` holds only +-1 (dvg_decoder_declare_spins): taken whatever becomes
+  // of the call, recorded for the backward call on this workspace
+  const int spin_pm1 = spin_promise_note_forward(ws) ? 1 : 0;
   DVG_TRY(check_common(p, n, N, ws, ws_bytes, pl));
   conv_precision_note_forward(ws);
   plan_note_forward(ws, pl.signature[mt != nullptr]);
@@ -237,6 +240,7 @@ int decoder_fwd_impl(const dvg_decoder_params_t* p, int n, const float* spins, i
     a.in = spins; a.wp = W + pl.wp_lin; a.bias = p->lin_b; a.bias_perm = n; a.out = W + pl.X0; a.stats = nullptr;  // bias'[p*n + c] = b[c*4 + p]
     a.M = N; a.Cin = n; a.Cout = 4 * n; a.L = 0; a.ntaps = 1; a.ups = 0; a.poolsum = 0;
     a.splitk_ws = W + pl.splitk;
+    a.spin_a = spin_pm1;
     DVG_TRY(launch_conv_igemm(a, s));
   }
   const float* x = W + pl.X0;
@@ -246,7 +250,7 @@ int decoder_fwd_impl(const dvg_decoder_params_t* p, int n, const float* spins, i
       ConvArgs a;
       a.in = x; a.wp = W + pl.wp[l]; a.bias = p->conv_b[l]; a.out = W + pl.Y[l];
       a.stats = training ? W + pl.stats[l] : nullptr;
-      if (l == 0 && pl.lc0) { a.in = spins; a.wp = W + pl.WcT; a.bias = W + pl.bc; }  // straight from the spins through the composed weight
+      if (l == 0 && pl.lc0) { a.in = spins; a.wp = W + pl.WcT; a.bias = W + pl.bc; a.spin_a = spin_pm1; }  // straight from the spins through the composed weight
       a.splitk_ws = W + pl.splitk; a.wino_cus = WINO_CUS_DEC;
       DVG_TRY(launch_conv_layer(pl.conv[l], PASS_FWD, a, s));
     } else if (pl.tail) {  // layer 2's activation happens while layer 3 stages its input (Xs[2] is never written)
@@ -278,6 +282,12 @@ int decoder_fwd_impl(const dvg_decoder_params_t* p, int n, const float* spins, i
   return DVG_OK;
 }
 }  // namespace
+
+extern "C" int dvg_decoder_declare_spins(const void* ws, int pm1) {
+  DVG_REQUIRE(ws, "decoder_declare_spins: null workspace");
+  spin_promise_declare(ws, pm1 != 0);
+  return DVG_OK;
+}
 
 extern "C" int dvg_decoder_fwd_ex(const dvg_decoder_params_t* p, int n, const float* spins, int64_t N, int training,
                                   const float* const dropout_keep[4], uint64_t seed, uint64_t offset, float* out, void* ws,
@@ -321,6 +331,7 @@ int decoder_bwd_impl(const dvg_decoder_params_t* p, int n, const float* spins, i
   if (!plan_matches_forward(ws, pl.signature[mt != nullptr]))
     return plan_mismatch_error("decoder_bwd", "dec_fold / dec_d22 / dec_lc0 / dec_wino / enc_wino4", "igemm_dma / dec_tail_fused / dec_wino4_mask", ", or the forward call was not of the same kind (dvg_decoder_fwd_ex / dvg_decoder_fwd_mse_ex)");
   DVG_REQUIRE(spins && (grad_out || mt) && g, "decoder_bwd: null argument");
+  const int spin_pm1 = spin_promise_of_forward(ws) ? 1 : 0;  // what the forward call on this workspace was promised about `spins`
   if (mt) DVG_REQUIRE(pl.tail && mt->images && mt->R >= 1 && N % mt->R == 0, "decoder_bwd_mse: images / R (N=%lld R=%d), option dec_tail_fused", (long long)N, mt->R);
   DVG_REQUIRE(g->lin_w && g->lin_b, "decoder_bwd: null linear gradient buffer");
   for (int l = 0; l < 5; ++l) DVG_REQUIRE(g->conv_w[l] && g->conv_b[l], "decoder_bwd: null conv gradient buffer %d", l);
@@ -422,7 +433,7 @@ int decoder_bwd_impl(const dvg_decoder_params_t* p, int n, const float* spins, i
     DVG_TRY(launch_lc0_lin_bias_grad(W + pl.dbc, W + pl.wpd[0], n, C, g->lin_b, s2));
     // dWc[i][o] = sum_images spins[i] dY[o]  (and its transpose)
     WgradArgs wa;
-    wa.in = spins; wa.dy = dY; wa.slabs = W + pl.slabs;
+    wa.in = spins; wa.dy = dY; wa.slabs = W + pl.slabs; wa.spin_x = spin_pm1;
     conv_layer_wgrad_geometry(pl.conv[0], wa);
     DVG_TRY(launch_conv_wgrad(wa, s2));
     DVG_TRY(launch_slab_sum(W + pl.slabs, wa.ksplit, n, C4, W + pl.dWc, W + pl.dWcT, s2));
@@ -454,7 +465,7 @@ int decoder_bwd_impl(const dvg_decoder_params_t* p, int n, const float* spins, i
     DVG_TRY(launch_rowsum_partial(dX, N, 4 * n, W + pl.partL, s2));
     DVG_REQUIRE(sums.add(W + pl.partL, EW_BLOCKS, 4 * n, 4 * n, 1.0f, g->lin_b, n, 4), "decoder_bwd: column-sum batch full");  // j' = p*n+c -> c*4+p
     WgradArgs wa;
-    wa.in = spins; wa.dy = dX; wa.slabs = W + pl.slabs;
+    wa.in = spins; wa.dy = dX; wa.slabs = W + pl.slabs; wa.spin_x = spin_pm1;
     wa.M = N; wa.Cin = n; wa.Cout = 4 * n; wa.L = 0; wa.ntaps = 1; wa.ups = 0; wa.ksplit = pl.ksplit_lin;
     DVG_TRY(launch_conv_wgrad(wa, s2));
     DVG_TRY(launch_wgrad_reduce(W + pl.slabs, pl.ksplit_lin, WeightMap{WM_LIN_FWD, n, 4 * n, 1}, g->lin_w, s2));

@@ -15,6 +15,7 @@ extern "C" int dvg_dev_conv_igemm(const float* in, const float* w, int mode, flo
   a.in = in; a.wp = wp; a.bias = bias; a.out = out; a.stats = stats;
   a.M = M; a.Cin = Cin; a.Cout = Cout; a.L = L; a.ntaps = ntaps; a.ups = ups; a.poolsum = poolsum;
   a.splitk_ws = splitk_ws;
+  a.spin_a = opt(OPT_DEV_SPIN_OPERAND) != 0;  // (test knob: the +-1 promise for `in`)
   return launch_conv_igemm(a, s);
 }
 
@@ -128,6 +129,7 @@ extern "C" int dvg_dev_conv_wgrad(const float* in, const float* dy, float* slabs
   WgradArgs wa;
   wa.in = in; wa.dy = dy; wa.slabs = slabs; wa.M = M; wa.Cin = Cin; wa.Cout = Cout; wa.L = L; wa.ntaps = ntaps;
   wa.ups = ups; wa.ksplit = wgrad_ksplit(M, Cin, Cout, ntaps);
+  wa.spin_x = opt(OPT_DEV_SPIN_OPERAND) != 0;  // (test knob: the +-1 promise for `in`)
   DVG_TRY(launch_conv_wgrad(wa, s));
   return launch_wgrad_reduce(slabs, wa.ksplit, WeightMap{mode, Cin, Cout, ntaps}, grad_w, s);
 }

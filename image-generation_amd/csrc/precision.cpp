@@ -59,6 +59,30 @@ bool conv_precision_matches_forward(const void* ws) {
   return it == g_ws_mode.end() || it->second == conv_precision_mode();
 }
 
+// The +-1 promise travels the same way: host-side bookkeeping per workspace pointer, no look at the data, no sync.
+namespace {
+std::unordered_map<const void*, int> g_ws_spin;  // bit 0: declared for the next forward; bit 1: the last forward had it
+}
+void spin_promise_declare(const void* ws, bool pm1) {
+  std::lock_guard<std::mutex> lock(g_ws_mutex);
+  if (g_ws_spin.size() > 4096) g_ws_spin.clear();
+  int& v = g_ws_spin[ws];
+  v = (v & ~1) | (pm1 ? 1 : 0);
+}
+bool spin_promise_note_forward(const void* ws) {
+  std::lock_guard<std::mutex> lock(g_ws_mutex);
+  auto it = g_ws_spin.find(ws);
+  if (it == g_ws_spin.end()) return false;
+  const bool pm1 = (it->second & 1) != 0;
+  it->second = pm1 ? 2 : 0;
+  return pm1;
+}
+bool spin_promise_of_forward(const void* ws) {
+  std::lock_guard<std::mutex> lock(g_ws_mutex);
+  auto it = g_ws_spin.find(ws);
+  return it != g_ws_spin.end() && (it->second & 2) != 0;
+}
+
 int conv_precision_mode() {
   int m = g_mode.load(std::memory_order_relaxed);
   if (m < 0) {  // never set: float32 (the mode is chosen through dvg_set_conv_precision, not the environment)

@@ -25,7 +25,7 @@ static const char* kNames[K_COUNT] = {
     "enc_proj_bwd", "dec_bn_act_fwd", "dec_bn_act_bwd_reduce",
     "dec_bn_act_bwd_apply", "dec_conv3_fwd", "dec_conv3_bwd", "dec_final_fwd", "dec_final_bwd",
     "mse", "adam", "misc", "conv_igemm_weight_space", "conv_wino_kernel", "conv_wino_wgrad_kernel",
-    "conv_wino4_kernel", "conv_wino4_wgrad_kernel", "packed_correlation_transpose_kernel", "packed_correlation_kernel",
+    "conv_wino4_kernel", "conv_wino4_wgrad_kernel", "conv_igemm_spin_kernel", "conv_wgrad_kernel_spin", "packed_correlation_transpose_kernel", "packed_correlation_kernel",
     "grbm_fields_packed_kernel", "grbm_fields_reduce_kernel", "grbm_descend_packed_kernel",
     "gibbs_quantum_kernel", "gibbs_cluster_kernel"};
 

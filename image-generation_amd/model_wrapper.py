@@ -509,11 +509,13 @@ class ModelWrapper:
             n_rows = int(spins.shape[0]) * int(spins.shape[1])
             want = self.fuse_decoder_mse if self.fuse_decoder_mse is not None else n_rows >= self.FUSE_DECODER_MSE_ROWS
             fused = bool(want) and _lib.get_option("dec_tail_fused") != 0
+            # (the spins of the library's own Gumbel kernel are exactly +-1, and the decoder is told so: Decoder.forward)
+            pm1 = raw is not None
             if fused:
-                mse_loss = dec.forward_mse(spins_cut, images)
+                mse_loss = dec.forward_mse(spins_cut, images, spins_pm1=pm1)
                 seed_t, seed_g = [mse_loss], None
             else:
-                reconstructed_images = dec(spins_cut)
+                reconstructed_images = dec(spins_cut, spins_pm1=pm1)
                 mse_loss, g_recon = F.replicated_mse_loss_and_grad(reconstructed_images, images)
                 seed_t, seed_g = [reconstructed_images], [g_recon]
             if not defer:

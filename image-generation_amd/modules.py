@@ -185,6 +185,13 @@ def _decoder_call_setup(spins, module, masks, seed, offset, params):
     return x, (B, R, n), st, training, prep, prepared, ws, mask_arr, keep
 
 
+def _declare_spins(ws, spins_pm1):
+    """The caller's promise for the forward call about to be made on ``ws`` that the spins hold only +-1
+    (``dvg_decoder_declare_spins``: include/dvg.h); no declaration is no promise."""
+    if spins_pm1:
+        check(lib().dvg_decoder_declare_spins(ws.data_ptr(), 1), "dvg_decoder_declare_spins")
+
+
 def _decoder_grad_struct(grads):
     gs = DecoderGrads()
     gs.lin_w, gs.lin_b = grads[0].data_ptr(), grads[1].data_ptr()
@@ -196,10 +203,10 @@ def _decoder_grad_struct(grads):
 
 
 class _DecoderFn(torch.autograd.Function):
-    """args: spins (B,R,n), module, masks (list or None), seed, offset, then the 28 trainable tensors."""
+    """args: spins (B,R,n), module, masks (list or None), seed, offset, spins_pm1, then the 28 trainable tensors."""
 
     @staticmethod
-    def forward(ctx, spins, module, masks, seed, offset, *params):
+    def forward(ctx, spins, module, masks, seed, offset, spins_pm1, *params):
         L = lib()
         x, (B, R, n), st, training, prep, prepared, ws, mask_arr, keep = _decoder_call_setup(spins, module, masks, seed, offset, params)
         N = B * R
@@ -208,6 +215,7 @@ class _DecoderFn(torch.autograd.Function):
             if prep is not None and not prepared:
                 # made for another call (shape, mode or parameters changed in between): wait it out and do without
                 torch.cuda.current_stream(x.device).wait_stream(prep["stream"])
+            _declare_spins(ws, spins_pm1)
             check(L.dvg_decoder_fwd_ex(ctypes.byref(st), n, x.data_ptr(), N, int(training),
                                        mask_arr if keep else None, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
                                        out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.DYN, int(prepared),
@@ -246,7 +254,7 @@ class _DecoderFn(torch.autograd.Function):
             # ws the moment this node is done, and a main-stream allocation made before the join could be carved out of
             # it.  The owner of the deferral (ModelWrapper) drops these references AFTER dvg_stream_join_side.
             module._deferred_keep = (ws, go, x, gx, tuple(grads))
-        return (gx, None, None, None, None, *_grad_returns(module, grads, direct))
+        return (gx, None, None, None, None, None, *_grad_returns(module, grads, direct))
 
 
 class _DecoderMseFn(torch.autograd.Function):
@@ -258,7 +266,7 @@ class _DecoderMseFn(torch.autograd.Function):
     differentiated has to go through ``Decoder.forward`` and ``replicated_mse_loss``."""
 
     @staticmethod
-    def forward(ctx, spins, images, module, masks, seed, offset, *params):
+    def forward(ctx, spins, images, module, masks, seed, offset, spins_pm1, *params):
         L = lib()
         if not module.training:
             raise _lib.DvgError("Decoder.forward_mse is a training-mode call (batch statistics, backward sums)")
@@ -270,6 +278,7 @@ class _DecoderMseFn(torch.autograd.Function):
         with torch.cuda.device(x.device):
             if prep is not None and not prepared:
                 torch.cuda.current_stream(x.device).wait_stream(prep["stream"])
+            _declare_spins(ws, spins_pm1)
             check(L.dvg_decoder_fwd_mse_ex(ctypes.byref(st), n, x.data_ptr(), B * R, mask_arr if keep else None,
                                            int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), im.data_ptr(), R, 1.0,
                                            loss.data_ptr(), ws.data_ptr(), ws.numel(), _lib.DYN, int(prepared),
@@ -301,7 +310,7 @@ class _DecoderMseFn(torch.autograd.Function):
                                            stream_ptr(x.device)), "dvg_decoder_bwd_mse_ex")
         if defer:
             module._deferred_keep = (ws, im, x, gx, tuple(grads))  # (see _DecoderFn.backward)
-        return (gx, None, None, None, None, None, *_grad_returns(module, grads, direct))
+        return (gx, None, None, None, None, None, None, *_grad_returns(module, grads, direct))
 
 
 class Decoder(torch.nn.Module):
@@ -382,18 +391,23 @@ class Decoder(torch.nn.Module):
         self._prepared = {"key": (N, n, training, seed, offset, dev), "params": tuple(params), "ws": ws, "st": st,
                           "stream": stream}
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, spins_pm1: bool = False) -> torch.Tensor:
+        """``spins_pm1=True`` is the caller's promise that every element of ``x`` is exactly +1 or -1 (the output of the
+        library's Gumbel kernel is): the input layer's GEMMs then multiply the spins as exact bf16 values with the weights
+        as three bf16 pieces on the bf16 matrix pipe -- float32-class results, faster.  It is not checked; on a false
+        promise ``x`` is rounded to bf16 in those GEMMs (finite results, float32 accuracy lost)."""
         masks, self._injected_masks = self._injected_masks, None
         offset = self._dropout_calls
         if self.training:
             self._dropout_calls += 1
-        return _DecoderFn.apply(x, self, masks, self.dropout_seed, offset, *self._trainable())
+        return _DecoderFn.apply(x, self, masks, self.dropout_seed, offset, bool(spins_pm1), *self._trainable())
 
-    def forward_mse(self, x: torch.Tensor, images: torch.Tensor) -> torch.Tensor:
+    def forward_mse(self, x: torch.Tensor, images: torch.Tensor, spins_pm1: bool = False) -> torch.Tensor:
         """``mse_loss(self(x), images.unsqueeze(1).repeat(1, R, ...))`` of a training step without the reconstruction
         ever being written (``_DecoderMseFn``): the same loss to rounding, the same gradients bit for bit, a fifth of the
-        memory traffic of the network's tail.  Training mode; differentiate the returned loss directly."""
+        memory traffic of the network's tail.  Training mode; differentiate the returned loss directly.  ``spins_pm1``: as in
+        :meth:`forward`."""
         masks, self._injected_masks = self._injected_masks, None
         offset = self._dropout_calls
         self._dropout_calls += 1
-        return _DecoderMseFn.apply(x, images, self, masks, self.dropout_seed, offset, *self._trainable())
+        return _DecoderMseFn.apply(x, images, self, masks, self.dropout_seed, offset, bool(spins_pm1), *self._trainable())

@@ -68,6 +68,11 @@ class DiscreteVariationalAutoencoder(torch.nn.Module):
     def forward(self, x: torch.Tensor, n_samples: int = 1):
         latents = self._encoder(x)
         discretes = self.latent_to_discrete(latents, n_samples)
+        # the default latent_to_discrete is the library's Gumbel kernel, whose spins are exactly +-1: the package's own
+        # decoder is told so (Decoder.forward: spins_pm1); a custom latent_to_discrete never makes that promise
+        from .modules import Decoder
+        if self._custom_l2d is None and isinstance(self._decoder, Decoder):
+            return latents, discretes, self._decoder(discretes, spins_pm1=True)
         return latents, discretes, self._decoder(discretes)
 
 

@@ -784,6 +784,19 @@ int dvg_decoder_fwd_mse_ex(const dvg_decoder_params_t *p, int n_latents, const f
 int dvg_decoder_bwd_mse_ex(const dvg_decoder_params_t *p, int n_latents, const float *spins, int64_t N,
                            const float *images, int R, float grad_scale, const dvg_decoder_grads_t *grads,
                            float *grad_spins, void *ws, size_t ws_bytes, int defer_join, dvg_stream_t stream);
+/* The caller's promise about the `spins` of the NEXT forward call on workspace `ws` (dvg_decoder_fwd, dvg_decoder_fwd_ex,
+ * dvg_decoder_fwd_mse_ex): pm1 != 0 declares that every element is exactly +1.0f or -1.0f, as the output of
+ * dvg_gumbel_fwd is.  The library never looks at the data to find out (no host sync).  The forward call takes the
+ * declaration -- it holds for that one call; a call without a declaration in front of it has made none -- and the
+ * backward call on the same workspace sees what its forward was given.  With the promise the decoder's input layer
+ * (Linear(n,4n), or its composition with the first ConvTranspose2d at large batches) multiplies the spins as exact bf16
+ * values with the float32 weights carried as three bf16 pieces, three exact products on the bf16 matrix pipe summed in
+ * float32, in its forward GEMM and its weight-gradient GEMM under DVG_PRECISION_F32 and DVG_PRECISION_F32_SPLIT3:
+ * float32-class results (the products themselves are exact) at a fraction of the f32 matrix time.
+ * A FALSE promise is not detected: the spins are rounded to bf16 (8 significant bits) in those two GEMMs, every result
+ * stays finite, float32 accuracy is lost.  Host-side bookkeeping only; call it from the thread that makes the forward
+ * call.  (Development option dec_spin_gemm = 0 ignores every declaration.) */
+int dvg_decoder_declare_spins(const void *ws, int pm1);
 
 /* ------------------------------------------------------------------ MSE
  * torch.nn.functional.mse_loss(reconstructed, images.unsqueeze(1).repeat(1,R,...))

@@ -44,3 +44,51 @@ for Cin, Cout, L, imgs in shapes:
         line += f" | {mode} {t:7.1f} us {fl/t/1e6:6.1f} TF/s err {err:.1e}"
     _lib.set_conv_precision("f32")
     print(line, flush=True)
+
+# The decoder head's own launches at c3 (the composed Linear o ConvTranspose map: rows x n x 4 C = 32768 x 512 x 512, one tap,
+# +-1 rows): the forward GEMM in the three operand modes and in the spin-operand form (dev option dev_spin_operand makes
+# the +-1 promise for the hook's input), and its weight-gradient GEMM dW = S^T dY in the float32 and the spin form.
+if len(sys.argv) <= 1:
+    M, Cin, Cout = 32768, 512, 512
+    torch.manual_seed(0)
+    x = (torch.randint(0, 2, (M, Cin), device="cuda").float() * 2 - 1).contiguous()
+    w9 = torch.zeros((Cout, Cin, 3, 3), device="cuda"); w9[:, :, 0, 0] = torch.randn((Cout, Cin), device="cuda") / Cin**0.5
+    dy = torch.randn(M, Cout, device="cuda")
+    want = x[:256].double() @ w9[:, :, 0, 0].double().T
+    fl = 2.0 * M * Cin * Cout
+
+    def head(reps=20):
+        wp = torch.empty(Cin * Cout * 2, device="cuda")
+        out = dev.conv_igemm(x, w9, 0, M, Cin, Cout, 0, 1, 0, 0, wp=wp)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            dev.conv_igemm(x, w9, 0, M, Cin, Cout, 0, 1, 0, 0, wp=wp, repack=False)
+        e1.record(); torch.cuda.synchronize()
+        return float((out[:256].double() - want).abs().max() / want.abs().max()), e0.elapsed_time(e1) / reps * 1e3
+
+    line = f"head fwd   M={M} Cin={Cin} Cout={Cout} 1 tap, +-1 rows "
+    for mode, spin in (("f32", 0), ("f32x3", 0), ("bf16", 0), ("f32", 1), ("f32x3", 1)):
+        _lib.set_conv_precision(mode)
+        _lib.set_option("dev_spin_operand", spin)
+        err, t = head()
+        line += f" | {mode}{' spin' if spin else ''} {t:7.1f} us {fl/t/1e6:6.1f} TF/s err {err:.1e}"
+    _lib.set_conv_precision("f32")
+    print(line, flush=True)
+    want_g = dy.double().T[:64] @ x.double()
+    line = f"head wgrad M={M} Cin={Cin} Cout={Cout} 1 tap, +-1 rows "
+    for spin in (0, 1):
+        _lib.set_option("dev_spin_operand", spin)
+        g = dev.conv_wgrad(x, dy, 0, (Cout, Cin, 3, 3), M, Cin, Cout, 0, ntaps=1)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            dev.conv_wgrad(x, dy, 0, (Cout, Cin, 3, 3), M, Cin, Cout, 0, ntaps=1)
+        e1.record(); torch.cuda.synchronize()
+        t = e0.elapsed_time(e1) / 20 * 1e3
+        err = float((g[:64, :, 0, 0].double() - want_g).abs().max() / want_g.abs().max())
+        line += f" | {'spin' if spin else 'f32 '} {t:7.1f} us (with its slab reduce) err {err:.1e}"
+    _lib.set_option("dev_spin_operand", 0)
+    print(line, flush=True)
