@@ -253,6 +253,11 @@ void spin_promise_declare(const void* ws, bool pm1);
 bool spin_promise_note_forward(const void* ws);
 bool spin_promise_of_forward(const void* ws);          // backward calls: what the forward on this workspace was promised
 int launch_conv_igemm(const ConvArgs& a, hipStream_t s);
+// What launch_conv_igemm decides for a launch from its geometry (M, Cin, Cout, L, ntaps, ups, poolsum, fold), force_f32,
+// spin_a, the options and the operand mode: the block tile bm x bn (cfg: its index in the launcher), the operand form pm
+// (ConvArgs.bf16), the split-K count (1 unless may_split: the launch has a workspace) and the tile order (ConvArgs.posmajor)
+struct IgemmForm { int cfg, bm, bn, pm, ksplit, posmajor, spin; };
+IgemmForm conv_igemm_form(const ConvArgs& a, bool may_split);
 // Winograd F(2x2,3x3) form of a stride-1 3x3 layer (conv_wino.hip): same ConvArgs, `wp` = the transformed pack of
 // launch_wino_weight_pack ([Cin][Cout][16] floats), stats rows = conv_wino_stats_blocks
 // (these files say which SHAPES a form can run and how it is launched; which launches take it is conv_plan.cpp's)
@@ -325,6 +330,11 @@ int launch_lc0_rank1_add(float* dweff, const float* lin_b, const float* dbc, int
 // grad_lin_w[(c*4 + p)][i] = t[(p*n + c)][i]   (rows of the [4n][n] product back into the Linear weight's row order)
 int launch_lc0_rows_to_linear(const float* t, int n, float* grad_lin_w, hipStream_t s);
 int launch_conv_wgrad(const WgradArgs& a, hipStream_t s);
+// Which kernel launch_conv_wgrad takes for a launch (from its geometry, fold, spin_x, the options and the operand mode):
+// the channel tile ba x bb, dma = the LDS-DMA kernel (conv_wgrad9_dma_kernel / conv_wgrad1_dma_kernel) instead of a
+// register-staged one, tap1 = the 1-tap 128 x 128 DMA kernel, spin = its spin form
+struct WgradForm { int ba, bb, dma, tap1, spin; };
+WgradForm conv_wgrad_form(const WgradArgs& a);
 // sums the slabs in order and scatters into the checkpoint layout (grad_w is overwritten)
 int launch_wgrad_reduce(const float* slabs, int ksplit, const WeightMap& map, float* grad_w, hipStream_t s);
 // Wp[tap][a][b] <- checkpoint-layout weight

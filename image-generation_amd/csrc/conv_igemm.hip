@@ -706,15 +706,33 @@ size_t conv_splitk_floats(int64_t M, int Cin, int Cout, int ntaps, int poolsum) 
   return k > 1 ? (size_t)k * (size_t)(poolsum ? M / 4 : M) * Cout : 0;
 }
 
-int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
-  ConvArgs a = a_in;
+// The form of one launch: tile, operand form, split-K count, tile order.  launch_conv_igemm runs what this returns, and
+// dvg_dev_conv_igemm_form reports it (may_split: the launch has a split-K workspace).
+IgemmForm conv_igemm_form(const ConvArgs& a, bool may_split) {
+  IgemmForm f;
+  const int64_t Mg = a.fold == 1 ? a.M * 4 : a.M;  // GEMM rows over all classes
   // (the packs were written in the matching format: launch_weight_pack_multi makes the same decision per job)
-  a.bf16 = conv_launch_mode(a.fold == 1 ? a.M * 4 : a.M, a.Cout);
-  if (a.force_f32 && a.bf16 > 3) a.bf16 = 3;
+  f.pm = conv_launch_mode(Mg, a.Cout);
+  if (a.force_f32 && f.pm > 3) f.pm = 3;
   // the caller's promise that the rows of `in` hold only +-1 (ConvArgs.spin_a): form 6 instead of the float32 or the
   // split form, unless option dec_spin_gemm = 0 ignores it.  (Forms 0 and 5 never switch.)
-  const bool spin = a.spin_a && !a.force_f32 && (a.bf16 == 3 || a.bf16 == 4) && opt(OPT_DEC_SPIN_GEMM) != 0;
-  if (spin) a.bf16 = 6;
+  f.spin = a.spin_a && !a.force_f32 && (f.pm == 3 || f.pm == 4) && opt(OPT_DEC_SPIN_GEMM) != 0;
+  if (f.spin) f.pm = 6;
+  f.cfg = igemm_cfg(Mg, a.Cout);
+  f.bm = igemm_bm(f.cfg);
+  f.bn = igemm_bn(f.cfg);
+  f.ksplit = may_split ? conv_igemm_ksplit(Mg, a.Cin, a.Cout, a.ntaps) : 1;
+  // position-major tiles: plain 3x3 launches of the LDS-DMA form whose images fill whole row blocks (then the grid and
+  // the BatchNorm partial rows are what they were).  option igemm_posmajor = 0: pixel-major tiles everywhere (A/B runs, tests)
+  const int64_t nimg = a.L >= 1 ? a.M >> (2 * a.L) : 0;
+  const bool taps9 = !a.fold && a.ntaps == 9;
+  f.posmajor = opt(OPT_IGEMM_POSMAJOR) != 0 && f.pm >= 3 && (taps9 || a.fold) && !a.ups && !a.poolsum && f.ksplit == 1 &&
+               a.L >= 1 && a.L <= 5 && nimg > 0 && (nimg << (2 * a.L)) == a.M && nimg % f.bm == 0;
+  return f;
+}
+
+int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
+  ConvArgs a = a_in;
   const bool taps_ok = a.fold == 1 ? a.ntaps == 4 : a.fold == 2 ? a.ntaps == 16 : (a.ntaps == 9 || a.ntaps == 1);
   if (a.fold && (a.ups || a.poolsum || !conv_fold_ok(a.M))) {
     set_error("conv_igemm: fold=%d needs ups=poolsum=0 and whole 128-row blocks (M=%lld)", a.fold, (long long)a.M);
@@ -724,6 +742,9 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     set_error("conv_igemm: unsupported shape Cin=%d Cout=%d M=%lld ntaps=%d", a.Cin, a.Cout, (long long)a.M, a.ntaps);
     return DVG_E_INVALID;
   }
+  const IgemmForm form = conv_igemm_form(a, a.splitk_ws != nullptr);
+  const bool spin = form.spin;
+  a.bf16 = form.pm; a.ksplit = form.ksplit; a.posmajor = form.posmajor;
   // the kernel addresses its input and weights with 32-bit byte offsets
   const double in_bytes = (double)(a.ups ? a.M / 4 : (a.fold == 2 ? a.M * 4 : a.M)) * a.Cin * 4.0;
   if (in_bytes >= 4294901760.0 || a.M >= 2147483647LL) {  // (0xFFFF0000: offsets from there up mean "padding")
@@ -733,16 +754,9 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
   // FLOPs executed (the folded forms do 4/9 of the 9-tap count): what the roofline is priced on
   const int64_t Mg = a.fold == 1 ? a.M * 4 : a.M;  // GEMM rows over all classes
   const double flops = 2.0 * (double)Mg * a.Cin * a.Cout * a.ntaps;
-  a.ksplit = a.splitk_ws ? conv_igemm_ksplit(Mg, a.Cin, a.Cout, a.ntaps) : 1;
   double flops_exec = flops;
   {
-    // position-major tiles: plain 3x3 launches of the LDS-DMA form whose images fill whole row blocks (then the grid and
-    // the BatchNorm partial rows are what they were).  option igemm_posmajor = 0: pixel-major tiles everywhere (A/B runs, tests)
-    const int bm_ = igemm_bm(igemm_cfg(Mg, a.Cout));
     const int64_t nimg = a.L >= 1 ? a.M >> (2 * a.L) : 0;
-    const bool taps9 = !a.fold && a.ntaps == 9;
-    a.posmajor = opt(OPT_IGEMM_POSMAJOR) != 0 && a.bf16 >= 3 && (taps9 || a.fold) && !a.ups && !a.poolsum && a.ksplit == 1 &&
-                 a.L >= 1 && a.L <= 5 && nimg > 0 && (nimg << (2 * a.L)) == a.M && nimg % bm_ == 0;
     if (a.posmajor) {
       // executed FLOPs: the (pixel, [class,] tap) combinations whose displacement stays inside the image
       const int H = 1 << a.L;
@@ -761,9 +775,9 @@ int launch_conv_igemm(const ConvArgs& a_in, hipStream_t s) {
     }
   }
   const unsigned kz = (unsigned)a.ksplit;
-  const int cfg = igemm_cfg(Mg, a.Cout);
+  const int cfg = form.cfg;
   const unsigned cm = a.fold == 1 ? 4u : 1u;
-  const int bm = igemm_bm(cfg), bn = igemm_bn(cfg);
+  const int bm = form.bm, bn = form.bn;
   const dim3 grid(cm * (unsigned)ceil_div(a.M, bm), (unsigned)(a.Cout / bn), kz);
   int rc;
   // (weight-space products of the composed decoder layers: their own profiler id, always float32; the spin-operand

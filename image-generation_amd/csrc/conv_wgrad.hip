@@ -816,22 +816,51 @@ static int launch_wgrad9_dma(int id, double flops, dim3 grid, const WgradArgs& a
   return DVG_OK;
 }
 
+// The kernel a launch takes; launch_conv_wgrad runs what this returns, and dvg_dev_conv_wgrad_form reports it.
+WgradForm conv_wgrad_form(const WgradArgs& a) {
+  WgradForm f;
+  f.tap1 = f.spin = 0;
+  if (a.fold) {
+    f.ba = f.bb = 32;
+    f.dma = wgrad_dma_on() && (double)a.M * a.Cin * 4.0 < 4294901760.0 && (double)a.M * 4.0 * a.Cout * 4.0 < 4294901760.0;
+    return f;
+  }
+  f.ba = a.Cin % 64 == 0 ? 64 : 32;
+  f.bb = a.Cout % 64 == 0 ? 64 : 32;
+  if (a.ntaps == 9) {
+    // LDS-DMA form (32-bit offsets: both tensors below 0xFFFF0000 bytes); option wgrad_dma = 0: the register-staged form
+    const double xbytes = (double)(a.ups ? a.M / 4 : a.M) * a.Cin * 4.0, ybytes = (double)a.M * a.Cout * 4.0;
+    f.dma = wgrad_dma_on() && xbytes < 4294901760.0 && ybytes < 4294901760.0;
+    return f;
+  }
+  f.dma = f.tap1 = a.ntaps == 1 && wgrad1_dma_ok(a.M, a.Cin, a.Cout);
+  if (f.tap1) {
+    f.ba = f.bb = 128;
+    // the caller's promise that `in` holds only +-1 (WgradArgs.spin_x): the spin form, unless option dec_spin_gemm = 0
+    // ignores it (2: the forward GEMM alone takes the form, A/B runs); never under bf16 GEMM inputs (as the forward
+    // kernel's form 5 never switches)
+    f.spin = a.spin_x && opt(OPT_DEC_SPIN_GEMM) == 1 && conv_precision_mode() != 1;
+  }
+  return f;
+}
+
 int launch_conv_wgrad(const WgradArgs& a, hipStream_t s) {
   if (a.Cin % 32 || a.Cout % 32 || a.M <= 0 || a.ksplit < 1) {
     set_error("conv_wgrad: unsupported shape Cin=%d Cout=%d M=%lld", a.Cin, a.Cout, (long long)a.M);
     return DVG_E_INVALID;
   }
+  const WgradForm form = conv_wgrad_form(a);
   if (a.fold) {
     if (a.ntaps != 16 || a.ups) { set_error("conv_wgrad: fold needs ntaps=16, ups=0"); return DVG_E_INVALID; }
     const double fl = 2.0 * (double)a.M * a.Cin * a.Cout * 16;  // executed FLOPs (4/9 of the 9-tap form)
-    if (wgrad_dma_on() && (double)a.M * a.Cin * 4.0 < 4294901760.0 && (double)a.M * 4.0 * a.Cout * 4.0 < 4294901760.0)
+    if (form.dma)
       return launch_wgrad9_dma<1, 1, 4, true>(K_WGRAD_FOLD, fl, dim3((unsigned)((a.Cin / 32) * (a.Cout / 32)), (unsigned)a.ksplit), a, s);
     DVG_LAUNCH_WORK(K_WGRAD_FOLD, fl, conv_wgrad_fold_kernel, dim3((unsigned)((a.Cin / 32) * (a.Cout / 32)), (unsigned)a.ksplit),
                     dim3(256), 0, s, a);
     return DVG_OK;
   }
-  const bool a64 = a.Cin % 64 == 0, b64 = a.Cout % 64 == 0;
-  const int ba = a64 ? 64 : 32, bb = b64 ? 64 : 32;
+  const bool a64 = form.ba == 64, b64 = form.bb == 64;
+  const int ba = form.ba, bb = form.bb;
   const double flops = 2.0 * (double)a.M * a.Cin * a.Cout * a.ntaps;
   if (a.ntaps == 9) {
     const dim3 g9((unsigned)((a.Cin / ba) * (a.Cout / bb)), (unsigned)a.ksplit);
@@ -839,9 +868,7 @@ int launch_conv_wgrad(const WgradArgs& a, hipStream_t s) {
     // (4 waves x 9 tiles, one per SIMD): +10 % on the kernel in-situ (c3 53 -> 59, c2 41 -> 45 TFLOP/s), steps neutral
     // to -1 %.  (The 4-wave form is still instantiated for the shapes that need it.)
     constexpr bool wt2 = true;
-    // LDS-DMA form (32-bit offsets: both tensors below 0xFFFF0000 bytes); option wgrad_dma = 0: the register-staged form
-    const double xbytes = (double)(a.ups ? a.M / 4 : a.M) * a.Cin * 4.0, ybytes = (double)a.M * a.Cout * 4.0;
-    if (wgrad_dma_on() && xbytes < 4294901760.0 && ybytes < 4294901760.0) {
+    if (form.dma) {
       if (a64 && b64) return launch_wgrad9_dma<2, 2, 2>(K_WGRAD_2x2, flops, g9, a, s);
       if (a64) return launch_wgrad9_dma<2, 1, 2>(K_WGRAD_2x1, flops, g9, a, s);
       if (b64) return launch_wgrad9_dma<1, 2, 2>(K_WGRAD_1x2, flops, g9, a, s);
@@ -854,12 +881,9 @@ int launch_conv_wgrad(const WgradArgs& a, hipStream_t s) {
     else DVG_LAUNCH_WORK(K_WGRAD_1x1, flops, (conv_wgrad9_kernel<1, 1, 4>), g9, dim3(256), 0, s, a);
     return DVG_OK;
   }
-  if (a.ntaps == 1 && wgrad1_dma_ok(a.M, a.Cin, a.Cout)) {
+  if (form.tap1) {
     const dim3 g1((unsigned)((a.Cin / 128) * (a.Cout / 128)), (unsigned)a.ksplit);
-    // the caller's promise that `in` holds only +-1 (WgradArgs.spin_x): the spin form, unless option dec_spin_gemm = 0
-    // ignores it (2: the forward GEMM alone takes the form, A/B runs); never under bf16 GEMM inputs (as the forward
-    // kernel's form 5 never switches)
-    if (a.spin_x && opt(OPT_DEC_SPIN_GEMM) == 1 && conv_precision_mode() != 1) {
+    if (form.spin) {
       auto kern = conv_wgrad1_dma_kernel<true>;
       static std::atomic<uint64_t> attr_done{0};
       DVG_TRY(raise_dynamic_lds(attr_done, (const void*)kern, 65536));

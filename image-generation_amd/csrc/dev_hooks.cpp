@@ -18,20 +18,34 @@ extern "C" int dvg_dev_conv_igemm(const float* in, const float* w, int mode, flo
   a.spin_a = opt(OPT_DEV_SPIN_OPERAND) != 0;  // (test knob: the +-1 promise for `in`)
   return launch_conv_igemm(a, s);
 }
+// The form launch_conv_igemm gives that launch under the current options and operand mode (conv_igemm_form; needs no device)
+extern "C" int dvg_dev_conv_igemm_form(int64_t M, int Cin, int Cout, int L, int ntaps, int ups, int poolsum, int out[5]) {
+  DVG_REQUIRE(out && M > 0 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0 && (ntaps == 9 || ntaps == 1),
+              "dev_conv_igemm_form: bad argument");
+  ConvArgs a;
+  a.in = a.wp = a.bias = nullptr; a.out = a.stats = a.splitk_ws = nullptr;
+  a.M = M; a.Cin = Cin; a.Cout = Cout; a.L = L; a.ntaps = ntaps; a.ups = ups; a.poolsum = poolsum;
+  a.spin_a = opt(OPT_DEV_SPIN_OPERAND) != 0;
+  const IgemmForm f = conv_igemm_form(a, true);
+  out[0] = f.bm; out[1] = f.bn; out[2] = f.pm; out[3] = f.ksplit; out[4] = f.posmajor;
+  return DVG_OK;
+}
 
 // The same layer in the Winograd F(2x2,3x3) form (conv_wino.hip): `u` takes the 16 Cin Cout transformed weights; stats rows =
-// dvg_dev_conv_wino_stats_blocks.  DVG_E_INVALID when the shape does not qualify (dvg_dev_conv_wino_ok).
+// dvg_dev_conv_wino_stats_blocks.  DVG_E_INVALID when the shape does not qualify (dvg_dev_conv_wino_shape).  um as in
+// dvg_dev_conv_wino4: 1 = the forward behind the x2 upsample, 2 = its data gradient; cus: CUs the persistent grid is sized for.
 extern "C" int dvg_dev_conv_wino(const float* in, const float* w, int mode, float* u, const float* bias, float* out,
-                                 float* stats, int64_t M, int Cin, int Cout, int L, dvg_stream_t stream) {
+                                 float* stats, int64_t M, int Cin, int Cout, int L, int cus, int um, dvg_stream_t stream) {
   DVG_REQUIRE(in && w && u && out, "dev_conv_wino: null argument");
   hipStream_t s = (hipStream_t)stream;
   DVG_TRY(launch_wino_weight_pack(w, WeightMap{mode, Cin, Cout, 9}, u, s));
   ConvArgs a;
   a.in = in; a.wp = u; a.bias = bias; a.out = out; a.stats = stats;
   a.M = M; a.Cin = Cin; a.Cout = Cout; a.L = L; a.ntaps = 9; a.ups = 0; a.poolsum = 0;
-  a.splitk_ws = nullptr;
+  a.splitk_ws = nullptr; a.wino_cus = cus; a.wino_um = um;
   return launch_conv_wino(a, s);
 }
+extern "C" int dvg_dev_conv_wino_shape(int64_t M, int Cin, int Cout, int L) { return conv_wino_shape(M, Cin, Cout, L) ? 1 : 0; }
 // The same layer in the Winograd F(4x4,3x3) form (conv_wino4.hip): `u` takes the 36 Cin Cout transformed weights; stats rows =
 // M / 1024.  DVG_E_INVALID when the shape does not qualify (dvg_dev_conv_wino4_shape).  The launch stands for the encoder layer
 // of its image side (L = 4, 3, 2: layers 1, 2, 3; mode 0 the forward, 1 the data gradient): with that launch's block-shape bit
@@ -132,6 +146,18 @@ extern "C" int dvg_dev_conv_wgrad(const float* in, const float* dy, float* slabs
   wa.spin_x = opt(OPT_DEV_SPIN_OPERAND) != 0;  // (test knob: the +-1 promise for `in`)
   DVG_TRY(launch_conv_wgrad(wa, s));
   return launch_wgrad_reduce(slabs, wa.ksplit, WeightMap{mode, Cin, Cout, ntaps}, grad_w, s);
+}
+// The kernel launch_conv_wgrad takes for that launch under the current options and operand mode (conv_wgrad_form; needs no device)
+extern "C" int dvg_dev_conv_wgrad_form(int64_t M, int Cin, int Cout, int ntaps, int ups, int out[5]) {
+  DVG_REQUIRE(out && M > 0 && Cin >= 32 && Cout >= 32 && Cin % 32 == 0 && Cout % 32 == 0 && (ntaps == 9 || ntaps == 1),
+              "dev_conv_wgrad_form: bad argument");
+  WgradArgs wa;
+  wa.in = wa.dy = nullptr; wa.slabs = nullptr; wa.M = M; wa.Cin = Cin; wa.Cout = Cout; wa.L = 0; wa.ntaps = ntaps;
+  wa.ups = ups; wa.ksplit = 1;
+  wa.spin_x = opt(OPT_DEV_SPIN_OPERAND) != 0;
+  const WgradForm f = conv_wgrad_form(wa);
+  out[0] = f.ba; out[1] = f.bb; out[2] = f.dma; out[3] = f.tap1; out[4] = f.spin;
+  return DVG_OK;
 }
 
 extern "C" size_t dvg_dev_wino_wgrad_slab_floats(int64_t M, int Cin, int Cout, int L) {

@@ -12,8 +12,11 @@ _SIGS = {
                            [ctypes.c_int64] + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_void_p]),
     "dvg_dev_conv_splitk_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_conv_stats_blocks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int]),
+    "dvg_dev_conv_igemm_form": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)]),
+    "dvg_dev_conv_wgrad_form": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)]),
     "dvg_dev_conv_wino": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 +
-                          [ctypes.c_int64] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+                          [ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "dvg_dev_conv_wino_shape": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dvg_dev_conv_wino4": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 +
                            [ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
     "dvg_dev_conv_wino4_shape": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
@@ -91,8 +94,31 @@ def conv_igemm(x_m, w, mode, M, Cin, Cout, L, ntaps=9, ups=0, poolsum=0, bias=No
     return (out, st) if stats else out
 
 
+def conv_igemm_form(M, Cin, Cout, L, ntaps=9, ups=0, poolsum=0):
+    """The form ``conv_igemm`` of these arguments takes under the current options and operand mode (the launcher's own
+    decision; no device needed): ``tile`` = (BM, BN), ``pm`` = the operand form (0 float32 through registers, 3 float32 by
+    LDS-DMA, 4 f32x3, 5 bf16 inputs, 6 spin A), ``ksplit`` = the split-K count (1: unsplit), ``posmajor``."""
+    o = (ctypes.c_int * 5)()
+    _lib.check(lib().dvg_dev_conv_igemm_form(M, Cin, Cout, L, ntaps, ups, poolsum, o), "dvg_dev_conv_igemm_form")
+    return dict(tile=(o[0], o[1]), pm=o[2], ksplit=o[3], posmajor=bool(o[4]))
+
+
+def conv_wgrad_form(M, Cin, Cout, ntaps=9, ups=0):
+    """The kernel ``conv_wgrad`` of these arguments takes under the current options and operand mode (no device needed):
+    ``tile`` = the channel tile (Cin x Cout), ``dma`` = an LDS-DMA kernel (``conv_wgrad9_dma_kernel<tile[0] / 32, tile[1] / 32, ..>``
+    or the 1-tap ``conv_wgrad1_dma_kernel``) instead of a register-staged one, ``tap1_dma``, ``spin`` = its spin form."""
+    o = (ctypes.c_int * 5)()
+    _lib.check(lib().dvg_dev_conv_wgrad_form(M, Cin, Cout, ntaps, ups, o), "dvg_dev_conv_wgrad_form")
+    return dict(tile=(o[0], o[1]), dma=bool(o[2]), tap1_dma=bool(o[3]), spin=bool(o[4]))
+
+
 def conv_wino_ok(M, Cin, Cout, L):
     return bool(lib().dvg_dev_conv_wino_ok(M, Cin, Cout, L))
+
+
+def conv_wino_shape(M, Cin, Cout, L):
+    """Whether the F(2x2,3x3) form can run the shape (whatever option enc_wino says)."""
+    return bool(lib().dvg_dev_conv_wino_shape(M, Cin, Cout, L))
 
 
 FORMS = ("direct", "fold", "d22", "lc0", "wino2", "wino4")  # csrc/conv_plan.h: ConvForm
@@ -175,15 +201,18 @@ def gibbs_exchange_plan(plan, n_ladders, n_replicas):
     return dict(_gibbs_plan_dict(o), ladders_per_workgroup=o[19])
 
 
-def conv_wino(x_m, w, mode, M, Cin, Cout, L, bias=None, stats=False):
-    """The stride-1 3x3 layer of conv_igemm (modes 0 / 1) in the Winograd F(2x2,3x3) form (csrc/conv_wino.hip)."""
+def conv_wino(x_m, w, mode, M, Cin, Cout, L, bias=None, stats=False, cus=0, um=0):
+    """The stride-1 3x3 layer of conv_igemm (modes 0 / 1) in the Winograd F(2x2,3x3) form (csrc/conv_wino.hip).  ``um`` as in
+    :func:`conv_wino4`: 1 = the Upsample(x2) + 3x3 forward (``x_m`` = the source map, M / L of the output grid; 9 of the 16
+    positions), 2 = its data gradient (``x_m`` = the fine-grid gradient, the result = the source map's gradient, M / 4 rows).
+    ``cus``: CUs the persistent grid is sized for (0 = 256)."""
     Lb = lib()
     dev = x_m.device
     u = torch.empty(16 * Cin * Cout, device=dev)
-    out = torch.empty((M, Cout), device=dev)
+    out = torch.empty((M // 4 if um == 2 else M, Cout), device=dev)
     st = torch.empty((Lb.dvg_dev_conv_wino_stats_blocks(M, Cout), Cout, 2), device=dev) if stats else None
     _lib.check(Lb.dvg_dev_conv_wino(x_m.data_ptr(), w.data_ptr(), mode, u.data_ptr(), _lib.ptr(bias), out.data_ptr(),
-                                    _lib.ptr(st), M, Cin, Cout, L, _lib.stream_ptr(dev)))
+                                    _lib.ptr(st), M, Cin, Cout, L, int(cus), int(um), _lib.stream_ptr(dev)))
     return (out, st) if stats else out
 
 

@@ -15,11 +15,22 @@ int dvg_dev_conv_igemm(const float *in, const float *w, int mode, float *wp, con
                        float *stats, int64_t M, int Cin, int Cout, int L, int ntaps, int ups, int poolsum,
                        int repack, float *splitk_ws, dvg_stream_t stream);
 size_t dvg_dev_conv_splitk_floats(int64_t M, int Cin, int Cout, int ntaps, int poolsum);
+/* The form that launch takes under the current options and operand mode (csrc/conv.h: conv_igemm_form, the launcher's own
+ * decision; needs no device): out[0], out[1] = the block tile BM x BN; out[2] = the operand form, the PM argument of
+ * conv_igemm_kernel (0 float32 through registers, 3 float32 by LDS-DMA, 4 f32x3, 5 bf16 inputs, 6 spin A under dev option
+ * dev_spin_operand); out[3] = the split-K count of a launch that has a workspace (1: unsplit); out[4] = position-major tiles. */
+int dvg_dev_conv_igemm_form(int64_t M, int Cin, int Cout, int L, int ntaps, int ups, int poolsum, int out[5]);
 /* The same stride-1 3x3 layer in the Winograd F(2x2,3x3) form the encoder uses from 256 workgroups up (option enc_wino):
  * `u` = scratch of 16*Cin*Cout floats (transformed weights), `stats` rows = dvg_dev_conv_wino_stats_blocks(M, Cout).
  * Replaces (with the implicit GEMM above) /root/reference/src/encoder.py:28-36's nn.Conv2d calls. */
 int dvg_dev_conv_wino(const float *in, const float *w, int mode, float *u, const float *bias, float *out, float *stats,
-                      int64_t M, int Cin, int Cout, int L, dvg_stream_t stream);
+                      int64_t M, int Cin, int Cout, int L, int cus, int um, dvg_stream_t stream);
+/* (cus = CUs the persistent grid is sized for, 0 = 256; um as in dvg_dev_conv_wino4 below: 1 = Upsample(x2) + 3x3 forward,
+ * `in` = the source map ([M / 4][Cin]), M and L of the output grid, 9 of 16 positions; 2 = its data gradient, `in` = the
+ * fine-grid gradient, `out` = the source map's gradient ([M / 4][Cout]).  Cout % 64 == 0 runs conv_wino8_kernel<2,2,8,um>,
+ * any other Cout % 32 == 0 conv_wino8_kernel<4,1,4,um>.)
+ * ... whether the form can run the shape at all (whatever option enc_wino says) */
+int dvg_dev_conv_wino_shape(int64_t M, int Cin, int Cout, int L);
 /* ... whether a training call's forward launch of this shape takes that form under the current options and operand mode */
 int dvg_dev_conv_wino_ok(int64_t M, int Cin, int Cout, int L);
 /* The kernel form every MFMA convolution layer of a network call takes under the current options and operand mode
@@ -84,6 +95,11 @@ int dvg_dev_conv_stats_blocks(int64_t M, int Cout);
 size_t dvg_dev_wgrad_slab_floats(int64_t M, int Cin, int Cout, int ntaps);
 int dvg_dev_conv_wgrad(const float *in, const float *dy, float *slabs, float *grad_w, int mode, int64_t M, int Cin,
                        int Cout, int L, int ntaps, int ups, dvg_stream_t stream);
+/* The kernel that launch takes under the current options and operand mode (csrc/conv.h: conv_wgrad_form, the launcher's own
+ * decision; needs no device): out[0], out[1] = the channel tile (Cin x Cout: 32 / 64 each, 128 x 128 for the 1-tap DMA
+ * kernel); out[2] = 1 LDS-DMA (conv_wgrad9_dma_kernel<out[0] / 32, out[1] / 32, ..> or conv_wgrad1_dma_kernel), 0 register-
+ * staged; out[3] = 1 the 1-tap DMA kernel; out[4] = its spin form (conv_wgrad1_dma_kernel<true>, dev option dev_spin_operand). */
+int dvg_dev_conv_wgrad_form(int64_t M, int Cin, int Cout, int ntaps, int ups, int out[5]);
 /* The same weight gradient in the Winograd F(2x2,3x3) form (conv_wino_wgrad.hip; ups = 1: `in` is the source map of an Upsample(x2) + 3x3 layer): slabs of
  * dvg_dev_wino_wgrad_slab_floats() floats (0 = the shape does not qualify). */
 size_t dvg_dev_wino_wgrad_slab_floats(int64_t M, int Cin, int Cout, int L);

@@ -205,6 +205,88 @@ def test_winograd_f4x4_data_gradient_behind_the_upsample(N, Cin, Cout, side):
     assert torch.equal(dx, dev.conv_wino4(gym, w.cuda(), 3, M, Cout, Cin, L, um=2))
 
 
+# F(2x2,3x3) behind the upsample (conv_wino8_kernel<2,2,8,UM> for 64-channel column blocks, <4,1,4,UM,0> for 32-channel ones).
+# N, Ci, Co (of the LAUNCH), side (of the fine grid), cus: a tile block is 256 fine-grid rows at Co % 64 == 0, 512 otherwise;
+# a chunk is 8 / 4 reduction channels; cus / (Co / 64 or 32) workgroups per column block share the tile blocks, and from
+# three blocks per workgroup the deal is dynamic.
+WINO2_UPS_CASES = [
+    (16, 16, 64, 4, 0),     # one tile block, two chunks (the first stage pair is the last)
+    (8, 8, 32, 8, 0),       # the same in the 32-channel tile
+    (32, 48, 64, 8, 0),     # three chunk pairs, 8 tile blocks on 8 workgroups
+    (128, 32, 128, 4, 4),   # two column blocks x 2 workgroups, 8 tile blocks: four per workgroup, dealt dynamically
+    (64, 24, 96, 8, 6),     # three 32-channel column blocks x 2 workgroups, 8 tile blocks, three chunk pairs
+    (64, 128, 64, 4, 1),    # the decoder's 128 -> 64 layer onto 4x4: one workgroup takes all four tile blocks
+    (32, 64, 32, 8, 1),     # its 64 -> 32 layer onto 8x8, likewise
+    (32, 32, 64, 8, 2),     # the 64 -> 32 layer's data gradient (launch 32 -> 64)
+]
+
+
+def _wino2_ups_geometry(N, Ci, Co, side, cus):
+    """(L, M) of a case, after checking on the host that it is what its comment says: the shape qualifies, whole tile blocks."""
+    from image_generation_amd import _lib
+    L, M = side.bit_length() - 1, N * side * side
+    assert dev.conv_wino_shape(M, Ci, Co, L) and M % (256 if Co % 64 == 0 else 512) == 0
+    _lib.lib().dvg_decoder_workspace_bytes(64, 64)  # (creates the device's tile counters: without them every deal is static)
+    return L, M
+
+
+def _pad_channels(t, dim):
+    """t with zero channels appended along dim up to a multiple of 32: the direct kernel's reduction runs over whole
+    32-channel groups, and zero channels times zero weights add exact zeros -- the same inputs, the same products."""
+    shape = list(t.shape)
+    shape[dim] = -shape[dim] % 32
+    return torch.cat([t, torch.zeros(shape)], dim) if shape[dim] else t
+
+
+@pytest.mark.parametrize("N,Cin,Cout,side,cus", WINO2_UPS_CASES)
+def test_winograd_f2x2_behind_the_upsample(N, Cin, Cout, side, cus):
+    """The decoder's Upsample(x2) + ConvTranspose2d 3x3 forward in the F(2x2,3x3) form with 9 of the 16 positions
+    (csrc/conv_wino.hip, UM = 1: a quad's patch is 3x3 source pixels) against conv_transpose2d of the nearest-upsampled map in
+    float64, at the plain F(2x2) form's rule: within 4x the direct kernel's own distance (conv_igemm with ups = 1) on the same
+    inputs, under that kernel's absolute bar, BatchNorm partials as the direct kernel's, the same launch twice the same bits."""
+    L, M = _wino2_ups_geometry(N, Cin, Cout, side, cus)
+    torch.manual_seed(N + Cin + side)
+    xs = torch.randn(N, Cin, side // 2, side // 2)
+    w = torch.randn(Cin, Cout, 3, 3) / (3 * Cin**0.5); b = torch.randn(Cout)
+    y64 = F.conv_transpose2d(F.interpolate(xs.double(), scale_factor=2, mode="nearest"), w.double(), b.double(), padding=1)
+    xm = dev.nchw_to_morton(xs).cuda()
+    out, st = dev.conv_wino(xm, w.cuda(), 2, M, Cin, Cout, L, bias=b.cuda(), stats=True, cus=cus, um=1)
+    xp, wp = _pad_channels(xs, 1), _pad_channels(w, 0)
+    out_d = dev.conv_igemm(dev.nchw_to_morton(xp).cuda(), wp.cuda(), 2, M, xp.shape[1], Cout, L, ups=1, bias=b.cuda())
+    e_w = _rel(dev.morton_to_nchw(out.cpu(), N, Cout, side), y64)
+    e_d = _rel(dev.morton_to_nchw(out_d.cpu(), N, Cout, side), y64)
+    print(f"F(2x2) behind the upsample vs float64 [N={N} {Cin}->{Cout} @{side} cus={cus}]: max {e_w:.2e}; direct max {e_d:.2e}")
+    assert e_w <= 4 * e_d + 1e-8 and e_w < 2e-6, (e_w, e_d)
+    s = st.sum(0).cpu().double()
+    assert _rel(s[:, 0], y64.sum((0, 2, 3))) < 1e-4 and _rel(s[:, 1], (y64 ** 2).sum((0, 2, 3))) < 1e-5
+    out2, st2 = dev.conv_wino(xm, w.cuda(), 2, M, Cin, Cout, L, bias=b.cuda(), stats=True, cus=cus, um=1)
+    assert torch.equal(out, out2) and torch.equal(st, st2)
+
+
+@pytest.mark.parametrize("N,Ci,Co,side,cus", WINO2_UPS_CASES)
+def test_winograd_f2x2_data_gradient_behind_the_upsample(N, Ci, Co, side, cus):
+    """The data gradient of the same layer onto the source map (csrc/conv_wino.hip, UM = 2: the fine-grid gradient's patches,
+    the 2x2 sum of the upsample's adjoint folded into the output transform, one output row per quad) against the adjoint in
+    float64, at the same rule: within 4x the direct kernel's distance (conv_igemm with poolsum = 1), under its absolute bar.
+    Ci: channels of the fine-grid gradient (the layer's Cout); Co: of the source map (the layer's Cin)."""
+    L, M = _wino2_ups_geometry(N, Ci, Co, side, cus)
+    torch.manual_seed(N + Ci + side + 1)
+    w = torch.randn(Co, Ci, 3, 3) / (3 * Ci**0.5)
+    gy = torch.randn(N, Ci, side, side)
+    # d/d(source) = the 2x2 sums of the transposed convolution's adjoint (a plain convolution with the same weight)
+    ref = F.conv2d(gy.double(), w.double(), padding=1).reshape(N, Co, side // 2, 2, side // 2, 2).sum((3, 5))
+    gym = dev.nchw_to_morton(gy).cuda()
+    dx = dev.conv_wino(gym, w.cuda(), 3, M, Ci, Co, L, cus=cus, um=2)
+    assert dx.shape == (M // 4, Co)
+    gp, wp = _pad_channels(gy, 1), _pad_channels(w, 1)
+    dd = dev.conv_igemm(dev.nchw_to_morton(gp).cuda(), wp.cuda(), 3, M, gp.shape[1], Co, L, poolsum=1)
+    g_w = _rel(dev.morton_to_nchw(dx.cpu(), N, Co, side // 2), ref)
+    g_d = _rel(dev.morton_to_nchw(dd.cpu(), N, Co, side // 2), ref)
+    print(f"F(2x2) data gradient behind the upsample vs float64 [N={N} {Ci}->{Co} @{side} cus={cus}]: max {g_w:.2e}; direct max {g_d:.2e}")
+    assert g_w <= 4 * g_d + 1e-8 and g_w < 3e-6, (g_w, g_d)
+    assert torch.equal(dx, dev.conv_wino(gym, w.cuda(), 3, M, Ci, Co, L, cus=cus, um=2))
+
+
 @pytest.mark.parametrize("N,Cin,Cout,side,cus", [(64, 32, 64, 16, 0), (256, 64, 128, 8, 0), (512, 128, 512, 4, 0),   # the encoder's layers 1-3
                                                  (36, 64, 64, 8, 0), (4, 32, 64, 4, 0), (8, 64, 32, 16, 0),          # few images (no split), the 64 x 32 tile on 16x16
                                                  (512, 128, 512, 4, 256), (64, 32, 64, 16, 256)])                   # the whole chip's split

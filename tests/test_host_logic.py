@@ -227,3 +227,63 @@ def test_benchmark_mmd_shapes_take_the_pinned_kernel_forms(config, options):
                     4 * p["splits"] * nx * d if p["splits"] > 1 else 0, 4, (nx + ny) * d, rows32 * d * 32 * 2, 2 * (d + 1) * 16,
                     (nx + ny) * d // 2 if d in (256, 512) else 0]
         assert sum(_align256(s) for s in segments) == ws
+
+
+def test_launch_form_hooks_report_the_launchers_rules():
+    """dev.conv_igemm_form / dev.conv_wgrad_form / dev.conv_wino_shape (no device): the launchers' own decisions, which the
+    under-load tests assert their instantiations through.  The expected values follow from the rules written in the
+    launchers: the block tile from the block counts (csrc/conv_igemm.hip: 128x128 from 512 such blocks at Cout % 128 == 0,
+    128x64 from 512, 64x64 from 96, else 32x64; 128x32 at Cout % 64 != 0), split K below 192 blocks (at most a third of the
+    K iterations), the operand form from the operand mode and the spin promise; the weight gradient's channel tile from
+    the channel counts and its 1-tap 128 x 128 kernel from 256 blocks of 256 rows."""
+    from image_generation_amd import _lib, dev
+    _lib.check(_lib.lib().dvg_reset_options(), "dvg_reset_options")
+    form = dev.conv_igemm_form
+    assert form(262144, 64, 128, 3) == dict(tile=(128, 128), pm=3, ksplit=1, posmajor=True)       # 2048 blocks of 128 x 128
+    assert form(65536, 32, 64, 3) == dict(tile=(128, 64), pm=3, ksplit=1, posmajor=True)          # 512 blocks of 128 x 64
+    assert form(65408, 32, 64, 3)["tile"] == (64, 64)                                             # 511
+    assert form(16384, 64, 64, 3) == dict(tile=(64, 64), pm=3, ksplit=1, posmajor=True)           # 256 blocks: unsplit
+    # 32 blocks of 64 x 64 -> 64 of 32 x 64; 36 K iterations of two 32-channel taps: ceil(512 / 64) = 8 <= 36 / 3
+    assert form(2048, 256, 64, 2) == dict(tile=(32, 64), pm=3, ksplit=8, posmajor=False)
+    assert form(16384, 64, 96, 3)["tile"] == (128, 32)
+    assert not form(16384, 64, 64, 3, ups=1)["posmajor"] and not form(16384, 64, 64, 3, poolsum=1)["posmajor"]
+    assert form(16384, 512, 512, 0, ntaps=1) == dict(tile=(128, 128), pm=3, ksplit=1, posmajor=False)  # 512 blocks exactly
+    assert form(16384 - 128, 512, 512, 0, ntaps=1)["tile"] == (128, 64)                               # 508: 1016 of 128 x 64
+    with _lib.option_scope(igemm_posmajor=0):
+        assert not form(16384, 64, 64, 3)["posmajor"]
+    with _lib.option_scope(igemm_dma=0):
+        assert form(16384, 64, 64, 3)["pm"] == 0
+    try:
+        for mode, pm, pm_spin in (("f32", 3, 6), ("f32x3", 4, 6), ("bf16", 5, 5)):
+            _lib.set_conv_precision(mode)
+            assert form(16384, 64, 128, 3)["pm"] == pm
+            with _lib.option_scope(dev_spin_operand=1):
+                assert form(16384, 64, 128, 3)["pm"] == pm_spin
+                with _lib.option_scope(dec_spin_gemm=0):
+                    assert form(16384, 64, 128, 3)["pm"] == pm
+                if mode == "bf16":
+                    assert not dev.conv_wgrad_form(16384, 256, 256, ntaps=1)["spin"]
+    finally:
+        _lib.set_conv_precision("f32")
+    with pytest.raises(_lib.DvgError):
+        form(16384, 16, 64, 3)
+    wform = dev.conv_wgrad_form
+    for Cin, Cout in ((128, 96), (96, 128), (96, 96), (128, 128)):
+        tile = (64 if Cin % 64 == 0 else 32, 64 if Cout % 64 == 0 else 32)
+        assert wform(16384, Cin, Cout) == wform(16384, Cin, Cout, ups=1) == dict(tile=tile, dma=True, tap1_dma=False, spin=False)
+        with _lib.option_scope(wgrad_dma=0):
+            assert not wform(16384, Cin, Cout)["dma"]
+    assert wform(16384, 256, 256, ntaps=1) == dict(tile=(128, 128), dma=True, tap1_dma=True, spin=False)  # 4 x 64 blocks
+    assert wform(16384 - 256, 256, 256, ntaps=1) == dict(tile=(64, 64), dma=False, tap1_dma=False, spin=False)  # 4 x 63
+    assert wform(65536, 128, 384, ntaps=1)["tile"] == (128, 128) and not wform(65536, 128, 192, ntaps=1)["tap1_dma"]
+    with _lib.option_scope(dev_spin_operand=1):
+        assert wform(16384, 256, 256, ntaps=1)["spin"] and not wform(16384, 128, 96)["spin"]
+        with _lib.option_scope(dec_spin_gemm=2):
+            assert not wform(16384, 256, 256, ntaps=1)["spin"]
+    with _lib.option_scope(wgrad_dma=0):
+        assert not wform(16384, 256, 256, ntaps=1)["tap1_dma"]
+    # the F(2x2) shape query does not look at option enc_wino: whole tile blocks (256 rows at Cout % 64 == 0, else 512)
+    with _lib.option_scope(enc_wino=0):
+        assert not dev.conv_wino_ok(256, 16, 64, 2)
+        assert dev.conv_wino_shape(256, 16, 64, 2) and not dev.conv_wino_shape(128, 16, 64, 2)
+        assert dev.conv_wino_shape(512, 8, 32, 3) and not dev.conv_wino_shape(256, 8, 32, 3) and not dev.conv_wino_shape(256, 8, 64, 2)
