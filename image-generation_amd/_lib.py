@@ -107,6 +107,12 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int,
          c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
     ),
+    "dvg_gibbs_sample_fields_ais": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_float, c_void_p, c_int64,
+         c_float, c_void_p, c_int, c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p],
+    ),
     "dvg_gibbs_sample_annealed": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_int,

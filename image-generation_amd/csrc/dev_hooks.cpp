@@ -98,7 +98,7 @@ extern "C" int dvg_dev_mmd_plan(int64_t nx, int64_t ny, int dim, int64_t out[24]
 extern "C" int dvg_dev_gibbs_draw_plan(int n, int n_colours, const int32_t* class_ptr, const int32_t* adj_ptr, int n_chains,
                                        int kind, int64_t out[19]) {
   DVG_REQUIRE(out && class_ptr && adj_ptr && n > 0 && n_colours > 0 && n_colours <= 64 && n_chains > 0 && kind >= GK_PLAIN &&
-                  (kind <= GK_WEIGH || kind == GK_TRACE || kind == GK_FIELD),
+                  (kind <= GK_WEIGH || kind == GK_TRACE || gibbs_field_kind((GibbsDrawKind)kind)),
               "dev_gibbs_draw_plan: bad argument");
   const GibbsGraphShape g = gibbs_graph_shape(n, n_colours, class_ptr, adj_ptr);
   GibbsDrawPlan p;

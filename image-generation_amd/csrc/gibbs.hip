@@ -99,9 +99,26 @@ struct GibbsFieldArgs : GibbsArgs {
   const float* fields;    // [n_chains or 1][n]: added to `linear`, in its raw units (finite: not checked)
   int64_t field_stride;   // n (a row per chain) or 0 (one row for all chains)
 };
-constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3, GIBBS_TRACE = 4, GIBBS_EXCHANGE_TRACE = 5, GIBBS_FIELD = 6;
+// Weighed per-chain-field draws (dvg_gibbs_sample_fields_ais, "DVG field AIS v1" in include/dvg.h): the per-chain-field draw on
+// the beta table of the AIS draw, with the field's STRENGTH looked up per sweep as well -- row_k = clamp(rn(prefactor *
+// rn(linear + rn(lambda_k * field)))) -- and the AIS draw's two accumulators, which also take the energy step of the row's
+// change at the head of a sweep.  An eighth mode of SCHED, GIBBS_FIELD_WEIGH: the AIS block plus the rows and the strengths.
+// The kernels treat it as GIBBS_FIELD where a spin's hs is read (`FIELD`) and as GIBBS_WEIGH at the head and the end (`AIS`);
+// `FWEIGH` adds the row step alone.  R chains share a row of `fields` (chain c reads row c / R).
+struct GibbsFieldAisArgs : GibbsAisArgs {
+  const float* fields;    // [ceil(n_chains / R) or 1][n]
+  int64_t field_stride;   // n or 0
+  int row_chains;         // R >= 1
+  const float* scales;    // [n_chains or 1][n_sweeps]: lambda of sweep k of the call; null: 1 throughout (the row never changes)
+  int64_t scale_stride;   // n_sweeps or 0
+  float scale_from;       // lambda_{-1}: the strength the start states are a sample under (scales == null: 1)
+};
+constexpr int GIBBS_TABLE = 1, GIBBS_WEIGH = 2, GIBBS_EXCHANGE = 3, GIBBS_TRACE = 4, GIBBS_EXCHANGE_TRACE = 5, GIBBS_FIELD = 6,
+              GIBBS_FIELD_WEIGH = 7;
 template <bool HELD, int SCHED = 0>
 using GibbsArgsT = std::conditional_t<
+    SCHED == GIBBS_FIELD_WEIGH, GibbsFieldAisArgs,
+    std::conditional_t<
     SCHED == GIBBS_FIELD, GibbsFieldArgs,
     std::conditional_t<
         SCHED == GIBBS_EXCHANGE_TRACE, GibbsExchangeTraceArgs,
@@ -110,7 +127,7 @@ using GibbsArgsT = std::conditional_t<
             std::conditional_t<SCHED == GIBBS_EXCHANGE, GibbsExchangeArgs,
                                std::conditional_t<SCHED == GIBBS_WEIGH, GibbsAisArgs,
                                                   std::conditional_t<SCHED == GIBBS_TABLE, GibbsSchedArgs,
-                                                                     std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>>>>;
+                                                                     std::conditional_t<HELD, GibbsHeldArgs, GibbsArgs>>>>>>>>;
 
 // A chain's start state, its LPC lanes each taking spins l, l + LPC, ...: from the INIT stream (init) or from `state`.
 // HELD (a conditional draw): held spins from `state` always, free ones as above.
@@ -397,6 +414,9 @@ __device__ __forceinline__ void gibbs_exchange_record(const GibbsExchangeTraceAr
 //     write its record to the row of the rung it NOW holds (gibbs_exchange_record), on the same countdown.
 //   GIBBS_FIELD: the plain draw's control -- the fixed beta, nothing at the head or the tail of a sweep; what differs is where
 //     the rolled kernel reads a spin's hs (FIELD: the chain's own row).  The lane-major kernel has no such instantiation.
+//   GIBBS_FIELD_WEIGH: the AIS draw's control on the field draw's rows (FIELD and AIS both hold).  With a table of strengths
+//     (FWEIGH and a.scales) the rolled kernel rewrites the chain's row before the head of a sweep (gibbs_field_step) and leaves
+//     the lane's share of the energy step in `d`; the head weighs it.  A lane reads its chain's strength a sweep ahead, as beta.
 // What the exchange modes rest on, in either kernel:
 //   * EVERY wave of a workgroup reaches EVERY barrier: the ones in gibbs_sweep_tail and the one in gibbs_finish.  The kernels
 //     let no wave leave or skip the sweep loop under EXCH -- the lanes of an idle slot run it without a spin to update;
@@ -404,10 +424,11 @@ __device__ __forceinline__ void gibbs_exchange_record(const GibbsExchangeTraceAr
 //   * the traced exchange draw sums `e` from a COPY (gibbs_exchange_record): the shares go on as in the draw without records.
 template <int SCHED>
 struct GibbsMode {
-  static constexpr bool AIS = SCHED == GIBBS_WEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE;
+  static constexpr bool FWEIGH = SCHED == GIBBS_FIELD_WEIGH;
+  static constexpr bool AIS = SCHED == GIBBS_WEIGH || FWEIGH, XTRACE = SCHED == GIBBS_EXCHANGE_TRACE;
   static constexpr bool EXCH = SCHED == GIBBS_EXCHANGE || XTRACE, ENERGY = AIS || EXCH;
-  static constexpr bool TABLE = SCHED == GIBBS_TABLE || SCHED == GIBBS_WEIGH, TRACE = SCHED == GIBBS_TRACE;
-  static constexpr bool FIELD = SCHED == GIBBS_FIELD;
+  static constexpr bool TABLE = SCHED == GIBBS_TABLE || AIS, TRACE = SCHED == GIBBS_TRACE;
+  static constexpr bool FIELD = SCHED == GIBBS_FIELD || FWEIGH;
 };
 // a lane's control registers; a mode leaves those of the others at zero and the compiler drops them
 struct GibbsControl {
@@ -416,6 +437,9 @@ struct GibbsControl {
   float beta_prev;        // AIS: the beta of the sweep before (first: beta_from)
   int rung;               // EXCH: the rung the chain holds
   double e, lw;           // ENERGY, AIS: the lane's shares of the chain's energy and log weight
+  const float* sc;        // FWEIGH: this chain's row of the table of strengths; null: none
+  float lam_next;         // FWEIGH: the strength of the coming sweep, read a sweep ahead
+  double d;               // FWEIGH: the lane's share of d_k, the energy step of the row's change at the head of the coming sweep
   uint32_t rec_at, rec_m;  // TRACE, XTRACE: the next recorded sweep (as k + 1) and its record
 };
 // before the first sweep (and the start-energy walk): the lanes of a valid chain or, EXCH, of any slot
@@ -431,6 +455,12 @@ __device__ __forceinline__ GibbsControl gibbs_begin(const Args& a, const GibbsEx
     c.beta_next = c.bt[0];
   }
   if constexpr (M::AIS) c.beta_prev = a.beta_from;
+  if constexpr (M::FWEIGH) {
+    if (a.scales) {  // (a kernel argument: uniform)
+      c.sc = a.scales + (int64_t)slot.chain * a.scale_stride;
+      c.lam_next = c.sc[0];
+    }
+  }
   if constexpr (M::TRACE || M::XTRACE) c.rec_at = (uint32_t)a.burn_in + (uint32_t)a.thin;
   return c;
 }
@@ -444,10 +474,17 @@ __device__ __forceinline__ float gibbs_sweep_head(const Args& a, uint32_t t, uin
     const float two_beta = __fmul_rn(2.0f, c.beta_next);
     if constexpr (M::AIS) {
       c.lw -= ((double)c.beta_next - (double)c.beta_prev) * c.e;
+      if constexpr (M::FWEIGH) {  // (d: what gibbs_field_step left; without a table of strengths it stays 0)
+        c.lw -= (double)c.beta_next * c.d;
+        c.e += c.d;
+      }
       c.beta_prev = c.beta_next;
     }
     const uint32_t kn = t - sweep0 + 1u;
     if (kn < (uint32_t)a.n_sweeps) c.beta_next = c.bt[kn];
+    if constexpr (M::FWEIGH) {
+      if (c.sc && kn < (uint32_t)a.n_sweeps) c.lam_next = c.sc[kn];
+    }
     return two_beta;
   } else {
     return a.two_beta;
@@ -514,10 +551,39 @@ __device__ __forceinline__ void gibbs_finish(const Args& a, const GibbsExchangeL
   } else if constexpr (M::AIS) {
     const double e = gibbs_chain_sum<LPC>(c.e), lw = gibbs_chain_sum<LPC>(c.lw);
     if (l == 0) {
-      a.log_weight_out[chain] = lw;
+      if (!M::FWEIGH || a.log_weight_out) a.log_weight_out[chain] = lw;  // (the field kind alone may go unweighed)
       if (a.energy_out) a.energy_out[chain] = e;
     }
   }
+}
+
+// ---------------------------------------------------------------- a chain's row of hs (GIBBS_FIELD, GIBBS_FIELD_WEIGH)
+// the chain's row of `fields`, and the strength its start states were drawn under
+template <int SCHED, typename Args>
+__device__ __forceinline__ const float* gibbs_field_row(const Args& a, int chain) {
+  if constexpr (GibbsMode<SCHED>::FWEIGH) return a.fields + (int64_t)(chain / a.row_chains) * a.field_stride;
+  else return a.fields + (int64_t)chain * a.field_stride;
+}
+// entry i of the row at strength lam: clamp(rn(prefactor * rn(linear + rn(lam * field)))); the field kind has no strength (1: the
+// product is the field itself, bit for bit)
+template <int SCHED, typename Args>
+__device__ __forceinline__ float gibbs_field_entry(const Args& a, const float* fr, int i, float lam) {
+  const float fi = GibbsMode<SCHED>::FWEIGH ? __fmul_rn(lam, fr[i]) : fr[i];
+  return clampf(__fmul_rn(a.prefactor, __fadd_rn(a.linear[i], fi)), a.h_lo, a.h_hi);
+}
+// FWEIGH with a table of strengths, before the head of a sweep: the lanes that own the row's entries (i = l, l + LPC, ...: as at
+// load) recompute them at the sweep's strength from `linear` and the chain's row of `fields` (global memory: L2 serves them),
+// rewrite them in place and return their share of  d_k = sum_i (row_k[i] - row_{k-1}[i]) s_i  (each addend exact in float64).
+// The caller fences behind it: a spin is not updated by the lane that owns its row entry.
+template <int LPC, int SCHED, typename Args>
+__device__ __forceinline__ double gibbs_field_step(const Args& a, const float* fr, float* hc, const _Float16* st, int l, float lam) {
+  double d = 0.0;
+  for (int i = l; i < a.n; i += LPC) {
+    const float now = gibbs_field_entry<SCHED>(a, fr, i, lam);
+    d += ((double)now - (double)hc[i]) * (double)(float)st[i];
+    hc[i] = now;
+  }
+  return d;
 }
 
 // LPC = lanes per chain (16, 32 or 64); WAVES waves per workgroup.  The rolled schedule: any graph; Philox per update.
@@ -525,7 +591,8 @@ __device__ __forceinline__ void gibbs_finish(const Args& a, const GibbsExchangeL
 // EXCH: the lanes of an idle slot find every class empty.  The rows are aligned to 4 bytes (gibbs_record's A16 = false).
 // FIELD: the chain's row of hs = clamp(rn(prefactor * rn(linear + field))) sits behind the state rows, float32 [n_pad] per chain
 // slot, written once when the chain is loaded by the lanes that read it (one wave: the fence below orders it); every read of
-// the image's shared hs goes to it instead.
+// the image's shared hs goes to it instead.  FWEIGH with a table of strengths: the same lanes rewrite the row at the head of
+// every sweep (gibbs_field_step), and one more fence stands before the first class.
 template <int LPC, int WAVES, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
@@ -578,9 +645,10 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
       }
     }
     if constexpr (M::FIELD) {
-      const float* fr = a.fields + (int64_t)chain * a.field_stride;
-      for (int i = l; i < n; i += LPC)
-        hc[i] = clampf(__fmul_rn(a.prefactor, __fadd_rn(a.linear[i], fr[i])), a.h_lo, a.h_hi);
+      const float* fr = gibbs_field_row<SCHED>(a, chain);
+      float lam = 1.0f;
+      if constexpr (M::FWEIGH) lam = a.scales ? a.scale_from : 1.0f;
+      for (int i = l; i < n; i += LPC) hc[i] = gibbs_field_entry<SCHED>(a, fr, i, lam);
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -596,6 +664,13 @@ __global__ __launch_bounds__(WAVES * 64) void gibbs_kernel(GibbsArgsT<HELD, SCHE
     }
     for (uint32_t t = sweep0; t < sweep0 + (uint32_t)a.n_sweeps; ++t) {
       const uint32_t tq = t >> 2, tw = t & 3u;
+      if constexpr (M::FWEIGH) {
+        if (a.scales) {  // (a kernel argument: uniform)
+          ctl.d = gibbs_field_step<LPC, SCHED>(a, gibbs_field_row<SCHED>(a, chain), hc, st, l, ctl.lam_next);
+          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
       const float two_beta = gibbs_sweep_head<SCHED>(a, t, sweep0, ctl);
       for (int k = 0; k < a.n_colours; ++k) {
         const int lo = L.cls[k], hi = (EXCH && !valid) ? lo : L.cls[k + 1];  // (an idle slot: every class empty)
@@ -830,7 +905,7 @@ __device__ __forceinline__ void gibbs_lane_class(float (&f)[NR], gu32x2 (&o)[NR]
 template <int LPC, int WAVES, int MB, int NR, int MAXS, bool HELD = false, int SCHED = 0>
 __global__ __launch_bounds__(WAVES * 64) void gibbs_fast_kernel(GibbsArgsT<HELD, SCHED> a) {
   static_assert(!(HELD && SCHED), "no annealed conditional draw");
-  static_assert(SCHED != GIBBS_FIELD, "the per-chain-field draw takes the rolled form alone: this image keeps h in registers");
+  static_assert(!GibbsMode<SCHED>::FIELD, "the per-chain-field draw takes the rolled form alone: this image keeps h in registers");
   using M = GibbsMode<SCHED>;
   constexpr bool EXCH = M::EXCH, ENERGY = M::ENERGY;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -1027,7 +1102,7 @@ using GibbsKernelT = void (*)(GibbsArgsT<HELD, SCHED>);
 // the instantiation a plan names; null: it has none.  The tables expand from the lists the plan chose from.
 template <bool HELD, int SCHED>
 static GibbsKernelT<HELD, SCHED> gibbs_kernel_of(const GibbsDrawPlan& p) {
-  if constexpr (SCHED != GIBBS_FIELD) {  // (the field kind is planned rolled on every graph and has no lane-major instantiation)
+  if constexpr (!GibbsMode<SCHED>::FIELD) {  // (the field kinds are planned rolled on every graph and have no lane-major instantiation)
 #define DVG_GIBBS_LANE_ENTRY(LPC, W, MB, NR, MAXS)                                                      \
   if (p.form == GF_LANE && p.lpc == LPC && p.waves == W && p.mb == MB && p.nr == NR && p.maxs == MAXS)  \
     return gibbs_fast_kernel<LPC, W, MB, NR, MAXS, HELD, SCHED>;
@@ -1071,6 +1146,7 @@ template <bool HELD, int SCHED = 0>
 static int gibbs_draw(const dvg_graph_t* g, GibbsArgsT<HELD, SCHED>& a, hipStream_t s) {
   constexpr GibbsDrawKind KIND = HELD                     ? GK_HELD
                                  : GibbsMode<SCHED>::EXCH ? GK_EXCHANGE
+                                 : SCHED == GIBBS_FIELD_WEIGH ? GK_FIELD_WEIGH
                                  : SCHED == GIBBS_WEIGH   ? GK_WEIGH
                                  : SCHED == GIBBS_TABLE   ? GK_TABLE
                                  : SCHED == GIBBS_TRACE   ? GK_TRACE
@@ -1302,6 +1378,47 @@ extern "C" int dvg_gibbs_sample_fields(const dvg_graph_t* g, const float* linear
                   n_sweeps, init, samples_out, nullptr);
   a.fields = fields; a.field_stride = field_chain_stride;
   return gibbs_draw<false, GIBBS_FIELD>(g, a, (hipStream_t)stream);
+}
+
+// The weighed per-chain-field draw ("DVG field AIS v1", include/dvg.h): the per-chain-field draw along a path in (beta, field
+// strength), both looked up per sweep, with the AIS draw's log weight and energy per chain; R chains share a row of `fields`.
+extern "C" int dvg_gibbs_sample_fields_ais(const dvg_graph_t* g, const float* linear, const float* quadratic,
+                                           float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                           const float* betas, int64_t beta_chain_stride, float beta_from,
+                                           const float* scales, int64_t scale_chain_stride, float scale_from,
+                                           int8_t* state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                                           uint32_t sweep0, int n_sweeps, int init,
+                                           const float* fields, int64_t field_chain_stride, int field_row_chains,
+                                           float* samples_out, double* log_weight_out, double* energy_out,
+                                           const dvg_step_state_t* dyn, dvg_stream_t stream) {
+  const char* who = "gibbs_fields_ais";
+  const GibbsStride stride{"field_chain_stride", field_chain_stride, "n", g ? g->n : 0};
+  DVG_TRY(gibbs_check(who, g, linear && quadratic && state,
+                      !fields  ? "null fields (a weighed draw without fields is dvg_gibbs_sample_ais)"
+                      : !betas ? "null betas"
+                               : nullptr,
+                      n_chains, n_sweeps, true, &stride));
+  DVG_REQUIRE(beta_chain_stride == 0 || beta_chain_stride == n_sweeps,
+              "%s: beta_chain_stride=%lld is neither 0 (one shared row) nor n_sweeps=%d (a row per chain)", who,
+              (long long)beta_chain_stride, n_sweeps);
+  DVG_REQUIRE(scale_chain_stride == 0 || scale_chain_stride == n_sweeps,
+              "%s: scale_chain_stride=%lld is neither 0 (one shared row) nor n_sweeps=%d (a row per chain)", who,
+              (long long)scale_chain_stride, n_sweeps);
+  DVG_REQUIRE(field_row_chains >= 1, "%s: field_row_chains=%d must be at least 1", who, field_row_chains);
+  DVG_REQUIRE(beta_from >= 0.0f && beta_from <= 3.4028234663852886e38f, "%s: beta_from=%g must be finite and >= 0", who, (double)beta_from);
+  DVG_REQUIRE(scale_from >= -3.4028234663852886e38f && scale_from <= 3.4028234663852886e38f, "%s: scale_from=%g must be finite", who,
+              (double)scale_from);
+  DVG_REQUIRE(init == 0 || beta_from == 0.0f,
+              "%s: init=%d with beta_from=%g (fresh chains are uniform: a sample at beta 0 and at no other)", who, init, (double)beta_from);
+  DVG_REQUIRE(!dyn, "%s: dyn must be NULL (the draw is one-off, not part of a captured step)", who);
+  GibbsFieldAisArgs a;
+  gibbs_fill_args(a, g, linear, quadratic, prefactor, h_lo, h_hi, j_lo, j_hi, 0.0f, state, n_chains, chain_id0, seed, sweep0,
+                  n_sweeps, init, samples_out, nullptr);
+  a.betas = betas; a.beta_stride = beta_chain_stride;
+  a.beta_from = beta_from; a.log_weight_out = log_weight_out; a.energy_out = energy_out;
+  a.fields = fields; a.field_stride = field_chain_stride; a.row_chains = field_row_chains;
+  a.scales = scales; a.scale_stride = scale_chain_stride; a.scale_from = scale_from;
+  return gibbs_draw<false, GIBBS_FIELD_WEIGH>(g, a, (hipStream_t)stream);
 }
 
 // The launch geometry dvg_gibbs_sample would use for `n_chains` chains on this graph (nothing is launched): workgroups,

@@ -74,7 +74,7 @@ static int gibbs_plan_slots(const GibbsGraphShape& g, int n_chains, int ch, Gibb
 // what a chain slot of the rolled form keeps in LDS behind the state rows: the held kind a row of flag bits, the field kind a
 // float32 row of hs
 static size_t gibbs_rolled_extra(const GibbsGraphShape& g, GibbsDrawKind kind) {
-  return kind == GK_HELD ? sizeof(uint32_t) * (size_t)gibbs_held_words(g.n) : kind == GK_FIELD ? gibbs_field_row_bytes(g.n) : 0;
+  return kind == GK_HELD ? sizeof(uint32_t) * (size_t)gibbs_held_words(g.n) : gibbs_field_kind(kind) ? gibbs_field_row_bytes(g.n) : 0;
 }
 static size_t gibbs_rolled_lds(const GibbsGraphShape& g, GibbsDrawKind kind, int lpc, int waves) {
   const int chains = waves * (64 / lpc);
@@ -82,7 +82,7 @@ static size_t gibbs_rolled_lds(const GibbsGraphShape& g, GibbsDrawKind kind, int
 }
 
 static int gibbs_plan_rolled(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, int lpc, int waves, GibbsDrawPlan* p) {
-  if (kind == GK_FIELD) {
+  if (gibbs_field_kind(kind)) {
     // The hs rows triple a chain's LDS: the largest WAVES of the list at this LPC, no larger than the one chosen, that fits
     // (1024 spins: ~105 KB of tables and 6 KB per chain -- 4 chains, not 16).  Nothing fits: the chosen one, reported below.
     int fit = 0;
@@ -98,7 +98,7 @@ static int gibbs_plan_rolled(const GibbsGraphShape& g, int n_chains, GibbsDrawKi
   p->lds = gibbs_rolled_lds(g, kind, lpc, waves);
   return gibbs_plan_finish(g, n_chains, p,
                            kind == GK_HELD    ? " (the held flags of a conditional draw included)"
-                           : kind == GK_FIELD ? " (the field rows of a per-chain-field draw included)"
+                           : gibbs_field_kind(kind) ? " (the field rows of a per-chain-field draw included)"
                                               : "");
 }
 
@@ -106,14 +106,15 @@ static int gibbs_plan_rolled(const GibbsGraphShape& g, int n_chains, GibbsDrawKi
 // graphs' many-chain draws run the rolled kernel in 16-wave workgroups, and the A/B forms 3 and 4 count as 0.
 // The annealed draw, weighed or not, and the traced draw: the same two exceptions.
 // The per-chain-field draw: the table kind's plan under gibbs_generic = 1, whatever the option -- the rolled form alone keeps
-// hs where a row per chain can stand in for it -- with the workgroup stepped down to what fits (gibbs_plan_rolled).
+// hs where a row per chain can stand in for it -- with the workgroup stepped down to what fits (gibbs_plan_rolled).  Weighed
+// (GK_FIELD_WEIGH) it keeps that plan: the accumulators are registers, the rows rewritten where they lie.
 int gibbs_draw_plan(const GibbsGraphShape& g, int n_chains, GibbsDrawKind kind, int64_t generic_option, GibbsDrawPlan* out) {
   GibbsDrawPlan& p = *out;
   p = GibbsDrawPlan{};
   const bool variant = kind != GK_PLAIN;
   // (option gibbs_generic = 1 forces the rolled reference schedule: A/B runs and the bit-exactness test of the fast one;
   // 2 = the fast schedule without its two-passes-side-by-side form)
-  const int64_t form = kind == GK_FIELD ? 1 : (variant && generic_option >= 3) ? 0 : generic_option;
+  const int64_t form = gibbs_field_kind(kind) ? 1 : (variant && generic_option >= 3) ? 0 : generic_option;
   // (4: the chains-side-by-side schedule in 8-chain workgroups whatever the size: A/B runs; graphs whose classes do not
   // make slots take what 0 gives them)
   if (!variant && form == 4 && gibbs_make_slots(g, 8, &p.slots)) return gibbs_plan_slots(g, n_chains, 8, &p);

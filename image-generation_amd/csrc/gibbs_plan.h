@@ -104,8 +104,10 @@ GibbsGraphShape gibbs_graph_shape(int n, int n_colours, const int32_t* class_ptr
 // state rows where they lie;
 // field: _fields (GIBBS_FIELD) -- the rolled form on every graph: the instantiation the table kind takes under gibbs_generic = 1,
 // its WAVES stepped down within DVG_GIBBS_ROLLED_KERNELS until the image fits with a float32 row of hs per chain slot behind the
-// state rows (6 bytes per spin and chain where the other kinds keep 2)
-enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE, GK_TRACE, GK_FIELD };
+// state rows (6 bytes per spin and chain where the other kinds keep 2);
+// field_weigh: _fields_ais (GIBBS_FIELD_WEIGH) -- the field kind's plan, the same LDS image: the weights are registers
+enum GibbsDrawKind : int { GK_PLAIN = 0, GK_HELD, GK_TABLE, GK_WEIGH, GK_EXCHANGE, GK_TRACE, GK_FIELD, GK_FIELD_WEIGH };
+constexpr bool gibbs_field_kind(GibbsDrawKind k) { return k == GK_FIELD || k == GK_FIELD_WEIGH; }
 //   GF_ROLLED  gibbs_kernel<lpc, waves, HELD, SCHED>: any graph
 //   GF_LANE    gibbs_fast_kernel<lpc, waves, mb, nr, maxs, HELD, SCHED>: graphs with a lane-major image
 //   GF_SLOTS   gibbs_slot_kernel<maxs, ch, fix>: ch chains of a 16-wave workgroup side by side; the plain draw only

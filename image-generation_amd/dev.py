@@ -162,21 +162,25 @@ GIBBS_KINDS = ("plain", "held", "table", "weigh")    # GibbsDrawKind
 # ... by name: "trace" (dvg_gibbs_sample_traced) is GK_TRACE = 5, behind GK_EXCHANGE, which dvg_dev_gibbs_exchange_plan plans;
 # "field" (dvg_gibbs_sample_fields) is GK_FIELD = 6
 GIBBS_KIND_IDS = dict({k: i for i, k in enumerate(GIBBS_KINDS)}, trace=5, field=6)
+# the weighed forms of the kinds above that plan as their unweighed one does: "field_weigh" (dvg_gibbs_sample_fields_ais) is
+# GK_FIELD_WEIGH = 7
+GIBBS_WEIGHED_KIND_IDS = dict(field_weigh=7)
 
 
 def gibbs_draw_plan(plan, n_chains, kind="plain"):
     """The kernel form a Gibbs draw of ``n_chains`` chains takes on the graph of ``plan`` (a ``graphs.GibbsPlan``) under
     the current option ``gibbs_generic`` (no device needed).  ``kind``: ``"plain"`` (``dvg_gibbs_sample``), ``"held"``
-    (``_clamped``), ``"table"`` (``_annealed``), ``"weigh"`` (``_ais``), ``"trace"`` (``_traced``: the table kind's plan) or ``"field"`` (``_fields``: rolled on every graph,
-    ``lds_bytes`` with the chains' rows of hs).  ``form``: ``"rolled"`` (``gibbs_kernel``),
+    (``_clamped``), ``"table"`` (``_annealed``), ``"weigh"`` (``_ais``), ``"trace"`` (``_traced``: the table kind's plan), ``"field"`` (``_fields``: rolled on every graph,
+    ``lds_bytes`` with the chains' rows of hs) or ``"field_weigh"`` (``_fields_ais``: the field kind's plan).  ``form``: ``"rolled"`` (``gibbs_kernel``),
     ``"lane"`` (``gibbs_fast_kernel``) or ``"slots"`` (``gibbs_slot_kernel``), ``params`` its template parameters;
     ``workgroups``, ``threads``, ``lds_bytes``: the launch, what ``dvg_gibbs_launch_info`` reports for the plain kind;
     ``lane_image``: the shape of the graph's lane-major image (csrc/graph.h), ``None`` for a graph that gets none."""
     class_ptr = np.ascontiguousarray(plan.class_ptr, dtype=np.int32)
     adj_ptr = np.ascontiguousarray(plan.adj_ptr, dtype=np.int32)
     o = (ctypes.c_int64 * 19)()
+    kind_id = GIBBS_WEIGHED_KIND_IDS[kind] if kind in GIBBS_WEIGHED_KIND_IDS else GIBBS_KIND_IDS[kind]
     _lib.check(lib().dvg_dev_gibbs_draw_plan(int(plan.n), int(plan.n_colours), class_ptr.ctypes.data, adj_ptr.ctypes.data,
-                                             int(n_chains), GIBBS_KIND_IDS[kind], o), "dvg_dev_gibbs_draw_plan")
+                                             int(n_chains), kind_id, o), "dvg_dev_gibbs_draw_plan")
     return _gibbs_plan_dict(o)
 
 

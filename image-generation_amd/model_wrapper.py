@@ -936,6 +936,29 @@ class ModelWrapper:
         return self._grbm.log_likelihood(spins, self.sampler, log_z=result.log_z, **ranges), result
 
     @torch.no_grad()
+    def prior_log_evidence(self, images: torch.Tensor, chains_per_image: int = 64, num_sweeps: int = 100, **kw):
+        """How much prior mass agrees with what the encoder believes about each image: ``log sum_z p(z) q(z | x)``, ``p`` the
+        distribution the sampler draws from and ``q`` the encoder's factorial posterior with logits ``l`` -- encode -> logits
+        -> ``GraphRestrictedBoltzmannMachine.log_evidence`` (``chains_per_image`` chains per image started from draws of the
+        prior, the image's evidence turned on over ``num_sweeps`` sweeps and every step weighed inside the kernel; ``burn_in``
+        and ``start`` are passed on) -> ``log_ratio - sum_i log(2 cosh(l_i / 2))``, since ``q(z | x) = prod_i exp(l_i z_i / 2) /
+        (2 cosh(l_i / 2))``.  No estimate of ``log Z`` is needed, and no code is hardened as ``prior_log_likelihood`` does.  This
+        is ``log sum_z p(z) q(z | x)`` exactly (in expectation of the weights) where no ``linear_range`` clamps the sum of the
+        prior's linear terms and the evidence; a range that does caps the evidence with it.  Returns the (B,) float64 values
+        on the device and the ``sampler.LogEvidence`` (its ``std_err`` is the estimate's, per image).  Rank-local and
+        eval-mode, like ``prior_log_likelihood``; of the sampler's counters only ``field_sweep_count`` and
+        ``field_ais_sweep_count`` move."""
+        self._dvae.eval()
+        self._grbm.eval()
+        images = images.to(self._device)
+        logits = self._dvae.encoder(images).to(torch.float32)  # (B, n)
+        ranges = dict(prefactor=self.PREFACTOR, linear_range=self.linear_range, quadratic_range=self.quadratic_range)
+        result = self._grbm.log_evidence(self.sampler, logits, chains_per_row=chains_per_image, num_sweeps=num_sweeps, **kw, **ranges)
+        half = 0.5 * logits.to(torch.float64).abs()
+        log_norm = (half + torch.log1p(torch.exp(-2.0 * half))).sum(dim=1)  # sum_i log(2 cosh(l_i / 2)), without overflow
+        return result.log_ratio - log_norm, result
+
+    @torch.no_grad()
     def prior_pseudo_likelihood(self, images: torch.Tensor, **kw) -> dict:
         """How well the prior fits given images' latent codes WITHOUT an estimate of ``log Z``: encode ``images`` -> hard spins
         (heaviside, H(0) = 0, as ``prior_log_likelihood`` does) -> their :class:`~.sampler.PseudoLikelihood` under the prior

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, functional as F
 from .graphs import GibbsPlan, build_plan
-from .sampler import GibbsSampler, GraphHandle, SampleSet
+from .sampler import GibbsSampler, GraphHandle, SampleSet, logit_fields
 
 
 class DiscreteVariationalAutoencoder(torch.nn.Module):
@@ -211,6 +211,23 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         betas = np.linspace(0.0, b, int(num_sweeps) + 1)[1:].astype(np.float32)
         return self.sample_population(sampler, betas, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range,
                                       num_reads=kw.pop("num_reads", 1024), num_populations=kw.pop("num_populations", 8), **kw)
+
+    def sample_fields(self, sampler, fields: torch.Tensor, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """Draw from the model with a linear field of its own per chain, ``(linear + fields[c], quadratic)`` -- soft evidence
+        (:meth:`GibbsSampler.sample_fields`; ``start``, ``sweeps``, ``num_reads`` are passed on; ``sampler.logit_fields`` makes
+        the fields of factorial logits).  Returns (C, n) float32 +-1 on the device.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "sample_fields")
+        return sampler.sample_fields(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, fields, **kw)
+
+    def log_evidence(self, sampler, logits: torch.Tensor, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """Per row of ``logits`` (rows, n), the log odds of ``z_i = +1`` under factorial evidence: the estimate of ``log sum_z
+        p(z) prod_i exp(logits[r, i] z_i / 2)``, ``p`` the distribution ``sampler`` draws from under the prefactor-scaled,
+        clamped ``(h, J)`` -- ``sampler.logit_fields`` followed by :meth:`GibbsSampler.log_evidence` (``chains_per_row``,
+        ``num_sweeps``, ``burn_in``, ``start`` are passed on).  Exact in expectation where no ``linear_range`` clamps the sum
+        of the linear terms and the fields.  Returns its :class:`~.sampler.LogEvidence`.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "log_evidence")
+        fields = logit_fields(logits.to(self._linear.device), sampler.beta, prefactor)
+        return sampler.log_evidence(self._linear, self._quadratic, prefactor, linear_range, quadratic_range, fields, **kw)
 
     def sample_population(self, sampler, betas, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
         """A population-annealing draw from the model under the prefactor-scaled, clamped ``(h, J)``: chains annealed through

@@ -145,11 +145,11 @@ def transverse_schedule(beta: float, gamma_start: float, gamma_end: float, num_s
     return beta_slice, kappa
 
 
-def _check_beta_table(betas, what: str, rows: Optional[int] = None):
+def _check_beta_table(betas, what: str, rows: Optional[int] = None, signed: bool = False):
     """The host-side checks of a table of betas, no device work: shape (S,) or (rows, S) with S >= 1; a CUDA tensor must
     be float32 (its values are the caller's business: looking would be a host sync); host values -- a sequence, an
-    array, a CPU tensor -- must be finite and >= 0 once rounded to float32.  Returns the float32 host array, or None
-    for a CUDA tensor."""
+    array, a CPU tensor -- must be finite and >= 0 once rounded to float32 (``signed``, a table of field strengths: finite).
+    Returns the float32 host array, or None for a CUDA tensor."""
     on_device = torch.is_tensor(betas) and betas.is_cuda
     if on_device:
         if betas.dtype != torch.float32:
@@ -167,15 +167,22 @@ def _check_beta_table(betas, what: str, rows: Optional[int] = None):
     want = "(sweeps,)" if rows is None else f"(sweeps,) or ({rows}, sweeps)"
     if len(shape) not in (1, 2) or int(np.prod(shape)) == 0 or (len(shape) == 2 and (rows is None or int(shape[0]) != rows)):
         raise _lib.DvgError(f"{what} must be {want} with at least one sweep, got {tuple(shape)}")
-    if host is not None and not (np.isfinite(host).all() and (host >= 0).all()):
+    if host is not None and signed and not np.isfinite(host).all():
+        raise ValueError(f"{what}: every entry must be finite")
+    if host is not None and not signed and not (np.isfinite(host).all() and (host >= 0).all()):
         raise ValueError(f"{what}: every beta must be finite and >= 0")
     return host
 
 
-def _beta_table(betas, device, what: str, rows: Optional[int] = None, own: bool = False) -> torch.Tensor:
+_UNCHECKED = object()
+
+
+def _beta_table(betas, device, what: str, rows: Optional[int] = None, own: bool = False, host=_UNCHECKED) -> torch.Tensor:
     """``betas``, checked (:func:`_check_beta_table`), as a contiguous float32 tensor on ``device``: host values are
-    uploaded, a CUDA tensor is used as it is (``own``: copied)."""
-    host = _check_beta_table(betas, what, rows)
+    uploaded, a CUDA tensor is used as it is (``own``: copied).  ``host``: what :func:`_check_beta_table` returned, where the
+    caller has run it already."""
+    if host is _UNCHECKED:
+        host = _check_beta_table(betas, what, rows)
     device = torch.device(device)
     if host is None:
         if device.type == "cuda" and device.index is not None and betas.device != device:
@@ -241,6 +248,31 @@ class LogPartition:
 
     def __repr__(self):
         return f"LogPartition(log_z={float(self.log_z):.6f}, ess={float(self.ess):.1f}, std_err={float(self.std_err):.4f})"
+
+
+class LogEvidence:
+    """What :meth:`GibbsSampler.log_evidence` returns, per row of ``fields``.  ``log_ratio`` (rows,) float64 on the device:
+    ``logsumexp(log_weights[r]) - log chains_per_row``, the estimate of ``log(Z_r / Z)``, ``Z_r`` the normaliser of the model
+    with row r added to its linear terms; ``ess``, ``std_err`` (rows,): the effective sample size ``(sum w)^2 / sum w^2`` of a
+    row's weights and the standard error of its ``log_ratio`` to first order, ``sqrt(1 / ess - 1 / chains_per_row)``, as
+    :class:`LogPartition` has them; ``log_weights`` (rows, chains_per_row) float64; ``samples`` (rows * chains_per_row, n)
+    float32: the chains, annealed draws of each row's posterior (row r: chains ``r * chains_per_row ...``)."""
+
+    def __init__(self, log_ratio, ess, std_err, log_weights, samples):
+        self.log_ratio, self.ess, self.std_err, self.log_weights, self.samples = log_ratio, ess, std_err, log_weights, samples
+
+    @classmethod
+    def from_weights(cls, log_weights: torch.Tensor, samples=None) -> "LogEvidence":
+        """``log_weights``: (rows, chains_per_row) float64."""
+        K = int(log_weights.shape[1])
+        lse = torch.logsumexp(log_weights, 1)
+        ess = torch.exp(2.0 * lse - torch.logsumexp(2.0 * log_weights, 1))
+        std_err = torch.sqrt(torch.clamp(1.0 / ess - 1.0 / K, min=0.0))
+        return cls(lse - float(np.log(K)), ess, std_err, log_weights, samples)
+
+    def __repr__(self):
+        return (f"LogEvidence(rows={int(self.log_ratio.shape[0])}, chains_per_row={int(self.log_weights.shape[1])}, "
+                f"mean log_ratio={float(self.log_ratio.mean()):.6f}, min ess={float(self.ess.min()):.1f})")
 
 
 class Tempered:
@@ -1404,6 +1436,9 @@ class GibbsSampler:
         # ... and the draws with a field per chain (sample_fields)
         self.field_seed = self.seed ^ 0x666C6431
         self.field_sweep_count = 0
+        # ... and their weighed, annealed form (sample_fields_ais, log_evidence)
+        self.field_ais_seed = self.seed ^ 0x66616931
+        self.field_ais_sweep_count = 0
         # set_beta_schedule: the (sweeps,) float32 device table the training draws anneal along; None: fixed beta
         self._betas: Optional[torch.Tensor] = None
         self._fixed_sweeps = self.sweeps
@@ -1426,6 +1461,7 @@ class GibbsSampler:
         self.pa_sweep_count = 0
         self.sqa_sweep_count = 0
         self.field_sweep_count = 0
+        self.field_ais_sweep_count = 0
 
     def set_beta_schedule(self, betas) -> None:
         """Make every draw of :meth:`sample_native` an annealed one: sweep k of a draw runs at ``betas[k]``, the same
@@ -1608,6 +1644,118 @@ class GibbsSampler:
                    rows_dev.data_ptr(), n if rows is not None else 0, out.data_ptr(), None)
         self.field_sweep_count += n_sweeps
         return out
+
+    def sample_fields_ais(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                          fields: torch.Tensor, betas=None, scales=None, *, chains_per_row: int = 1,
+                          start: Optional[torch.Tensor] = None, num_reads: Optional[int] = None, beta_from: float = 0.0,
+                          scale_from: float = 1.0):
+        """The per-chain-field draw along a path in (beta, field strength), weighed (``dvg_gibbs_sample_fields_ais``, "DVG field
+        AIS v1" in include/dvg.h): sweep k of chain c runs at ``betas[k]`` (or ``betas[c, k]``) on the model ``(linear +
+        scales[k] * fields[row of c], quadratic)``, and the kernel carries the chain's energy and the log importance weight of
+        annealed importance sampling along that path.  Over the chains of one row, ``logsumexp(log_weights) - log(count)``
+        estimates ``log Z(betas[-1], scales[-1]) - log Z(beta_from, scale_from)`` of that row's model (:meth:`log_evidence`).
+
+        ``fields``: as for :meth:`sample_fields`; (rows, n) makes ``rows * chains_per_row`` chains, chain c reading row ``c //
+        chains_per_row`` (the rows are not replicated in memory); (n,): one row for all chains, ``start`` or ``num_reads``
+        naming them.  ``betas``, ``scales``: (S,) or (C, S) tables under the rules of :meth:`sample_annealed` -- host values
+        are checked (finite; betas >= 0) and uploaded, a CUDA float32 tensor is used as it is.  ``betas=None``: the sampler's
+        own beta on every sweep; ``scales=None``: strength 1 throughout; one of the two must be given, and both must name the
+        same S.  ``beta_from``, ``scale_from``: the point of the path ``start`` is a sample at; fresh chains (``start=None``)
+        are uniform and need ``beta_from == 0``.  Returns ``(samples, log_weights, energies)``: (C, n) float32 +-1, (C,)
+        float64, (C,) float64 on the device; no host sync.
+
+        Its own key ``field_ais_seed`` and counter ``field_ais_sweep_count``: every other stream, the persistent chains,
+        ``sweep_count`` and ``calls`` are left alone; chain ids are ``chain_offset + arange(C)``."""
+        n = self.plan.n
+        if not torch.is_tensor(fields):
+            raise _lib.DvgError(f"fields must be a tensor, got {type(fields).__name__}")
+        if fields.dtype != torch.float32:
+            raise _lib.DvgError(f"fields must be float32, got {fields.dtype}")
+        if fields.dim() not in (1, 2) or fields.shape[-1] != n or fields.shape[0] < 1:
+            raise _lib.DvgError(f"fields must be (rows, {n}) or ({n},), got {tuple(fields.shape)}")
+        R = _whole("chains_per_row", chains_per_row)
+        rows = int(fields.shape[0]) if fields.dim() == 2 else None
+        if betas is None and scales is None:
+            raise ValueError("sample_fields_ais needs betas, scales or both: they name the sweeps")
+        bf, sf = float(beta_from), float(scale_from)
+        with np.errstate(over="ignore"):
+            if not np.isfinite(np.float32(bf)) or bf < 0.0:
+                raise ValueError(f"beta_from={beta_from!r} must be finite and >= 0")
+            if not np.isfinite(np.float32(sf)):
+                raise ValueError(f"scale_from={scale_from!r} must be finite")
+        if start is None and np.float32(bf) != 0.0:
+            raise ValueError(f"beta_from={beta_from!r} with fresh chains: they are uniform, a sample at beta 0 and at no other; "
+                             "give the chains' states as `start`")
+        if num_reads is not None:
+            num_reads = _whole("num_reads", num_reads)
+        if start is not None:
+            C = self._check_start(start, count=num_reads)
+        elif num_reads is not None:
+            C = num_reads
+        elif rows is not None:
+            C = rows * R
+        else:
+            raise ValueError(f"fields of shape ({n},) need start or num_reads to know how many chains to draw")
+        if rows is not None and rows * R != C:
+            raise _lib.DvgError(f"fields has {rows} rows of {R} chains each but the draw has {C} chains")
+        host_b = None if betas is None else _check_beta_table(betas, "betas", rows=C)
+        host_s = None if scales is None else _check_beta_table(scales, "scales", rows=C, signed=True)
+        shapes = [tuple(t.shape) if hasattr(t, "shape") else np.shape(t) for t in (betas, scales) if t is not None]
+        S = int(shapes[0][-1])
+        if any(int(sh[-1]) != S for sh in shapes):
+            raise _lib.DvgError(f"betas names {int(shapes[0][-1])} sweeps, scales {int(shapes[1][-1])}")
+        _on_gpu("fields", fields)
+        lin, quad = self._parameters(linear, quadratic, start=start, fields=fields, betas=betas, scales=scales)
+        if betas is None:
+            b_table = torch.full((S,), self.beta, dtype=torch.float32, device=lin.device)
+        else:
+            b_table = _beta_table(betas, lin.device, "betas", rows=C, host=host_b)
+        s_table = None if scales is None else _beta_table(scales, lin.device, "scales", rows=C, host=host_s)
+        state, init = self._own_chains(start, C, lin.device)
+        rows_dev = fields.detach().contiguous()
+        out = torch.empty((C, n), dtype=torch.float32, device=lin.device)
+        log_w = torch.empty((C,), dtype=torch.float64, device=lin.device)
+        energy = torch.empty((C,), dtype=torch.float64, device=lin.device)
+        self._call("dvg_gibbs_sample_fields_ais", lin, quad, prefactor, linear_range, quadratic_range,
+                   b_table.data_ptr(), S if b_table.dim() == 2 else 0, bf,
+                   None if s_table is None else s_table.data_ptr(), S if s_table is not None and s_table.dim() == 2 else 0, sf,
+                   state.data_ptr(), C, self.chain_offset & 0xFFFFFFFF, self.field_ais_seed,
+                   self.field_ais_sweep_count & 0xFFFFFFFF, S, init, rows_dev.data_ptr(), n if rows is not None else 0, R,
+                   out.data_ptr(), log_w.data_ptr(), energy.data_ptr(), None)
+        self.field_ais_sweep_count += S
+        return out, log_w, energy
+
+    def log_evidence(self, linear: torch.Tensor, quadratic: torch.Tensor, prefactor: float, linear_range, quadratic_range,
+                     fields: torch.Tensor, *, chains_per_row: int = 64, num_sweeps: int = 100, burn_in: Optional[int] = None,
+                     start: Optional[torch.Tensor] = None) -> "LogEvidence":
+        """Per row of ``fields`` (rows, n), the estimate of ``log(Z_r / Z)``: ``Z`` the normaliser of the distribution the
+        sampler draws from, ``Z_r`` that of the same model with row r added to its linear terms.  With ``fields =
+        logit_fields(logits, ...)`` this is the log of the prior mass that agrees with the evidence, ``log sum_z p(z) prod_i
+        exp(l_i z_i / 2)``, without an estimate of ``log Z``.
+
+        ``chains_per_row`` chains per row start as draws of the prior -- ``start`` (rows * chains_per_row, n) if given, else
+        one :meth:`sample_fields` call with a shared all-zero row and ``burn_in`` sweeps (default: the sampler's ``sweeps``) from
+        fresh chains -- and one :meth:`sample_fields_ais` call at the sampler's beta turns the rows on linearly over
+        ``num_sweeps`` sweeps, ``scales = linspace(0, 1, num_sweeps + 1)[1:]``, weighing each step.  Returns a
+        :class:`LogEvidence`; its reductions are torch ops on the device, no host sync.
+
+        The estimate is unbiased in ``Z_r / Z`` only if the start states are draws of the prior: chains that are not yet at
+        equilibrium after ``burn_in`` sweeps bias it, and the standard error does not show that."""
+        n = self.plan.n
+        if not torch.is_tensor(fields) or fields.dim() != 2 or fields.shape[-1] != n or fields.shape[0] < 1:
+            raise _lib.DvgError(f"fields must be a (rows, {n}) tensor, got "
+                                f"{tuple(fields.shape) if torch.is_tensor(fields) else type(fields).__name__}")
+        R, S = _whole("chains_per_row", chains_per_row), _whole("num_sweeps", num_sweeps)
+        rows = int(fields.shape[0])
+        burn = self.sweeps if burn_in is None else _whole("burn_in", burn_in, low=0)
+        if start is None:
+            zero = torch.zeros((n,), dtype=torch.float32, device=fields.device)
+            start = self.sample_fields(linear, quadratic, prefactor, linear_range, quadratic_range, zero, sweeps=burn,
+                                       num_reads=rows * R)
+        scales = np.linspace(0.0, 1.0, S + 1)[1:].astype(np.float32)
+        samples, log_w, _energy = self.sample_fields_ais(linear, quadratic, prefactor, linear_range, quadratic_range, fields, None,
+                                                         scales, chains_per_row=R, start=start, beta_from=self.beta, scale_from=0.0)
+        return LogEvidence.from_weights(log_w.view(rows, R), samples)
 
     def _annealed_arguments(self, linear, quadratic, betas, num_reads, start, beta_from=None):
         """The argument checks and buffers :meth:`sample_annealed` and :meth:`sample_ais` share; every check comes before

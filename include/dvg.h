@@ -154,7 +154,8 @@ int dvg_gibbs_sample_clamped(const dvg_graph_t *g, const float *linear, const fl
  *     dyn != NULL (the draw is one-off, not part of a captured step).  It takes the rolled kernel form on every graph
  *     (csrc/gibbs_plan.h), a float32 row of hs_c per chain beside the state rows in LDS -- workgroups of fewer chains on large
  *     graphs; DVG_E_UNSUPPORTED if the graph's image does not fit the LDS with one chain's rows beside it.  Every other argument as
- *     for dvg_gibbs_sample.  No held, annealed, weighed, exchange or traced form of this draw. */
+ *     for dvg_gibbs_sample.  Its annealed and weighed form is dvg_gibbs_sample_fields_ais; no held, exchange or traced form of
+ *     this draw. */
 int dvg_gibbs_sample_fields(const dvg_graph_t *g, const float *linear, const float *quadratic,
                             float prefactor, float h_lo, float h_hi, float j_lo, float j_hi, float beta,
                             int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
@@ -204,6 +205,51 @@ int dvg_gibbs_sample_ais(const dvg_graph_t *g, const float *linear, const float 
                          uint32_t sweep0, int n_sweeps, int init, float *samples_out,
                          double *log_weight_out, double *energy_out,
                          const dvg_step_state_t *dyn, dvg_stream_t stream);
+/* The weighed per-chain-field draw ("DVG field AIS v1"): dvg_gibbs_sample_fields along a path in (beta, field strength), both
+ * looked up per sweep, with the log importance weight and the energy of "DVG AIS v1" per chain.  The use: start from draws of the
+ * prior, turn a chain's evidence on over the sweeps, weigh each step -- the weights of the chains that share a row estimate
+ * log (Z_row / Z), the log evidence of that row under the prior, and the chains end as annealed posterior draws.
+ *   Rows.  fields, field_chain_stride: as for dvg_gibbs_sample_fields, except that with field_chain_stride == n chain c reads
+ *     row r = c / field_row_chains (R >= 1; c counts from 0 within the call): R consecutive chains share a row, which is stored
+ *     once; fields then has ceil(n_chains / R) rows.  With stride 0 all chains read row 0 and R is ignored.
+ *   Tables.  betas, beta_chain_stride, beta_from: as for dvg_gibbs_sample_ais (stride 0 or n_sweeps; finite and >= 0, not checked
+ *     on the device).  scales: DEVICE pointer, float32, the field strength lambda of every sweep, or NULL: 1 throughout;
+ *     scale_chain_stride = 0: one row of n_sweeps entries shared by all chains, = n_sweeps: a row per chain.  The values must be
+ *     finite (not checked on the device).  scale_from: the strength the start states are a sample under.
+ *   For chain c with row r and sweep k of the call (global index sweep0 + k), in float32:
+ *     lambda_k  = scales ? scales[c * scale_chain_stride + k] : 1,     lambda_{-1} = scales ? scale_from : 1
+ *     row_k[i]  = clamp(rn(prefactor * rn(linear[i] + rn(lambda_k * fields[r][i]))), h_lo, h_hi)
+ *   Sweep k is one "DVG block-Gibbs v1" sweep at beta_k = betas[c * beta_chain_stride + k] with hs = row_k: the CSR-order signed
+ *     adds starting from row_k[i], two_beta = 2 * beta_k, spec_exp, the decision, the Philox counter (spin, chain id,
+ *     (sweep0 + k) >> 2, STREAM_GIBBS), the INIT stream.  With lambda == 1, row_k is hs_c of "DVG field v1", bit for bit.
+ *   The energy is carried as in "DVG AIS v1": E = sum_i 1/2 s_i (row_{-1}[i] + f_i(s; row_{-1})) at the start, and every update
+ *     adds (s_new - s_old) f_i, f_i the float32 field the decision used.  At the head of sweep k, with s the state before the
+ *     sweep, in float64:
+ *       d_k    = sum_i ((double)row_k[i] - (double)row_{k-1}[i]) * s_i           (each addend exact)
+ *       log_w -= (beta_k - beta_{k-1}) * E  +  beta_k * d_k                      (beta_{-1} = beta_from)
+ *       E     += d_k
+ *     so that log_w = -sum_k [beta_k E_k(s^(k)) - beta_{k-1} E_{k-1}(s^(k))], E_k the energy under row_k: the AIS weight along
+ *     any path in (beta, lambda).  With scales == NULL, d_k is identically 0 and is not computed.  Only the order of the float64
+ *     additions is the implementation's.
+ *   log_weight_out[c] = log_w, energy_out[c] = E behind the last sweep: DEVICE pointers, float64, [n_chains].  Either may be
+ *     NULL; without log_weight_out this is the annealed per-chain-field draw, unweighed.
+ *   The estimate, over the chains that share a row:  log Z(beta_last, lambda_last) - log Z(beta_from, scale_from) ~=
+ *     logsumexp(log_w) - log(count).  Fresh chains (init != 0) are uniform: init != 0 needs beta_from == 0.
+ *   With scales == NULL and every beta equal to beta_from the spins are dvg_gibbs_sample_fields' and log_w == 0 exactly; with
+ *     all fields zero the spins, weights and energies are dvg_gibbs_sample_ais'.  A chain's result is a function of its id, its
+ *     row, its table rows, the model and the graph alone.
+ *   DVG_E_INVALID, before any launch (nothing is written): what dvg_gibbs_sample_fields and dvg_gibbs_sample_ais each reject
+ *     (log_weight_out == NULL excepted); a scale stride that is neither 0 nor n_sweeps; field_row_chains < 1; scale_from not
+ *     finite; dyn != NULL.  The kernel form and its LDS are dvg_gibbs_sample_fields' (csrc/gibbs_plan.h: GK_FIELD_WEIGH). */
+int dvg_gibbs_sample_fields_ais(const dvg_graph_t *g, const float *linear, const float *quadratic,
+                                float prefactor, float h_lo, float h_hi, float j_lo, float j_hi,
+                                const float *betas, int64_t beta_chain_stride, float beta_from,
+                                const float *scales, int64_t scale_chain_stride, float scale_from,
+                                int8_t *state, int n_chains, uint32_t chain_id0, uint64_t seed,
+                                uint32_t sweep0, int n_sweeps, int init,
+                                const float *fields, int64_t field_chain_stride, int field_row_chains,
+                                float *samples_out, double *log_weight_out, double *energy_out,
+                                const dvg_step_state_t *dyn, dvg_stream_t stream);
 /* The exchange draw ("DVG PT v1"): parallel tempering (replica exchange).  Chains of one model run side by side at the
  * inverse temperatures of a LADDER and, every few sweeps, chains on neighbouring rungs exchange their rungs on a Metropolis
  * coin, inside the kernel: the chain at the target beta keeps being fed states that crossed between modes where it is hot.
