@@ -146,6 +146,12 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
     ),
+    "dvg_packed_distinct_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "dvg_packed_distinct": (
+        c_int,
+        [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
+    ),
     "dvg_grbm_energy_packed": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64, c_int64,

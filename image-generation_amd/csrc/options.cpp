@@ -42,6 +42,7 @@ const OptDef kDefs[OPT_COUNT] = {
     {"mmd_gram_fp4", 1, "MMD: exact Gram of +-1 rows on the FP4 matrix pipe (scaled 32x32x64 MFMA on a packed e2m1 copy of the rows: the same integers at half the operand bytes and k-steps) in the 256-row distance-sum kernel and the 128-row-block pair kernel at d = 256, 512 (default); 0: the int8 form (A/B reference, same bits)", true},
     {"dec_spin_gemm", 1, "decoder input layer on spins the caller declared +-1 (dvg_decoder_declare_spins): 1 (default) its forward GEMM and its weight-gradient GEMM multiply the spins as exact bf16 values with the float32 operand as three bf16 pieces (three exact products on the bf16 matrix pipe); 2 the forward GEMM alone (A/B runs); 0 every declaration is ignored: the kernels of the operand mode, bit for bit", true},
     {"dev_spin_operand", 0, "test knob: 1 = the development hooks dvg_dev_conv_igemm / dvg_dev_conv_wgrad make the +-1 promise for their input operand", true},
+    {"distinct_hash_bits", -1, "test knob of dvg_packed_distinct: -1 (default) the full 32-bit hash of a row picks its start slot; k >= 0 keeps the low k bits of the hash (0: every row starts at slot 0) -- long probe chains and wrap-around at small sizes, the same results", true},
 };
 std::atomic<int64_t> g_val[OPT_COUNT];
 std::once_flag g_once;

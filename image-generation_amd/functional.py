@@ -467,6 +467,79 @@ def packed_correlation(bits, *, n, spin_sums=True, out=None):
     return spin_sum, pair_sum
 
 
+DistinctRows = collections.namedtuple("DistinctRows", "first id rep count other_id other_hits")
+
+
+def packed_distinct(bits, other=None, *, n):
+    """Which bit-packed +-1 rows are the same state and how often each state occurs, exactly (``dvg_packed_distinct``, "DVG
+    distinct v1").  ``bits``: (rows, W) or (C, M, W) int32 on the device (``sampler.pack_spins``, ``sampler.Trace.bits``; bits
+    of spins >= n are ignored and never distinguish rows); the T rows are pooled under the flattened index t = c M + m.  The
+    last dimension must have stride 1, the other strides are taken from the tensor, so slices need no copy.  ``other``: None or
+    a (rows, W) int32 set on the same device whose rows are looked up among the classes, never inserted.  Returns the
+    namedtuple ``DistinctRows``: ``first`` (T,) int32, the smallest index with row t's content; ``id`` (T,) int32, row t's
+    class, the classes numbered by first occurrence; ``rep`` (D,) int32, the classes' first rows; ``count`` (D,) int64, their
+    sizes; with ``other`` ``other_id`` (rows_other,) int32, the class equal to each row of ``other`` or -1, and
+    ``other_hits`` (D,) int64, how many rows of ``other`` each class equals -- else None.  It allocates its workspace (about
+    32 bytes a row) and reads the number of classes D back: one host sync."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError(f"n must be an integer >= 1, got {n!r}")
+    n = int(n)
+    W = (n + 31) // 32
+    rows, rs, groups, gs = _packed_rows(bits, "bits", W)
+    rows_o = o_rs = 0
+    if other is not None:
+        if torch.is_tensor(other) and other.dim() == 3:
+            raise _lib.DvgError(f"other must be a flat (rows >= 1, {W}) int32 set, got {tuple(other.shape)}")
+        rows_o, o_rs, _groups, _gs = _packed_rows(other, "other", W)
+        if other.device != bits.device:
+            raise _lib.DvgError(f"other must be on the device of bits ({bits.device}), got {other.device}")
+    T = rows * groups
+    if T >= 2 ** 31 or rows_o >= 2 ** 31:
+        raise _lib.DvgError(f"packed_distinct indexes rows by int32: {T} rows and {rows_o} rows of other must stay below 2^31")
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    bd, od = bits.detach(), other.detach() if other is not None else None
+    dev = bd.device
+    first, ident, rep = (torch.empty((T,), dtype=torch.int32, device=dev) for _ in range(3))
+    count = torch.empty((T,), dtype=torch.int64, device=dev)
+    n_distinct = torch.empty((1,), dtype=torch.int64, device=dev)
+    other_id = torch.empty((rows_o,), dtype=torch.int32, device=dev) if od is not None else None
+    other_hits = torch.empty((T,), dtype=torch.int64, device=dev) if od is not None else None
+    with torch.cuda.device(dev):
+        ws = _ws(lib().dvg_packed_distinct_workspace_bytes(rows, groups, n), dev)
+        check(lib().dvg_packed_distinct(bd.data_ptr(), rows, rs, groups, gs, n, _lib.ptr(od), rows_o, o_rs, first.data_ptr(),
+                                        ident.data_ptr(), rep.data_ptr(), count.data_ptr(), n_distinct.data_ptr(), _lib.ptr(other_id),
+                                        _lib.ptr(other_hits), ws.data_ptr(), ws.numel(), stream_ptr(dev)), "dvg_packed_distinct")
+    D = int(n_distinct.item())  # the one host read
+    if D < 1:
+        raise _lib.DvgError(f"dvg_packed_distinct: the table of {T} rows overflowed (n_distinct = {D})")
+    return DistinctRows(first, ident, rep[:D], count[:D], other_id, other_hits[:D] if other_hits is not None else None)
+
+
+def packed_distinct_counts(bits, *, n):
+    """The number of distinct rows of every group of a (C, M, W) int32 set of bit-packed rows, each group on its own: (C,)
+    int64 on the device.  One call of ``dvg_packed_distinct`` per group on its slice of ``bits`` -- only ``n_distinct`` is
+    asked for, element c of the result -- through one workspace; no copy and no host sync."""
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+        raise ValueError(f"n must be an integer >= 1, got {n!r}")
+    n = int(n)
+    if not torch.is_tensor(bits) or bits.dim() != 3:
+        raise _lib.DvgError(f"bits must be (chains >= 1, records >= 1, {(n + 31) // 32}) int32, got "
+                            f"{(tuple(bits.shape), bits.dtype) if torch.is_tensor(bits) else type(bits).__name__}")
+    rows, rs, groups, gs = _packed_rows(bits, "bits", (n + 31) // 32)
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    bd = bits.detach()
+    out = torch.empty((groups,), dtype=torch.int64, device=bd.device)
+    with torch.cuda.device(bd.device):
+        ws = _ws(lib().dvg_packed_distinct_workspace_bytes(rows, 1, n), bd.device)
+        for c in range(groups):
+            check(lib().dvg_packed_distinct(bd.data_ptr() + 4 * c * gs, rows, rs, 1, 0, n, None, 0, 0, None, None, None, None,
+                                            out.data_ptr() + 8 * c, None, None, ws.data_ptr(), ws.numel(), stream_ptr(bd.device)),
+                  "dvg_packed_distinct")
+    return out
+
+
 Fields = collections.namedtuple("Fields", "log_pl unstable cond_sum cond_pair fields")
 
 

@@ -1145,6 +1145,46 @@ class ModelWrapper:
         return dict(nearest_dist=dist, nearest_row=row, overlap=Overlap.from_hist(hist, n), data_nearest_dist=data_dist)
 
     @torch.no_grad()
+    def prior_distinct(self, **kw):
+        """How many distinct states one draw of the sampler holds on the prior: the :class:`~.sampler.Distinct` of the draw
+        ``generate_images`` takes (``kw`` go on top of the sampler's keyword arguments, ``num_reads`` for instance) --
+        ``distinct``, ``entropy``, ``collision_share``, ``unseen_mass``.  Rank-local and eval-mode, like ``generate_images``."""
+        from .sampler import distinct, pack_spins
+
+        self._dvae.eval()
+        self._grbm.eval()
+        samples = self._grbm.sample(self.sampler, prefactor=self.PREFACTOR, device=self._device, linear_range=self.linear_range,
+                                    quadratic_range=self.quadratic_range, sample_params=dict(self.sampler_kwargs, **kw))
+        return distinct(pack_spins(samples.to(self._device)), n=int(samples.shape[1]))
+
+    @torch.no_grad()
+    def latent_usage(self, images: torch.Tensor, samples: Optional[torch.Tensor] = None) -> dict:
+        """Exact copies between generated and data latents, and how many codes the encoder uses: ``images`` and ``samples``
+        are encoded, packed and drawn as ``latent_novelty`` does.  Returns a dict: ``data``, the :class:`~.sampler.Distinct` of
+        the data latents (few classes: the encoder collapses onto a few codes); ``drawn``, the :class:`~.sampler.Distinct` of
+        the generated latents with the data latents looked up among them; ``copied_share``, the share of generated rows that
+        are exactly a data code (``latent_novelty``'s ``nearest_dist == 0``); ``data_found_share``, the share of data rows
+        whose code the draw contains -- float64 scalars on the device.  Rank-local and eval-mode, like ``generate_images``."""
+        from .sampler import distinct, pack_spins
+
+        self._dvae.eval()
+        self._grbm.eval()
+        images = images.to(self._device)
+        spins = F.heaviside_latent_to_discrete(self._dvae.encoder(images)).squeeze(1)  # (B, n) +-1
+        n = int(spins.shape[1])
+        if samples is None:
+            samples = self._grbm.sample(self.sampler, prefactor=self.PREFACTOR, device=self._device,
+                                        linear_range=self.linear_range, quadratic_range=self.quadratic_range,
+                                        sample_params=self.sampler_kwargs)
+        samples = samples.to(self._device)
+        if samples.dim() != 2 or int(samples.shape[1]) != n:
+            raise ValueError(f"samples must be (rows, {n}) spins, got {tuple(samples.shape)}")
+        data, drawn = pack_spins(spins), pack_spins(samples)
+        of_data, of_drawn = distinct(data, n=n), distinct(drawn, data, n=n)
+        copied = (of_drawn.other_hits > 0)[of_drawn.index.to(torch.int64)].to(torch.float64).mean()
+        return dict(data=of_data, drawn=of_drawn, copied_share=copied, data_found_share=of_drawn.coverage[0])
+
+    @torch.no_grad()
     def reconstruct_images(self, batch: Optional[torch.Tensor] = None, sharpen: bool = False,
                            lower: float = LOWER_THRESHOLD, upper: float = UPPER_THRESHOLD) -> torch.Tensor:
         """Eval-mode encode -> discretise -> decode of one batch of training images, interleaved with the originals:

@@ -195,9 +195,10 @@ def _beta_table(betas, device, what: str, rows: Optional[int] = None, own: bool 
 
 
 class _Record:
-    def __init__(self, sample, energy):
+    def __init__(self, sample, energy, num_occurrences=None):
         self.sample = sample
         self.energy = energy
+        self.num_occurrences = num_occurrences
 
 
 class SampleSet:
@@ -205,16 +206,19 @@ class SampleSet:
     (/root/reference/src/losses.py:59, /root/reference/src/utils/persistent_qpu_sampler.py:90-95):
     ``.record.sample`` (reads x variables, int8), ``.record.energy``, ``.variables``, ``.vartype``.
     ``device_tensor`` keeps the float32 samples on the GPU so ``sampleset_to_tensor``
-    needs no host round trip."""
+    needs no host round trip.  ``.record.num_occurrences`` (reads,) int64: all ones for a raw set, the multiplicities of the
+    distinct reads for an aggregated one (:meth:`aggregate`)."""
 
     def __init__(self, samples: np.ndarray, variables: Sequence, energy=None, vartype="SPIN", device_tensor=None,
-                 device_energy=None):
+                 device_energy=None, num_occurrences=None, device_occurrences=None):
         self._samples = samples
         self._energy = energy
         self.variables = list(variables)
         self.vartype = vartype
         self.device_tensor = device_tensor
         self.device_energy = device_energy  # (reads,) float32 on the GPU: the per-read energy, not yet on the host
+        self._occurrences = num_occurrences
+        self.device_occurrences = device_occurrences  # (reads,) int64 on the GPU, or None
 
     @property
     def record(self):
@@ -222,10 +226,60 @@ class SampleSet:
             self._samples = self.device_tensor.to(torch.int8).cpu().numpy()
         if self._energy is None and self.device_energy is not None:
             self._energy = self.device_energy.cpu().numpy()
-        return _Record(self._samples, self._energy)
+        if self._occurrences is None:
+            self._occurrences = self.device_occurrences.cpu().numpy() if self.device_occurrences is not None else \
+                np.ones(len(self), dtype=np.int64)
+        return _Record(self._samples, self._energy, self._occurrences)
 
     def __len__(self):
         return int(self.device_tensor.shape[0]) if self.device_tensor is not None else len(self._samples)
+
+    def aggregate(self) -> "SampleSet":
+        """``dimod.SampleSet.aggregate()``: a new set of the distinct reads in the order of their first occurrence, each once,
+        ``record.num_occurrences`` the sum of the occurrences of its copies and ``record.energy`` the first copy's.  Two reads
+        are equal when the same variables are > 0.  A device-held set stays on the device (``pack_spins`` and
+        ``dvg_packed_distinct``: one host read, the number of distinct reads); a host-only set takes the same definition in
+        numpy."""
+        if self.device_tensor is not None:
+            from . import functional as F  # (functional imports this module)
+
+            t = self.device_tensor
+            d = F.packed_distinct(pack_spins(t), n=int(t.shape[1]))
+            rep = d.rep.to(torch.int64)
+            occ = d.count
+            if self.device_occurrences is not None or self._occurrences is not None:
+                had = self.device_occurrences if self.device_occurrences is not None else torch.from_numpy(np.asarray(self._occurrences))
+                occ = torch.zeros_like(d.count).index_add_(0, d.id.to(torch.int64), had.to(device=t.device, dtype=torch.int64))
+            energy = self.device_energy[rep] if self.device_energy is not None else None
+            host_energy = np.asarray(self._energy)[rep.cpu().numpy()] if energy is None and self._energy is not None else None
+            return SampleSet(None, self.variables, energy=host_energy, vartype=self.vartype, device_tensor=t[rep],
+                             device_energy=energy, device_occurrences=occ)
+        rec = self.record
+        samples = np.asarray(rec.sample)
+        keys = np.packbits(samples > 0, axis=1)
+        seen, rep, ident = {}, [], np.empty(len(samples), dtype=np.int64)
+        for t in range(len(samples)):
+            k = keys[t].tobytes()
+            if k not in seen:
+                seen[k] = len(rep)
+                rep.append(t)
+            ident[t] = seen[k]
+        occ = np.bincount(ident, weights=None if rec.num_occurrences is None else np.asarray(rec.num_occurrences),
+                          minlength=len(rep)).astype(np.int64)
+        energy = np.asarray(rec.energy)[rep] if rec.energy is not None else None
+        return SampleSet(samples[rep], self.variables, energy=energy, vartype=self.vartype, num_occurrences=occ)
+
+    def _sorted_by_energy(self) -> "SampleSet":
+        """The same reads by rising energy, ties in their present order (a stable sort, on the device for a device-held set)."""
+        if self.device_tensor is not None and self.device_energy is not None:
+            order = torch.sort(self.device_energy, stable=True).indices
+            occ = self.device_occurrences[order] if self.device_occurrences is not None else None
+            return SampleSet(None, self.variables, vartype=self.vartype, device_tensor=self.device_tensor[order],
+                             device_energy=self.device_energy[order], device_occurrences=occ)
+        rec = self.record
+        order = np.argsort(np.asarray(rec.energy), kind="stable")
+        return SampleSet(np.asarray(rec.sample)[order], self.variables, energy=np.asarray(rec.energy)[order], vartype=self.vartype,
+                         num_occurrences=np.asarray(rec.num_occurrences)[order])
 
 
 class LogPartition:
@@ -989,6 +1043,110 @@ def _popcount32(words):
     return ((x * 0x01010101) >> 24) & 0xFF
 
 
+class Distinct:
+    """Which of T bit-packed +-1 rows are the same state, and how often each state occurs (``dvg_packed_distinct``, "DVG
+    distinct v1"; :func:`distinct`, :meth:`Trace.distinct`, :meth:`Minima.distinct`): the D classes of the rows under equality
+    on the spins < n, numbered in the order of their first occurrence.  ``rows`` (D, W) int32: the classes' first rows, pad
+    bits cleared; ``counts`` (D,) int64: their sizes; ``index`` and ``first``, int32 of the input's leading shape: every
+    row's class and the smallest flattened index with the row's content; ``other_id`` (rows_other,) int32 and ``other_hits``
+    (D,) int64 where a second set was looked up (else None): the class equal to each of its rows, -1 for none, and how many of
+    its rows each class equals; ``n`` the number of spins.  Every member is torch on the data's device (CPU tensors too); no
+    host sync except ``count`` and ``distinct``, which read shapes:
+
+    ``count``: T;  ``distinct``: D;  ``singletons``: the classes of size 1, int64;
+    ``entropy``: the plug-in entropy ``-sum p log p`` of p = counts / T, float64 (nats);
+    ``collision_share``: ``sum c (c - 1) / (T (T - 1))``, the share of ordered pairs of rows that are equal (NaN for T = 1);
+    ``unseen_mass``: the Good-Turing estimate ``singletons / T`` of the probability of states not seen;
+    ``top(k)``: ``(rows, counts, classes)`` of the ``k`` largest classes (all if fewer), by falling size, ties by first
+    occurrence;
+    ``coverage``: ``(found, hit)`` float64 -- the share of ``other``'s rows that equal a class and the share of classes that
+    equal a row of ``other`` -- or None without ``other``."""
+
+    def __init__(self, rows, counts, index, first, n, other_id=None, other_hits=None):
+        self.rows, self.counts, self.index, self.first, self.n = rows, counts, index, first, int(n)
+        self.other_id, self.other_hits = other_id, other_hits
+
+    @classmethod
+    def from_outputs(cls, bits, first, id, rep, count, n, other_id=None, other_hits=None) -> "Distinct":
+        """From the rows ``bits`` ((T, W) or (C, M, W) int32) and ``functional.packed_distinct``'s outputs for them."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n must be an integer >= 1, got {n!r}")
+        W = (int(n) + 31) // 32
+        if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() not in (2, 3) or bits.shape[-1] != W or bits.numel() < 1:
+            raise ValueError(f"bits must be an int32 tensor of shape (rows >= 1, {W}) or (chains >= 1, records >= 1, {W})")
+        lead = bits.shape[:-1]
+        T = int(np.prod(lead))
+        for name, t in (("first", first), ("id", id)):
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or t.numel() != T:
+                raise ValueError(f"{name} must be an int32 tensor of the {T} rows")
+        if not torch.is_tensor(rep) or rep.dtype != torch.int32 or rep.dim() != 1 or not 1 <= rep.numel() <= T:
+            raise ValueError(f"rep must be a (D,) int32 tensor, 1 <= D <= {T}")
+        if not torch.is_tensor(count) or count.dtype != torch.int64 or count.shape != rep.shape:
+            raise ValueError(f"count must be a ({rep.numel()},) int64 tensor")
+        if (other_id is None) != (other_hits is None):
+            raise ValueError("other_id and other_hits go together")
+        if other_hits is not None and (not torch.is_tensor(other_hits) or other_hits.dtype != torch.int64 or other_hits.shape != rep.shape):
+            raise ValueError(f"other_hits must be a ({rep.numel()},) int64 tensor")
+        r = rep.to(torch.int64)
+        rows = bits[r] if bits.dim() == 2 else bits[r // int(lead[1]), r % int(lead[1])]
+        if int(n) % 32:
+            mask = torch.full((W,), -1, dtype=torch.int32, device=rows.device)
+            mask[-1] = (1 << (int(n) % 32)) - 1
+            rows = rows & mask
+        return cls(rows, count, id.view(lead), first.view(lead), n, other_id, other_hits)
+
+    @property
+    def count(self) -> int:
+        return int(self.index.numel())
+
+    @property
+    def distinct(self) -> int:
+        return int(self.counts.numel())
+
+    @property
+    def singletons(self):
+        return (self.counts == 1).sum()
+
+    @property
+    def entropy(self):
+        p = self.counts.to(torch.float64) / float(self.count)
+        return -(p * torch.log(p)).sum()
+
+    @property
+    def collision_share(self):
+        T = self.count
+        return (self.counts * (self.counts - 1)).sum().to(torch.float64) / float(T * (T - 1))
+
+    @property
+    def unseen_mass(self):
+        return self.singletons.to(torch.float64) / float(self.count)
+
+    def top(self, k: int):
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError(f"k must be an integer >= 1, got {k!r}")
+        pick = torch.sort(self.counts, descending=True, stable=True).indices[:int(k)]
+        return self.rows[pick], self.counts[pick], pick
+
+    @property
+    def coverage(self):
+        if self.other_id is None:
+            return None
+        return (self.other_id >= 0).to(torch.float64).mean(), (self.other_hits > 0).to(torch.float64).mean()
+
+    def __repr__(self):
+        return f"Distinct(n={self.n}, count={self.count}, distinct={self.distinct})"
+
+
+def distinct(bits, other=None, *, n) -> Distinct:
+    """The :class:`Distinct` of bit-packed rows ((rows, W) or (C, M, W) int32 on the device, views welcome; a 3-D set is pooled):
+    one call of ``dvg_packed_distinct`` -- the rows stay packed and ``bits`` is left as it is.  ``other``: a flat (rows, W) set
+    to look up among the classes (``other_id``, ``other_hits``, ``coverage``), never inserted."""
+    from . import functional as F  # (functional imports this module)
+
+    d = F.packed_distinct(bits, other, n=n)
+    return Distinct.from_outputs(bits.detach(), d.first, d.id, d.rep, d.count, int(n), d.other_id, d.other_hits)
+
+
 class Minima:
     """What a zero-temperature descent of T +-1 rows arrived at (``dvg_grbm_descend_packed``, "DVG descent v1";
     :func:`descend`, :meth:`Trace.descend`): ``start_bits`` and ``bits`` (T, W) or (C, M, W) int32, the rows before and after
@@ -1004,6 +1162,7 @@ class Minima:
     ``unique()``: ``(rows, counts, index)`` -- the distinct final rows (U, W) int32, their multiplicities (U,) int64 and every
     row's index into them (leading shape, int64); ordered by falling multiplicity, ties in the order of
     ``torch.unique(dim=0)`` on the words;
+    ``distinct()``: the same partition as a :class:`Distinct` (``dvg_packed_distinct``), the classes by first occurrence;
     ``basin_entropy``: ``-sum p log p`` of the multiplicities over T;
     ``lowest(k)``: ``(rows, energy, counts)`` of the ``k`` distinct final rows of lowest energy (all of them if fewer), by
     rising energy, ties in ``unique()``'s order."""
@@ -1069,6 +1228,11 @@ class Minima:
         rank = torch.empty_like(perm)
         rank[perm] = torch.arange(perm.numel(), dtype=perm.dtype, device=perm.device)
         return rows[perm], counts[perm], rank[inverse.reshape(-1)].view(self.bits.shape[:-1])
+
+    def distinct(self) -> Distinct:
+        """The distinct final rows as a :class:`Distinct` (``dvg_packed_distinct``: the rows stay packed, on the device): the
+        partition of :meth:`unique`, the classes in the order of their first occurrence."""
+        return distinct(self.bits, n=self.n)
 
     @property
     def basin_entropy(self):
@@ -1250,6 +1414,18 @@ class Trace:
         the chains sat above (``dvg_grbm_descend_packed``: the records stay packed and are left as they are)."""
         return descend(self.bits, graph, linear, quadratic, prefactor=prefactor, linear_range=linear_range,
                        quadratic_range=quadratic_range, max_sweeps=max_sweeps)
+
+    def distinct(self, pooled: bool = True):
+        """Which states the chains visited (``dvg_packed_distinct``: the records stay packed).  ``pooled=True``: the
+        :class:`Distinct` of all C M records under the flattened index c M + m -- ``distinct`` states in all, the plug-in
+        ``entropy`` of their visit counts, the Good-Turing ``unseen_mass``.  ``pooled=False``: a (C,) int64 tensor on the
+        device, the number of distinct states every chain visited on its own (one call per chain on its slice of ``bits``,
+        no copy and no host sync)."""
+        if pooled:
+            return distinct(self.bits, n=self.n)
+        from . import functional as F  # (functional imports this module)
+
+        return F.packed_distinct_counts(self.bits, n=self.n)
 
     def correlations(self) -> Correlations:
         """The full pair correlations over all C M records, pooled (``dvg_packed_correlation``: the records stay packed), as
@@ -2238,7 +2414,12 @@ class GibbsSampler:
         they do not go together with ``beta_range`` / ``beta_schedule``.
 
         The returned set carries the per-read Ising energy ``h.s + sum J s_i s_j`` of the ``(h, J)`` given, computed on
-        the device (``dvg_grbm_energy``) and brought to the host when ``.record`` is read."""
+        the device (``dvg_grbm_energy``) and brought to the host when ``.record`` is read.
+
+        ``answer_mode="histogram"`` (a D-Wave sampler's own default) returns every distinct read once, with
+        ``record.num_occurrences``, by rising energy and ties by first occurrence (:meth:`SampleSet.aggregate` of the raw
+        reads; the energy is that of the first copy).  ``"raw"``, which the reference passes, and every other value return
+        the reads as drawn."""
         if auto_scale:
             raise ValueError("auto_scale=True is not supported: the sampler draws from the distribution it is given")
         betas = tables = None
@@ -2298,7 +2479,10 @@ class GibbsSampler:
 
         with torch.no_grad():
             energy = F.grbm_energy(t, lin, quad, self.graph)
-        return SampleSet(None, self.nodes, energy=None, device_tensor=t, device_energy=energy)
+        raw = SampleSet(None, self.nodes, energy=None, device_tensor=t, device_energy=energy)
+        if isinstance(answer_mode, str) and answer_mode == "histogram":
+            return raw.aggregate()._sorted_by_energy()
+        return raw
 
 
 def get_sampler_and_sampler_kwargs(num_reads: int, annealing_time: float, n_latents: int, random_seed: int, qpu: str,

@@ -597,6 +597,49 @@ int dvg_packed_overlap(const uint32_t *a, int64_t rows_a, int64_t a_row_stride, 
                        const uint32_t *b, int64_t rows_b, int64_t b_row_stride, int64_t b_group_stride,
                        int groups, int n,
                        int64_t *hist, int64_t *nearest, int accumulate, dvg_stream_t stream);
+/* Which bit-packed spin rows are the same state, and how often each state occurs, exactly ("DVG distinct v1"): the equivalence
+ * classes of the rows under equality on the spins < n.  Rows are packed as in "DVG trace v1": W = (n + 31) / 32 words, bit b of
+ * word w = spin 32 w + b is +1.  Strides count words, as in dvg_grbm_energy_packed: row r of group g starts at bits + g
+ * group_stride + r row_stride; a flat set is groups = 1, row_stride = W; slices of a trace need no copy.  The T = groups rows
+ * rows are pooled under the flattened index t = g rows + r.  The KEY of a row is its W words with the bits of spins >= n
+ * cleared: pad bits may hold anything and never distinguish rows.  With D the number of distinct keys:
+ *   first[t]      = the smallest t' whose key equals the key of t                                   int32 [T]
+ *   n_distinct[0] = D                                                                                int64 [1], required
+ *   classes are numbered in the order of their first occurrence:
+ *   rep[d]        = the d-th smallest value that first takes (rep is increasing, rep[0] = 0)         int32 [T], d < D written
+ *   id[t]         = the d with rep[d] == first[t]                                                    int32 [T]
+ *   count[d]      = the number of t with id[t] == d (the counts sum to T)                            int64 [T], d < D written
+ *   with other != NULL, a flat set of rows_other rows of the same n, row u at other + u other_row_stride:
+ *   other_id[u]   = the d whose key equals the key of row u of other, -1 if there is none            int32 [rows_other]
+ *   other_hits[d] = the number of u with other_id[u] == d                                            int64 [T], d < D written
+ *   Rows of other are looked up, never inserted: they add no class and change none of the outputs above.
+ * first, id, rep, count, other_id and other_hits are each optional (NULL: not written); rep, count and other_hits are owned by
+ * the caller with room for T elements, and nothing is written beyond their first D.  All pointers are DEVICE pointers.  Every
+ * value is an exact integer and the result is a function of the input alone -- not of the arrival order of threads, of the
+ * grid or of the hash: two calls return the same bits.  The entry needs n only, no graph; it allocates nothing and enqueues
+ * on `stream`.
+ *   How: an open-addressing table of int32 row indices in the workspace, capacity the power of two >= 2 T, filled with EMPTY
+ *   = -1.  A row hashes its key to a start slot and probes linearly: atomicCAS(EMPTY -> t) at device scope claims a free slot;
+ *   a slot that holds t' is compared with the row word by word from the read-only input (no hash is stored: every match is a
+ *   full comparison) -- equal: atomicMin(slot, t), done; different: the next slot.  A slot's class never changes once set and
+ *   the rows of a class walk one probe sequence, so a class ends in exactly one slot, holding its smallest index.  A row is
+ *   held by a group of lanes (16 bytes each where bits and the strides are multiples of 16 bytes).  Then separate
+ *   stream-ordered launches: first[t] and the class sizes (integer atomics); the flags first[t] == t compacted in order by
+ *   block sums, a scan of the sums and apply (as dvg_population_resample: no workgroup waits for another); id, rep, count; the
+ *   read-only lookups of other.  Every probe loop is bounded by the capacity and no thread waits for another.  A probe that
+ *   exhausts the bound cannot happen at load <= 0.5; if it did, n_distinct[0] = -1 and no other output is defined.
+ *   ws: DEVICE memory, aligned to 4 bytes, of dvg_packed_distinct_workspace_bytes(rows, groups, n) bytes (the table and 16
+ *       bytes per row: about 24 to 32 T bytes); the query is > 0, monotone in rows, and 0 for arguments the entry rejects.
+ * DVG_E_INVALID, before any HIP call: bits, n_distinct or ws null (or ws not aligned to 4 bytes); rows, groups or n < 1;
+ * row_stride < W; group_stride < 0; other != NULL with rows_other < 1 or other_row_stride < W; other_id or other_hits given
+ * with other == NULL.  DVG_E_UNSUPPORTED: T >= 2^31 or rows_other >= 2^31 (a row index is an int32).  DVG_E_WORKSPACE:
+ * ws_bytes below the query.  A rejected call writes nothing. */
+size_t dvg_packed_distinct_workspace_bytes(int64_t rows, int64_t groups, int n);
+int dvg_packed_distinct(const uint32_t *bits, int64_t rows, int64_t row_stride, int64_t groups, int64_t group_stride, int n,
+                        const uint32_t *other, int64_t rows_other, int64_t other_row_stride,
+                        int32_t *first, int32_t *id, int32_t *rep, int64_t *count, int64_t *n_distinct,
+                        int32_t *other_id, int64_t *other_hits,
+                        void *ws, size_t ws_bytes, dvg_stream_t stream);
 /* The full pair-correlation sums of bit-packed spin rows, exactly ("DVG corr v1"): s_i s_j summed over the rows for EVERY pair
  * of spins, not the graph's edges only (dvg_grbm_moments_packed) -- the spins x spins product of the +-1 rows, taken on their
  * bits.  Rows are packed as in "DVG trace v1": W = (n + 31) / 32 words, bit b of word w = spin 32 w + b is +1; bits of spins

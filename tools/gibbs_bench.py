@@ -64,6 +64,9 @@ effective sample size, and AIS between 8 groups of its chains -- the populations
 `chain_fields`: also the draw with a linear field per chain (dvg_gibbs_sample_fields, "DVG field v1"), timed as the ais rows are -- the
 raw call on persistent chains -- with N(0, 1) fields, a row per chain, and with one shared row; it runs the rolled kernel, so the
 row to hold it against is `rolled reference`; a second line gives the plans of the two (workgroup, LDS).
+`distinct`: also dvg_packed_distinct (the equivalence classes of bit-packed rows under equality, "DVG distinct v1": first, id, rep and
+count) on 65 536 rows of n = 256 and 16 384 rows of n = 1024, all rows distinct and rows drawn from a pool of 256 states, against
+torch.unique(dim=0, return_inverse=True, return_counts=True) on the same device rows; a second line says whether the two agree.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -722,3 +725,36 @@ if "population" in sys.argv:
               f"{int(pa.survivors.min())} .. {int(pa.survivors.max())} of {C // 8}, worst step ess {float(pa.ess.min()):.1f});  AIS log_z "
               f"{float(lp.log_z):.4f} std_err by ess {float(lp.std_err):.4f} (ess {float(lp.ess):.1f}), between 8 groups "
               f"{float(z.std(unbiased=True) / z.mean() / 8 ** 0.5):.4f}")
+if "distinct" in sys.argv:
+    # dvg_packed_distinct ("DVG distinct v1") against torch.unique(dim=0, return_inverse=True, return_counts=True) on the same
+    # device rows: 65 536 rows of n = 256 and 16 384 rows of n = 1024, all rows distinct and rows drawn from a pool of 256 states
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:34s} {t:9.1f} us per call  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    g = torch.Generator(device="cuda").manual_seed(seed % 2 ** 31)
+    for Td, nd in ((65536, 256), (16384, 1024)):
+        Wd = nd // 32
+        fresh = torch.randint(-2 ** 31, 2 ** 31, (Td, Wd), device="cuda", generator=g, dtype=torch.int64).to(torch.int32)
+        pooled = fresh[:256][torch.randint(0, 256, (Td,), device="cuda", generator=g)].contiguous()
+        for what, rows_d in (("all rows distinct", fresh), ("a pool of 256 states", pooled)):
+            first, ident, rep = (torch.empty((Td,), dtype=torch.int32, device="cuda") for _ in range(3))
+            count = torch.empty((Td,), dtype=torch.int64, device="cuda")
+            n_distinct = torch.empty((1,), dtype=torch.int64, device="cuda")
+            ws = torch.empty((int(_lib.lib().dvg_packed_distinct_workspace_bytes(Td, 1, nd)),), dtype=torch.uint8, device="cuda")
+
+            def entry():
+                _lib.check(_lib.lib().dvg_packed_distinct(rows_d.data_ptr(), Td, Wd, 1, 0, nd, None, 0, 0, first.data_ptr(), ident.data_ptr(),
+                                                          rep.data_ptr(), count.data_ptr(), n_distinct.data_ptr(), None, None, ws.data_ptr(),
+                                                          ws.numel(), _lib.stream_ptr()), "dvg_packed_distinct")
+                return count
+
+            ts, _ = timed(entry)
+            t_entry = report(f"distinct, {Td} x n={nd}", ts, what)
+            ts, (u_rows, u_inverse, u_counts) = timed(lambda: torch.unique(rows_d, dim=0, return_inverse=True, return_counts=True))
+            report("the same by torch.unique(dim=0)", ts, f"{float(np.median(ts)) / t_entry:.2f} x the entry")
+            D = int(n_distinct.item())
+            same = D == int(u_rows.shape[0]) and sorted(count[:D].tolist()) == sorted(u_counts.tolist()) and \
+                bool(torch.equal(rows_d[rep[:D].long()][ident.long()], u_rows[u_inverse]))
+            print(f"  {'':34s} the two give the same classes: {same}  (D = {D})")
