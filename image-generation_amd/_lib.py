@@ -10,286 +10,32 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int8, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import c_int64
+
+from . import _abi
+from ._abi import DvgError  # noqa: F401  (the one error type of the binding; the header reader raises it too)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DVG_LIBRARY: development override (A/B runs of two builds in one process launch); the product path is in-tree
 LIB_PATH = os.environ.get("DVG_LIBRARY") or os.path.join(_HERE, "libdvg.so")
 
 _lib = None
+_dev_option_names = None  # of the loaded library: static per build
 
 
-class DvgError(RuntimeError):
-    pass
-
-
-class MmdCfg(ctypes.Structure):
-    _fields_ = [
-        ("n_kernels", c_int32),
-        ("factor", c_float),
-        ("bandwidth", c_float),
-        ("squared", c_int32),
-        ("reduce_mean", c_int32),
-        ("biased", c_int32),
-    ]
-
-
-class EncoderParams(ctypes.Structure):
-    _fields_ = [
-        ("conv_w", c_void_p * 4),
-        ("conv_b", c_void_p * 4),
-        ("bn_g", c_void_p * 4),
-        ("bn_b", c_void_p * 4),
-        ("bn_rm", c_void_p * 4),
-        ("bn_rv", c_void_p * 4),
-        ("bn_nbt", c_void_p * 4),
-        ("proj_w", c_void_p),
-        ("proj_b", c_void_p),
-    ]
-
-
-class EncoderGrads(ctypes.Structure):
-    _fields_ = [
-        ("conv_w", c_void_p * 4),
-        ("conv_b", c_void_p * 4),
-        ("bn_g", c_void_p * 4),
-        ("bn_b", c_void_p * 4),
-        ("proj_w", c_void_p),
-        ("proj_b", c_void_p),
-    ]
-
-
-class DecoderParams(ctypes.Structure):
-    _fields_ = [
-        ("lin_w", c_void_p),
-        ("lin_b", c_void_p),
-        ("conv_w", c_void_p * 5),
-        ("conv_b", c_void_p * 5),
-        ("bn_g", c_void_p * 4),
-        ("bn_b", c_void_p * 4),
-        ("bn_rm", c_void_p * 4),
-        ("bn_rv", c_void_p * 4),
-        ("bn_nbt", c_void_p * 4),
-    ]
-
-
-class DecoderGrads(ctypes.Structure):
-    _fields_ = [
-        ("lin_w", c_void_p),
-        ("lin_b", c_void_p),
-        ("conv_w", c_void_p * 5),
-        ("conv_b", c_void_p * 5),
-        ("bn_g", c_void_p * 4),
-        ("bn_b", c_void_p * 4),
-    ]
-
-
-# name -> (restype, argtypes); must list every symbol include/dvg.h declares
-_I32P = POINTER(c_int32)
-SIGNATURES = {
-    "dvg_version": (c_int, []),
-    "dvg_source_hash": (c_char_p, []),
-    "dvg_last_error": (c_char_p, []),
-    "dvg_graph_create": (c_int, [c_int, c_int, _I32P, _I32P, _I32P, _I32P, c_int, _I32P, _I32P, _I32P, POINTER(c_void_p)]),
-    "dvg_graph_destroy": (c_int, [c_void_p]),
-    "dvg_gibbs_sample": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int,
-         c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_clamped": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int,
-         c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_fields": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int,
-         c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_fields_ais": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_float, c_void_p, c_int64,
-         c_float, c_void_p, c_int, c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p,
-         c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_annealed": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_int,
-         c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_ais": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_float, c_void_p,
-         c_int, c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_tempered": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p,
-         c_int, c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_traced": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int, c_uint32, c_uint64,
-         c_uint32, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_tempered_traced": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p,
-         c_int, c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-         c_int, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_launch_info": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-    "dvg_grbm_moments_packed": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
-    "dvg_trace_autocorr": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
-    "dvg_packed_overlap": (
-        c_int,
-        [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p],
-    ),
-    "dvg_packed_distinct_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-    "dvg_packed_distinct": (
-        c_int,
-        [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
-         c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_grbm_energy_packed": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64, c_int64,
-         c_void_p, c_void_p],
-    ),
-    "dvg_grbm_fields_packed_workspace_bytes": (c_size_t, [c_void_p, c_int64, c_int64]),
-    "dvg_grbm_fields_packed": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64,
-         c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_grbm_descend_packed": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64, c_int64, c_int64, c_int64,
-         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_sample_quantum": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
-         c_uint32, c_uint64, c_uint32, c_int, c_int, c_void_p, c_void_p],
-    ),
-    "dvg_gibbs_cluster_move": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_packed_correlation_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-    "dvg_packed_correlation": (
-        c_int,
-        [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_population_resample_workspace_bytes": (c_size_t, [c_int]),
-    "dvg_population_resample": (
-        c_int,
-        [c_void_p, c_int, c_int, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-         c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_grbm_energy": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dvg_grbm_suffstats_workspace_bytes": (c_size_t, [c_void_p]),
-    "dvg_grbm_suffstats": (
-        c_int,
-        [c_void_p, c_void_p, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_gumbel_fwd": (
-        c_int,
-        [c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p],
-    ),
-    "dvg_gumbel_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "dvg_gumbel_bwd2": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "dvg_scalar_add": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "dvg_heaviside_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
-    "dvg_resize_binarise": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "dvg_gather_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
-    "dvg_mmd_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-    "dvg_mmd_spin_flops": (c_int, [c_int64, c_int64, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int)]),
-    "dvg_mmd_fwd_bwd": (
-        c_int,
-        [c_void_p, c_int64, c_void_p, c_int64, c_int, POINTER(MmdCfg), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_encoder_workspace_bytes": (c_size_t, [c_int64, c_int]),
-    "dvg_encoder_fwd": (
-        c_int,
-        [POINTER(EncoderParams), c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_encoder_bwd": (
-        c_int,
-        [POINTER(EncoderParams), c_int, c_void_p, c_int64, c_void_p, POINTER(EncoderGrads), c_void_p, c_size_t, c_void_p],
-    ),
-    "dvg_decoder_workspace_bytes": (c_size_t, [c_int64, c_int]),
-    "dvg_decoder_fwd": (
-        c_int,
-        [POINTER(DecoderParams), c_int, c_void_p, c_int64, c_int, POINTER(c_void_p), c_uint64, c_uint64, c_void_p,
-         c_void_p, c_size_t, c_void_p, c_void_p],
-    ),
-    "dvg_decoder_prepare": (
-        c_int,
-        [POINTER(DecoderParams), c_int, c_int64, c_int, c_uint64, c_uint64, c_void_p, c_size_t, c_void_p, c_void_p],
-    ),
-    "dvg_decoder_fwd_ex": (
-        c_int,
-        [POINTER(DecoderParams), c_int, c_void_p, c_int64, c_int, POINTER(c_void_p), c_uint64, c_uint64, c_void_p,
-         c_void_p, c_size_t, c_void_p, c_int, c_void_p],
-    ),
-    "dvg_decoder_bwd": (
-        c_int,
-        [POINTER(DecoderParams), c_int, c_void_p, c_int64, c_void_p, POINTER(DecoderGrads), c_void_p, c_void_p,
-         c_size_t, c_void_p],
-    ),
-    "dvg_decoder_bwd_ex": (
-        c_int,
-        [POINTER(DecoderParams), c_int, c_void_p, c_int64, c_void_p, POINTER(DecoderGrads), c_void_p, c_void_p,
-         c_size_t, c_int, c_void_p],
-    ),
-    "dvg_stream_join_side": (c_int, [c_void_p]),
-    "dvg_decoder_fwd_mse_ex": (
-        c_int,
-        [POINTER(DecoderParams), c_int, c_void_p, c_int64, POINTER(c_void_p), c_uint64, c_uint64, c_void_p, c_int, c_float,
-         c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_void_p],
-    ),
-    "dvg_decoder_bwd_mse_ex": (
-        c_int,
-        [POINTER(DecoderParams), c_int, c_void_p, c_int64, c_void_p, c_int, c_float, POINTER(DecoderGrads), c_void_p,
-         c_void_p, c_size_t, c_int, c_void_p],
-    ),
-    "dvg_decoder_declare_spins": (c_int, [c_void_p, c_int]),
-    "dvg_mse_workspace_bytes": (c_size_t, []),
-    "dvg_mse_fwd_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "dvg_adam_step": (
-        c_int,
-        [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int64,
-         c_float, c_void_p, c_int, c_void_p],
-    ),
-    "dvg_stream_anchor": (c_int, [c_void_p]),
-    "dvg_set_conv_precision": (c_int, [c_int]),
-    "dvg_get_conv_precision": (c_int, []),
-    "dvg_option_count": (c_int, []),
-    "dvg_option_name": (c_char_p, [c_int]),
-    "dvg_option_doc": (c_char_p, [c_int]),
-    "dvg_set_option": (c_int, [c_char_p, c_int64]),
-    "dvg_get_option": (c_int, [c_char_p, POINTER(c_int64)]),
-    "dvg_reset_options": (c_int, []),
-    "dvg_prof_enable": (c_int, [c_uint64]),
-    "dvg_prof_reset": (c_int, []),
-    "dvg_prof_num_kernels": (c_int, []),
-    "dvg_prof_kernel_name": (c_char_p, [c_int]),
-    "dvg_prof_query": (c_int, [c_int, POINTER(c_double), POINTER(c_int64)]),
-    "dvg_prof_query_work": (c_int, [c_int, POINTER(c_double)]),
-    "dvg_prof_query_share": (c_int, [c_int, POINTER(c_double)]),
-}
-
-
+# The binding is read from the headers themselves (_abi.py): name -> (restype, argtypes) of every symbol include/dvg.h
+# declares, and the Structures of its typedefs.  No compiled library is needed to build these.
+SIGNATURES = _abi.signatures("dvg.h")
 # include/dvg_dev.h: the A/B references and test knobs (not part of the drop-in boundary; SIGNATURES covers exactly dvg.h)
-DEV_OPTION_SIGNATURES = {
-    "dvg_dev_option_count": (c_int, []),
-    "dvg_dev_option_name": (c_char_p, [c_int]),
-    "dvg_dev_option_doc": (c_char_p, [c_int]),
-    "dvg_dev_set_option": (c_int, [c_char_p, c_int64]),
-    "dvg_dev_get_option": (c_int, [c_char_p, POINTER(c_int64)]),
-}
+DEV_OPTION_SIGNATURES = {name: _abi.signatures("dvg_dev.h")[name] for name in (
+    "dvg_dev_option_count", "dvg_dev_option_name", "dvg_dev_option_doc", "dvg_dev_set_option", "dvg_dev_get_option")}
+
+_structures = _abi.read("dvg.h").structures
+MmdCfg = _structures["dvg_mmd_cfg_t"]
+EncoderParams = _structures["dvg_encoder_params_t"]
+EncoderGrads = _structures["dvg_encoder_grads_t"]
+DecoderParams = _structures["dvg_decoder_params_t"]
+DecoderGrads = _structures["dvg_decoder_grads_t"]
 
 
 def build(verbose: bool = False) -> str:
@@ -378,9 +124,12 @@ def set_conv_precision(mode: str) -> None:
     check(lib().dvg_set_conv_precision(modes[mode]), "dvg_set_conv_precision")
 
 
-def _dev_names() -> set:
+def _dev_names() -> frozenset:
+    global _dev_option_names
     L = lib()
-    return {L.dvg_dev_option_name(i).decode() for i in range(L.dvg_dev_option_count())}
+    if _dev_option_names is None or _dev_option_names[0] is not L:
+        _dev_option_names = (L, frozenset(L.dvg_dev_option_name(i).decode() for i in range(L.dvg_dev_option_count())))
+    return _dev_option_names[1]
 
 
 def set_option(name: str, value: int) -> None:

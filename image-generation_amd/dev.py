@@ -5,40 +5,10 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
-_SIGS = {
-    "dvg_dev_conv_igemm": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 +
-                           [ctypes.c_int64] + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_void_p]),
-    "dvg_dev_conv_splitk_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "dvg_dev_conv_stats_blocks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int]),
-    "dvg_dev_conv_igemm_form": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)]),
-    "dvg_dev_conv_wgrad_form": (ctypes.c_int, [ctypes.c_int64] + [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_int)]),
-    "dvg_dev_conv_wino": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 +
-                          [ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
-    "dvg_dev_conv_wino_shape": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "dvg_dev_conv_wino4": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 4 +
-                           [ctypes.c_int64] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
-    "dvg_dev_conv_wino4_shape": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "dvg_dev_wino4_wgrad_slab_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "dvg_dev_conv_wino4_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 4 +
-                                 [ctypes.c_void_p]),
-    "dvg_dev_conv_wino_ok": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "dvg_dev_plan_forms": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
-    "dvg_dev_mmd_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
-    "dvg_dev_gibbs_draw_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                               ctypes.POINTER(ctypes.c_int64)]),
-    "dvg_dev_gibbs_exchange_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                                   ctypes.POINTER(ctypes.c_int64)]),
-    "dvg_dev_conv_wino_stats_blocks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int]),
-    "dvg_dev_wgrad_slab_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "dvg_dev_conv_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 +
-                           [ctypes.c_void_p]),
-    "dvg_dev_encoder_layout": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
-    "dvg_dev_wino_wgrad_slab_floats": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "dvg_dev_conv_wino_wgrad": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int64] + [ctypes.c_int] * 5 +
-                                [ctypes.c_void_p]),
-}
+# every function of include/dvg_dev.h but the option accessors, which _lib binds with the library
+_SIGS = {k: v for k, v in _abi.signatures("dvg_dev.h").items() if k not in _lib.DEV_OPTION_SIGNATURES}
 _bound = False
 
 

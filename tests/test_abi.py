@@ -1,6 +1,7 @@
 """CPU-side checks of the C ABI: the library loads and exports every symbol include/dvg.h declares."""
 import os
 import re
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 import pytest
 
@@ -22,8 +23,23 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert len(declared) >= 25
     for name in declared:
         assert hasattr(handle, name), f"{name} declared in include/dvg.h but not exported"
-    # and the binding table covers exactly the header
+    # and the binding table, which is read from the header, covers exactly the header ...
     assert sorted(_lib.SIGNATURES) == declared
+    # ... and reads it right: a few rows written out by hand as the types ctypes is given
+    P, DP = POINTER(c_void_p), POINTER(_lib.DecoderParams)
+    assert _lib.SIGNATURES["dvg_gibbs_sample"] == (c_int, [
+        c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int, c_uint32, c_uint64,
+        c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p])
+    assert _lib.SIGNATURES["dvg_mmd_fwd_bwd"] == (c_int, [
+        c_void_p, c_int64, c_void_p, c_int64, c_int, POINTER(_lib.MmdCfg), c_void_p, c_void_p, c_void_p, c_size_t, c_void_p])
+    assert _lib.SIGNATURES["dvg_decoder_fwd_mse_ex"] == (c_int, [
+        DP, c_int, c_void_p, c_int64, P, c_uint64, c_uint64, c_void_p, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p,
+        c_int, c_void_p])
+    assert _lib.SIGNATURES["dvg_packed_distinct"] == (c_int, [
+        c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p])
+    assert _lib.SIGNATURES["dvg_packed_distinct_workspace_bytes"] == (c_size_t, [c_int64, c_int64, c_int])
+    assert _lib.SIGNATURES["dvg_source_hash"] == (c_char_p, [])
 
 
 def test_version_and_error_string():

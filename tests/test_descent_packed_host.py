@@ -17,32 +17,19 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import descent_oracle as do  # noqa: E402
 import fields_oracle as fo  # noqa: E402
 import trace_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dvg_grbm_descend_packed"
 
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG descent v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text)
-    assert NAME in _lib.SIGNATURES and len(_lib.SIGNATURES[NAME][1]) == 19
-    assert hasattr(_lib.lib(), NAME)
-    names = {_lib.lib().dvg_prof_kernel_name(i).decode() for i in range(_lib.lib().dvg_prof_num_kernels())}
-    assert "grbm_descend_packed_kernel" in names
+    support.assert_declared_bound_exported(NAME, markers=["DVG descent v1"], kernels=["grbm_descend_packed_kernel"], arity={NAME: 19})
 
 
-def _stand_in(n=64, n_edges=0):
-    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first fields: n, n_edges)
-    (ctypes.c_int32 * 2).from_buffer(graph)[:] = [n, n_edges]
-    arena = ctypes.create_string_buffer(1 << 16)  # host words the pointers below point into; nothing reads or writes them
-    base = (ctypes.cast(arena, ctypes.c_void_p).value + 15) & ~15
-    return graph, ctypes.cast(graph, ctypes.c_void_p), base, arena
+_stand_in = support.graph_stand_in
 
 
 def _set_n(graph, n, n_edges=0):
@@ -114,28 +101,16 @@ def test_c_argument_validation_without_gpu():
 
 
 # ------------------------------------------------------------------------------------------------ the Python surface
-@functools.lru_cache(maxsize=None)
-def _ring_plan(n=12):
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    return graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+_ring_plan = support.ring_plan
 
 
-@functools.lru_cache(maxsize=None)
-def _random_plan(n=77, p_edge=0.35):
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    return graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
+_random_plan = support.random_plan
 
 
 @pytest.fixture
 def untouched(monkeypatch):
     """The library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
 
 
 class _Handle:  # (what the wrapper reads before the library: the plan)

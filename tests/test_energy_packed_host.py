@@ -17,29 +17,19 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import energy_oracle as eo  # noqa: E402
 import trace_oracle  # noqa: E402
-from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
+import support  # noqa: E402
+from image_generation_amd import _lib, functional as F, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dvg_grbm_energy_packed"
 
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG energy v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
-    assert NAME in _lib.SIGNATURES
-    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+    support.assert_declared_bound_exported(NAME, markers=["DVG energy v1"])
 
 
-def _stand_in(n=64):
-    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first field: the spin count)
-    ctypes.c_int32.from_buffer(graph).value = n
-    dummy = ctypes.create_string_buffer(16)
-    return graph, ctypes.cast(graph, ctypes.c_void_p), ctypes.cast(dummy, ctypes.c_void_p), dummy
+_stand_in = support.graph_stand_in
 
 
 def _call(g, lin, quad, bits, out, *, prefactor=1.0, rows=5, row_stride=2, groups=1, group_stride=0):
@@ -87,28 +77,16 @@ def test_c_argument_validation_without_gpu():
 
 
 # ------------------------------------------------------------------------------------------------ the Python surface
-@functools.lru_cache(maxsize=None)
-def _ring_plan(n=12):
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    return graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+_ring_plan = support.ring_plan
 
 
-@functools.lru_cache(maxsize=None)
-def _random_plan(n=77, p_edge=0.35):
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    return graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
+_random_plan = support.random_plan
 
 
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
     plan = _ring_plan()
     s = smp.GibbsSampler(plan, list(range(plan.n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     return s, torch.zeros(plan.n), torch.zeros(plan.n_edges)

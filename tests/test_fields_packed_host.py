@@ -17,33 +17,20 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fields_oracle as fo  # noqa: E402
 import trace_oracle  # noqa: E402
-from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
+import support  # noqa: E402
+from image_generation_amd import _lib, functional as F, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME, QUERY = "dvg_grbm_fields_packed", "dvg_grbm_fields_packed_workspace_bytes"
 
 
 # ------------------------------------------------------------------------------------------------ the symbols and their checks
 def test_symbols_are_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG fields v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text) and re.search(r"\bsize_t\s+" + QUERY + r"\s*\(", text)
-    assert NAME in _lib.SIGNATURES and QUERY in _lib.SIGNATURES
-    assert hasattr(_lib.lib(), NAME) and hasattr(_lib.lib(), QUERY)
-    names = {_lib.lib().dvg_prof_kernel_name(i).decode() for i in range(_lib.lib().dvg_prof_num_kernels())}
-    assert {"grbm_fields_packed_kernel", "grbm_fields_reduce_kernel"} <= names
+    support.assert_declared_bound_exported({NAME: "int", QUERY: "size_t"}, markers=["DVG fields v1"],
+                                           kernels=["grbm_fields_packed_kernel", "grbm_fields_reduce_kernel"])
 
 
-def _stand_in(n=64, n_edges=0):
-    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first fields: n, n_edges)
-    (ctypes.c_int32 * 2).from_buffer(graph)[:] = [n, n_edges]
-    dummy = ctypes.create_string_buffer(64)
-    p = ctypes.cast(dummy, ctypes.c_void_p)
-    p = ctypes.c_void_p((p.value + 15) & ~15)  # aligned to 16 bytes
-    return graph, ctypes.cast(graph, ctypes.c_void_p), p, dummy
+_stand_in = support.graph_stand_in
 
 
 def _set_n(graph, n, n_edges=0):
@@ -79,7 +66,7 @@ def test_c_argument_validation_without_gpu():
     assert rc == -1 and b"cond_pair" in msg and b"cond_sum" in msg, (rc, msg)
     rc, msg = _call(g, p, p, p, every, ws=None)
     assert rc == -1 and re.search(rb"\bws\b", msg) and b"null" in msg, (rc, msg)
-    rc, msg = _call(g, p, p, p, every, ws=ctypes.c_void_p(p.value + 8))
+    rc, msg = _call(g, p, p, p, every, ws=p + 8)
     assert rc == -1 and re.search(rb"\bws\b", msg) and b"aligned" in msg, (rc, msg)
     for name in ("rows", "groups"):
         for bad in (0, -1, -2 ** 40):
@@ -140,28 +127,16 @@ def test_workspace_query_is_monotone_and_zero_for_rejected_arguments():
 
 
 # ------------------------------------------------------------------------------------------------ the Python surface
-@functools.lru_cache(maxsize=None)
-def _ring_plan(n=12):
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    return graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+_ring_plan = support.ring_plan
 
 
-@functools.lru_cache(maxsize=None)
-def _random_plan(n=77, p_edge=0.35):
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    return graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
+_random_plan = support.random_plan
 
 
 @pytest.fixture
 def untouched(monkeypatch):
     """The library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
 
 
 class _Handle:  # (what the wrapper reads before the library: the plan)

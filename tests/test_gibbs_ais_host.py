@@ -3,7 +3,6 @@ itself (``tests/ais_oracle.py``) against float64 energies and against enumeratio
 the Python surface -- raised before the library is touched."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -12,10 +11,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ais_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dvg_gibbs_sample_ais"
 SEED = 775321899904
 
@@ -122,12 +121,7 @@ def test_log_partition_reductions_match_the_helper():
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
-    assert NAME in _lib.SIGNATURES
-    _lib.build()
-    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+    support.assert_declared_bound_exported(NAME)
 
 
 def _call(g, lin, quad, state, betas, stride, n_sweeps, log_w, beta_from=0.0, init=1, n_chains=4):
@@ -171,13 +165,9 @@ def test_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    n = 12
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch)
+    plan = support.ring_plan()
+    n = plan.n
     s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     lin, quad = torch.zeros(n), torch.zeros(plan.n_edges)
     return s, lin, quad

@@ -1,16 +1,14 @@
 """CPU-side checks of the annealed block-Gibbs draw (``dvg_gibbs_sample_annealed``, include/dvg.h): the schedule
 builder, the symbol, and every argument error of the Python surface -- raised before the library is touched."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from image_generation_amd import _lib, graphs, sampler as smp
+import support
+from image_generation_amd import _lib, sampler as smp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dvg_gibbs_sample_annealed"
 
 
@@ -51,12 +49,7 @@ def test_beta_schedule_rejects(args):
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
-    assert NAME in _lib.SIGNATURES
-    _lib.build()
-    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+    support.assert_declared_bound_exported(NAME)
 
 
 def _call(g, lin, quad, state, betas, stride, n_sweeps, n_chains=4):
@@ -94,13 +87,9 @@ def test_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    n = 12
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch)
+    plan = support.ring_plan()
+    n = plan.n
     s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     lin, quad = torch.zeros(n), torch.zeros(plan.n_edges)
     return s, lin, quad

@@ -6,7 +6,6 @@ a move that flips the cluster in one twin only breaks."""
 import ctypes
 import functools
 import os
-import re
 import sys
 from types import SimpleNamespace
 
@@ -17,6 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cluster_oracle as co  # noqa: E402
 import tempered_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
@@ -26,16 +26,9 @@ NAME = "dvg_gibbs_cluster_move"
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG ICM v1" in text and "STREAM_ICM = 7" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
-    assert NAME in _lib.SIGNATURES
-    _lib.build()
-    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+    support.assert_declared_bound_exported(NAME, markers=["DVG ICM v1", "STREAM_ICM = 7"], kernels=["gibbs_quantum_kernel"])
     assert "STREAM_ICM = 7" in open(os.path.join(ROOT, "image-generation_amd", "csrc", "philox.h")).read()
-    names = [_lib.lib().dvg_prof_kernel_name(i).decode() for i in range(_lib.lib().dvg_prof_num_kernels())]
-    assert names[-1] == "gibbs_cluster_kernel" and "gibbs_quantum_kernel" in names
+    assert support.prof_kernel_names()[-1] == "gibbs_cluster_kernel"
 
 
 def test_argument_validation_without_gpu():
@@ -83,13 +76,9 @@ def test_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    n = 12
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch)
+    plan = support.ring_plan()
+    n = plan.n
     s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     lin, quad = torch.zeros(n), torch.zeros(plan.n_edges)
     return s, lin, quad

@@ -1,22 +1,15 @@
 """CPU-side checks of the conditional block-Gibbs entry point (``dvg_gibbs_sample_clamped``, include/dvg.h): the symbol is
 declared and exported, and its argument checks answer before any device work."""
 import ctypes
-import os
-import re
 
+import support
 from image_generation_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dvg_gibbs_sample_clamped"
 
 
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
-    assert NAME in _lib.SIGNATURES
-    _lib.build()
-    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+    support.assert_declared_bound_exported(NAME)
 
 
 def _call(g, lin, quad, state, clamp, stride, n_chains=4):

@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from image_generation_amd import _lib, graphs, sampler as smp
+import support
+from image_generation_amd import _lib, sampler as smp
 
 N, R = 12, 3
 LADDER = [0.1, 1.0, 2.0]  # R rungs
@@ -17,12 +18,8 @@ SCHEDULE = [0.5, 1.0, 2.0]
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test.  The parameters are
     CPU tensors, so a call whose other arguments pass ends at them, still before the library."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    ei, ej = np.arange(N, dtype=np.int64), (np.arange(N, dtype=np.int64) + 1) % N
-    plan = graphs.build_plan(N, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch)
+    plan = support.ring_plan(N)
     s = smp.GibbsSampler(plan, list(range(N)), beta=2.0, sweeps=5, seed=3, device="cuda")
     return s, torch.zeros(N), torch.zeros(plan.n_edges)
 

@@ -5,7 +5,6 @@ joins, every argument error of the C entry point (before any HIP call) and of ``
 estimator of ``tests/ais_oracle.py``."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -17,10 +16,10 @@ import ais_oracle  # noqa: E402
 import field_ais_oracle as fao  # noqa: E402
 import field_oracle  # noqa: E402
 import test_gibbs_plan_host as pinned  # noqa: E402  (its graphs)
+import support  # noqa: E402
 from image_generation_amd import _lib, dev, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 775321899904
 # (graph, chains) of tests/test_gpu_gibbs_field_ais.py
 GPU_ROWS = (("random77", 19), ("random77", 20), ("random77", 21), ("zephyr128", 5), ("zephyr128", 1025), ("zephyr512", 9),
@@ -29,15 +28,9 @@ GPU_ROWS = (("random77", 19), ("random77", 20), ("random77", 21), ("zephyr128", 
 
 # ------------------------------------------------------------------------------------------------ the symbol
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG field AIS v1" in text
-    assert "No held, annealed, weighed, exchange or traced form of this draw" not in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
     name = "dvg_gibbs_sample_fields_ais"
-    assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-    assert name in _lib.SIGNATURES
-    assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
+    support.assert_declared_bound_exported(name, markers=["DVG field AIS v1"])
+    assert "No held, annealed, weighed, exchange or traced form of this draw" not in support.header_text()
     # dvg_gibbs_sample_fields' arguments without the fixed beta, the two tables in its place, R behind the stride and the two
     # float64 outputs behind samples_out
     c = ctypes
@@ -192,11 +185,7 @@ def test_the_weight_is_the_ais_weight_along_the_path():
 
 
 # ------------------------------------------------------------------------------------------------ the C entry point's checks
-def _stand_in(n=64):
-    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first field: the spin count)
-    ctypes.c_int32.from_buffer(graph).value = n
-    dummy = ctypes.create_string_buffer(16)
-    return graph, ctypes.cast(graph, ctypes.c_void_p), ctypes.cast(dummy, ctypes.c_void_p), dummy
+_stand_in = support.graph_stand_in
 
 
 def _call(g, lin, quad, state, fields, betas, *, scales=None, stride=64, beta_stride=0, scale_stride=0, beta_from=0.0, scale_from=1.0,
@@ -260,13 +249,9 @@ def test_argument_validation_without_gpu():
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test.  The parameters are CPU
     tensors, as is every tensor a machine without a GPU can make: a call whose other arguments pass ends at the first of them."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    n = 12
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch)
+    plan = support.ring_plan()
+    n = plan.n
     s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     return s, torch.zeros(n), torch.zeros(plan.n_edges)
 

@@ -5,7 +5,6 @@ plan the draw takes -- rolled on every graph, a float32 row of hs per chain slot
 fits -- with the other kinds' plans where they were, and ``logit_fields`` against enumeration."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,10 +14,10 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import field_oracle  # noqa: E402
 import test_gibbs_plan_host as pinned  # noqa: E402  (the table of the existing kinds' plans, and its graphs)
+import support  # noqa: E402
 from image_generation_amd import _lib, dev, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 775321899904
 # (graph, chains) of tests/test_gpu_gibbs_fields.py
 GPU_ROWS = (("random77", 19), ("zephyr128", 5), ("zephyr128", 1025), ("zephyr512", 9), ("zephyr1024", 5), ("zephyr1024", 512))
@@ -28,14 +27,8 @@ LDS_MAX = 160 * 1024
 
 # ------------------------------------------------------------------------------------------------ the symbol
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG field v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
     name = "dvg_gibbs_sample_fields"
-    assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-    assert name in _lib.SIGNATURES
-    assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
+    support.assert_declared_bound_exported(name, markers=["DVG field v1"])
     # the draw's arguments are dvg_gibbs_sample's with (fields, stride) in front of samples_out
     plain, field = _lib.SIGNATURES["dvg_gibbs_sample"][1], _lib.SIGNATURES[name][1]
     assert field == plain[:16] + [ctypes.c_void_p, ctypes.c_int64] + plain[16:]
@@ -72,11 +65,7 @@ def test_field_oracle_is_the_oracle_chain_by_chain():
 
 
 # ------------------------------------------------------------------------------------------------ the C entry point's checks
-def _stand_in(n=64):
-    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first field: the spin count)
-    ctypes.c_int32.from_buffer(graph).value = n
-    dummy = ctypes.create_string_buffer(16)
-    return graph, ctypes.cast(graph, ctypes.c_void_p), ctypes.cast(dummy, ctypes.c_void_p), dummy
+_stand_in = support.graph_stand_in
 
 
 def _fields(g, lin, quad, state, fields, *, stride=64, n_chains=8, n_sweeps=7, dyn=None):
@@ -119,13 +108,9 @@ def test_argument_validation_without_gpu():
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test.  The parameters are CPU
     tensors, as is every tensor a machine without a GPU can make: a call whose other arguments pass ends at the first of them."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    n = 12
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch)
+    plan = support.ring_plan()
+    n = plan.n
     s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     return s, torch.zeros(n), torch.zeros(plan.n_edges)
 

@@ -14,32 +14,16 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import quantum_oracle as qo  # noqa: E402
 import trace_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dvg_gibbs_sample_quantum"
 
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG SQA v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text)
-    assert NAME in _lib.SIGNATURES and len(_lib.SIGNATURES[NAME][1]) == 20
-    assert hasattr(_lib.lib(), NAME)
-    names = {_lib.lib().dvg_prof_kernel_name(i).decode() for i in range(_lib.lib().dvg_prof_num_kernels())}
-    assert "gibbs_quantum_kernel" in names
+    support.assert_declared_bound_exported(NAME, markers=["DVG SQA v1"], kernels=["gibbs_quantum_kernel"], arity={NAME: 20})
     assert "sqa" not in _lib.options() and len(_lib.options()) <= 8  # (no switch of its own)
-
-
-def _stand_in(n=70, n_edges=0):
-    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first fields: n, n_edges)
-    (ctypes.c_int32 * 2).from_buffer(graph)[:] = [n, n_edges]
-    arena = ctypes.create_string_buffer(1 << 16)  # host words the pointers below point into; nothing reads or writes them
-    base = (ctypes.cast(arena, ctypes.c_void_p).value + 15) & ~15
-    return graph, ctypes.cast(graph, ctypes.c_void_p), base, arena
 
 
 def _call(g, lin, quad, bs, kp, slices, *, prefactor=1.0, n_chains=5, n_slices=16, n_sweeps=6, init=1):
@@ -53,7 +37,7 @@ def _call(g, lin, quad, bs, kp, slices, *, prefactor=1.0, n_chains=5, n_slices=1
 def test_c_argument_validation_without_gpu():
     """Every error of the header's list, with its code (DVG_E_INVALID = -1, DVG_E_UNSUPPORTED = -4) and a message that names
     the argument, on host stand-in pointers: nothing reaches HIP."""
-    graph, g, base, _keep = _stand_in()
+    graph, g, base, _keep = support.graph_stand_in(70)
     ptrs = [g, base, base + 1024, base + 2048, base + 3072, base + 8192]
     for k, word in enumerate((rb"\bg\b", rb"\blinear\b", rb"\bquadratic\b", rb"\bbeta_slice\b", rb"\bkappa\b", rb"\bslices\b")):
         args = list(ptrs)
@@ -84,11 +68,7 @@ def test_c_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """The library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
 
 
 def _triangle_plan():

@@ -5,7 +5,6 @@ the plan an exchange draw takes on the graphs the GPU tests use."""
 import ctypes
 import functools
 import os
-import re
 import sys
 
 import numpy as np
@@ -14,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import tempered_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, dev, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
@@ -24,13 +24,7 @@ SEED = 775321899904
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG PT v1" in text and "STREAM_SWAP = 4" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
-    assert NAME in _lib.SIGNATURES
-    _lib.build()
-    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+    support.assert_declared_bound_exported(NAME, markers=["DVG PT v1", "STREAM_SWAP = 4"])
     assert "STREAM_SWAP = 4" in open(os.path.join(ROOT, "image-generation_amd", "csrc", "philox.h")).read()
 
 
@@ -82,13 +76,9 @@ def test_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    n = 12
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch)
+    plan = support.ring_plan()
+    n = plan.n
     s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     lin, quad = torch.zeros(n), torch.zeros(plan.n_edges)
     return s, lin, quad
@@ -251,21 +241,10 @@ def test_two_calls_continue_the_draw():
 
 
 # ------------------------------------------------------------------------------------------------ the plan
-@functools.lru_cache(maxsize=None)
-def _solver_plan(fam, n):
-    g = graphs.pegasus_graph(16) if fam == "pegasus" else graphs.zephyr_graph(12)
-    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, g))
-    _nodes, ei, ej = graphs.edges_of(mg)
-    return graphs.build_plan(n, ei, ej)
+_solver_plan = support.solver_plan
 
 
-@functools.lru_cache(maxsize=None)
-def _random_plan(n=77, p_edge=0.35):
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    keep &= (iu != 3) & (ju != 3)
-    return graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
+_random_plan = functools.partial(support.random_plan, isolated=3)
 
 
 def _lane(lpc, waves, mb, nr, maxs):

@@ -6,7 +6,6 @@ the helper's records on a 12-spin ring against enumeration."""
 import ctypes
 import functools
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,23 +17,17 @@ import tempered_oracle  # noqa: E402
 import tempered_trace_oracle as tto  # noqa: E402
 import test_gpu_gibbs_tempered as shapes  # noqa: E402  (TABLE, parameters, SEED, SWEEP0: no GPU is touched by importing it)
 import trace_oracle  # noqa: E402
-from image_generation_amd import _lib, graphs, sampler as smp  # noqa: E402
+import support  # noqa: E402
+from image_generation_amd import _lib, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dvg_gibbs_sample_tempered_traced"
 
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG PT trace v1" in text
-    assert "No traced form of" not in text  # (the sentence that said there was none)
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    assert re.search(r"\bint\s+" + NAME + r"\s*\(", text), f"{NAME} is not declared in include/dvg.h"
-    assert NAME in _lib.SIGNATURES and len(_lib.SIGNATURES[NAME][1]) == 29
-    _lib.build()
-    assert hasattr(_lib.lib(), NAME), f"{NAME} is not exported by the built library"
+    support.assert_declared_bound_exported(NAME, markers=["DVG PT trace v1"], arity={NAME: 29})
+    assert "No traced form of" not in support.header_text()  # (the sentence that said there was none)
 
 
 def _call(g, lin, quad, state, ladder, rung, trace, *, R=4, swap_every=1, n_chains=8, n_sweeps=7, burn_in=0, thin=1, dyn=None,
@@ -98,19 +91,13 @@ def test_argument_validation_without_gpu():
 
 
 # ------------------------------------------------------------------------------------------------ the Python surface
-@functools.lru_cache(maxsize=None)
-def _ring_plan(n=12):
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    return graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+_ring_plan = support.ring_plan
 
 
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
+    support.out_of_reach(monkeypatch)
     plan = _ring_plan()
     s = smp.GibbsSampler(plan, list(range(plan.n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     return s, torch.zeros(plan.n), torch.zeros(plan.n_edges)

@@ -6,7 +6,6 @@ averages over the helper's history (``tests/trace_oracle.py``) against enumerati
 import ctypes
 import functools
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,31 +14,19 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import trace_oracle  # noqa: E402
-from image_generation_amd import _lib, dev, graphs, sampler as smp  # noqa: E402
+import support  # noqa: E402
+from image_generation_amd import _lib, dev, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dvg_gibbs_sample_traced", "dvg_grbm_moments_packed")
-SEED = 775321899904
 
 
 # ------------------------------------------------------------------------------------------------ the symbols and their checks
 def test_symbols_are_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG trace v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    for name in NAMES:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-        assert name in _lib.SIGNATURES
-        assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
+    support.assert_declared_bound_exported(NAMES, markers=["DVG trace v1"])
 
 
-def _stand_in(n=64):
-    graph = ctypes.create_string_buffer(4096)  # a host-memory stand-in for the graph handle (first field: the spin count)
-    ctypes.c_int32.from_buffer(graph).value = n
-    dummy = ctypes.create_string_buffer(16)
-    return graph, ctypes.cast(graph, ctypes.c_void_p), ctypes.cast(dummy, ctypes.c_void_p), dummy
+_stand_in = support.graph_stand_in
 
 
 def _traced(g, lin, quad, state, trace, *, n_chains=8, n_sweeps=7, burn_in=0, thin=1, dyn=None):
@@ -96,19 +83,13 @@ def test_moments_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
+    support.out_of_reach(monkeypatch)
     plan = _ring_plan()
     s = smp.GibbsSampler(plan, list(range(plan.n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     return s, torch.zeros(plan.n), torch.zeros(plan.n_edges)
 
 
-@functools.lru_cache(maxsize=None)
-def _ring_plan(n=12):
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    return graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+_ring_plan = support.ring_plan
 
 
 def test_sample_trace_rejects_bad_arguments(untouched):
@@ -255,31 +236,13 @@ def test_moments_from_sums_on_cpu():
 
 
 # ------------------------------------------------------------------------------------------------ the plan
-@functools.lru_cache(maxsize=None)
-def _solver_plan(fam, n):
-    g = graphs.pegasus_graph(16) if fam == "pegasus" else graphs.zephyr_graph(12)
-    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, g))
-    _nodes, ei, ej = graphs.edges_of(mg)
-    return graphs.build_plan(n, ei, ej)
+_solver_plan = support.solver_plan
 
 
-@functools.lru_cache(maxsize=None)
-def _random_plan(n=77, p_edge=0.35):
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    keep &= (iu != 3) & (ju != 3)
-    return graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
+_random_plan = functools.partial(support.random_plan, isolated=3)
 
 
-@functools.lru_cache(maxsize=None)
-def _clique_plan(k=14, m=50):
-    ei, ej = [], []
-    for c in range(m):
-        for a in range(k):
-            for b in range(a + 1, k):
-                ei.append(c * k + a); ej.append(c * k + b)
-    return graphs.build_plan(k * m, np.asarray(ei, np.int64), np.asarray(ej, np.int64))
+_clique_plan = support.clique_plan
 
 
 # the nine shapes of tests/test_gpu_gibbs_ais.py: graph, chains, gibbs_generic, the form its draw takes

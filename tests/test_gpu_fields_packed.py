@@ -21,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fields_oracle as fo  # noqa: E402
 import trace_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
@@ -36,23 +37,10 @@ OUT = ("log_pl", "unstable", "cond_sum", "cond_pair", "field_out")
 U = fo.U
 
 
-@functools.lru_cache(maxsize=None)
-def _solver_plan(fam, n):
-    g = graphs.pegasus_graph(16) if fam == "pegasus" else graphs.zephyr_graph(12)
-    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, g))
-    nodes, ei, ej = graphs.edges_of(mg)
-    return graphs.build_plan(n, ei, ej), nodes
+_solver_plan = functools.partial(support.solver_plan, with_nodes=True)
 
 
-@functools.lru_cache(maxsize=None)
-def _random_plan(n=77, p_edge=0.35):
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    keep &= (iu != 3) & (ju != 3)
-    plan = graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
-    assert np.diff(plan.adj_ptr)[3] == 0
-    return plan
+_random_plan = functools.partial(support.random_plan, isolated=3)
 
 
 @functools.lru_cache(maxsize=None)

@@ -22,6 +22,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ais_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, dev, graphs, sampler as smp  # noqa: E402
 from oracle import cref, gibbs  # noqa: E402
 
@@ -34,37 +35,14 @@ EXACT_LOG_Z_16 = 24.417731
 
 
 # ------------------------------------------------------------------------------------------------ graphs
-@functools.lru_cache(maxsize=None)
-def _solver_plan(fam, n):
-    g = graphs.pegasus_graph(16) if fam == "pegasus" else graphs.zephyr_graph(12)
-    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, g))
-    nodes, ei, ej = graphs.edges_of(mg)
-    return graphs.build_plan(n, ei, ej), nodes
+_solver_plan = functools.partial(support.solver_plan, with_nodes=True)
 
 
-@functools.lru_cache(maxsize=None)
-def _random_plan(n=77, p_edge=0.35):
-    """Degrees beyond 20 (two rounds of the neighbour sum), spin 3 isolated, an odd spin count."""
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    keep &= (iu != 3) & (ju != 3)
-    plan = graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
-    deg = np.diff(plan.adj_ptr)
-    assert deg[3] == 0 and deg.max() > 20
-    return plan
+# degrees beyond 20 (two rounds of the neighbour sum), spin 3 isolated, an odd spin count
+_random_plan = functools.partial(support.random_plan, isolated=3, max_degree_above=20)
 
 
-@functools.lru_cache(maxsize=None)
-def _clique_plan(k=14, m=50):
-    ei, ej = [], []
-    for c in range(m):
-        for a in range(k):
-            for b in range(a + 1, k):
-                ei.append(c * k + a); ej.append(c * k + b)
-    plan = graphs.build_plan(k * m, np.asarray(ei, np.int64), np.asarray(ej, np.int64))
-    assert plan.n_colours == k and np.diff(plan.class_ptr).max() == m
-    return plan
+_clique_plan = support.clique_plan
 
 
 # name: (plan, chains, sweeps, gibbs_generic, h scale, J scale, prefactor, beta, first chain id)

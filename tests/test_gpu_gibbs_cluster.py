@@ -21,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cluster_oracle as co  # noqa: E402
 import tempered_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, graphs, sampler as smp  # noqa: E402
 from oracle import gibbs  # noqa: E402
 
@@ -39,17 +40,8 @@ def _zephyr_plan(n=128):
     return graphs.build_plan(n, ei, ej), nodes
 
 
-@functools.lru_cache(maxsize=None)
 def _random_plan(n, hub_degree=0, p_edge=0.08):
-    rng = np.random.default_rng(n)
-    iu, ju = np.triu_indices(n, 1)
-    keep = rng.uniform(size=iu.size) < p_edge
-    if hub_degree:
-        keep = (keep & (iu != 0)) | ((iu == 0) & (ju <= hub_degree))
-    plan = graphs.build_plan(n, iu[keep].astype(np.int64), ju[keep].astype(np.int64))
-    if hub_degree:
-        assert np.diff(plan.adj_ptr)[0] == hub_degree
-    return plan, list(range(n))
+    return support.random_plan(n, p_edge, hub_degree=hub_degree, with_nodes=True)
 
 
 @functools.lru_cache(maxsize=None)

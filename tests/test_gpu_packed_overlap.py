@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import overlap_oracle as oo  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -30,12 +31,7 @@ TRACES = [(1, 5), (2, 1), (41, 7), (65, 3), (130, 2)]  # (chains C, records M)
 P = dict(h_scale=0.05, j_scale=5.0, prefactor=0.05)
 
 
-@functools.lru_cache(maxsize=None)
-def _solver_plan(fam, n):
-    g = graphs.pegasus_graph(16) if fam == "pegasus" else graphs.zephyr_graph(12)
-    mg, _ = graphs.get_graph_mapping(graphs.greedy_get_subgraph(n, SEED, g))
-    nodes, ei, ej = graphs.edges_of(mg)
-    return graphs.build_plan(n, ei, ej), nodes
+_solver_plan = functools.partial(support.solver_plan, with_nodes=True)
 
 
 def _fields(plan):

@@ -16,6 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import correlation_oracle as co  # noqa: E402
 import trace_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,16 +25,8 @@ SEED = 775321899904
 
 # ------------------------------------------------------------------------------------------------ the symbols and their checks
 def test_symbols_are_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG corr v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    for kind, name in (("int", "dvg_packed_correlation"), ("size_t", "dvg_packed_correlation_workspace_bytes")):
-        assert re.search(r"\b" + kind + r"\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-        assert name in _lib.SIGNATURES
-        assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
-    names = {_lib.lib().dvg_prof_kernel_name(i).decode() for i in range(_lib.lib().dvg_prof_num_kernels())}
-    assert {"packed_correlation_transpose_kernel", "packed_correlation_kernel"} <= names
+    support.assert_declared_bound_exported({"dvg_packed_correlation": "int", "dvg_packed_correlation_workspace_bytes": "size_t"}, markers=["DVG corr v1"],
+                                           kernels=["packed_correlation_transpose_kernel", "packed_correlation_kernel"])
     # the slab bound the wrap argument rests on, where the tests can read it
     src = open(os.path.join(ROOT, "image-generation_amd", "csrc", "correlation.hip")).read()
     assert "static_assert(CR_SLAB_ROWS == 1 << 18" in src and F.PACKED_CORRELATION_SLAB_ROWS == 1 << 18
@@ -120,11 +113,7 @@ def test_workspace_query():
 @pytest.fixture
 def untouched(monkeypatch):
     """The library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
 
 
 def test_functional_wrapper_rejects_bad_arguments(untouched):
@@ -191,10 +180,7 @@ def _path_plan(n):
 
 
 def _random_plan(n, edges, seed):
-    rng = np.random.default_rng(seed)
-    pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
-    pick = [pairs[k] for k in rng.permutation(len(pairs))[:edges]]
-    return graphs.build_plan(n, np.array([p[0] for p in pick], dtype=np.int64), np.array([p[1] for p in pick], dtype=np.int64))
+    return support.random_plan(n, edges=edges, seed=seed)
 
 
 def _correlations(x):

@@ -13,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import distinct_oracle as do  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,14 +22,7 @@ INVALID, WORKSPACE, UNSUPPORTED = -1, -3, -4
 
 # ------------------------------------------------------------------------------------------------ the symbols and their checks
 def test_symbols_are_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG distinct v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    for name, ret in (("dvg_packed_distinct", "int"), ("dvg_packed_distinct_workspace_bytes", "size_t")):
-        assert re.search(r"\b" + ret + r"\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-        assert name in _lib.SIGNATURES
-        assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
+    support.assert_declared_bound_exported({"dvg_packed_distinct": "int", "dvg_packed_distinct_workspace_bytes": "size_t"}, markers=["DVG distinct v1"])
 
 
 def test_error_codes_are_the_headers():
@@ -110,11 +104,7 @@ def test_workspace_query():
 @pytest.fixture
 def untouched(monkeypatch):
     """The library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
 
 
 def test_functional_wrapper_rejects_bad_arguments(untouched):

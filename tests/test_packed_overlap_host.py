@@ -17,22 +17,15 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import overlap_oracle as oo  # noqa: E402
 import trace_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 775321899904
 
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG overlap v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    name = "dvg_packed_overlap"
-    assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-    assert name in _lib.SIGNATURES
-    assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
+    support.assert_declared_bound_exported("dvg_packed_overlap", markers=["DVG overlap v1"])
 
 
 def _call(a, b, hist, *, rows_a=5, a_rs=2, a_gs=0, rows_b=7, b_rs=2, b_gs=0, groups=1, n=64, nearest=None):
@@ -97,11 +90,7 @@ def test_c_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """The library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
 
 
 def test_functional_wrapper_rejects_bad_arguments(untouched):

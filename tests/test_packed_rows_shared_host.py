@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import support
 from image_generation_amd import _lib, functional as F, graphs
 
 ENTRIES = ("grbm_energy_packed", "grbm_fields_packed", "grbm_descend_packed", "packed_correlation")
@@ -30,10 +31,7 @@ C_LAYOUTS = (
 def _c_call(entry, *, n=64, rows=5, row_stride=W, groups=1, group_stride=0):
     """The entry on host stand-ins for its pointers (a graph handle's first fields are n, n_edges); nothing reads the rest."""
     L = _lib.lib()
-    graph = ctypes.create_string_buffer(4096)
-    (ctypes.c_int32 * 2).from_buffer(graph)[:] = [n, 0]
-    arena = ctypes.create_string_buffer(1 << 16)
-    base = (ctypes.cast(arena, ctypes.c_void_p).value + 15) & ~15
+    graph, _g, base, _keep = support.graph_stand_in(n)
     g, lin, quad, bits, out, ws = (ctypes.c_void_p(v) for v in (ctypes.addressof(graph), base, base + 64, base + 8192, base + 32768, base + 49152))
     model = (g, lin, quad, 1.0, -4.0, 4.0, -1.0, 1.0)
     geometry = (bits, rows, row_stride, groups, group_stride)
@@ -101,11 +99,7 @@ PY_LAYOUTS = (
 
 @pytest.mark.parametrize("layout,make,start", PY_LAYOUTS, ids=[c[0] for c in PY_LAYOUTS])
 def test_python_wrappers_agree_on_a_bad_row_layout(layout, make, start, monkeypatch):
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
     messages = set()
     for entry, call in _wrappers().items():
         with pytest.raises(_lib.DvgError) as err:

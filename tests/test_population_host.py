@@ -18,7 +18,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ais_oracle  # noqa: E402
 import population_oracle as po  # noqa: E402
 from test_gibbs_ais_host import zephyr16_case  # noqa: E402
-from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
+import support  # noqa: E402
+from image_generation_amd import _lib, functional as F, sampler as smp  # noqa: E402
 from oracle import cref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,15 +29,8 @@ NAMES = ("dvg_population_resample", "dvg_population_resample_workspace_bytes")
 
 # ------------------------------------------------------------------------------------------------ the symbols and their checks
 def test_symbols_are_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG PA v1" in text and "STREAM_RESAMPLE = 5" in text
+    support.assert_declared_bound_exported(dict(zip(NAMES, ("int", "size_t"))), markers=["DVG PA v1", "STREAM_RESAMPLE = 5"])
     assert "STREAM_RESAMPLE = 5" in open(os.path.join(ROOT, "image-generation_amd", "csrc", "philox.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    for name, ret in zip(NAMES, ("int", "size_t")):
-        assert re.search(r"\b" + ret + r"\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-        assert name in _lib.SIGNATURES
-        assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
 
 
 def _call(lw, parent, ws, *, n_chains=12, P=3, state_in=None, state_out=None, n=5, family_in=None, family_out=None,
@@ -90,14 +84,9 @@ def test_c_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """A sampler on a 12-spin ring, with the library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
-    n = 12
-    ei, ej = np.arange(n, dtype=np.int64), (np.arange(n, dtype=np.int64) + 1) % n
-    plan = graphs.build_plan(n, np.minimum(ei, ej), np.maximum(ei, ej))
+    support.out_of_reach(monkeypatch, F)
+    plan = support.ring_plan()
+    n = plan.n
     s = smp.GibbsSampler(plan, list(range(n)), beta=2.0, sweeps=5, seed=3, device="cuda")
     return s, torch.zeros(n), torch.zeros(plan.n_edges)
 

@@ -15,21 +15,14 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import autocorr_oracle as ao  # noqa: E402
 import trace_oracle  # noqa: E402
+import support  # noqa: E402
 from image_generation_amd import _lib, functional as F, graphs, sampler as smp  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ------------------------------------------------------------------------------------------------ the symbol and its checks
 def test_symbol_is_declared_bound_and_exported():
-    text = open(os.path.join(ROOT, "include", "dvg.h")).read()
-    assert "DVG acf v1" in text
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    _lib.build()
-    name = "dvg_trace_autocorr"
-    assert re.search(r"\bint\s+" + name + r"\s*\(", text), f"{name} is not declared in include/dvg.h"
-    assert name in _lib.SIGNATURES
-    assert hasattr(_lib.lib(), name), f"{name} is not exported by the built library"
+    support.assert_declared_bound_exported("dvg_trace_autocorr", markers=["DVG acf v1"])
 
 
 def _call(bits, lag_sum, spin_sum, *, n_chains=3, n_records=10, n=64, max_lag=4, chain_sum=None):
@@ -68,11 +61,7 @@ def test_c_argument_validation_without_gpu():
 @pytest.fixture
 def untouched(monkeypatch):
     """The library out of reach: any call into it fails the test."""
-    def boom(*_a, **_k):
-        raise AssertionError("the library was touched before the argument error was raised")
-
-    monkeypatch.setattr(_lib, "lib", boom)
-    monkeypatch.setattr(F, "lib", boom)
+    support.out_of_reach(monkeypatch, F)
 
 
 def test_functional_wrapper_rejects_bad_arguments(untouched):
