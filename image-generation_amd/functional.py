@@ -390,6 +390,93 @@ def packed_overlap(a, b=None, *, n, nearest=False, out=None):
     return hist, (dist, row)
 
 
+def packed_bonds(bits, graph, quadratic=None):
+    """The bonds t_e = s_i s_j of bit-packed +-1 rows as bit-packed rows (``dvg_packed_bonds``, "DVG bonds v1").  ``bits``:
+    (rows, W) or (C, M, W) int32 on the device (``sampler.pack_spins``, ``sampler.Trace.bits``; bits of spins >= n are
+    ignored); the last dimension must have stride 1, the other strides are taken from the tensor, so slices need no copy.
+    ``graph`` a ``GraphHandle`` with at least one edge.  ``quadratic``: None -- product mode, bit e of a bond row is set iff
+    s_i s_j = +1 on edge e -- or the model's (E,) float32 couplings on the same device -- satisfied mode, the bit is set iff
+    the bond is satisfied (J_e > 0: the spins differ; J_e < 0: they agree; +-0 or NaN: always).  Returns (rows, WE) or (C, M,
+    WE) int32, WE = (E + 31) // 32, dense, bits >= E cleared: packed rows of E "spins" that every function on packed rows
+    takes with ``n=E``.  Pure bit operations; no host sync."""
+    n, E = int(graph.plan.n), int(graph.plan.n_edges)
+    rows, rs, groups, gs = _packed_rows(bits, "bits", (n + 31) // 32)
+    if E < 1:
+        raise _lib.DvgError("graph: the graph has no edge, so there are no bonds")
+    if quadratic is not None and (not torch.is_tensor(quadratic) or quadratic.dtype != torch.float32 or quadratic.numel() != E):
+        raise _lib.DvgError(f"quadratic must be None or a float32 tensor of the graph's {E} values, got "
+                            f"{(tuple(quadratic.shape), quadratic.dtype) if torch.is_tensor(quadratic) else type(quadratic).__name__}")
+    if not bits.is_cuda:
+        raise _lib.DvgError(f"bits must live on the GPU (got {bits.device}); the HIP path has no CPU fallback")
+    if quadratic is not None and quadratic.device != bits.device:
+        raise _lib.DvgError(f"quadratic must be on the device of bits ({bits.device}), got {quadratic.device}")
+    bd = bits.detach()
+    quad = quadratic.detach().contiguous() if quadratic is not None else None
+    WE = (E + 31) // 32
+    out = torch.empty((groups * rows, WE), dtype=torch.int32, device=bd.device)
+    with torch.cuda.device(bd.device):
+        check(lib().dvg_packed_bonds(graph.ptr, _lib.ptr(quad), bd.data_ptr(), rows, rs, groups, gs, out.data_ptr(),
+                                     stream_ptr(bd.device)), "dvg_packed_bonds")
+    return out.view(groups, rows, WE) if bits.dim() == 3 else out
+
+
+def packed_link_overlap(a, a_bonds, b=None, b_bonds=None, *, n, n_edges, out=None):
+    """Spin and bond distances of all pairs of bit-packed +-1 rows, together and exactly (``dvg_packed_overlap_link``, "DVG link
+    overlap v1").  ``a`` / ``b``: spin rows as :func:`packed_overlap` takes them -- (rows, W) or (C, M, W) int32 on the device,
+    the 3-D form M groups of C rows; ``b`` None (self mode: the pairs r < r' of ``a`` in each group), 2-D (with a 3-D ``a``:
+    shared by every group) or 3-D with the same M.  ``a_bonds`` / ``b_bonds``: the sides' bond rows (:func:`packed_bonds`, or
+    views of them), int32 with the leading shape of their spin rows and WE = (n_edges + 31) // 32 words; ``b_bonds`` goes with
+    ``b``.  Row and group strides are taken from each tensor.  Returns ``(hist (n + 1,), link_hist (n_edges + 1,), link_sum
+    (n + 1,), link_sq (n + 1,))`` int64: pairs per spin distance d (``packed_overlap``'s histogram), pairs per bond distance
+    l, and per d the sums of l and of l^2 -- ``sampler.LinkOverlap.from_sums`` turns them into estimates.  ``out``: such a
+    quadruple to add onto.  No host sync."""
+    for name, v in (("n", n), ("n_edges", n_edges)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    n, E = int(n), int(n_edges)
+    W, WE = (n + 31) // 32, (E + 31) // 32
+    rows_a, a_rs, groups, a_gs = _packed_rows(a, "a", W, groups_first=False)
+    _rows, ab_rs, _groups, ab_gs = _packed_rows(a_bonds, "a_bonds", WE, groups_first=False)
+    if tuple(a_bonds.shape[:-1]) != tuple(a.shape[:-1]):
+        raise _lib.DvgError(f"a_bonds must have the leading shape of a, got a {tuple(a.shape)} and a_bonds {tuple(a_bonds.shape)}")
+    if a_bonds.device != a.device:
+        raise _lib.DvgError(f"a_bonds must be on the device of a ({a.device}), got {a_bonds.device}")
+    rows_b = b_rs = b_gs = bb_rs = bb_gs = 0
+    if (b is None) != (b_bonds is None):
+        raise _lib.DvgError("b and b_bonds go together: both None (self mode) or both given")
+    if b is not None:
+        rows_b, b_rs, groups_b, b_gs = _packed_rows(b, "b", W, groups_first=False)
+        if b.dim() == 3 and (a.dim() != 3 or groups_b != groups):
+            raise _lib.DvgError(f"b: a 3-D b needs a 3-D a with the same number of records, got a {tuple(a.shape)} and b {tuple(b.shape)}")
+        _rows, bb_rs, _groups, bb_gs = _packed_rows(b_bonds, "b_bonds", WE, groups_first=False)
+        if tuple(b_bonds.shape[:-1]) != tuple(b.shape[:-1]):
+            raise _lib.DvgError(f"b_bonds must have the leading shape of b, got b {tuple(b.shape)} and b_bonds {tuple(b_bonds.shape)}")
+        if b.dim() == 2:
+            b_gs = bb_gs = 0
+        for name, t in (("b", b), ("b_bonds", b_bonds)):
+            if t.device != a.device:
+                raise _lib.DvgError(f"{name} must be on the device of a ({a.device}), got {t.device}")
+    shapes = ((n + 1,), (E + 1,), (n + 1,), (n + 1,))
+    names = ("hist", "link_hist", "link_sum", "link_sq")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise _lib.DvgError("out must be a quadruple (hist, link_hist, link_sum, link_sq)")
+        for name, t, shape in zip(names, out, shapes):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                    t.device != a.device:
+                raise _lib.DvgError(f"out: {name} must be a contiguous {shape} int64 tensor on {a.device}")
+    if not a.is_cuda:
+        raise _lib.DvgError(f"a must live on the GPU (got {a.device}); the HIP path has no CPU fallback")
+    ad, abd = a.detach(), a_bonds.detach()
+    bd, bbd = (b.detach(), b_bonds.detach()) if b is not None else (None, None)
+    sums = tuple(out) if out is not None else tuple(torch.empty(s, dtype=torch.int64, device=ad.device) for s in shapes)
+    with torch.cuda.device(ad.device):
+        check(lib().dvg_packed_overlap_link(ad.data_ptr(), abd.data_ptr(), rows_a, a_rs, a_gs, ab_rs, ab_gs, _lib.ptr(bd), _lib.ptr(bbd),
+                                            rows_b, b_rs, b_gs, bb_rs, bb_gs, groups, n, E, *(t.data_ptr() for t in sums),
+                                            int(out is not None), stream_ptr(ad.device)), "dvg_packed_overlap_link")
+    return sums
+
+
 def _clamp_range(r, name):
     """``(lo, hi)`` floats of a solver range, None meaning no clamp."""
     if r is None:

@@ -1116,6 +1116,20 @@ class ModelWrapper:
                                           quadratic_range=self.quadratic_range, **kw)
 
     @torch.no_grad()
+    def prior_link_overlap(self, **kw):
+        """Whether the sampler's chains differ by compact domains or everywhere on the prior: the
+        :class:`~.sampler.LinkOverlap` between distinct chains at equal times of one traced draw
+        (``GraphRestrictedBoltzmannMachine.link_overlap``; ``num_reads``, ``num_sweeps``, ``burn_in``, ``thin``, ``start`` are
+        passed on, ``num_reads`` defaults to NUM_READS) -- ``link_given_q`` against ``q``, ``corr_q2_link`` and ``fit()``.
+        Rank-local and eval-mode, like ``prior_overlap``."""
+        self._dvae.eval()
+        self._grbm.eval()
+        if "num_reads" not in kw and "start" not in kw:
+            kw["num_reads"] = int(self.sampler_kwargs.get("num_reads", 1))
+        return self._grbm.link_overlap(self.sampler, prefactor=self.PREFACTOR, linear_range=self.linear_range,
+                                       quadratic_range=self.quadratic_range, **kw)
+
+    @torch.no_grad()
     def latent_novelty(self, images: torch.Tensor, samples: Optional[torch.Tensor] = None) -> dict:
         """How far generated latents lie from the data's: encode ``images`` -> hard spins (heaviside, H(0) = 0, as
         ``generate_variations`` does) -> packed rows (``sampler.pack_spins``); ``samples`` (rows, n) +-1 spins, or None for

@@ -433,6 +433,26 @@ class GraphRestrictedBoltzmannMachine(torch.nn.Module):
         return trace.overlap()
 
     @torch.no_grad()
+    def bonds(self, x_or_bits: torch.Tensor, satisfied: bool = False) -> torch.Tensor:
+        """The bond rows of spin rows, bit-packed ((rows, WE) or (C, M, WE) int32, ``dvg_packed_bonds``): bit e set iff s_i s_j
+        = +1 on edge e, or with ``satisfied=True`` iff the bond is satisfied under this model's couplings -- the popcount of
+        such a row is its number of satisfied couplings.  ``x_or_bits``: bit-packed rows ((rows, W) or (C, M, W) int32:
+        ``Trace.bits``) or +-1 rows ((..., n), any other dtype; packed with ``sampler.pack_spins``), on the GPU."""
+        from .sampler import bonds
+
+        bits = self._packed_bits(x_or_bits)
+        return bonds(bits, self.graph_handle(bits.device), self._quadratic.detach() if satisfied else None)
+
+    @torch.no_grad()
+    def link_overlap(self, sampler, *, prefactor: float, linear_range=None, quadratic_range=None, **kw):
+        """Do the sampler's chains differ by compact domains or everywhere?  One traced draw (:meth:`sample_trace`, ``**kw``
+        passed on) and the :class:`~.sampler.LinkOverlap` between its distinct chains at equal times
+        (:meth:`Trace.link_overlap`): ``link_given_q``, ``corr_q2_link``, ``fit()``.  The local :class:`GibbsSampler` only."""
+        self._need_local_sampler(sampler, "link_overlap")
+        trace = self.sample_trace(sampler, prefactor=prefactor, linear_range=linear_range, quadratic_range=quadratic_range, **kw)
+        return trace.link_overlap(self.graph_handle(trace.bits.device))
+
+    @torch.no_grad()
     def log_likelihood(self, x: torch.Tensor, sampler, *, prefactor: float, linear_range=None, quadratic_range=None,
                        log_z=None, **kw) -> torch.Tensor:
         """``log p(x) = -beta E_s(x) - log Z`` per row of ``x`` ((B, n) +-1 on the device) under the distribution

@@ -793,6 +793,119 @@ class Overlap:
         return f"Overlap(n={self.n})"
 
 
+class LinkOverlap:
+    """The link overlap q_l = (1 / E) sum_e t_e^a t_e^b = 1 - 2 l / E of pairs of +-1 rows -- t_e = s_i s_j the bonds on the
+    graph's E edges -- beside their spin overlap q = 1 - 2 d / n, from the exact sums of ``dvg_packed_overlap_link`` ("DVG link
+    overlap v1"): ``hist`` (n + 1,), pairs per spin distance d; ``link_hist`` (E + 1,), pairs per bond distance l; ``link_sum``
+    and ``link_sq`` (n + 1,), per d the sums of l and l^2; all int64.  Flipping a compact domain moves q a lot and q_l little
+    (only the domain's surface changes bonds), so q_l against q^2 tells droplets from rows that differ everywhere.  Every
+    property is float64 torch on the sums' device (CPU tensors too), no host sync:
+
+    ``pairs`` ();  ``spin``: the :class:`Overlap` of ``hist``;  ``link``: the :class:`Overlap` of ``link_hist`` over E -- P(q_l),
+    ``mean_q``, ``q2``, ``binder`` of the link overlap;  ``q`` (n + 1,): the grid 1 - 2 d / n;
+    ``link_given_q`` (n + 1,): the mean of q_l over the pairs at each d, ``1 - 2 link_sum / (E hist)``, NaN in empty bins;
+    ``link_var_given_q`` (n + 1,): the variance of q_l over the pairs at each d, NaN in empty bins;
+    ``mean_link``: the mean of q_l over all pairs;  ``corr_q2_link``: the Pearson correlation of q^2 and q_l over the pairs;
+    ``fit()``: ``(a, b)`` of the least-squares line q_l = a + b q^2 over the pairs (the ``hist``-weighted fit of
+    ``link_given_q``).  No pairs at all give NaN, as IEEE division does."""
+
+    def __init__(self, hist, link_hist, link_sum, link_sq, n, n_edges):
+        self.hist, self.link_hist, self.link_sum, self.link_sq = hist, link_hist, link_sum, link_sq
+        self.n, self.n_edges = int(n), int(n_edges)
+
+    @classmethod
+    def from_sums(cls, hist, link_hist, link_sum, link_sq, n: int, n_edges: int) -> "LinkOverlap":
+        for name, v in (("n", n), ("n_edges", n_edges)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        for name, t, k in (("hist", hist, n), ("link_hist", link_hist, n_edges), ("link_sum", link_sum, n), ("link_sq", link_sq, n)):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (int(k) + 1,):
+                raise ValueError(f"{name} must be a ({int(k) + 1},) int64 tensor")
+            if t.device != hist.device:
+                raise ValueError(f"{name} must be on the device of hist ({hist.device}), got {t.device}")
+        return cls(hist, link_hist, link_sum, link_sq, n, n_edges)
+
+    @property
+    def spin(self) -> Overlap:
+        return Overlap(self.hist, self.n)
+
+    @property
+    def link(self) -> Overlap:
+        return Overlap(self.link_hist, self.n_edges)
+
+    @property
+    def pairs(self):
+        return self.hist.to(torch.float64).sum()
+
+    @property
+    def q(self):
+        return self.spin.q
+
+    def _per_bin(self):
+        """(hist, sum of q_l, sum of q_l^2) over the pairs at each d, float64."""
+        h, s, sq, E = self.hist.to(torch.float64), self.link_sum.to(torch.float64), self.link_sq.to(torch.float64), float(self.n_edges)
+        return h, h - 2.0 * s / E, h - 4.0 * s / E + 4.0 * sq / (E * E)
+
+    @property
+    def link_given_q(self):
+        return 1.0 - 2.0 * self.link_sum.to(torch.float64) / (float(self.n_edges) * self.hist.to(torch.float64))
+
+    @property
+    def link_var_given_q(self):
+        h, s1, s2 = self._per_bin()
+        return s2 / h - (s1 / h) ** 2
+
+    @property
+    def mean_link(self):
+        return 1.0 - 2.0 * self.link_sum.to(torch.float64).sum() / (float(self.n_edges) * self.pairs)
+
+    def _moments(self):
+        """(mean of q^2, mean of q_l, var of q^2, var of q_l, their covariance) over the pairs, each sum centred."""
+        h, s1, _s2 = self._per_bin()
+        P, x = self.pairs, self.q ** 2
+        mx, my = (h * x).sum() / P, self.mean_link
+        link = self.link
+        var_x = (h * (x - mx) ** 2).sum() / P
+        var_y = (link._h() * (link.q - my) ** 2).sum() / P
+        cov = ((x - mx) * (s1 - my * h)).sum() / P
+        return mx, my, var_x, var_y, cov
+
+    @property
+    def corr_q2_link(self):
+        _mx, _my, var_x, var_y, cov = self._moments()
+        return cov / torch.sqrt(var_x * var_y)
+
+    def fit(self):
+        mx, my, var_x, _var_y, cov = self._moments()
+        b = cov / var_x
+        return my - b * mx, b
+
+    def __repr__(self):
+        return f"LinkOverlap(n={self.n}, n_edges={self.n_edges})"
+
+
+def bonds(bits, graph, quadratic=None) -> torch.Tensor:
+    """The bond rows of bit-packed rows ((rows, W) or (C, M, W) int32 on the device, views welcome): bit e set iff s_i s_j = +1
+    on edge e of ``graph`` (a :class:`GraphHandle`), or with the model's ``quadratic`` iff the bond is satisfied
+    (``dvg_packed_bonds``, "DVG bonds v1").  The result is packed rows of E "spins": :func:`distinct` on it counts states
+    modulo a global flip, ``functional.packed_correlation`` gives edge-edge correlations."""
+    from . import functional as F  # (functional imports this module)
+
+    return F.packed_bonds(bits, graph, quadratic)
+
+
+def link_overlap(bits, graph, other=None) -> LinkOverlap:
+    """The :class:`LinkOverlap` of bit-packed rows ((rows, W), or (C, M, W): M groups of C rows) with themselves (the pairs r
+    < r' of each group) or with ``other`` (rows as ``functional.packed_overlap``'s ``b``): product-mode bonds of both sides
+    (``dvg_packed_bonds``), then one call of ``dvg_packed_overlap_link``; the rows stay packed."""
+    from . import functional as F  # (functional imports this module)
+
+    n, E = int(graph.plan.n), int(graph.plan.n_edges)
+    a_bonds = F.packed_bonds(bits, graph)
+    b_bonds = F.packed_bonds(other, graph) if other is not None else None
+    return LinkOverlap.from_sums(*F.packed_link_overlap(bits, a_bonds, other, b_bonds, n=n, n_edges=E), n, E)
+
+
 class Correlations:
     """Full pair correlations of +-1 rows from their exact sums (``dvg_packed_correlation``, "DVG corr v1"): ``spin_sum`` (n,)
     int64 = sum over rows of s_i, ``pair_sum`` (n, n) int64 = sum over rows of s_i s_j for EVERY pair of spins, ``count`` = T
@@ -1397,6 +1510,24 @@ class Trace:
         hist, near = F.packed_overlap(self.bits, b, n=self.n, nearest=bool(nearest))
         o = Overlap.from_hist(hist, self.n)
         return (o, near) if nearest else o
+
+    def bonds(self, graph, quadratic=None) -> torch.Tensor:
+        """The records' bond rows, (C, M, WE) int32 (:func:`bonds`, ``dvg_packed_bonds``: the records stay packed): bit e set
+        iff s_i s_j = +1 on edge e of ``graph``, or with ``quadratic`` iff the bond is satisfied."""
+        return bonds(self.bits, graph, quadratic)
+
+    def link_overlap(self, graph, other=None) -> LinkOverlap:
+        """The equal-time :class:`LinkOverlap` (``dvg_packed_overlap_link``: the records stay packed): over every record the
+        pairs of distinct chains of this trace, or with ``other`` -- a :class:`Trace` with as many records, its ``bits``, or
+        a flat (rows, W) set shared by every record -- the pairs (chain, row of ``other``), as :meth:`overlap` takes them."""
+        return link_overlap(self.bits, graph, other.bits if isinstance(other, Trace) else other)
+
+    def satisfied(self, graph, quadratic) -> torch.Tensor:
+        """The number of satisfied couplings of every record under ``quadratic``, int64 (C, M): the popcount of the
+        satisfied-mode bond rows (:meth:`bonds`); ``E`` minus it is the record's frustrated bonds."""
+        if quadratic is None:
+            raise ValueError("satisfied needs the model's quadratic: without it the bonds are products, not satisfied couplings")
+        return _popcount32(self.bonds(graph, quadratic)).sum(-1)
 
     def pseudo_likelihood(self, graph, linear, quadratic, *, beta, prefactor: float = 1.0, linear_range=None,
                           quadratic_range=None) -> PseudoLikelihood:

@@ -597,6 +597,55 @@ int dvg_packed_overlap(const uint32_t *a, int64_t rows_a, int64_t a_row_stride, 
                        const uint32_t *b, int64_t rows_b, int64_t b_row_stride, int64_t b_group_stride,
                        int groups, int n,
                        int64_t *hist, int64_t *nearest, int accumulate, dvg_stream_t stream);
+/* The bonds of bit-packed spin rows as bit-packed rows ("DVG bonds v1"): t_e = s_i s_j on the graph's edges (i, j) = (edge_i[e],
+ * edge_j[e]).  Input rows are packed as in "DVG trace v1" (W = (n + 31) / 32 words, bit b of word w = spin 32 w + b is +1; bits of
+ * spins >= n are ignored and may hold anything) and addressed by (rows, row_stride, groups, group_stride) in words exactly as in
+ * dvg_grbm_energy_packed.
+ *   Output.  bonds_out: DEVICE, dense [groups rows][WE], WE = (E + 31) / 32, E = n_edges, indexed by the flattened t = g rows + r.
+ *     Bit b of word w is bond e = 32 w + b in the graph's edge order -- the order of edge_i / edge_j given to dvg_graph_create
+ *     and of quadratic -- and is set iff t_e = +1: a bond row is a packed +-1 row of E "spins" in the same convention, and every
+ *     entry on packed rows takes it with n = E.  Bits >= E of the last word are written 0; nothing is written beyond groups
+ *     rows WE words.  bits and bonds_out must not overlap.
+ *   Value.  quadratic == NULL (product mode): t_e = s_i s_j.  quadratic given (DEVICE, [n_edges]; satisfied mode): t_e = +1 iff
+ *     the bond is satisfied under E(s) = hs.s + sum_e Js_e s_i s_j:  J_e > 0: t_e = -s_i s_j;  J_e < 0: t_e = s_i s_j;  a J_e
+ *     that is neither (+0, -0, NaN): t_e = +1.  Only the sign of the raw quadratic is read -- prefactor and ranges keep it, so
+ *     the entry takes neither.  The popcount of a satisfied-mode bond row is the row's number of satisfied couplings.
+ *   Pure bit operations: the result is a function of the input alone and two calls give the same words.  The call enqueues
+ *   on `stream`, allocates nothing and needs no workspace.
+ * DVG_E_INVALID, before any HIP call: g, bits or bonds_out null; a graph with no edge; rows < 1; groups < 1; row_stride < W;
+ * group_stride < 0; the input's word range overlapping bonds_out.  DVG_E_UNSUPPORTED: groups rows >= 2^62; n > 8192 or n + E >
+ * 16384 (a tile's spin and bond columns are kept in 8 (n + E) bytes of LDS, 128 KiB at the most).  A rejected call writes
+ * nothing. */
+int dvg_packed_bonds(const dvg_graph_t *g, const float *quadratic,
+                     const uint32_t *bits, int64_t rows, int64_t row_stride, int64_t groups, int64_t group_stride,
+                     uint32_t *bonds_out, dvg_stream_t stream);
+/* Spin and bond distances between bit-packed rows, together and exactly ("DVG link overlap v1"): the link overlap q_l(a, b) =
+ * (1 / E) sum_e t_e(a) t_e(b) = 1 - 2 l / E beside the spin overlap q = 1 - 2 d / n of the same pair.  The pairs are those of
+ * "DVG overlap v1", with the same strides in words: cross mode (b != NULL) all rows_a rows_b pairs of every group, self mode (b
+ * == NULL) the unordered pairs r < r' of A (rows_b, b_bonds and the strides of B are ignored), b_group_stride = 0 (and
+ * b_bond_group_stride = 0) one B shared by the groups.  Each side brings its spin rows (a, b: W = (n + 31) / 32 words) and its
+ * bond rows (a_bonds, b_bonds: WE = (n_edges + 31) / 32 words, as dvg_packed_bonds writes them) under strides of their own, so
+ * that entry's dense output and views of it both work; row r of group g of the bonds of A starts at a_bonds + g
+ * a_bond_group_stride + r a_bond_row_stride.  Bits of spins >= n and of bonds >= E = n_edges are ignored.  For a pair,
+ * d = popc(x ^ y over the spins < n) and l = popc(t(x) ^ t(y) over the bonds < E):
+ *   hist[d]      (+)= 1        int64 [n + 1]   equal to dvg_packed_overlap's hist on the same rows, bit for bit
+ *   link_hist[l] (+)= 1        int64 [E + 1]
+ *   link_sum[d]  (+)= l        int64 [n + 1]
+ *   link_sq[d]   (+)= l l      int64 [n + 1]
+ * All four are required DEVICE pointers; accumulate == 0 overwrites them, 1 adds onto their contents.  Every value is an exact
+ * integer; workgroups combine through 64-bit integer atomics only, so the result is deterministic.  Nothing is written beyond
+ * those sizes.  The entry needs n and n_edges only, no graph.
+ * DVG_E_INVALID, before any HIP call: a, a_bonds, hist, link_hist, link_sum or link_sq null; b != NULL with b_bonds null;
+ * rows_a, groups, n or n_edges < 1; b != NULL with rows_b < 1; a row stride < W or a bond row stride < WE (of B only when b !=
+ * NULL); a group stride < 0.  DVG_E_UNSUPPORTED: n > 4096 or n_edges > 16384 (a workgroup keeps its counters in LDS, 20 (n + 1) +
+ * 4 (n_edges + 1) bytes); rows_a or rows_b >= 2^31; groups rows_a rows_b >= 2^62; pairs n_edges^2 >= 2^63 (link_sq would wrap). */
+int dvg_packed_overlap_link(const uint32_t *a, const uint32_t *a_bonds, int64_t rows_a, int64_t a_row_stride,
+                            int64_t a_group_stride, int64_t a_bond_row_stride, int64_t a_bond_group_stride,
+                            const uint32_t *b, const uint32_t *b_bonds, int64_t rows_b, int64_t b_row_stride,
+                            int64_t b_group_stride, int64_t b_bond_row_stride, int64_t b_bond_group_stride,
+                            int groups, int n, int n_edges,
+                            int64_t *hist, int64_t *link_hist, int64_t *link_sum, int64_t *link_sq,
+                            int accumulate, dvg_stream_t stream);
 /* Which bit-packed spin rows are the same state, and how often each state occurs, exactly ("DVG distinct v1"): the equivalence
  * classes of the rows under equality on the spins < n.  Rows are packed as in "DVG trace v1": W = (n + 31) / 32 words, bit b of
  * word w = spin 32 w + b is +1.  Strides count words, as in dvg_grbm_energy_packed: row r of group g starts at bits + g

@@ -67,6 +67,9 @@ row to hold it against is `rolled reference`; a second line gives the plans of t
 `distinct`: also dvg_packed_distinct (the equivalence classes of bit-packed rows under equality, "DVG distinct v1": first, id, rep and
 count) on 65 536 rows of n = 256 and 16 384 rows of n = 1024, all rows distinct and rows drawn from a pool of 256 states, against
 torch.unique(dim=0, return_inverse=True, return_counts=True) on the same device rows; a second line says whether the two agree.
+`link`: also dvg_packed_bonds ("DVG bonds v1") and dvg_packed_overlap_link ("DVG link overlap v1", self mode at equal times) on the thin =
+1 trace, against the stock torch path on the same rows (unpack to float32, gather the bonds, two batched matmuls, bincount and
+index_add); further lines say whether the four sums agree and what the link overlap of the draw is.
 `repeat=K`: K timings of each row instead of one (the spread of a row is max - min of its K)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -758,3 +761,57 @@ if "distinct" in sys.argv:
             same = D == int(u_rows.shape[0]) and sorted(count[:D].tolist()) == sorted(u_counts.tolist()) and \
                 bool(torch.equal(rows_d[rep[:D].long()][ident.long()], u_rows[u_inverse]))
             print(f"  {'':34s} the two give the same classes: {same}  (D = {D})")
+if "link" in sys.argv:
+    # dvg_packed_bonds ("DVG bonds v1") and dvg_packed_overlap_link ("DVG link overlap v1") on the thin = 1 trace, in self mode at
+    # equal times, against the stock torch path on the same rows: unpack to float32, gather the bonds, two batched matmuls,
+    # bincount and index_add
+    s = smp.GibbsSampler(plan, nodes, beta=20.0, sweeps=sweeps, seed=seed, persistent=True)
+    trace = s.sample_trace(lin, quad, 0.05, (-4, 4), (-1, 1), num_reads=C)  # burn_in 0, thin 1: chains x sweeps records
+    E, W, M = plan.n_edges, (n + 31) // 32, sweeps
+    WE = (E + 31) // 32
+    bonds = torch.empty((C, M, WE), dtype=torch.int32, device="cuda")
+    sums = [torch.empty((k + 1,), dtype=torch.int64, device="cuda") for k in (n, E, n, n)]
+
+    def report(name, ts, what):
+        t = float(np.median(ts))
+        print(f"  {name:34s} {t:9.1f} us per call  {what}  (min {min(ts):.1f} max {max(ts):.1f})")
+        return t
+
+    def packed_bonds():
+        _lib.check(_lib.lib().dvg_packed_bonds(s.graph.ptr, None, trace.bits.data_ptr(), M, W, C, M * W, bonds.data_ptr(), _lib.stream_ptr()),
+                   "dvg_packed_bonds")
+        return bonds
+
+    def packed_link():
+        _lib.check(_lib.lib().dvg_packed_overlap_link(trace.bits.data_ptr(), bonds.data_ptr(), C, M * W, W, M * WE, WE, None, None, 0, 0, 0, 0,
+                                                      0, M, n, E, *(t.data_ptr() for t in sums), 0, _lib.stream_ptr()),
+                   "dvg_packed_overlap_link")
+        return sums[0]
+
+    ts, _ = timed(packed_bonds)
+    t_bonds = report("bonds, packed trace", ts, f"{C} x {M} rows x {4 * W} B -> {4 * WE} B, E = {E}")
+    ts, _ = timed(packed_link)
+    pairs = M * C * (C - 1) // 2
+    t_link = report("link overlap, packed trace", ts, f"{M} groups x {C} rows x {4 * (W + WE)} B, {pairs} pairs, "
+                    f"{pairs * (W + WE) / float(np.median(ts)) / 1e3:.1f} G popcounts/s")
+    ei_d, ej_d = torch.from_numpy(plan.edge_i).cuda(), torch.from_numpy(plan.edge_j).cuda()
+    iu = torch.triu_indices(C, C, 1, device="cuda")
+
+    def stock():
+        x = smp.unpack_spins(trace.bits, n).transpose(0, 1).contiguous()  # (M, C, n) float32
+        t = x[:, :, ei_d] * x[:, :, ej_d]                                   # (M, C, E)
+        d = ((n - torch.bmm(x, x.transpose(1, 2))) / 2)[:, iu[0], iu[1]].reshape(-1).long()
+        l = ((E - torch.bmm(t, t.transpose(1, 2))) / 2)[:, iu[0], iu[1]].reshape(-1).long()
+        zero = torch.zeros((n + 1,), dtype=torch.int64, device="cuda")
+        return (torch.bincount(d, minlength=n + 1), torch.bincount(l, minlength=E + 1), zero.index_add(0, d, l),
+                zero.index_add(0, d, l * l))
+
+    ts, by_torch = timed(stock)
+    t_stock = report("the same by torch, float32", ts, f"{M} x {C} rows x {4 * (n + E)} B   {float(np.median(ts)) / (t_bonds + t_link):.1f} x the two entries")
+    same = all(bool(torch.equal(a, b)) for a, b in zip(by_torch, sums))
+    print(f"  {'':34s} the two give the same four sums: {same}; not slower than the stock path: {t_bonds + t_link <= t_stock}  "
+          f"(pairs {int(sums[0].sum())}, sum of l {int(sums[2].sum())}, of l^2 {int(sums[3].sum())})")
+    lo = smp.LinkOverlap.from_sums(*sums, n, E)
+    a_fit, b_fit = lo.fit()
+    print(f"  {'':34s} mean q_l {float(lo.mean_link):.4f}, spin q2 {float(lo.spin.q2):.4f}, corr(q^2, q_l) {float(lo.corr_q2_link):.4f}, "
+          f"fit q_l = {float(a_fit):.4f} + {float(b_fit):.4f} q^2")
